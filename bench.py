@@ -2,6 +2,8 @@
 """ACR hot-path benchmark: frames/s (2-hand mesh) at 512x512, batch 64 per GPU, HRNet-W32 fp32.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                  (+ everything measured behind the headline)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR      (+ the last timed step's results as DIR/*.npy)
     python bench.py --gpus N --steps K --warmup W          (spawns its own N ranks: one process per GPU over RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          (the driver's form: ranks already exist)
@@ -10,6 +12,10 @@ A step = one pass of the whole path (uint8 frames resident in HBM -> backbone ->
 MANO -> verts/joints, plus for N>1 the RCCL all-gather of every rank's result slots) over one batch of
 64 synthetic frames per GPU (weak scaling).  Synthetic seeded checkpoint + MANO tables (the real assets
 are not redistributable).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else the line can carry (the
+roofline pass, point heads, one context, cpu_baseline + parity, latency, live PMC, the 16-bit programs, the other configs,
+the multi-GPU diagnostics) runs behind the timed region only with --full; the --no-* switches trim that set.
 """
 import argparse
 import importlib
@@ -668,14 +674,17 @@ def standin_main(args, rank, world):
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
     ok = True
     multi = None
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-        multi = multi_gpu_diagnostics(dist, runner, eng, last, B, world, rank, dt, args.steps, 'cpu',
-                                      frames_for_rank=lambda r: torch.from_numpy(synth.make_frames(B, seed=r, structured=False)))
+        if args.full:
+            multi = multi_gpu_diagnostics(dist, runner, eng, last, B, world, rank, dt, args.steps, 'cpu',
+                                          frames_for_rank=lambda r: torch.from_numpy(synth.make_frames(B, seed=r, structured=False)))
         # every rank holds every rank's rows, in frame order
         for r in range(world):
             want = parallel.alloc_result(B, eng.device)[1]
@@ -700,6 +709,24 @@ def standin_main(args, rank, world):
         raise SystemExit('stand-in run: gathered rows differ from what the ranks produced')
 
 
+def dump_outputs(last, dirname, limit=64 << 20):
+    """--dump-outputs DIR: what the timed path returned for its last step - slots [N,2,176], verts [N,2,778,3], joints
+    [N,2,21,3], float32, N = every rank's frames for N > 1 (the gathered rows) - one DIR/<name>.npy each (1.3 MB at batch 64).
+    Above `limit` bytes in all, the same fixed, seeded sample of frames is kept of every array (`frames.npy` = their indices).
+    The inputs are seeded, so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(dirname, exist_ok=True)
+    names = ('slots', 'verts', 'joints')
+    n = int(last['slots'].shape[0])
+    per_frame = sum(last[k][0].numel() * 4 for k in names) if n else 0
+    rows = None
+    if n * per_frame > limit:
+        rows = np.sort(np.random.RandomState(0).choice(n, (limit - 4096) // (per_frame + 8), replace=False))
+        np.save(os.path.join(dirname, 'frames.npy'), rows.astype(np.float64))
+    for k in names:
+        a = last[k].detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(dirname, k + '.npy'), a if rows is None else a[rows])
+
+
 def guarded(out, key, fn):
     """A measurement leg BEHIND the timed region must not cost the headline line: a leg that raises
     leaves {'error': ...} under its key and the line is still printed."""
@@ -720,6 +747,8 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=64, help='frames per GPU')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run the legs behind the timed region: roofline pass, point heads, one context, cpu_baseline + parity, latency, live PMC, reduced precision, other configs, multi-GPU diagnostics (the --no-* switches below trim them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (slots / verts / joints, float32) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-latency', action='store_true', help='skip the batch-1 / batch-8 latency measurement (profiling runs)')
     ap.add_argument('--no-point-heads', action='store_true', help='skip the separately reported point-heads variant')
@@ -729,8 +758,8 @@ def main():
     ap.add_argument('--precision', default='fp32', help='fp32 = the headline (BASELINE.json configs[2]); fp16 / bf16 run the 16-bit program as the timed workload - for profiling runs (tools/profile_round.sh), NOT the headline: the line then says so in dtype / config')
     ap.add_argument('--lanes', type=int, default=0, help='HIP streams the independent chains of the program run on (ACRMI_OPT_LANES; 0 = library default, 1 per context with --pipeline >= 2)')
     ap.add_argument('--pipeline', type=int, default=2, help='contexts taking batches in turn on their own streams (engine.EnginePool): the tail of one batch overlaps the head of the next; 1 = one context')
-    ap.add_argument('--profile-out', default=None, help='write the per-op HIP-event timings (JSON) here')
-    ap.add_argument('--leg-timeout', type=int, default=900, help='seconds the legs BEHIND the timed region (roofline pass, point heads, cpu_baseline, latency, PMC child, other configs) may take before the line is printed without the unfinished ones (0 = no watchdog)')
+    ap.add_argument('--profile-out', default=None, help='with --full: write the per-op HIP-event timings (JSON) of the roofline pass here')
+    ap.add_argument('--leg-timeout', type=int, default=900, help='with --full: seconds the legs BEHIND the timed region (roofline pass, point heads, cpu_baseline, latency, PMC child, other configs) may take before the line is printed without the unfinished ones (0 = no watchdog)')
     ap.add_argument('--standin', action='store_true', help=argparse.SUPPRESS)     # CPU plumbing run over gloo (tests only)
     args = ap.parse_args()
 
@@ -828,12 +857,15 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)       # before anything behind the timed region reuses the result buffers
     multi = None
     if use_dist:
         cdev = 'cpu' if dist.get_backend() == 'gloo' else 'cuda'
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if use_dist and args.full:
         # self-diagnosis of a multi-GPU run (no 8-GPU box was available to any round): every rank's own
         # step time, the all-gather by itself, and how many ranks' rows arrived - in the line, so that a first hardware SCALE
         # run that scales badly says where
@@ -923,136 +955,142 @@ def main():
                'roofline': None}
         if multi is not None:
             out['multi_gpu'] = multi
-        # Watchdog: a leg behind the timed region that HANGS (a GPU fault inside a library call never returns to Python, so
-        # guarded() cannot catch it) must not cost the measured headline either: after --leg-timeout seconds a daemon thread
-        # prints the line as far as it got - `post_timeout` says so - and ends the process.  Disarmed when the legs are done.
-        import threading
+        if args.full:
+            # Watchdog: a leg behind the timed region that HANGS (a GPU fault inside a library call never returns to Python, so
+            # guarded() cannot catch it) must not cost the measured headline either: after --leg-timeout seconds a daemon thread
+            # prints the line as far as it got - `post_timeout` says so - and ends the process.  Disarmed when the legs are done.
+            import threading
 
-        def _give_up():
-            out['post_timeout'] = ('a measurement leg behind the timed region did not return within %d s; the line holds what '
-                                   'was finished until then' % args.leg_timeout)
-            try:
-                sys.stdout.write(json.dumps(out, default=str) + '\n')
-                sys.stdout.flush()
-            finally:
-                os._exit(0)
-        watchdog = threading.Timer(args.leg_timeout, _give_up)
-        watchdog.daemon = True
-        if world == 1 and args.leg_timeout > 0:
-            watchdog.start()
-        guarded(out, 'roofline', roofline_leg)
-        prof = prof_box.get('prof', [])
-        if isinstance(out.get('roofline'), dict) and 'error' not in out['roofline']:
-            # the contract's figure at top level (VERDICT r5 item 4 iii): whole-path ALGORITHMIC flop rate / the fp32 matrix peak
-            out['roofline']['contract_frac'] = out['roofline']['whole_path_frac']
-            out['roofline']['contract_frac_definition'] = (
-                'frames/s x %.1f algorithmic GFLOP per frame (SURVEY.md 8d: 2*MAC of the direct form) / %.1f TFLOP/s; above the '
-                'executed `frac` by the Winograd / polyphase MAC reduction, not by skipped work' % (GFLOP_PER_FRAME, PEAK_F32_MFMA_TFLOPS))
-        single = world == 1 and not use_dist
-        state = {'pool': pool, 'oracle': None}
+            def _give_up():
+                out['post_timeout'] = ('a measurement leg behind the timed region did not return within %d s; the line holds what '
+                                       'was finished until then' % args.leg_timeout)
+                try:
+                    sys.stdout.write(json.dumps(out, default=str) + '\n')
+                    sys.stdout.flush()
+                finally:
+                    os._exit(0)
+            watchdog = threading.Timer(args.leg_timeout, _give_up)
+            watchdog.daemon = True
+            if world == 1 and args.leg_timeout > 0:
+                watchdog.start()
+            guarded(out, 'roofline', roofline_leg)
+            prof = prof_box.get('prof', [])
+            if isinstance(out.get('roofline'), dict) and 'error' not in out['roofline']:
+                # the contract's figure at top level (VERDICT r5 item 4 iii): whole-path ALGORITHMIC flop rate / the fp32 matrix peak
+                out['roofline']['contract_frac'] = out['roofline']['whole_path_frac']
+                out['roofline']['contract_frac_definition'] = (
+                    'frames/s x %.1f algorithmic GFLOP per frame (SURVEY.md 8d: 2*MAC of the direct form) / %.1f TFLOP/s; above the '
+                    'executed `frac` by the Winograd / polyphase MAC reduction, not by skipped work' % (GFLOP_PER_FRAME, PEAK_F32_MFMA_TFLOPS))
+            single = world == 1 and not use_dist
+            state = {'pool': pool, 'oracle': None}
 
-        def close_pool():
-            # everything behind the headline runs single calls on `eng` with the library's lanes: the lane streams must be created
-            # AFTER the pool's streams are gone - lanes created while other streams are alive share hardware queues with them
-            # (8-10 ms per batch-1 call instead of 3.5; DESIGN.md section 2 "Parallel lanes")
-            if state['pool'] is not None:
-                state['pool'].close(keep_first=True)
-                state['pool'] = None
+            def close_pool():
+                # everything behind the headline runs single calls on `eng` with the library's lanes: the lane streams must be created
+                # AFTER the pool's streams are gone - lanes created while other streams are alive share hardware queues with them
+                # (8-10 ms per batch-1 call instead of 3.5; DESIGN.md section 2 "Parallel lanes")
+                if state['pool'] is not None:
+                    state['pool'].close(keep_first=True)
+                    state['pool'] = None
 
-        if world == 1 and not args.no_point_heads and args.precision == 'fp32':
-            def point_leg():
-                pl = state['pool']
-                setter = (lambda on: pl.configure(lambda e: e.set_point_heads(on))) if pl is not None else eng.set_point_heads
-                return point_heads_rate(setter, run_steps, B, args.steps, args.warmup)       # (switches the mode back itself)
-            guarded(out, 'point_heads', point_leg)
-        if single and pool is not None and not args.no_latency:
-            def single_leg():
-                # the same K batches on ONE context with the library's lanes (what `value` was before round 2's EnginePool)
-                eng.set_lanes(args.lanes)
-                for _ in range(args.warmup):
-                    eng.forward(frames, out=views)
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(args.steps):
-                    eng.forward(frames, out=views)
-                torch.cuda.synchronize()
-                dt1 = time.perf_counter() - t1
-                return {'value': round(B * args.steps / dt1, 2), 'unit': 'frames/s', 'ms_per_step': round(dt1 / args.steps * 1e3, 3),
-                        'note': 'one context, batches back to back on one stream (+ its parallel lanes)'}
-            guarded(out, 'single_context', single_leg)
-        if single:
-            guarded(out, 'pool_close', close_pool)
-        if world == 1 and not args.no_cpu_baseline:
-            def cpu_leg():
-                state['oracle'], res = cpu_baseline(sd, tables)
-                return res
-            guarded(out, 'cpu_baseline', cpu_leg)
-            if state['oracle'] is not None:
-                # the headline program (large-batch lowering) on the sample's 8 frames
-                guarded(out, 'parity', lambda: parity(eng, state['oracle']))
-        if single and not args.no_latency:
-            def latency_leg():
-                # single calls (the way the reference is driven, acr/main.py:126-141: one frame per call), on a context built
-                # for small batches as acr.model.ACR builds it (max_batch <= 8: the packer keeps F(2x2,3x3) for every 3x3
-                # layer).  Measured with every other context and stream of this process gone and BEFORE the later sections
-                # create theirs: lane streams that are created while other streams are alive share hardware queues with them
-                # (9.9 instead of 3.5 ms per batch-1 call with the throughput context still alive; 8 ms with torch's stream
-                # pool alive - DESIGN.md section 2).  The SAME context is re-programmed rather than a new one created: a
-                # context created this late gets lane streams that share hardware queues
-                eng.load_state_dict(sd, max_batch=8, precision=args.precision)
-                eng.set_lanes(0)
-                lat = latency(eng, frames, lambda b: parallel.alloc_result(b, eng.device)[1])
-                lat['context'] = 'max_batch 8 (small-batch lowering: F(2x2,3x3) only)'
-                lat['program_ops_per_call'] = sum(1 for o in eng.program['ops'] if o.mode != 2 and o.kind != 8)
-                lat['launches_note'] = 'one launch per op except attention pooling (3); + decode (1) + MANO (1 per side)'
-                return lat
-            guarded(out, 'latency', latency_leg)
-            guarded(out, 'engine_close', eng.close)
-        if single and not args.no_pmc and args.precision == 'fp32' and isinstance(out.get('roofline'), dict) and 'error' not in out['roofline']:
-            def pmc_leg():
-                # counters of THIS box, THIS run (the committed profiles/ figures stay as the fallback, labelled as such)
-                live = live_pmc(B)
-                if live is None:
-                    out['roofline']['traffic_source'] = 'committed: ' + str(out['roofline']['traffic_source'])
+            if world == 1 and not args.no_point_heads and args.precision == 'fp32':
+                def point_leg():
+                    pl = state['pool']
+                    setter = (lambda on: pl.configure(lambda e: e.set_point_heads(on))) if pl is not None else eng.set_point_heads
+                    return point_heads_rate(setter, run_steps, B, args.steps, args.warmup)       # (switches the mode back itself)
+                guarded(out, 'point_heads', point_leg)
+            if single and pool is not None and not args.no_latency:
+                def single_leg():
+                    # the same K batches on ONE context with the library's lanes (what `value` was before round 2's EnginePool)
+                    eng.set_lanes(args.lanes)
+                    for _ in range(args.warmup):
+                        eng.forward(frames, out=views)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(args.steps):
+                        eng.forward(frames, out=views)
+                    torch.cuda.synchronize()
+                    dt1 = time.perf_counter() - t1
+                    return {'value': round(B * args.steps / dt1, 2), 'unit': 'frames/s', 'ms_per_step': round(dt1 / args.steps * 1e3, 3),
+                            'note': 'one context, batches back to back on one stream (+ its parallel lanes)'}
+                guarded(out, 'single_context', single_leg)
+            if single:
+                guarded(out, 'pool_close', close_pool)
+            if world == 1 and not args.no_cpu_baseline:
+                def cpu_leg():
+                    state['oracle'], res = cpu_baseline(sd, tables)
+                    return res
+                guarded(out, 'cpu_baseline', cpu_leg)
+                if state['oracle'] is not None:
+                    # the headline program (large-batch lowering) on the sample's 8 frames
+                    guarded(out, 'parity', lambda: parity(eng, state['oracle']))
+            if single and not args.no_latency:
+                def latency_leg():
+                    # single calls (the way the reference is driven, acr/main.py:126-141: one frame per call), on a context built
+                    # for small batches as acr.model.ACR builds it (max_batch <= 8: the packer keeps F(2x2,3x3) for every 3x3
+                    # layer).  Measured with every other context and stream of this process gone and BEFORE the later sections
+                    # create theirs: lane streams that are created while other streams are alive share hardware queues with them
+                    # (9.9 instead of 3.5 ms per batch-1 call with the throughput context still alive; 8 ms with torch's stream
+                    # pool alive - DESIGN.md section 2).  The SAME context is re-programmed rather than a new one created: a
+                    # context created this late gets lane streams that share hardware queues
+                    eng.load_state_dict(sd, max_batch=8, precision=args.precision)
+                    eng.set_lanes(0)
+                    lat = latency(eng, frames, lambda b: parallel.alloc_result(b, eng.device)[1])
+                    lat['context'] = 'max_batch 8 (small-batch lowering: F(2x2,3x3) only)'
+                    lat['program_ops_per_call'] = sum(1 for o in eng.program['ops'] if o.mode != 2 and o.kind != 8)
+                    lat['launches_note'] = 'one launch per op except attention pooling (3); + decode (1) + MANO (1 per side)'
+                    return lat
+                guarded(out, 'latency', latency_leg)
+                guarded(out, 'engine_close', eng.close)
+            if single and not args.no_pmc and args.precision == 'fp32' and isinstance(out.get('roofline'), dict) and 'error' not in out['roofline']:
+                def pmc_leg():
+                    # counters of THIS box, THIS run (the committed profiles/ figures stay as the fallback, labelled as such)
+                    live = live_pmc(B)
+                    if live is None:
+                        out['roofline']['traffic_source'] = 'committed: ' + str(out['roofline']['traffic_source'])
+                        return None
+                    fam = {k: v for k, v in live['traffic'].items() if 'wino' in k}
+                    top = max(fam, key=lambda k: fam[k]['launches_profiled']) if fam else None      # the family's most-launched kernel
+                    t2 = fam[top]['hbm_bytes_per_launch'] if top else None
+                    out['roofline']['traffic_kernel'] = top
+                    out['roofline']['traffic'] = t2 or out['roofline']['traffic']
+                    out['roofline']['traffic_source'] = live['source'] if t2 else out['roofline']['traffic_source']
+                    # algorithmic bytes per launch of every conv family (packer: input slice + output + residual once, x frames),
+                    # so that wasted re-reads are a printed ratio, not an inference
+                    alg = {}
+                    for p in prof:
+                        if p['kind'] == L.OP_CONV and p.get('kernel'):
+                            a = alg.setdefault(p['kernel'], [0.0, 0])
+                            a[0] += p['bytes'] * B
+                            a[1] += 1
+                    for k, v in live['traffic'].items():
+                        if k in alg and alg[k][1]:
+                            v['algorithmic_bytes_per_launch'] = round(alg[k][0] / alg[k][1])
+                            v['launches_per_step'] = alg[k][1]
+                            v['traffic_over_algorithmic'] = round(v['hbm_bytes_per_launch'] / max(1.0, alg[k][0] / alg[k][1]), 3)
+                    out['roofline']['traffic_per_kernel'] = live['traffic']
+                    out['roofline']['traffic_per_kernel_note'] = (
+                        'algorithmic_bytes_per_launch / traffic_over_algorithmic attribute ops to kernel families as the packer predicts '
+                        'launch_conv routes them at batch 64 on 256 CUs (packer op_info kernel); at another --batch only the '
+                        'measured hbm_bytes_per_launch columns are exact' if B == 64 else
+                        'batch %d: the op -> kernel attribution behind algorithmic_bytes_per_launch assumes batch 64' % B)
+                    out['roofline']['mfma_busy_pmc'] = dict(live['mfma_busy'], source=live['source'])
                     return None
-                fam = {k: v for k, v in live['traffic'].items() if 'wino' in k}
-                top = max(fam, key=lambda k: fam[k]['launches_profiled']) if fam else None      # the family's most-launched kernel
-                t2 = fam[top]['hbm_bytes_per_launch'] if top else None
-                out['roofline']['traffic_kernel'] = top
-                out['roofline']['traffic'] = t2 or out['roofline']['traffic']
-                out['roofline']['traffic_source'] = live['source'] if t2 else out['roofline']['traffic_source']
-                # algorithmic bytes per launch of every conv family (packer: input slice + output + residual once, x frames),
-                # so that wasted re-reads are a printed ratio, not an inference
-                alg = {}
-                for p in prof:
-                    if p['kind'] == L.OP_CONV and p.get('kernel'):
-                        a = alg.setdefault(p['kernel'], [0.0, 0])
-                        a[0] += p['bytes'] * B
-                        a[1] += 1
-                for k, v in live['traffic'].items():
-                    if k in alg and alg[k][1]:
-                        v['algorithmic_bytes_per_launch'] = round(alg[k][0] / alg[k][1])
-                        v['launches_per_step'] = alg[k][1]
-                        v['traffic_over_algorithmic'] = round(v['hbm_bytes_per_launch'] / max(1.0, alg[k][0] / alg[k][1]), 3)
-                out['roofline']['traffic_per_kernel'] = live['traffic']
-                out['roofline']['traffic_per_kernel_note'] = (
-                    'algorithmic_bytes_per_launch / traffic_over_algorithmic attribute ops to kernel families as the packer predicts '
-                    'launch_conv routes them at batch 64 on 256 CUs (packer op_info kernel); at another --batch only the '
-                    'measured hbm_bytes_per_launch columns are exact' if B == 64 else
-                    'batch %d: the op -> kernel attribution behind algorithmic_bytes_per_launch assumes batch 64' % B)
-                out['roofline']['mfma_busy_pmc'] = dict(live['mfma_busy'], source=live['source'])
-                return None
-            guarded(out, 'pmc_leg', pmc_leg)
-        if single and not args.no_reduced_precision and args.precision == 'fp32':
-            guarded(out, 'reduced_precision', lambda: reduced_precision(sd, tables, frames, B, args.steps, args.warmup, state['oracle'], local_rank))
-            guarded(out, 'other_configs', lambda: other_configs(tables, args.steps, args.warmup, local_rank))
-            if not isinstance(out.get('other_configs'), dict):
-                out['other_configs'] = {}
-            # (a host that cannot pin 200 MB must not cost the headline line)
-            guarded(out['other_configs'], 'configs[3] 1080p stream, per-GPU shard (32 frames), host memory -> meshes',
-                    lambda: config3_video_stream(sd, tables, args.steps, args.warmup, local_rank))
-        pool = state['pool']
-        watchdog.cancel()
+                guarded(out, 'pmc_leg', pmc_leg)
+            if single and not args.no_reduced_precision and args.precision == 'fp32':
+                guarded(out, 'reduced_precision', lambda: reduced_precision(sd, tables, frames, B, args.steps, args.warmup, state['oracle'], local_rank))
+                guarded(out, 'other_configs', lambda: other_configs(tables, args.steps, args.warmup, local_rank))
+                if not isinstance(out.get('other_configs'), dict):
+                    out['other_configs'] = {}
+                # (a host that cannot pin 200 MB must not cost the headline line)
+                guarded(out['other_configs'], 'configs[3] 1080p stream, per-GPU shard (32 frames), host memory -> meshes',
+                        lambda: config3_video_stream(sd, tables, args.steps, args.warmup, local_rank))
+            pool = state['pool']
+            watchdog.cancel()
+        elif world == 1 and not use_dist:
+            # the contexts and their streams go before the interpreter does, as after the legs of --full
+            if pool is not None:
+                pool.close(keep_first=True)
+            eng.close()
         line = json.dumps(out)
     else:
         line = None

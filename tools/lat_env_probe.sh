@@ -1,4 +1,4 @@
-B="python bench.py --no-reduced-precision --no-pmc --steps 10"
+B="python bench.py --full --no-reduced-precision --no-pmc --steps 10"
 p() { tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['value'], d.get('latency',{}).get('batch1_ms'), d.get('latency',{}).get('batch8_ms'), d.get('latency',{}).get('batch1_lanes'))"; }
 $B 2>/dev/null | p "unset, full legs"
 $B --no-cpu-baseline 2>/dev/null | p "unset, no cpu baseline"
