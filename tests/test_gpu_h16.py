@@ -167,63 +167,18 @@ def test_every_op_of_the_16bit_program_is_correctly_rounded(precision, width, fr
     B = eng.backbone_heads(x.cuda())
     torch.cuda.synchronize()
     prog = eng.program
-    hipbufs = [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))]
-    it = oprog.Interp(prog, B)
-    it.bufs = [b.clone() for b in hipbufs]
-    checked, skipped, worst_frac = 0, 0, 0.0
-    ops = [(op, info) for op, info in zip(prog['ops'], prog['op_info']) if op.mode != oprog.MODE_POINT]
-
-    def in_place(op):
-        return op.kind == oprog.OP_POW11 or (op.kind == oprog.OP_CONV and op.res_buf == op.out_buf)
-
-    for n, (op, info) in enumerate(ops):
-        k = op.kind
-        out = op.out_buf
-        # A buffer that a LATER op updates in place (the cam exit before 1.1**x, the params x mix map before the cam / pare
-        # term is accumulated) no longer holds this op's result on the GPU: the interpreter's value is kept instead and
-        # flows into that in-place op, whose result is then compared - the chain is checked as one unit.
-        chained = any(in_place(o) and o.out_buf == out for o, _ in ops[n + 1:])
-        if k == oprog.OP_POW11:
-            it.pow11(op)
-        elif k == oprog.OP_CONV:
-            it.conv(op, info)
-        elif k == oprog.OP_STEM:
-            it.stem(op, info, x)
-        elif k == oprog.OP_FUSESUM:
-            it.fuse_sum(op)
-        elif k == oprog.OP_BILINEAR2X:
-            it.bilinear2x(op)
-        elif k == oprog.OP_MAXPOOL:
-            it.maxpool(op)
-        elif k == oprog.OP_COORDFILL:
-            it.coordfill(op)
-        elif k == oprog.OP_ATTPOOL:
-            it.attpool(op)
-        elif k == oprog.OP_PAREBIAS:
-            it.parebias(op)
-        else:
-            raise AssertionError('unexpected op kind %d' % k)
-        if chained:
-            skipped += 1
-            continue
-        want, got = it.bufs[out], hipbufs[out]
-        d = (want - got).abs()
-        if prog['bufs'][out][4] == 0:      # fp32 output: accumulation order only
-            tol = 2e-5 * max(1.0, float(want.abs().max()))
-            assert float(d.max()) <= tol, (info['name'], float(d.max()), tol)
-        else:
-            # one ulp of the storage type + the kernels' fp32 accumulation error (absolute: it exceeds the spacing of the
-            # storage type where large terms cancel to a tiny result)
-            u = ulp(want.double(), precision).float() + 2e-6 * max(1.0, float(want.abs().max()))
-            bad = d > u * 1.001
-            assert not bool(bad.any()), (info['name'], float(d.max()), float((d / u).max()))
-            frac = float((d > 0).float().mean())
-            worst_frac = max(worst_frac, frac)
-            assert frac < 0.02, (info['name'], frac)
-        it.bufs[out] = hipbufs[out].clone()      # later ops see the GPU's values
-        checked += 1
+    # every dense op on the GPU's own inputs (oracle.program.check_program): a 16-bit output within ONE ulp of the storage
+    # type plus the fp32 accumulation error (absolute: it exceeds the spacing of the storage type where large terms cancel
+    # to a tiny result), fewer than 2 % of its elements not bit-equal; an fp32 output within 2e-5 x max(1, max |want|)
+    # and its per-element bound.  A buffer that a LATER op updates in place (the cam exit before 1.1**x, the params x mix
+    # map before the cam / pare term is accumulated) no longer holds this op's result on the GPU: the interpreter's value
+    # is kept instead and flows into that in-place op, whose result is then compared - the chain is checked as one unit.
+    res = oprog.check_program(prog, [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))], x)
+    assert not res['failures'], res['failures'][:10]
+    checked, skipped, worst_frac = res['checked'], res['chained'], res['worst_frac_16bit']
     _report('per_op_%s_w%s' % (precision, width), {'ops_checked': checked, 'ops_checked_through_their_in_place_successor': skipped,
-                                                    'worst_fraction_of_elements_off_by_one_ulp': worst_frac})
+                                                    'worst_fraction_of_elements_off_by_one_ulp': worst_frac,
+                                                    'worst_ratio_by_class': oprog.worst_by_class(res['rows'])})
     assert checked >= (320 if width != 'resnet50' else 75) and skipped <= 8
     eng.close()
 

@@ -34,6 +34,23 @@ def _flip_left(tables):
     return t
 
 
+def _per_op_rows(eng, x, rows_only=True):
+    """Runs the dense program on frames x and checks every op on the GPU's own inputs (oracle.program.check_program:
+    per-element bounds, every output of every op, unwritten channels still 0.0); returns the check's rows, one per
+    compared output, with the keys the per-layer reports use."""
+    prog = eng.program
+    B = eng.backbone_heads(x.cuda())
+    torch.cuda.synchronize()
+    res = oprog.check_program(prog, [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))], x)
+    assert not res['failures'], res['failures'][:10]
+    rows = res['rows']
+    if rows_only:
+        rows = [{'op': r['op'], 'algo': r['algo'], 'rel_err': r['rel_err'], 'out_absmax': r['scale'], 'in_absmax': r['in_absmax'],
+                 'worst_ratio': r['ratio'], 'class': r['class']}
+                for r in rows if r['kind'] == oprog.OP_CONV and r['out'] == 'out']
+    return rows
+
+
 @pytest.mark.parametrize('name', list(cases.INTERIOR_CASES))
 def test_interior_centers_through_the_network(name, mano_tables):
     """Centers >= 9 px from every border (planted center bias, tests/golden/cases.py INTERIOR_CASES) through the WHOLE
@@ -99,31 +116,8 @@ def test_hostile_checkpoint_against_the_reference_and_per_layer_winograd_error(m
         worst_v = max(worst_v, float(np.abs(out['verts'][b].cpu().numpy() - g['f%d_verts' % b]).max()),
                       float(np.abs(out['joints'][b].cpu().numpy() - g['f%d_j3d' % b]).max()))
     assert worst_v < 1e-4, worst_v
-    # ---- per-layer error on the GPU's own inputs
-    prog = eng.program
-    B = 1
-    eng.backbone_heads(x[:1].cuda())
-    torch.cuda.synchronize()
-    hip = [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))]
-    it = oprog.Interp(prog, B)
-    it.bufs = [b.clone() for b in hip]
-    rows = []
-    for i, (op, info) in enumerate(zip(prog['ops'], prog['op_info'])):
-        if op.mode == oprog.MODE_POINT or op.kind != oprog.OP_CONV or op.res_buf == op.out_buf:
-            continue
-        later_in_place = any(o.kind == oprog.OP_CONV and o.res_buf == o.out_buf and o.out_buf == op.out_buf
-                             for o in prog['ops'][i + 1:]) or any(o.kind == oprog.OP_POW11 and o.out_buf == op.out_buf
-                                                                   for o in prog['ops'][i + 1:])
-        if later_in_place:
-            continue
-        it.conv(op, info)
-        n = op.groups * op.cout
-        want = it.bufs[op.out_buf][..., op.out_coff:op.out_coff + n]
-        got = hip[op.out_buf][..., op.out_coff:op.out_coff + n]
-        scale = float(want.abs().max())
-        rows.append({'op': info['name'], 'algo': info.get('algo'), 'rel_err': float((want - got).abs().max()) / max(scale, 1e-20),
-                     'out_absmax': scale, 'in_absmax': float(hip[op.in_buf][..., op.in_coff:op.in_coff + op.groups * op.cin].abs().max())})
-        it.bufs[op.out_buf] = hip[op.out_buf].clone()
+    # ---- per-layer error on the GPU's own inputs (every op: oracle.program.check_program)
+    rows = _per_op_rows(eng, x[:1])
     wino = [r for r in rows if r['algo'] and r['algo'].startswith('winograd')]
     direct = [r for r in rows if r['algo'] == 'direct']
     wino.sort(key=lambda r: -r['rel_err'])
@@ -164,30 +158,7 @@ def test_split_operand_program_on_the_hostile_checkpoint(mano_tables, frames2, p
         worst_v = max(worst_v, float(np.abs(out['verts'][b].cpu().numpy() - g['f%d_verts' % b]).max()),
                       float(np.abs(out['joints'][b].cpu().numpy() - g['f%d_j3d' % b]).max()))
     assert worst_v < tol_v, worst_v      # (fp16x3 measured 3.7e-7 m; the fp32 program: 2.9e-7 m)
-    prog = eng.program
-    B = 1
-    eng.backbone_heads(x[:1].cuda())
-    torch.cuda.synchronize()
-    hip = [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))]
-    it = oprog.Interp(prog, B)
-    it.bufs = [b.clone() for b in hip]
-    rows = []
-    for i, (op, info) in enumerate(zip(prog['ops'], prog['op_info'])):
-        if op.mode == oprog.MODE_POINT or op.kind != oprog.OP_CONV or op.res_buf == op.out_buf or not str(info.get('algo')).startswith('split_'):
-            continue
-        later_in_place = any(o.kind == oprog.OP_CONV and o.res_buf == o.out_buf and o.out_buf == op.out_buf
-                             for o in prog['ops'][i + 1:]) or any(o.kind == oprog.OP_POW11 and o.out_buf == op.out_buf
-                                                                   for o in prog['ops'][i + 1:])
-        if later_in_place:
-            continue
-        it.conv(op, info)
-        n = op.groups * op.cout
-        want = it.bufs[op.out_buf][..., op.out_coff:op.out_coff + n]
-        got = hip[op.out_buf][..., op.out_coff:op.out_coff + n]
-        scale = float(want.abs().max())
-        rows.append({'op': info['name'], 'rel_err': float((want - got).abs().max()) / max(scale, 1e-20), 'out_absmax': scale,
-                     'in_absmax': float(hip[op.in_buf][..., op.in_coff:op.in_coff + op.groups * op.cin].abs().max())})
-        it.bufs[op.out_buf] = hip[op.out_buf].clone()
+    rows = [r for r in _per_op_rows(eng, x[:1]) if str(r['algo']).startswith('split_')]
     rows.sort(key=lambda r: -r['rel_err'])
     rep = {'end_to_end_max_vertex_joint_abs_err_m': worst_v, 'split_operand_layers': len(rows),
            'worst_rel_err': rows[0]['rel_err'], 'max_activation': max(r['in_absmax'] for r in rows), 'worst_layers': rows[:5]}
@@ -240,20 +211,13 @@ def test_layer1_pair_kernel_matches_its_two_convolutions(law, frames2):
     pairs = [(i, o) for i, o in enumerate(prog['ops']) if o.kind == L.OP_PAIR1X1]
     assert len(pairs) == 3
     x = torch.from_numpy(np.concatenate([frames2, frames2[:1]]))
-    B = eng.backbone_heads(x.cuda())
-    torch.cuda.synchronize()
-    hip = [eng.buffer(i, B).float().cpu() for i in range(len(prog['bufs']))]
-    it = oprog.Interp(prog, B)
-    it.bufs = [b.clone() for b in hip]
     rep = {}
-    for i, op in pairs:
-        it.pair1x1(op, prog['op_info'][i])
-        for name, buf, n in (('out', op.out_buf, 256), ('aux', op.aux_buf, 64)):
-            want, got = it.bufs[buf][..., :n], hip[buf][..., :n]
-            err, scale = float((want - got).abs().max()), float(want.abs().max())
-            rep['%s.%s' % (prog['op_info'][i]['name'], name)] = [err, scale]
-            assert err <= 2e-6 * max(1.0, scale), (prog['op_info'][i]['name'], name, err, scale)
-        it.bufs[op.out_buf], it.bufs[op.aux_buf] = hip[op.out_buf].clone(), hip[op.aux_buf].clone()
+    rows = [r for r in _per_op_rows(eng, x, rows_only=False) if r['kind'] == L.OP_PAIR1X1]
+    assert len(rows) == 6
+    for r in rows:
+        err, scale = r['err'], r['scale']
+        rep['%s.%s' % (r['op'], r['out'])] = [err, scale]
+        assert err <= 2e-6 * max(1.0, scale), (r['op'], r['out'], err, scale)
     _report('pair1x1_' + law, rep)
     eng.close()
 

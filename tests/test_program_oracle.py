@@ -228,3 +228,118 @@ def test_layer1_pairs_are_lowered_only_where_they_pay(synth_sd):
         m, h = lane % 32, lane // 32
         assert a2[c, nt, g, lane, e] == np.float32(w1[32 * nt + m, 32 * c + 8 * g + 4 * h + e])
     assert np.array_equal(img[32768:32768 + 256], b3.astype(np.float32)) and np.array_equal(img[-64:], b1.astype(np.float32))
+
+
+# the programs tests/test_gpu_program_ops.py checks per op: (width, precision, context max_batch)
+PER_OP_PROGRAMS = [(32, 'fp32', 64), (32, 'fp32', 8), (32, 'fp16x3', 64), (32, 'bf16x3', 64), (48, 'fp16x3', 64),
+                   ('resnet50', 'bf16x3', 32)]
+
+
+@pytest.mark.parametrize('width,precision,max_batch', PER_OP_PROGRAMS)
+def test_keep_all_lowering_is_the_production_lowering(width, precision, max_batch):
+    """The per-op GPU check runs the keep_all=True / keep_weights=True lowering (no buffer reuse, folded filters kept):
+    it speaks for the benchmarked program only if that lowering IS the production one (Engine.load_state_dict: F(2x4,3x3)
+    and no split-K from max_batch 16 on) in every Op field but the buffer ids, with the same geometry and storage type
+    behind every buffer an op references, and the same packed weights."""
+    packer = pkg('packer')
+    sd = pkg('synth').make_state_dict(seed=0, width=width)
+    small = max_batch < 16
+    kw = dict(precision=precision, wino24=False if small else None, splitk=small)
+    prod = packer.lower(sd, **kw)
+    kept = packer.lower(sd, keep_weights=True, keep_all=True, **kw)
+    assert np.array_equal(prod['blob'], kept['blob'])
+    assert len(prod['ops']) == len(kept['ops'])
+    ids = ('in_buf', 'out_buf', 'res_buf', 'aux_buf')
+    for n, (a, b, ia, ib) in enumerate(zip(prod['ops'], kept['ops'], prod['op_info'], kept['op_info'])):
+        assert ia['name'] == ib['name'] and ia.get('algo') == ib.get('algo') and ia.get('kernel') == ib.get('kernel'), n
+        for f, _t in a._fields_:
+            if f in ids or f == 'term_buf':
+                continue
+            va, vb = getattr(a, f), getattr(b, f)
+            if hasattr(va, '__len__'):
+                va, vb = list(va), list(vb)
+            assert va == vb, (n, ia['name'], f, va, vb)
+        pairs = [(getattr(a, f), getattr(b, f)) for f in ids] + list(zip(a.term_buf[:a.nterms], b.term_buf[:b.nterms]))
+        for x, y in pairs:
+            assert (x < 0) == (y < 0), (n, ia['name'])
+            if x >= 0:
+                pa, pb = prod['bufs'][x], kept['bufs'][y]
+                assert pa[:3] == pb[:3] and pa[4] == pb[4], (n, ia['name'], pa, pb)
+    hp, hk = prod['heads'], kept['heads']
+    for f, _t in hp._fields_:
+        for x, y in zip(*[list(v) if hasattr(v, '__len__') else [v] for v in (getattr(hp, f), getattr(hk, f))]):
+            assert prod['bufs'][x][:3] == kept['bufs'][y][:3] and prod['bufs'][x][4] == kept['bufs'][y][4], f
+
+
+def test_per_op_checker_flags_exactly_the_planted_fault(synth_sd, frame):
+    """oracle.program.check_program on the interpreter's own buffers of one fp32 frame (the large-batch lowering) passes
+    with every ratio 0; then one fault per run - planted behind its op, so that every later op reads it as it would read
+    a kernel's wrong result - and the checker must name exactly that op or buffer:
+      * 2^-12 relative at one element of a border tile of a direct conv's output, where |y| < 2 % of the layer's largest
+        output and |y| >= M / 8 (M: the per-element magnitude) - which the layer-relative bound alone does not see;
+      * a non-zero channel that no op writes;
+      * a wrong value in the second output (aux_buf) of a CONV_DUAL conv."""
+    torch.set_num_threads(8)
+    packer = pkg('packer')
+    prog = packer.lower(synth_sd, keep_weights=True, keep_all=True)
+    clean = oprog.Interp(prog, 1).run(frame)
+    res = oprog.check_program(prog, clean.bufs, frame)
+    assert res['failures'] == [] and res['checked'] >= 312 and res['zero_checked_buffers'] >= 1
+    assert all(r['ratio'] == 0.0 for r in res['rows'])
+    ops = list(zip(prog['ops'], prog['op_info']))
+
+    def planted(at, fn):
+        return oprog.check_program(prog, oprog.Interp(prog, 1).run(frame, after=lambda n, op, info, it: fn(it) if n == at else None).bufs,
+                                   frame)['failures']
+
+    # (1) a small element of a border tile of a direct convolution
+    target = None
+    for n, (op, info) in enumerate(ops):
+        if op.mode == oprog.MODE_POINT or op.kind != oprog.OP_CONV or info['algo'] != 'direct' or op.res_buf == op.out_buf \
+                or op.nterms or any(o.kind == oprog.OP_POW11 and o.out_buf == op.out_buf for o in prog['ops']):
+            continue
+        n_out = op.groups * op.cout
+        y = clean.bufs[op.out_buf][0, ..., op.out_coff:op.out_coff + n_out].double()
+        if y.shape[0] < 8:
+            continue
+        m = oprog._pool7(oprog.conv_magnitude(clean, op, info)[0])[0]
+        border = torch.zeros(y.shape[:2], dtype=torch.bool)
+        border[0, :], border[-1, :], border[:, 0], border[:, -1] = True, True, True, True
+        ok = border[..., None] & (y.abs() < 0.02 * y.abs().max()) & (y.abs() >= m / 8) & (y != 0)
+        if bool(ok.any()):
+            yy, xx, c = [int(v) for v in torch.nonzero(ok)[0]]
+            target = (n, op, info, yy, xx, c, float(y[yy, xx, c]), float(m[yy, xx, c]), float(y.abs().max()))
+            break
+    assert target is not None
+    n, op, info, yy, xx, c, val, mag, scale = target
+    assert abs(val) < 0.02 * scale and abs(val) >= mag / 8                    # the conditions the plant is meant to meet
+
+    def bump(it):
+        it.bufs[op.out_buf][0, yy, xx, op.out_coff + c] *= 1.0 + 2.0 ** -12
+    fails = planted(n, bump)
+    assert [(f.get('op'), f.get('out')) for f in fails] == [(info['name'], 'out')], fails
+    assert fails[0]['rules'] == ['element'], fails        # the layer-relative bound alone misses it
+    assert fails[0]['where'] == [0, yy, xx, op.out_coff + c]
+
+    # (2) a non-zero value in a channel no op writes
+    cover = {}
+    for o in prog['ops']:
+        if o.kind in oprog.FRAME_LOCAL:
+            for b, reg in oprog.written(o):
+                if reg[0] == 'ch':
+                    cover.setdefault(b, set()).update(range(reg[1], reg[2]))
+    b, ch = next((b, max(range(prog['bufs'][b][2]))) for b in sorted(cover)
+                 if (prog['bufs'][b][2] - 1) not in cover[b] and prog['bufs'][b][:2] != (1, 1))
+    bufs = [t.clone() if i == b else t for i, t in enumerate(clean.bufs)]
+    bufs[b][0, 1, 2, ch] = 1.0
+    fails = oprog.check_program(prog, bufs, frame)['failures']
+    assert [(f.get('buf'), f['rules']) for f in fails] == [(b, ['zero'])] and fails[0]['where'] == [0, 1, 2, ch], fails
+
+    # (3) the second output of a CONV_DUAL conv
+    n, (op, info) = next((n, oi) for n, oi in enumerate(ops) if oi[0].kind == oprog.OP_CONV and oi[0].flags & oprog.CONV_DUAL)
+
+    def wrong(it):
+        t = it.bufs[op.aux_buf]
+        t[0, 3, 5, 7] = t[0, 3, 5, 7] * 1.01 + 0.01
+    fails = planted(n, wrong)
+    assert [(f.get('op'), f.get('out')) for f in fails] == [(info['name'], 'aux')], fails
