@@ -56,7 +56,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_comm_unique_id', 'acrmi_comm_init', 'acrmi_comm_destroy', 'acrmi_allgather', 'acrmi_parebias',
            'acrmi_buffer_dtype', 'acrmi_conv2d_h16', 'acrmi_conv2d_splitk', 'acrmi_conv2d_splitk_workspace',
            'acrmi_decode_gated', 'acrmi_decode_maps_gated', 'acrmi_share_weights', 'acrmi_mano_rotmat', 'acrmi_heads',
-           'acrmi_backbone_channels', 'acrmi_check_range', 'acrmi_prior_gate', 'acrmi_preprocess_frames']
+           'acrmi_backbone_channels', 'acrmi_check_range', 'acrmi_prior_gate', 'acrmi_preprocess_frames',
+           'acrmi_mesh_topology', 'acrmi_render_workspace', 'acrmi_rasterize', 'acrmi_load_faces', 'acrmi_render']
 
 _lib = None
 
@@ -144,9 +145,17 @@ def lib():
     L.acrmi_comm_destroy.argtypes = [vp]
     L.acrmi_allgather.argtypes = [vp, vp, f32p, f32p, C.c_size_t, vp]
     L.acrmi_parebias.argtypes = [f32p, i32, i32, f32p, f32p, f32p, f32p, f32p, i32, f32p, i32, vp]
+    L.acrmi_mesh_topology.argtypes = [vp, i32, i32, vp, i32]
+    L.acrmi_render_workspace.argtypes = [i32, i32]
+    L.acrmi_render_workspace.restype = C.c_size_t
+    L.acrmi_rasterize.argtypes = [f32p, f32p, i32, i32, i32, vp, vp, vp, vp, f32p, f32p, C.c_float, C.c_float, u8p, u8p, i32,
+                                  i32, i32, vp, vp, vp]
+    L.acrmi_load_faces.argtypes = [vp, i32, vp, i32]
+    L.acrmi_render.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, C.c_float, C.c_float, u8p, u8p, i32, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats'):
+        if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
+                        'acrmi_render_workspace'):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -4,8 +4,13 @@
     results = acr(bgr_frame, path)           # {path: [per-hand dict of float16 arrays]}  or  {path: {}}
     results = acr.forward_batch(frames, paths)   # the batched form the reference never had
 
-Rendering / video IO (acr/visualization.py, acr/renderer/*) are out of scope: results are returned,
-nothing is drawn.
+Drawing (acr/visualization.py:100-218 with show_items=['mesh'], acr/renderer/*): with `renderer='hip'` the hand meshes
+are rasterised over the frames on the GPU (csrc/render.hip; conventions in DESIGN.md "Rendering") -
+    results = acr(bgr_frame, path); frame = acr.rendering['mesh_rendering_orgimgs'][0]      # uint8 [H,W,3] BGR, numpy
+    results, frames = acr.forward_raw_batch(bgr_frames, paths, render=True)                # device tensors, original sizes
+    results, frames = acr.forward_batch(rgb512, paths, render=rgb512)                      # the network input
+'none' and the reference's 'pyrender' / 'pytorch3d' draw nothing; the results never depend on the renderer.  Key-point /
+heat-map views and video or image files stay out of scope.
 """
 import logging
 
@@ -30,6 +35,7 @@ class ACR(object):
         logging.basicConfig(level=logging.INFO)
         self._args = a
         self._device = device
+        self.rendering = None      # renderer='hip': {'mesh_rendering_orgimgs': [frame]} of the last forward()
         self._build_model_(state_dict, mano_tables, device, max_batch)
         if self.temporal_optimization:
             # acr/main.py:45-47: one filter set per hand type; the state lives in the engine's context
@@ -90,12 +96,33 @@ class ACR(object):
         else:
             print('no hand detected!')
             results = {path: {}}
+        if self.renderer == 'hip':
+            self.rendering = {'mesh_rendering_orgimgs': [self._render_single(bgr_frame, outputs)]}
         return results
+
+    def _render_single(self, bgr_frame, outputs):
+        """The reference's 'mesh_rendering_orgimgs' (acr/visualization.py:196-218): the original frame with the detected
+        hands drawn over it - uint8 [H,W,3] BGR numpy.  No detection: a copy of the frame."""
+        from .. import ops
+        frame = np.ascontiguousarray(np.asarray(bgr_frame, np.uint8))
+        if outputs is None or outputs.get('verts') is None or not len(outputs['verts']):
+            return frame.copy()
+        dev = outputs['verts'].device
+        side = outputs['output_hand_type'].to(torch.int32)
+        ml = self.mano_regression.mano_layer
+        cols = torch.tensor([list(reversed(c)) for c in ops.HAND_COLORS_RGB])[side.long().cpu()]      # BGR
+        n = len(side)
+        img = ops.render_meshes(outputs['verts'], (ml['l'].th_faces, ml['r'].th_faces), torch.from_numpy(frame)[None].to(dev),
+                                mesh_frame=torch.zeros(n, dtype=torch.int32), trans=outputs['cam_trans'], colors=cols,
+                                view=ops.view_from_offsets(outputs['meta_data']['offsets'][:1]),
+                                focal_length=float(self.focal_length), topo_index=side)
+        return img[0].cpu().numpy()
 
     __call__ = forward
 
     @torch.no_grad()
-    def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None):
+    def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
+                      render_bgr=False):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -103,10 +130,15 @@ class ACR(object):
         dense heads as `forward` does.
         batch_semantics: 'frame' | 'reference' (None = the model's ResultParser setting, args().batch_semantics): with
         'reference' the fused call applies the reference's batch-wide prior rules (acr/result_parser.py:42-47,102-145) on
-        the device - decode, acrmi_prior_gate, gated decode - still ONE call (ACRMI_OPT_BATCH_PRIOR)."""
+        the device - decode, acrmi_prior_gate, gated decode - still ONE call (ACRMI_OPT_BATCH_PRIOR).
+        render: frames to draw the meshes over (Engine.render) - uint8 device tensor [B,H,W,3], or a list of B frames
+        [H_i,W_i,3] of different sizes (one render call per size, output order = input order): the network input itself
+        when `offsets` is None, else the original frames the offsets rows describe; render_bgr: their channel order.
+        The return value is then (results, rendered); `results` is what it is without `render`."""
         eng = self.model.engine(rgb_u8_frames.shape[0])
         semantics = batch_semantics or self.model._result_parser.batch_semantics
         B = rgb_u8_frames.shape[0]
+        render_offsets = offsets
         if offsets is None:
             offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
         eng.set_point_heads(point_heads)
@@ -144,16 +176,39 @@ class ACR(object):
                                   'pj2d_org': host['pj2d_org'][b, h].astype(np.float16),
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
             results[path] = hands if hands else {}
-        return results
+        if render is None:
+            return results
+        return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
+
+    def _render_batch(self, eng, out, frames, offsets, bgr):
+        kw = dict(focal_length=float(self.focal_length), bgr=bgr)
+        if not isinstance(frames, (list, tuple)):
+            return eng.render(out, frames, offsets=offsets, **kw)
+        if len(frames) != out['slots'].shape[0]:
+            raise ValueError('one frame to draw into per input frame')
+        groups = {}
+        for i, f in enumerate(frames):
+            groups.setdefault(tuple(f.shape), []).append(i)
+        rendered = [None] * len(frames)
+        for idx in groups.values():
+            sel = torch.tensor(idx, device=out['slots'].device)
+            sub = {k: out[k].index_select(0, sel) for k in ('slots', 'verts', 'cam_trans')}
+            got = eng.render(sub, torch.stack([frames[i] for i in idx]),
+                             offsets=None if offsets is None else torch.as_tensor(offsets)[idx], **kw)
+            for j, i in enumerate(idx):
+                rendered[i] = got[j]
+        return rendered
 
 
-def _forward_raw_batch(self, bgr_frames_dev, paths):
+def _forward_raw_batch(self, bgr_frames_dev, paths, render=False):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
-    then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels."""
+    then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
+    render=True: -> (results, frames with the hand meshes drawn over them: a tensor like the input, or a list in input order)."""
     from .utils import img_preprocess_gpu
     meta = img_preprocess_gpu(bgr_frames_dev, paths)
-    return self.forward_batch(meta['image'], paths, offsets=meta['offsets'])
+    return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=bgr_frames_dev if render else None,
+                              render_bgr=True)
 
 
 ACR.forward_raw_batch = _forward_raw_batch

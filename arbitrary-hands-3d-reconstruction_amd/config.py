@@ -17,11 +17,15 @@ DEFAULTS = dict(
     prior_mode='cross', dataset='internet', centermap_conf_thresh=0.35, max_hand=2, kernel_sizes=[5], align_idx=9,
     mano_mesh_root_align=True, perspective_proj=False, focal_length=1265, temporal_optimization=False,
     smooth_coeff=4.0, save_dict_results=False, save_visualization_on_img=False, val_batch_size=1, GPUS=0,
+    # renderer: 'hip' = the meshes are drawn over the frames on the GPU (csrc/render.hip); 'none' / 'pyrender' / 'pytorch3d'
+    # draw nothing.  render_size is read from reference YAMLs and ignored: drawing happens at the frame's own resolution
     renderer='none', render_size=512,
     # not a reference flag: 'frame' = every frame as a batch of one (default); 'reference' = the reference's batch-wide
     # prior rules when a batch > 1 is parsed (acr/result_parser.py:42-47,131; result_parser.reference_prior_gate)
     batch_semantics='frame',
 )
+
+RENDERERS = ('hip', 'none', 'pyrender', 'pytorch3d')
 
 _ARGS = argparse.Namespace(**copy.deepcopy(DEFAULTS))
 
@@ -88,6 +92,11 @@ def validate(ns):
         raise ValueError('align_idx must be a joint index 0..20')
     if getattr(ns, 'batch_semantics', 'frame') not in ('frame', 'reference'):
         raise ValueError("batch_semantics %r: 'frame' or 'reference'" % (ns.batch_semantics,))
+    if getattr(ns, 'renderer', 'none') not in RENDERERS:
+        # 'hip' draws the meshes over the frames on the GPU (csrc/render.hip); 'none' and the reference's two back ends
+        # (acr/config.py: --renderer pyrender | pytorch3d, which a reference YAML may carry) draw nothing
+        raise ValueError("renderer %r: 'hip' (draw on the GPU), 'none', or the reference's 'pyrender' / 'pytorch3d' (nothing "
+                         "is drawn)" % (ns.renderer,))
     if ns.model_precision not in ('fp32', 'fp16', 'bf16', 'fp16x3', 'bf16x3'):
         # acr/config.py:96: fp32 (configs/demo.yml) | fp16 (the argparse default: autocast, acr/model.py:33-37);
         # bf16 = the same 16-bit program on the other gfx950 MFMA type (packer.lower); fp16x3 / bf16x3 = fp32 tensors with

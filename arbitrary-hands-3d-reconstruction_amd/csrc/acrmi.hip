@@ -62,6 +62,9 @@ void acrmi_destroy(acrmi_ctx* c) {
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   release_weights(c);
   if (c->smooth_state) (void)hipFree(c->smooth_state);
+  if (c->render_ws) (void)hipFree(c->render_ws);
+  for (int32_t* p : c->faces_topo)
+    if (p) (void)hipFree(p);
   for (auto& side : c->mano_allocs)
     for (float* p : side)
       if (p) (void)hipFree(p);
@@ -496,6 +499,71 @@ int acrmi_forward(acrmi_ctx* c, const uint8_t* img, int B, const float* offsets,
   return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
 }
 
+// ---- mesh overlay (csrc/render.hip) --------------------------------------------------------------------------------
+int acrmi_load_faces(acrmi_ctx* c, int side, const int32_t* faces_host, int n_faces) {
+  if (!c || side < 0 || side > 1 || !faces_host || n_faces <= 0) return fail(c, ACRMI_EINVAL, "acrmi_load_faces: bad arguments");
+  if (c->faces_topo[1 - side] && c->n_faces[1 - side] != n_faces)
+    return fail(c, ACRMI_EINVAL, "acrmi_load_faces: %d faces, the other side has %d (one face count for both hands)", n_faces,
+                c->n_faces[1 - side]);
+  std::vector<int32_t> blob((size_t)mesh_topology_ints(n_faces, 778));
+  if (!build_mesh_topology(faces_host, n_faces, 778, blob.data()))
+    return fail(c, ACRMI_EINVAL, "acrmi_load_faces: a face names a vertex outside [0, 778)");
+  ON_DEVICE(c);
+  HIPCHK(c, hipDeviceSynchronize());      // a reload: nothing of an earlier launch may still read the old table
+  if (c->faces_topo[side]) (void)hipFree(c->faces_topo[side]);
+  c->faces_topo[side] = nullptr;
+  c->n_faces[side] = 0;
+  int32_t* d = nullptr;
+  HIPCHK(c, hipMalloc(&d, blob.size() * sizeof(int32_t)));
+  const hipError_t e = hipMemcpy(d, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return fail(c, ACRMI_EHIP, "acrmi_load_faces: hipMemcpy: %s", hipGetErrorString(e));
+  }
+  c->faces_topo[side] = d;
+  c->n_faces[side] = n_faces;
+  return ACRMI_OK;
+}
+
+int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
+                 const float* colors_host, float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out, int H,
+                 int W, int32_t* ids_out, void* stream) {
+  if (!c || !verts || !cam_trans || !slots || !img_in || !img_out || B <= 0 || H <= 0 || W <= 0 || !(focal > 0.f) ||
+      !(visible_weight >= 0.f && visible_weight <= 1.f))
+    return fail(c, ACRMI_EINVAL, "acrmi_render: bad arguments");
+  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "acrmi_render: MANO faces not loaded (acrmi_load_faces)");
+  ON_DEVICE(c);
+  const int M = 2 * B, F = c->n_faces[0];
+  const size_t head = (size_t)M * 4 * 2 + (size_t)M * 3 * 4 + (size_t)B * 4 * 4;      // mesh_frame, mesh_topo, rgb, view
+  const size_t head_al = (head + 255) / 256 * 256;
+  if (B > c->render_ws_frames) {      // (first call / a larger batch: the one place this call allocates)
+    if (c->render_ws) {
+      HIPCHK(c, hipDeviceSynchronize());
+      (void)hipFree(c->render_ws);
+      c->render_ws = nullptr;
+      c->render_ws_frames = 0;
+    }
+    HIPCHK(c, hipMalloc(&c->render_ws, head_al + render_workspace_bytes(M, F)));
+    c->render_ws_frames = B;
+  }
+  int32_t* mesh_frame = (int32_t*)c->render_ws;
+  int32_t* mesh_topo = mesh_frame + M;
+  float* rgb = (float*)(mesh_topo + M);
+  float* view = rgb + 3 * M;
+  // the reference's colours by hand type (acr/visualization.py:76), as RGB
+  static const float kDefault[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};
+  hipError_t e = launch_render_prep(slots, offsets, B, ACRMI_SLOT, ACRMI_SLOT_FLAG, colors_host ? colors_host : kDefault,
+                                    mesh_frame, mesh_topo, rgb, view, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render prep: %s", hipGetErrorString(e));
+  RenderArgs a{};
+  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
+  a.mesh_topo = mesh_topo; a.mesh_frame = mesh_frame; a.rgb = rgb; a.view = offsets ? view : nullptr;
+  a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
+  a.ws = c->render_ws + head_al;
+  a.n_meshes = M; a.n_verts = 778; a.n_faces = F; a.n_frames = B; a.H = H; a.W = W;
+  e = launch_render(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render: %s", hipGetErrorString(e));
+}
 
 // Plain HIP streams for hosts that have no stream API of their own at hand (Python: torch.cuda.Stream() instantiates
 // torch's whole pool of 32 streams per priority, and with that many streams alive the few in use share hardware

@@ -82,6 +82,12 @@ struct acrmi_ctx {
   bool temporal = false;
   float smooth_coeff = 4.0f;
   float* smooth_state = nullptr;   // [2][3][64] floats + 2 ints (One-Euro state of one video stream)
+  // mesh overlay (acrmi_load_faces / acrmi_render): one topology blob per side on the device, and the scratch of a call
+  // (per-mesh frame / topology index / colour, per-frame viewport, the rasteriser's workspace), grown on demand
+  int32_t* faces_topo[2] = {nullptr, nullptr};
+  int n_faces[2] = {0, 0};
+  char* render_ws = nullptr;
+  int render_ws_frames = 0;
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;
   int comm_ranks = 0;

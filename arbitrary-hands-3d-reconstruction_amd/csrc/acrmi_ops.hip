@@ -269,4 +269,39 @@ int acrmi_cam_trans(const float* joints_dev, const float* pj2d_dev, int n, float
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "cam_trans: %s", hipGetErrorString(e));
 }
 
+// ---- mesh overlay (csrc/render.hip) ----
+int acrmi_mesh_topology(const int32_t* faces_host, int n_faces, int n_verts, int32_t* blob_host, int n_ints) {
+  if (n_faces <= 0 || n_verts <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_topology: bad arguments");
+  const long long need = mesh_topology_ints(n_faces, n_verts);
+  if (need > 0x7fffffffll) return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_topology: mesh too large");
+  if (!blob_host) return (int)need;      // size query
+  if (!faces_host || n_ints < need) return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_topology: bad arguments (%lld ints needed)", need);
+  if (!build_mesh_topology(faces_host, n_faces, n_verts, blob_host))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_topology: a face names a vertex outside [0, %d)", n_verts);
+  return (int)need;
+}
+
+size_t acrmi_render_workspace(int n_meshes, int n_faces) {
+  return n_meshes > 0 && n_faces > 0 ? render_workspace_bytes(n_meshes, n_faces) : 0;
+}
+
+int acrmi_rasterize(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                    const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                    const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
+                    float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                    int32_t* ids_out_dev, void* ws_dev, void* stream) {
+  if (!verts_dev || !topo_dev || !mesh_frame_dev || !rgb_dev || !img_in_dev || !img_out_dev || !ws_dev || n_meshes <= 0 ||
+      n_verts <= 0 || n_verts > RENDER_MAX_VERTS || n_faces <= 0 || n_frames <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384 ||
+      (long long)n_meshes * n_faces > 0x7fffffffll || n_frames > 65535 || !(focal > 0.f) ||
+      !(visible_weight >= 0.f && visible_weight <= 1.f))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_rasterize: bad arguments");
+  RenderArgs a{};
+  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
+  a.mesh_frame = mesh_frame_dev; a.rgb = rgb_dev; a.view = view_dev; a.focal = focal; a.visible_weight = visible_weight;
+  a.img_in = img_in_dev; a.img_out = img_out_dev; a.ids_out = ids_out_dev; a.ws = (char*)ws_dev;
+  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_frames = n_frames; a.H = H; a.W = W;
+  hipError_t e = launch_render(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "rasterize: %s", hipGetErrorString(e));
+}
+
 }  // extern "C"

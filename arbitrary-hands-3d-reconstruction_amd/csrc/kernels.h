@@ -263,4 +263,29 @@ struct ManoArgs {
 hipError_t launch_mano(const ManoArgs& a, hipStream_t s);
 hipError_t launch_cam_trans(const float* joints, const float* pj2d, int n, float focal, float img, float* out, hipStream_t s);
 
+// Mesh overlay (csrc/render.hip; DESIGN.md "Rendering"): M meshes of one vertex / face count drawn into N equal-sized frames.
+struct RenderArgs {
+  const float* verts;            // [M, n_verts, 3]
+  const float* trans;            // [M, 3] or null
+  const int32_t* topo[2];        // mesh topology blobs (build_mesh_topology) on the device; [1] may be null
+  const int32_t* mesh_topo;      // [M] 0 / 1 = which blob, or null (all 0)
+  const int32_t* mesh_frame;     // [M] frame the mesh is drawn into, < 0 = not drawn
+  const float* rgb;              // [M, 3] base colour, channel order of the image
+  const float* view;             // [N, 4] scale x, scale y, shift x, shift y of the 512 canvas, or null (identity)
+  float focal, visible_weight;
+  const uint8_t* img_in;         // [N, H, W, 3]
+  uint8_t* img_out;              // may be img_in
+  int32_t* ids_out;              // [N, H, W] or null
+  char* ws;                      // render_workspace_bytes(M, n_faces)
+  size_t ws_box_off, ws_rec_off; // (launch_render fills these)
+  int n_meshes, n_verts, n_faces, n_frames, H, W;
+};
+constexpr int RENDER_MAX_VERTS = 4000;      // 16 bytes of LDS per vertex in the setup kernel
+long long mesh_topology_ints(int n_faces, int n_verts);
+bool build_mesh_topology(const int32_t* faces, int n_faces, int n_verts, int32_t* blob);
+size_t render_workspace_bytes(int n_meshes, int n_faces);
+hipError_t launch_render(const RenderArgs& a, hipStream_t s);
+hipError_t launch_render_prep(const float* slots, const float* offsets, int B, int slot_stride, int flag_at, const float* colors,
+                              int32_t* mesh_frame, int32_t* mesh_topo, float* rgb, float* view, hipStream_t s);
+
 }  // namespace acrmi

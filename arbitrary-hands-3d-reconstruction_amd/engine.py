@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib, packer
+from .ops import HAND_COLORS_RGB
 
 
 def _ptr(t):
@@ -47,6 +48,8 @@ class Engine(object):
         self.smooth_coeff = None          # None = the library default (4.0)
         self.comm_ranks = 0
         self._mano_tables = {}
+        self.have_faces = False
+        self._faces = {}
 
     def close(self):
         # (the handle is dropped first and without touching module globals: during interpreter shutdown `C` may already
@@ -306,6 +309,21 @@ class Engine(object):
         self._mano_tables[name] = {k: a for k, a in zip(('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights',
                                                           'hands_mean'), arrs)}
         self.have_mano = len(self._mano_tables) == 2
+        if t.get('faces') is not None:      # tables without faces load as before; `render` then raises the ACRMI_ESTATE error
+            self.load_faces(name, t['faces'])
+
+    def load_faces(self, name, faces):
+        """One side's triangles (mano/manolayer.py:68 `faces`, [F,3] over the 778 vertices) for `render` (acrmi_load_faces)."""
+        side = {'left': 0, 'right': 1}[name]
+        f = faces.detach().cpu().numpy() if hasattr(faces, 'detach') else np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError('faces must be [F,3]')
+        f = np.ascontiguousarray(f.astype(np.int32))
+        _lib.check(self.L.acrmi_load_faces(self.ctx, side, f.ctypes.data_as(C.c_void_p), f.shape[0]), self.ctx)
+        if name in self._mano_tables:
+            self._mano_tables[name]['faces'] = f
+        self._faces[name] = f
+        self.have_faces = len(self._faces) == 2
 
     # ---- hot path ------------------------------------------------------------------------------
     def _check_img(self, img):
@@ -455,6 +473,56 @@ class Engine(object):
                                         _stream(dev) if stream is None else C.c_void_p(stream)), self.ctx)
         return out
 
+    def render(self, out, images, offsets=None, cam_trans=None, focal_length=1265., visible_weight=0.9, colors=None,
+               bgr=False, dst=None, return_ids=False, stream=None):
+        """The hands of `out` (what `forward(..., project=True)` returned: slots, verts, joints, pj2d) drawn over `images`
+        (acrmi_render; the reference's Visualizer 'mesh' view, acr/visualization.py:100-218, conventions in DESIGN.md
+        "Rendering").  images uint8 [B,H,W,3] on the device: the 512 x 512 network input when offsets is None, else the
+        original frames the `offsets` rows [B,10] describe (the mesh lands on pj2d / pj2d_org).  A hand is drawn when its
+        slot's flag is set.  cam_trans [B,2,3]: computed from out['joints'] / out['pj2d'] (acrmi_cam_trans) when None.
+        colors [2,3] left / right in the images' channel order (default: the reference's, RGB or - bgr=True - BGR).
+        dst: uint8 tensor like images to draw into (may be `images` itself: in place).  Returns the frames, or (frames,
+        ids int32 [B,H,W] = (2 * frame + hand) * F + face, -1 where no hand is) with return_ids.  stream: as `forward`."""
+        dev = self.device
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError('images must be uint8 [B,H,W,3] on the device')
+        B, H, W, _ = images.shape
+        if tuple(out['verts'].shape) != (B, 2, 778, 3) or tuple(out['slots'].shape) != (B, 2, _lib.SLOT):
+            raise ValueError('out does not hold the results of %d frames' % B)
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        if cam_trans is None:
+            if out.get('cam_trans') is not None:
+                cam_trans = out['cam_trans']
+            else:
+                if out.get('pj2d') is None:
+                    raise ValueError('cam_trans is needed (or out from forward(..., project=True))')
+                cam_trans = torch.empty(B, 2, 3, dtype=torch.float32, device=dev)
+                _lib.check(self.L.acrmi_cam_trans(_ptr(out['joints']), _ptr(out['pj2d']), 2 * B, float(focal_length), 512.0,
+                                                  _ptr(cam_trans), st))
+        cam_trans = cam_trans.to(dev, torch.float32).contiguous()
+        if offsets is not None:
+            offsets = offsets.to(dev, torch.float32).contiguous()
+            if tuple(offsets.shape) != (B, 10):
+                raise ValueError('offsets must be [B,10]')
+        col = None
+        if colors is not None or bgr:
+            c = np.asarray(colors if colors is not None else [list(reversed(x)) for x in HAND_COLORS_RGB], np.float32)
+            if c.shape != (2, 3):
+                raise ValueError('colors must be [2,3] (left, right)')
+            col = np.ascontiguousarray(c)
+        src = images.contiguous()
+        if dst is None:
+            dst = torch.empty_like(src)
+        elif dst.dtype != torch.uint8 or tuple(dst.shape) != (B, H, W, 3) or not dst.is_contiguous() or dst.device != src.device:
+            raise ValueError('dst must be a contiguous uint8 tensor shaped like images, on their device')
+        ids = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_ids else None
+        verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
+        _lib.check(self.L.acrmi_render(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, _ptr(offsets),
+                                       None if col is None else col.ctypes.data_as(C.c_void_p), float(focal_length),
+                                       float(visible_weight), _ptr(src), _ptr(dst), H, W, _ptr(ids), st), self.ctx)
+        self._render_keep = (verts, slots, cam_trans, offsets, src)      # referenced until the next call has been queued
+        return (dst, ids) if return_ids else dst
+
     def profile_ops(self, img):
         img = self._check_img(img)
         B = img.shape[0]
@@ -584,6 +652,27 @@ class EnginePool(object):
         ticket = {'slot': i, 'event': done, 'out': res, 'img': img, 'offsets': offsets}
         self._busy[i] = ticket
         return ticket
+
+    def render(self, ticket, images, offsets=None, **kw):
+        """Engine.render of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True) and collect().  `images` (and offsets) as the caller's current stream left them.  collect() then
+        also orders the caller's stream behind the drawing.  Returns what Engine.render returns."""
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('render() belongs between submit() and collect() of its ticket')
+        images = images.contiguous()
+        if offsets is not None:
+            offsets = offsets.to(self.device, torch.float32).contiguous()
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        self.streams[i].wait_event(ready)
+        res = self.engines[i].render(ticket['out'], images, offsets=offsets, stream=self._raw[i].value, **kw)
+        done = torch.cuda.Event()
+        done.record(self.streams[i])
+        # as in submit: everything the drawing touches stays referenced by the ticket until its event has completed
+        ticket['event'] = done
+        ticket['render'] = (res, images, offsets, self.engines[i]._render_keep)
+        return res
 
     def _reap(self):
         self._inflight = [t for t in self._inflight if not t['event'].query()]

@@ -148,7 +148,8 @@ class ManoLayer(object):
     def tables(self):
         return {'v_template': self.th_v_template[0].numpy(), 'shapedirs': self.th_shapedirs.numpy(),
                 'posedirs': self.th_posedirs.numpy(), 'J_regressor': self.th_J_regressor.numpy(),
-                'weights': self.th_weights.numpy(), 'hands_mean': self.th_hands_mean[0].numpy()}
+                'weights': self.th_weights.numpy(), 'hands_mean': self.th_hands_mean[0].numpy(),
+                'faces': self.th_faces.numpy()}
 
     def forward(self, th_pose_coeffs, th_betas=torch.zeros(1), th_trans=torch.zeros(1), root_palm=torch.Tensor([0]),
                 share_betas=torch.Tensor([0])):

@@ -314,3 +314,101 @@ def prior_gate(slots):
     gate = torch.empty(slots.shape[0], dtype=torch.int32, device=slots.device)
     _lib.check(_lib.lib().acrmi_prior_gate(None, _p(slots), slots.shape[0], _p(gate), _s(slots)))
     return gate
+
+
+# ---- mesh overlay (csrc/render.hip; DESIGN.md "Rendering") -------------------------------------------------------------
+HAND_COLORS_RGB = ((0.46, 0.59, 0.64), (0.94, 0.71, 0.53))      # left, right (reference acr/visualization.py:76)
+
+
+def mesh_topology(faces, n_verts):
+    """faces [F,3] (numpy / torch integers) of a mesh with n_verts vertices -> the int32 blob acrmi_rasterize reads
+    ([F, V | faces | CSR row | CSR col]: faces + the vertex -> faces table, acrmi_mesh_topology).  Pure host: works
+    without a GPU.  Upload it once (`torch.from_numpy(blob).cuda()`) and hand it to render_meshes for every call."""
+    f = faces.detach().cpu().numpy() if hasattr(faces, 'detach') else np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('faces must be [F,3]')
+    f = np.ascontiguousarray(f.astype(np.int32))
+    L = _lib.lib()
+    n = _lib.check(L.acrmi_mesh_topology(None, f.shape[0], int(n_verts), None, 0))
+    blob = np.empty(n, np.int32)
+    _lib.check(L.acrmi_mesh_topology(f.ctypes.data_as(C.c_void_p), f.shape[0], int(n_verts), blob.ctypes.data_as(C.c_void_p), n))
+    return blob
+
+
+def view_from_offsets(offsets):
+    """`offsets` rows [N,10] (ops.preprocess / acr.utils.img_preprocess) -> the viewport rows [N,4] render_meshes takes:
+    the 512 canvas mapped into the original frame exactly like pj2d -> pj2d_org (x_org = x_512 * padded_w / 512 + left)."""
+    o = torch.as_tensor(offsets, dtype=torch.float32)
+    return torch.stack([o[:, 0] / 512., o[:, 1] / 512., o[:, 5] - o[:, 9], o[:, 2] - o[:, 6]], 1)
+
+
+def _topology_on(t, n_verts, device):
+    if isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int32:
+        blob = t
+    elif isinstance(t, np.ndarray) and t.ndim == 1 and t.dtype == np.int32:
+        blob = torch.from_numpy(t)
+    else:
+        blob = torch.from_numpy(mesh_topology(t, n_verts))
+    return blob.to(device).contiguous()
+
+
+def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None, view=None, focal_length=1265.,
+                  visible_weight=0.9, out=None, return_ids=False, topo_index=None):
+    """Draws M meshes over N equal-sized frames on the GPU (acrmi_rasterize; the reference's Visualizer 'mesh' view,
+    acr/visualization.py:100-218, with the conventions of DESIGN.md "Rendering").
+    verts [M,V,3] device fp32 (metres, camera axes); trans [M,3] added to them (cam_trans) or None.
+    faces: [F,3] integers, or a mesh_topology blob (host or device int32) - or a pair of either for meshes of two
+    topologies with the same V and F (left / right MANO), chosen per mesh by topo_index [M] (0 / 1).
+    images uint8 [N,H,W,3] device; mesh_frame [M] = the frame each mesh is drawn into, -1 = not drawn (default: mesh m
+    into frame m when M == N, into frame m // (M / N) when N divides M).  colors [M,3] or [3] in the images' channel
+    order (default: the reference's right-hand colour as RGB).  view [N,4] = scale x, scale y, shift x, shift y of the 512
+    canvas (view_from_offsets) or None = the 512 network input.  out: uint8 tensor like images (may BE images: in place).
+    Returns out, or (out, ids int32 [N,H,W]: mesh * F + face of the visible triangle, -1 = none) with return_ids."""
+    _need_cuda(verts, images, out)
+    if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
+        raise ValueError('verts must be [M,V,3]')
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or images.shape[0] < 1:
+        raise ValueError('images must be uint8 [N,H,W,3]')
+    dev = images.device
+    M, V, _ = verts.shape
+    N, H, W, _ = images.shape
+    pair = isinstance(faces, (tuple, list)) and len(faces) == 2 and not np.isscalar(faces[0]) and np.ndim(faces[0]) >= 1
+    topos = [_topology_on(t, V, dev) for t in (faces if pair else [faces])]
+    head = [t[:2].tolist() for t in topos]      # (one small D2H copy per topology; [F, V])
+    F = head[0][0]
+    if any(h != [F, V] for h in head):
+        raise ValueError('topology is for (faces, verts) = %s, verts have %d vertices' % (head, V))
+    v = verts.to(dev, torch.float32).contiguous()
+    t = None if trans is None else trans.to(dev, torch.float32).contiguous().view(M, 3)
+    if mesh_frame is None:
+        if M % N:
+            raise ValueError('mesh_frame is needed when the frames do not divide the meshes')
+        mesh_frame = torch.arange(M, dtype=torch.int32) // (M // N)
+    mf = torch.as_tensor(mesh_frame).to(dev, torch.int32).contiguous()
+    if mf.numel() != M:
+        raise ValueError('mesh_frame must hold one int per mesh')
+    ti = None
+    if topo_index is not None:
+        ti = torch.as_tensor(topo_index).to(dev, torch.int32).contiguous()
+        if ti.numel() != M or not pair:
+            raise ValueError('topo_index needs a pair of topologies and one int per mesh')
+    c = torch.as_tensor(HAND_COLORS_RGB[1] if colors is None else colors, dtype=torch.float32)
+    c = (c.view(1, 3).repeat(M, 1) if c.numel() == 3 else c.reshape(M, 3)).to(dev).contiguous()
+    vw = None
+    if view is not None:
+        vw = torch.as_tensor(view, dtype=torch.float32).to(dev).contiguous()
+        if tuple(vw.shape) != (N, 4):
+            raise ValueError('view must be [N,4]')
+    src = images.contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous uint8 tensor shaped like images, on their device')
+    ids = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_ids else None
+    L = _lib.lib()
+    ws = torch.empty(int(L.acrmi_render_workspace(M, F)) + 256, dtype=torch.uint8, device=dev)
+    ws_p = (ws.data_ptr() + 255) // 256 * 256
+    _lib.check(L.acrmi_rasterize(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(mf), _p(c),
+                                 _p(vw), float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids),
+                                 C.c_void_p(ws_p), _s(src)))
+    return (out, ids) if return_ids else out

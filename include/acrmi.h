@@ -390,6 +390,50 @@ int acrmi_set_option_f(acrmi_ctx* ctx, int option, float value);
 int acrmi_smooth(acrmi_ctx* ctx, float* slots_dev, int B, void* stream);
 int acrmi_smooth_reset(acrmi_ctx* ctx, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Mesh overlay: acr/visualization.py:100-218 (Visualizer.visulize_result_live, show_items=['mesh'], settings ['put_org'])
+ * + acr/renderer/renderer_pyrd.py / renderer_pt3d.py - the frame with the hand meshes drawn over it.  Nothing of those
+ * renderers is used; the conventions are (DESIGN.md "Rendering"): camera-space point P = v + trans, +Z away from the
+ * camera; on the 512 canvas x = 256 + focal X / Z, y = 256 + focal Y / Z; the frame's viewport x' = x * view[0] + view[2],
+ * y' = y * view[1] + view[3] (the pj2d -> pj2d_org map of acrmi_mano); positions snapped to 1/256 pixel, exact integer
+ * coverage with the top-left rule, pixel centres at +0.5; 1/Z depth test, the lower global face id wins a tie; smooth
+ * shading 0.3 + 0.7 |n_z| interpolated perspective-correctly; covered pixel = floor(w 255 rgb shade + (1 - w) img), every
+ * other pixel = img.  Triangles of zero area, with a vertex at Z <= 0.05 or with a snapped coordinate beyond +-2^22 are
+ * dropped whole.  No atomics: results are deterministic.
+ * ------------------------------------------------------------------------------------- */
+/* Pure host (works without a GPU): faces [n_faces,3] of a mesh with n_verts vertices -> one int32 blob
+ * [n_faces, n_verts | faces 3F | row V+1 | col 3F], (row, col) = the vertex -> faces table in CSR form, one entry per corner,
+ * by face and then by corner: the order in which acrmi_rasterize sums a vertex's face normals.  Returns the number of ints
+ * of the blob (also when blob_host == NULL: size query); n_ints = capacity of blob_host. */
+int acrmi_mesh_topology(const int32_t* faces_host, int n_faces, int n_verts, int32_t* blob_host, int n_ints);
+/* Bytes of device workspace acrmi_rasterize needs for n_meshes meshes of n_faces faces (0 for non-positive sizes). */
+size_t acrmi_render_workspace(int n_meshes, int n_faces);
+/* verts_dev [n_meshes,n_verts,3] fp32, trans_dev [n_meshes,3] or NULL; topo_dev = an acrmi_mesh_topology blob on the device,
+ * topo2_dev (may be NULL) a second one with the SAME vertex and face counts (left / right MANO), mesh_topo_dev [n_meshes]
+ * int32 0 / 1 = which of the two (NULL: all the first); mesh_frame_dev [n_meshes] int32 = the frame a mesh is drawn into,
+ * < 0 = not drawn; rgb_dev [n_meshes,3] base colour in the image's channel order; view_dev [n_frames,4] (scale x, scale y,
+ * shift x, shift y) or NULL = identity; img_in_dev / img_out_dev uint8 [n_frames,H,W,3] (may be the same buffer: drawn in
+ * place); ids_out_dev int32 [n_frames,H,W] or NULL: mesh * n_faces + face of the visible triangle, -1 where none;
+ * ws_dev: acrmi_render_workspace() bytes, 256-byte aligned, not shared by launches that may overlap.  All meshes of a frame
+ * go through ONE depth-tested pass.  n_verts <= 4000. */
+int acrmi_rasterize(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                    const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                    const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
+                    float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                    int32_t* ids_out_dev, void* ws_dev, void* stream);
+/* mano/manolayer.py:68,115 (th_faces) for side 0 = left, 1 = right: faces_host int32 [n_faces,3] over the 778 MANO vertices
+ * (both sides the same face count). */
+int acrmi_load_faces(acrmi_ctx* ctx, int side, const int32_t* faces_host, int n_faces);
+/* The outputs of acrmi_forward in, frames out: verts_dev [B,2,778,3], cam_trans_dev [B,2,3] (acrmi_cam_trans), slots_dev
+ * [B,2,ACRMI_SLOT] (a hand is drawn when its ACRMI_SLOT_FLAG > 0.5; hand type = slot index), offsets_dev [B,10] or NULL
+ * (NULL: the 512 x 512 network input, identity viewport; else the frames the `offsets` rows describe), colors_host [2][3]
+ * left / right in the image's channel order (NULL: the reference's, as RGB), img_in / img_out uint8 [B,H,W,3] on the device
+ * (may alias), ids_out int32 [B,H,W] or NULL ((2 b + hand) * n_faces + face).  The context's scratch is allocated at the
+ * first call (and when B grows); otherwise asynchronous on `stream`.  ACRMI_ESTATE before both sides' faces are loaded. */
+int acrmi_render(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int B,
+                 const float* offsets_dev, const float* colors_host, float focal, float visible_weight,
+                 const uint8_t* img_in_dev, uint8_t* img_out_dev, int H, int W, int32_t* ids_out_dev, void* stream);
+
 /* Multi-GPU (replaces nn.DataParallel's scatter/gather, acr/main.py:61): frames are sharded by the caller, one
  * process per GPU; the only collective is ONE all-gather per batch of each rank's flat result buffer
  * [slots | verts | joints] over RCCL/xGMI.  recv_dev holds n_ranks * n_floats floats, rank-major.
