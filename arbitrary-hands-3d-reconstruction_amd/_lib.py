@@ -20,6 +20,7 @@ DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 SLOT = 176
 SLOT_FLAG, SLOT_FLATIND, SLOT_SCORE, SLOT_CAM, SLOT_POSES, SLOT_BETAS, SLOT_PARAMS = 0, 1, 2, 3, 6, 54, 64
 E_INVAL, E_HIP, E_STATE, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5
+OVERLAY_SKELETON, OVERLAY_CENTERMAP = 0, 1      # acrmi_overlay `what`
 
 
 class BufferDesc(C.Structure):
@@ -57,7 +58,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_buffer_dtype', 'acrmi_conv2d_h16', 'acrmi_conv2d_splitk', 'acrmi_conv2d_splitk_workspace',
            'acrmi_decode_gated', 'acrmi_decode_maps_gated', 'acrmi_share_weights', 'acrmi_mano_rotmat', 'acrmi_heads',
            'acrmi_backbone_channels', 'acrmi_check_range', 'acrmi_prior_gate', 'acrmi_preprocess_frames',
-           'acrmi_mesh_topology', 'acrmi_render_workspace', 'acrmi_rasterize', 'acrmi_load_faces', 'acrmi_render']
+           'acrmi_mesh_topology', 'acrmi_render_workspace', 'acrmi_rasterize', 'acrmi_load_faces', 'acrmi_render',
+           'acrmi_overlay_tables', 'acrmi_draw_skeletons', 'acrmi_draw_heatmaps', 'acrmi_overlay']
 
 _lib = None
 
@@ -152,6 +154,11 @@ def lib():
                                   i32, i32, vp, vp, vp]
     L.acrmi_load_faces.argtypes = [vp, i32, vp, i32]
     L.acrmi_render.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, C.c_float, C.c_float, u8p, u8p, i32, i32, vp, vp]
+    L.acrmi_overlay_tables.argtypes = [i32, u8p, u8p]
+    L.acrmi_draw_skeletons.argtypes = [f32p, vp, i32, u8p, i32, i32, i32, u8p, u8p, i32, i32, i32, vp]
+    L.acrmi_draw_heatmaps.argtypes = [f32p, f32p, C.c_longlong, i32, i32, i32, f32p, C.c_float, u8p, i32, u8p, u8p, u8p, i32,
+                                      i32, vp]
+    L.acrmi_overlay.argtypes = [vp, i32, f32p, f32p, i32, f32p, i32, u8p, u8p, u8p, i32, i32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',

@@ -9,8 +9,16 @@ are rasterised over the frames on the GPU (csrc/render.hip; conventions in DESIG
     results = acr(bgr_frame, path); frame = acr.rendering['mesh_rendering_orgimgs'][0]      # uint8 [H,W,3] BGR, numpy
     results, frames = acr.forward_raw_batch(bgr_frames, paths, render=True)                # device tensors, original sizes
     results, frames = acr.forward_batch(rgb512, paths, render=rgb512)                      # the network input
-'none' and the reference's 'pyrender' / 'pytorch3d' draw nothing; the results never depend on the renderer.  Key-point /
-heat-map views and video or image files stay out of scope.
+'none' and the reference's 'pyrender' / 'pytorch3d' draw nothing; the results never depend on the renderer.
+
+The other views of Visualizer.visulize_result_live (acr/visualization.py:228-254) are drawn on the GPU as well
+(csrc/overlay.hip; rules in DESIGN.md "Key-point and heat-map views"): list them in `show_items` -
+    acr.show_items = ['mesh', 'pj2d', 'centermap']         # default ['mesh']; also 'org_img'
+    results = acr(bgr_frame, path); acr.rendering['pj2d'][0]; left, right = acr.rendering['centermap'][0]
+    results, views = acr.forward_raw_batch(bgr_frames, paths, render=True, show_items=('mesh', 'pj2d', 'centermap'))
+    views['pj2d'], views['centermap']                      # frames like the input; the centre view as [2 (left, right), ...]
+'pj2d' = the 21 projected key points of each hand as a coloured skeleton, 'centermap' = the left and right centre heat
+maps in false colour over the frame.  The 'j3d' plot and video or image files stay out of scope.
 """
 import logging
 
@@ -22,6 +30,20 @@ from .mano_wrapper import MANOWrapper
 from .model import ACR as ACR_v1
 from .utils import (create_OneEuroFilter, get_remove_keys, img_preprocess, justify_detection_state, load_model,
                     reorganize_results, save_results, smooth_results)
+
+
+SHOW_ITEMS = ('mesh', 'pj2d', 'centermap', 'org_img')      # the views of acr/visualization.py:174-254 that are built
+
+
+def check_show_items(show_items):
+    """None stays None; else the list of view names, ValueError for one that is not in SHOW_ITEMS."""
+    if show_items is None:
+        return None
+    items = [show_items] if isinstance(show_items, str) else list(show_items)
+    for name in items:
+        if name not in SHOW_ITEMS:
+            raise ValueError('show_items: %r is not one of %s' % (name, SHOW_ITEMS))
+    return items
 
 
 class ACR(object):
@@ -36,6 +58,7 @@ class ACR(object):
         self._args = a
         self._device = device
         self.rendering = None      # renderer='hip': {'mesh_rendering_orgimgs': [frame]} of the last forward()
+        self.show_items = ['mesh']      # the views `forward` leaves on `rendering` (SHOW_ITEMS); the reference's default
         self._build_model_(state_dict, mano_tables, device, max_batch)
         if self.temporal_optimization:
             # acr/main.py:45-47: one filter set per hand type; the state lives in the engine's context
@@ -97,8 +120,38 @@ class ACR(object):
             print('no hand detected!')
             results = {path: {}}
         if self.renderer == 'hip':
-            self.rendering = {'mesh_rendering_orgimgs': [self._render_single(bgr_frame, outputs)]}
+            self.rendering = self._views_single(bgr_frame, outputs, check_show_items(self.show_items))
         return results
+
+    def _views_single(self, bgr_frame, outputs, items):
+        """`rendering` of one forward(): 'mesh' -> 'mesh_rendering_orgimgs' (the reference's key), 'pj2d' -> [frame],
+        'centermap' -> [(left, right)], 'org_img' -> [frame]; uint8 [H,W,3] BGR numpy, original size."""
+        from .. import ops
+        views = {}
+        frame = np.ascontiguousarray(np.asarray(bgr_frame, np.uint8))
+        for name in items:
+            if name == 'mesh':
+                views['mesh_rendering_orgimgs'] = [self._render_single(bgr_frame, outputs)]
+            elif name == 'org_img':
+                views['org_img'] = [frame.copy()]
+            elif name == 'pj2d':
+                kps = None if outputs is None else outputs.get('pj2d_org')
+                if kps is None or not len(kps):
+                    views['pj2d'] = [frame.copy()]
+                    continue
+                img = torch.from_numpy(frame)[None].to(kps.device)
+                drawn = ops.draw_skeletons(kps.float().contiguous(), img, hand_frame=torch.zeros(len(kps), dtype=torch.int32),
+                                           bgr=True)
+                views['pj2d'] = [drawn[0].cpu().numpy()]
+            elif name == 'centermap':
+                if outputs is None or outputs.get('l_center_map') is None:
+                    views['centermap'] = [(frame.copy(), frame.copy())]
+                    continue
+                maps = torch.cat([outputs['l_center_map'][:1], outputs['r_center_map'][:1]], 1)      # [1,2,h,w]
+                img = torch.from_numpy(frame)[None].to(maps.device)
+                both = ops.draw_heatmaps(maps, img, view=ops.view_from_offsets(outputs['meta_data']['offsets'][:1]), bgr=True)
+                views['centermap'] = [(both[0, 0].cpu().numpy(), both[1, 0].cpu().numpy())]
+        return views
 
     def _render_single(self, bgr_frame, outputs):
         """The reference's 'mesh_rendering_orgimgs' (acr/visualization.py:196-218): the original frame with the detected
@@ -122,7 +175,7 @@ class ACR(object):
 
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
-                      render_bgr=False):
+                      render_bgr=False, show_items=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -134,7 +187,13 @@ class ACR(object):
         render: frames to draw the meshes over (Engine.render) - uint8 device tensor [B,H,W,3], or a list of B frames
         [H_i,W_i,3] of different sizes (one render call per size, output order = input order): the network input itself
         when `offsets` is None, else the original frames the offsets rows describe; render_bgr: their channel order.
-        The return value is then (results, rendered); `results` is what it is without `render`."""
+        The return value is then (results, rendered); `results` is what it is without `render`.
+        show_items: names from SHOW_ITEMS - the views to draw over `render` instead of the meshes alone; the return value is
+        then (results, {name: frames}): 'mesh' as above, 'pj2d' the key-point skeletons, 'centermap' the left and right centre
+        heat maps as [2,B,H,W,3] (a list of [2,H_i,W_i,3] for a list of frames), 'org_img' the frames themselves."""
+        show_items = check_show_items(show_items)
+        if show_items is not None and render is None:
+            raise ValueError('show_items needs the frames to draw over (render=)')
         eng = self.model.engine(rgb_u8_frames.shape[0])
         semantics = batch_semantics or self.model._result_parser.batch_semantics
         B = rgb_u8_frames.shape[0]
@@ -178,7 +237,17 @@ class ACR(object):
             results[path] = hands if hands else {}
         if render is None:
             return results
-        return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
+        if show_items is None:
+            return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
+        views = {}
+        for name in show_items:
+            if name == 'mesh':
+                views[name] = self._render_batch(eng, out, render, render_offsets, render_bgr)
+            elif name == 'org_img':
+                views[name] = render
+            else:
+                views[name] = self._overlay_batch(eng, out, render, name, render_offsets, render_bgr)
+        return results, views
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
         kw = dict(focal_length=float(self.focal_length), bgr=bgr)
@@ -199,16 +268,47 @@ class ACR(object):
                 rendered[i] = got[j]
         return rendered
 
+    def _overlay_batch(self, eng, out, frames, what, offsets, bgr):
+        """'pj2d' / 'centermap' over a tensor of frames (Engine.overlay) or a list of frames of different sizes (one call
+        per size, output order = input order)."""
+        from .. import ops
+        if not isinstance(frames, (list, tuple)):
+            return eng.overlay(out, frames, what, offsets=offsets, bgr=bgr)
+        B = out['slots'].shape[0]
+        if len(frames) != B:
+            raise ValueError('one frame to draw into per input frame')
+        groups = {}
+        for i, f in enumerate(frames):
+            groups.setdefault(tuple(f.shape), []).append(i)
+        drawn = [None] * len(frames)
+        maps = eng.center_maps(B) if what == 'centermap' else None
+        for idx in groups.values():
+            sel = torch.tensor(idx, device=out['slots'].device)
+            imgs = torch.stack([frames[i] for i in idx])
+            off = None if offsets is None else torch.as_tensor(offsets)[idx]
+            if what == 'pj2d':
+                sub = {k: out[k].index_select(0, sel) for k in ('slots', 'pj2d', 'pj2d_org') if out.get(k) is not None}
+                got = eng.overlay(sub, imgs, what, offsets=off, bgr=bgr)
+            else:      # the context's maps are those of the whole batch: a subset goes through the stand-alone operator
+                got = ops.draw_heatmaps(maps.index_select(0, sel), imgs, view=None if off is None else ops.view_from_offsets(off),
+                                        bgr=bgr).transpose(0, 1)
+            for j, i in enumerate(idx):
+                drawn[i] = got[j]
+        return drawn
 
-def _forward_raw_batch(self, bgr_frames_dev, paths, render=False):
+
+def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
-    render=True: -> (results, frames with the hand meshes drawn over them: a tensor like the input, or a list in input order)."""
+    render=True: -> (results, frames with the hand meshes drawn over them: a tensor like the input, or a list in input order);
+    with show_items (names from SHOW_ITEMS) -> (results, {name: frames}) as forward_batch."""
     from .utils import img_preprocess_gpu
     meta = img_preprocess_gpu(bgr_frames_dev, paths)
+    if show_items is not None and not render:
+        raise ValueError('show_items needs render=True')
     return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=bgr_frames_dev if render else None,
-                              render_bgr=True)
+                              render_bgr=True, show_items=show_items)
 
 
 ACR.forward_raw_batch = _forward_raw_batch

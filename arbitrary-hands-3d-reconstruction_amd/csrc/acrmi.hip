@@ -565,6 +565,42 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render: %s", hipGetErrorString(e));
 }
 
+// ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------
+int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d, int B, const float* offsets, int bgr,
+                  const uint8_t* img_in, uint8_t* out, uint8_t* out2, int H, int W, void* stream) {
+  if (!c || !img_in || !out || B <= 0 || B > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM ||
+      (what != ACRMI_OVERLAY_SKELETON && what != ACRMI_OVERLAY_CENTERMAP))
+    return fail(c, ACRMI_EINVAL, "acrmi_overlay: bad arguments");
+  if (what == ACRMI_OVERLAY_SKELETON ? (!slots || !pj2d) : (!out2 || out2 == out || out2 == img_in))
+    return fail(c, ACRMI_EINVAL, "acrmi_overlay: bad arguments");
+  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "acrmi_overlay: no program has run");
+  ON_DEVICE(c);
+  hipError_t e;
+  if (what == ACRMI_OVERLAY_SKELETON) {
+    SkeletonArgs a{};
+    a.kps = pj2d; a.slots = slots; a.slot_stride = ACRMI_SLOT; a.flag_at = ACRMI_SLOT_FLAG; a.normalized = offsets ? 0 : 1;
+    a.n_hands = 2 * B; a.n_frames = B; a.H = H; a.W = W; a.line_width = 3; a.circle_rad = 3;
+    a.img_in = img_in; a.img_out = out;
+    skeleton_default_colors(bgr != 0, a.colors);
+    e = launch_skeleton(a, (hipStream_t)stream);
+  } else {
+    // the maps are the head buffers the last program run left (NHWC, channel 0, the buffer's channel stride between two
+    // cells); a 16-bit storage program's are converted to fp32 as heatmap_kernel stages them in LDS
+    if (B != c->last_batch)
+      return fail(c, ACRMI_ESTATE, "acrmi_overlay: the resident centre maps are those of a batch of %d, not %d", c->last_batch, B);
+    const acrmi_head_layout& hl = c->heads;
+    const acrmi_buffer_desc& d = c->bufs[hl.center_buf[0]];
+    HeatmapArgs a{};
+    a.maps[0] = c->buf_ptr[hl.center_buf[0]]; a.maps[1] = c->buf_ptr[hl.center_buf[1]];
+    a.pix_stride = d.cs; a.frame_stride = (long long)d.h * d.w * d.cs; a.dtype = d.dtype;
+    a.n = B; a.h = d.h; a.w = d.w; a.H = H; a.W = W; a.offsets = offsets; a.weight = 0.7f;
+    a.img_in = img_in; a.out[0] = out; a.out[1] = out2;
+    heatmap_default_lut(bgr != 0, a.lut);
+    e = launch_heatmap(a, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay: %s", hipGetErrorString(e));
+}
+
 // Plain HIP streams for hosts that have no stream API of their own at hand (Python: torch.cuda.Stream() instantiates
 // torch's whole pool of 32 streams per priority, and with that many streams alive the few in use share hardware
 // queues); engine.EnginePool runs its contexts on these.

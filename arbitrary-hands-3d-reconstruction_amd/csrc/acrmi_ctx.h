@@ -88,6 +88,7 @@ struct acrmi_ctx {
   int n_faces[2] = {0, 0};
   char* render_ws = nullptr;
   int render_ws_frames = 0;
+  int last_batch = 0;          // batch of the last program run: whose centre maps the head buffers hold (acrmi_overlay)
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;
   int comm_ranks = 0;

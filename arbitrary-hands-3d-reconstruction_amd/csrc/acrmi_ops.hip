@@ -304,4 +304,48 @@ int acrmi_rasterize(const float* verts_dev, const float* trans_dev, int n_meshes
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "rasterize: %s", hipGetErrorString(e));
 }
 
+// ---- key-point skeleton and heat-map views (csrc/overlay.hip) ----
+int acrmi_overlay_tables(int bgr, uint8_t* colors_host, uint8_t* lut_host) {
+  if (colors_host) skeleton_default_colors(bgr != 0, colors_host);
+  if (lut_host) heatmap_default_lut(bgr != 0, lut_host);
+  return ACRMI_OK;
+}
+
+static bool overlay_image_ok(int n, int H, int W) {
+  return n > 0 && n <= OVERLAY_MAX_FRAMES && H > 0 && W > 0 && H <= OVERLAY_MAX_DIM && W <= OVERLAY_MAX_DIM;
+}
+
+int acrmi_draw_skeletons(const float* kps_dev, const int32_t* hand_frame_dev, int n_hands, const uint8_t* colors_host, int bgr,
+                         int line_width, int circle_rad, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H,
+                         int W, void* stream) {
+  if (!kps_dev || !hand_frame_dev || !img_in_dev || !img_out_dev || n_hands <= 0 || !overlay_image_ok(n_frames, H, W) ||
+      line_width < 1 || line_width > OVERLAY_MAX_WIDTH || circle_rad < 0 || circle_rad > OVERLAY_MAX_RAD)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_draw_skeletons: bad arguments (line_width 1..%d, circle_rad 0..%d, H, W <= %d)",
+                OVERLAY_MAX_WIDTH, OVERLAY_MAX_RAD, OVERLAY_MAX_DIM);
+  SkeletonArgs a{};
+  a.kps = kps_dev; a.hand_frame = hand_frame_dev; a.n_hands = n_hands; a.n_frames = n_frames; a.H = H; a.W = W;
+  a.line_width = line_width; a.circle_rad = circle_rad; a.img_in = img_in_dev; a.img_out = img_out_dev;
+  if (colors_host) std::memcpy(a.colors, colors_host, 63);
+  else skeleton_default_colors(bgr != 0, a.colors);
+  hipError_t e = launch_skeleton(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_skeletons: %s", hipGetErrorString(e));
+}
+
+int acrmi_draw_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long long frame_stride, int n, int h, int w,
+                        const float* view_dev, float weight, const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev,
+                        uint8_t* out_l_dev, uint8_t* out_r_dev, int H, int W, void* stream) {
+  if (!maps_l_dev || !img_in_dev || !out_l_dev || (maps_r_dev != nullptr) != (out_r_dev != nullptr) || out_l_dev == out_r_dev ||
+      (out_r_dev && out_r_dev == img_in_dev) || !overlay_image_ok(n, H, W) || h <= 0 || w <= 0 || h > OVERLAY_MAX_DIM ||
+      w > OVERLAY_MAX_DIM || frame_stride < (long long)h * w || !(weight >= 0.f && weight <= 1.f))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_draw_heatmaps: bad arguments");
+  HeatmapArgs a{};
+  a.maps[0] = maps_l_dev; a.maps[1] = maps_r_dev; a.frame_stride = frame_stride; a.pix_stride = 1; a.dtype = ACRMI_DT_F32;
+  a.n = n; a.h = h; a.w = w; a.H = H; a.W = W; a.view = view_dev; a.weight = weight; a.img_in = img_in_dev;
+  a.out[0] = out_l_dev; a.out[1] = out_r_dev;
+  if (lut_host) std::memcpy(a.lut, lut_host, 768);
+  else heatmap_default_lut(bgr != 0, a.lut);
+  hipError_t e = launch_heatmap(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_heatmaps: %s", hipGetErrorString(e));
+}
+
 }  // extern "C"

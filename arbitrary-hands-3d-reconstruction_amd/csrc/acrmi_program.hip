@@ -25,6 +25,7 @@ void free_program(acrmi_ctx* c) {
   if (c->range_flag) (void)hipFree(c->range_flag);
   c->range_flag = nullptr;
   c->have_program = false;
+  c->last_batch = 0;
 }
 
 
@@ -673,6 +674,7 @@ int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool poin
   if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_backbone_heads: no program");
   if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
   ON_DEVICE(c);
+  c->last_batch = B;
   static const bool dbg_sync = getenv("ACRMI_DEBUG_SYNC") != nullptr;   // attribute a fault/hang to an op
   if (c->sched[point ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0].n_lanes > 1 && !dbg_sync && first_op <= 0)
     return run_program_lanes(c, img, B, (hipStream_t)stream, point);

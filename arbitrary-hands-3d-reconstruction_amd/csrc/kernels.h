@@ -288,4 +288,37 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s);
 hipError_t launch_render_prep(const float* slots, const float* offsets, int B, int slot_stride, int flag_at, const float* colors,
                               int32_t* mesh_frame, int32_t* mesh_topo, float* rgb, float* view, hipStream_t s);
 
+// Key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views").
+struct SkeletonArgs {
+  const float* kps;              // [n_hands, 21, 2] MANO joint order; pixels of the image, or (normalized) [-1, 1] of the 512 canvas
+  const int32_t* hand_frame;     // [n_hands] frame a hand is drawn into, < 0 = not drawn - or null with `slots`:
+  const float* slots;            // [n_hands, slot_stride]: hand h belongs to frame h / 2, drawn when its flag_at > 0.5
+  int slot_stride, flag_at, normalized;
+  int n_hands, n_frames, H, W, line_width, circle_rad;
+  const uint8_t* img_in;         // [n_frames, H, W, 3]
+  uint8_t* img_out;              // may be img_in
+  int wide;                      // (launch_skeleton fills this)
+  uint8_t colors[64];            // [21][3] in the image's channel order
+};
+struct HeatmapArgs {
+  const void* maps[2];           // left / right; [1] null = one view
+  long long frame_stride;        // elements between the maps of two frames
+  int pix_stride;                // elements between two cells of a row (1; the channel stride of a head buffer)
+  int dtype;                     // 0 fp32, 1 f16, 2 bf16 (ACRMI_DT_*)
+  int n, h, w, H, W;
+  const float* view;             // [n, 4] scale x, scale y, shift x, shift y, or null
+  const float* offsets;          // [n, 10] the view is taken from these rows instead (null: `view`, or none)
+  float weight;
+  const uint8_t* img_in;         // [n, H, W, 3]
+  uint8_t* out[2];
+  int wide;                      // (launch_heatmap fills this)
+  uint8_t lut[768];              // [256][3] in the image's channel order
+};
+constexpr int OVERLAY_MAX_DIM = 16384, OVERLAY_MAX_FRAMES = 65535, OVERLAY_MAX_WIDTH = 11, OVERLAY_MAX_RAD = 255;
+extern const uint8_t kSkeletonRGB[21][3];
+void skeleton_default_colors(bool bgr, uint8_t* out63);
+void heatmap_default_lut(bool bgr, uint8_t* out768);
+hipError_t launch_skeleton(const SkeletonArgs& a, hipStream_t s);
+hipError_t launch_heatmap(const HeatmapArgs& a, hipStream_t s);
+
 }  // namespace acrmi

@@ -1,0 +1,398 @@
+// Key-point skeleton and centre heat-map views over the frames (DESIGN.md "Key-point and heat-map views").  The reference
+// draws them on the host with PIL and cv2 (acr/visualization.py:228-300); nothing of those is used here, only the
+// conventions: the joint order and tree, the colours, the painter's order, bilinear maps in false colour at weight 0.7.
+//
+//   skeleton_kernel   one 256-thread block per (128 x 32 pixel tile, frame).  The hands of the frame are found in hand
+//                     order (ballot + mbcnt compaction of the hand -> frame index), two at a time their 21 key points are
+//                     snapped and turned into 61 primitive records each in LDS (bone / disc, clipped pixel box, the int64
+//                     constants of the bone test), and every thread walks the records that meet the tile for its 4 x 4
+//                     pixels.  The rule is integer throughout; the last primitive that covers a pixel wins.
+//   heatmap_kernel    the same tiling; the part of the left and right maps a tile samples (and the 256 x 3 colour table)
+//                     is staged in LDS - 16-bit maps of a 16-bit storage program are converted to fp32 there - and every
+//                     thread samples, colours and blends its pixels in fp32, each operation rounded on its own.  One read
+//                     of the image, two writes.
+// Pixels move as 4 pixels = 3 dwords per thread and row when the row length is a multiple of 4 and the buffers are dword
+// aligned, byte by byte otherwise.  A thread reads and writes only its own pixels, so drawing in place is safe; there are
+// no atomics on global memory, so the result is deterministic.
+#include "kernels.h"
+
+#include <hip/hip_fp16.h>
+
+#include <climits>
+#include <cstring>
+
+namespace acrmi {
+
+namespace {
+
+constexpr int TW = 128, TH = 32;      // block tile: 32 threads x 4 pixels wide, 8 threads x 4 rows high
+constexpr int PX = 4, ROWS = 4, ROW_STEP = 8;
+constexpr int HAND_PRIMS = 61;        // 20 x (bone, disc, parent's disc) + the wrist's disc
+constexpr int PAIR = 2;               // hands whose records are resident in LDS at a time
+constexpr float COORD_LIMIT = 16384.f;
+constexpr long long CROSS_LIMIT = 1ll << 18;
+constexpr int MAP_CAP = 48 * 48;      // map cells per side staged in LDS; a larger footprint is read from memory
+
+struct Prim {
+  int x0, x1, y0, y1;      // inclusive pixel box, clipped to the image; empty (x0 > x1) when the primitive is dropped
+  int ax, ay, dx, dy;      // bone: start and direction; disc: the centre in (ax, ay)
+  long long L2, lim;       // bone: |d|^2 and w^2 |d|^2; disc: L2 = -1 and lim = r^2 + r
+  int color, pad;
+};
+
+__device__ inline int lane_rank(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+}
+
+// the skeleton of mano/skeleton.txt (first 21 rows): five fingers of four joints, tip to base, then the wrist
+__device__ inline int skeleton_parent(int i) { return i == 20 ? -1 : ((i & 3) == 3 ? 20 : i + 1); }
+// mano2interhand_mapper (acr/visualization.py:25): skeleton joint i is MANO joint ...
+__device__ inline int skeleton_mano_joint(int i) { return i == 20 ? 0 : (i & ~3) + 4 - (i & 3); }
+
+__device__ inline bool prim_covers(const Prim& r, int x, int y) {
+  const int ux = x - r.ax, uy = y - r.ay;
+  if (r.L2 < 0) return (long long)(ux * ux + uy * uy) <= r.lim;      // (|u| <= r inside the box)
+  const long long dot = (long long)ux * r.dx + (long long)uy * r.dy;
+  if (dot < 0 || dot > r.L2) return false;
+  long long cr = (long long)ux * r.dy - (long long)uy * r.dx;
+  cr = cr < 0 ? -cr : cr;
+  if (cr >= CROSS_LIMIT) return false;
+  return 4 * cr * cr <= r.lim;
+}
+
+// 4 pixels of one row <-> 3 dwords: channel c of pixel j is byte 3 j + c
+__device__ inline void load_px(const uint8_t* p, bool wide, int n, uint32_t d[3]) {
+  if (wide) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
+    return;
+  }
+  d[0] = d[1] = d[2] = 0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k)
+    if (k < 3 * n) d[k >> 2] |= (uint32_t)p[k] << ((k & 3) * 8);
+}
+
+__device__ inline void store_px(uint8_t* p, bool wide, int n, const uint32_t d[3]) {
+  if (wide) {
+    uint32_t* q = reinterpret_cast<uint32_t*>(p);
+    q[0] = d[0]; q[1] = d[1]; q[2] = d[2];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k)
+    if (k < 3 * n) p[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
+}
+
+__device__ inline uint32_t get_byte(const uint32_t d[3], int k) { return (d[k >> 2] >> ((k & 3) * 8)) & 0xffu; }
+__device__ inline void set_byte(uint32_t d[3], int k, uint32_t v) {
+  d[k >> 2] = (d[k >> 2] & ~(0xffu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
+}
+
+}  // namespace
+
+// ---- skeleton ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void skeleton_kernel(SkeletonArgs a) {
+  __shared__ Prim s_prim[PAIR * HAND_PRIMS];
+  __shared__ int s_k[PAIR][21][2];
+  __shared__ int s_far[PAIR][21];
+  __shared__ int s_bad[PAIR];
+  __shared__ int s_box[4];
+  __shared__ int s_list[256];
+  __shared__ int s_cnt[4];
+  __shared__ uint32_t s_col[64];
+  const int tid = threadIdx.x, f = blockIdx.z;
+  const int X0 = blockIdx.x * TW, Y0 = blockIdx.y * TH;
+  const int xt = X0 + PX * (tid & 31), yt = Y0 + (tid >> 5);
+  if (tid < 63) s_col[tid] = a.colors[tid];
+  int cid[ROWS][PX];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+    for (int j = 0; j < PX; ++j) cid[r][j] = -1;
+
+  // the hands of this frame, in hand order: with `slots` they are 2 f and 2 f + 1, else the index is searched
+  const int hb = a.slots ? 2 * f : 0, he = a.slots ? min(2 * f + 2, a.n_hands) : a.n_hands;
+  for (int base = hb; base < he; base += 256) {
+    const int h = base + tid;
+    bool mine = false;
+    if (h < he) mine = a.slots ? a.slots[(size_t)h * a.slot_stride + a.flag_at] > 0.5f : a.hand_frame[h] == f;
+    const unsigned long long mask = __ballot(mine);
+    const int wave = tid >> 6;
+    if ((tid & 63) == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int off = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_cnt[w];
+      off += w < wave ? c : 0;
+      total += c;
+    }
+    if (mine) s_list[off + lane_rank(mask)] = h;
+    __syncthreads();
+    for (int j0 = 0; j0 < total; j0 += PAIR) {
+      const int nh = min(PAIR, total - j0);
+      if (tid < 4) s_box[tid] = (tid & 1) ? INT_MIN : INT_MAX;      // x0, x1, y0, y1 of everything these hands draw
+      if (tid < PAIR) s_bad[tid] = 0;
+      __syncthreads();
+      if (tid < nh * 21) {      // snap: truncation toward zero
+        const int q = tid / 21, i = tid - q * 21;
+        const float* kp = a.kps + ((size_t)s_list[j0 + q] * 21 + skeleton_mano_joint(i)) * 2;
+        float fx = kp[0], fy = kp[1];
+        if (a.normalized) {      // (pj2d + 1) / 2 * 512, acr/visualization.py:241
+          fx = ((fx + 1.f) / 2.f) * 512.f;
+          fy = ((fy + 1.f) / 2.f) * 512.f;
+        }
+        if (!(fabsf(fx) < INFINITY && fabsf(fy) < INFINITY)) atomicOr(&s_bad[q], 1);      // NaN / inf: the hand is not drawn
+        const bool far = !(fabsf(fx) < COORD_LIMIT && fabsf(fy) < COORD_LIMIT);
+        s_k[q][i][0] = far ? 0 : (int)fx;
+        s_k[q][i][1] = far ? 0 : (int)fy;
+        s_far[q][i] = far;
+      }
+      __syncthreads();
+      if (tid < nh * HAND_PRIMS) {      // records in painter's order: per joint bone(i, p), disc(i), disc(p)
+        const int q = tid / HAND_PRIMS, p = tid - q * HAND_PRIMS;
+        const int i = p == 60 ? 20 : p / 3, kind = p == 60 ? 1 : p - 3 * (p / 3);
+        const int par = skeleton_parent(i);
+        Prim r{};
+        bool ok = !s_bad[q];
+        int m = 0;
+        if (kind == 0) {
+          ok = ok && !s_far[q][i] && !s_far[q][par];
+          const int bx = s_k[q][par][0], by = s_k[q][par][1];
+          r.ax = s_k[q][i][0]; r.ay = s_k[q][i][1];
+          r.dx = bx - r.ax; r.dy = by - r.ay;
+          r.L2 = (long long)r.dx * r.dx + (long long)r.dy * r.dy;
+          r.lim = (long long)(a.line_width * a.line_width) * r.L2;
+          ok = ok && r.L2 > 0;
+          r.color = par;
+          m = a.line_width;      // a covered pixel is within w / 2 of the segment
+          r.x0 = min(r.ax, bx) - m; r.x1 = max(r.ax, bx) + m;
+          r.y0 = min(r.ay, by) - m; r.y1 = max(r.ay, by) + m;
+        } else {
+          const int j = kind == 1 ? i : par;
+          ok = ok && !s_far[q][j];
+          r.ax = s_k[q][j][0]; r.ay = s_k[q][j][1];
+          r.L2 = -1;
+          r.lim = (long long)a.circle_rad * a.circle_rad + a.circle_rad;
+          r.color = j;
+          m = a.circle_rad;      // r^2 + r < (r + 1)^2
+          r.x0 = r.ax - m; r.x1 = r.ax + m; r.y0 = r.ay - m; r.y1 = r.ay + m;
+        }
+        r.x0 = max(r.x0, 0); r.x1 = min(r.x1, a.W - 1);
+        r.y0 = max(r.y0, 0); r.y1 = min(r.y1, a.H - 1);
+        ok = ok && r.x0 <= r.x1 && r.y0 <= r.y1;
+        if (!ok) { r.x0 = 1; r.x1 = 0; r.y0 = 1; r.y1 = 0; }
+        s_prim[tid] = r;
+        if (ok) {
+          atomicMin(&s_box[0], r.x0); atomicMax(&s_box[1], r.x1);
+          atomicMin(&s_box[2], r.y0); atomicMax(&s_box[3], r.y1);
+        }
+      }
+      __syncthreads();
+      if (s_box[0] < X0 + TW && s_box[1] >= X0 && s_box[2] < Y0 + TH && s_box[3] >= Y0) {      // (the same for every thread)
+        for (int p = 0; p < nh * HAND_PRIMS; ++p) {
+          const Prim& r = s_prim[p];
+          if (r.x1 < X0 || r.x0 >= X0 + TW || r.y1 < Y0 || r.y0 >= Y0 + TH) continue;
+          if (r.x1 < xt || r.x0 > xt + PX - 1) continue;
+#pragma unroll
+          for (int rr = 0; rr < ROWS; ++rr) {
+            const int y = yt + ROW_STEP * rr;
+            if (y < r.y0 || y > r.y1) continue;
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+              const int x = xt + j;
+              if (x >= r.x0 && x <= r.x1 && prim_covers(r, x, y)) cid[rr][j] = r.color;
+            }
+          }
+        }
+      }
+      __syncthreads();      // the records are rewritten by the next pair
+    }
+  }
+
+  if (xt >= a.W) return;
+  const bool in_place = a.img_in == a.img_out;
+  const int n = min(PX, a.W - xt);
+#pragma unroll
+  for (int rr = 0; rr < ROWS; ++rr) {
+    const int y = yt + ROW_STEP * rr;
+    if (y >= a.H) continue;
+    const bool any = cid[rr][0] >= 0 || cid[rr][1] >= 0 || cid[rr][2] >= 0 || cid[rr][3] >= 0;
+    if (in_place && !any) continue;      // nothing to move
+    const size_t at = (((size_t)f * a.H + y) * a.W + xt) * 3;
+    uint32_t d[3];
+    load_px(a.img_in + at, a.wide, n, d);
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+      if (cid[rr][j] < 0) continue;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) set_byte(d, 3 * j + c, s_col[cid[rr][j] * 3 + c]);
+    }
+    store_px(a.img_out + at, a.wide, n, d);
+  }
+}
+
+// ---- heat maps --------------------------------------------------------------------------------------------------------
+namespace {
+
+struct Tap { int i0, i1; float l0, l1; };
+
+// source position of canvas coordinate c on a map of n cells (scale m = n / 512): the half-pixel-centre bilinear rule
+__device__ inline Tap map_tap(float c, float m, int n) {
+  const float s = fmaxf(c * m - 0.5f, 0.f);
+  Tap t;
+  t.i0 = min((int)s, n - 1);
+  t.i1 = min(t.i0 + 1, n - 1);
+  t.l1 = s - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
+__device__ inline float map_load(const void* p, int dtype, size_t at) {
+  if (dtype == 0) return static_cast<const float*>(p)[at];
+  const uint16_t bits = static_cast<const uint16_t*>(p)[at];
+  if (dtype == 1) return __half2float(__ushort_as_half(bits));
+  return __uint_as_float((uint32_t)bits << 16);      // bf16
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
+  __shared__ float s_map[2][MAP_CAP];
+  __shared__ uint32_t s_lut[768];
+  const int tid = threadIdx.x, f = blockIdx.z;
+  const int X0 = blockIdx.x * TW, Y0 = blockIdx.y * TH;
+  const int xt = X0 + PX * (tid & 31), yt = Y0 + (tid >> 5);
+  const int views = a.maps[1] ? 2 : 1;
+  for (int t = tid; t < 768; t += 256) s_lut[t] = a.lut[t];
+
+  // the frame's viewport: canvas coordinate of pixel x = (x + 0.5 - ox) / sx, or (x + 0.5) * (512 / W) without one
+  const bool has_view = a.view || a.offsets;
+  float sx = 1.f, sy = 1.f, ox = 0.f, oy = 0.f;
+  if (a.view) {
+    sx = a.view[f * 4]; sy = a.view[f * 4 + 1]; ox = a.view[f * 4 + 2]; oy = a.view[f * 4 + 3];
+  } else if (a.offsets) {      // as ops.view_from_offsets / render_prep_kernel
+    const float* of = a.offsets + (size_t)f * 10;
+    sx = of[0] / 512.f; sy = of[1] / 512.f; ox = of[5] - of[9]; oy = of[2] - of[6];
+  }
+  const float kx = 512.f / (float)a.W, ky = 512.f / (float)a.H;
+  const float mx = (float)a.w / 512.f, my = (float)a.h / 512.f;
+  auto canvas_x = [&](int x) { return has_view ? ((float)x + 0.5f - ox) / sx : ((float)x + 0.5f) * kx; };
+  auto canvas_y = [&](int y) { return has_view ? ((float)y + 0.5f - oy) / sy : ((float)y + 0.5f) * ky; };
+  const bool frame_ok = sx > 0.f && sy > 0.f;      // (false for NaN) a viewport that does not face the canvas draws nothing
+
+  // what this tile samples: the map coordinate is monotone in the pixel coordinate, so the taps of the first and the last
+  // pixel (clamped into the canvas) bound those of every pixel between them
+  const float cx_a = canvas_x(X0), cx_b = canvas_x(min(X0 + TW, a.W) - 1);
+  const float cy_a = canvas_y(Y0), cy_b = canvas_y(min(Y0 + TH, a.H) - 1);
+  const bool tile_ok = frame_ok && cx_b >= 0.f && cx_a < 512.f && cy_b >= 0.f && cy_a < 512.f;
+  int ix_lo = 0, iy_lo = 0, fw = 0, fh = 0;
+  bool staged = false;
+  if (tile_ok) {
+    ix_lo = map_tap(fminf(fmaxf(cx_a, 0.f), 512.f), mx, a.w).i0;
+    iy_lo = map_tap(fminf(fmaxf(cy_a, 0.f), 512.f), my, a.h).i0;
+    fw = map_tap(fminf(fmaxf(cx_b, 0.f), 512.f), mx, a.w).i1 - ix_lo + 1;
+    fh = map_tap(fminf(fmaxf(cy_b, 0.f), 512.f), my, a.h).i1 - iy_lo + 1;
+    staged = fw * fh <= MAP_CAP;
+    if (staged) {
+      for (int v = 0; v < views; ++v)
+        for (int t = tid; t < fw * fh; t += 256) {
+          const int r = t / fw, c = t - r * fw;
+          s_map[v][t] = map_load(a.maps[v], a.dtype,
+                                 (size_t)f * a.frame_stride + ((size_t)(iy_lo + r) * a.w + ix_lo + c) * a.pix_stride);
+        }
+    }
+  }
+  __syncthreads();
+  if (xt >= a.W) return;
+  const int n = min(PX, a.W - xt);
+  const float wgt = a.weight, iw = 1.f - a.weight;
+#pragma unroll
+  for (int rr = 0; rr < ROWS; ++rr) {
+    const int y = yt + ROW_STEP * rr;
+    if (y >= a.H) continue;
+    const size_t at = (((size_t)f * a.H + y) * a.W + xt) * 3;
+    uint32_t d[3], o[2][3];
+    load_px(a.img_in + at, a.wide, n, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[0][k] = o[1][k] = d[k];
+    const float cy = canvas_y(y);
+    if (tile_ok && cy >= 0.f && cy < 512.f) {
+      const Tap ty = map_tap(cy, my, a.h);
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        const float cx = canvas_x(xt + j);
+        if (!(cx >= 0.f && cx < 512.f)) continue;
+        const Tap tx = map_tap(cx, mx, a.w);
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+          if (v >= views) continue;
+          float p00, p01, p10, p11;
+          if (staged) {
+            const float* m = s_map[v];
+            const int r0 = (ty.i0 - iy_lo) * fw - ix_lo, r1 = (ty.i1 - iy_lo) * fw - ix_lo;
+            p00 = m[r0 + tx.i0]; p01 = m[r0 + tx.i1]; p10 = m[r1 + tx.i0]; p11 = m[r1 + tx.i1];
+          } else {
+            const size_t fb = (size_t)f * a.frame_stride, r0 = (size_t)ty.i0 * a.w, r1 = (size_t)ty.i1 * a.w;
+            p00 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i0) * a.pix_stride);
+            p01 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i1) * a.pix_stride);
+            p10 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i0) * a.pix_stride);
+            p11 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i1) * a.pix_stride);
+          }
+          const float val = ty.l0 * (tx.l0 * p00 + tx.l1 * p01) + ty.l1 * (tx.l0 * p10 + tx.l1 * p11);
+          const int idx = (int)fminf(fmaxf(val * 255.f, 0.f), 255.f);      // truncates, as .byte() does; NaN -> 0
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float img = (float)get_byte(d, 3 * j + c);
+            set_byte(o[v], 3 * j + c, (uint32_t)floorf(wgt * (float)s_lut[idx * 3 + c] + iw * img));
+          }
+        }
+      }
+    }
+    store_px(a.out[0] + at, a.wide, n, o[0]);
+    if (views == 2) store_px(a.out[1] + at, a.wide, n, o[1]);
+  }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------
+// get_keypoint_rgb (acr/visualization.py:331-381) over mano/skeleton.txt, in skeleton order, RGB: finger tips and the wrist
+// fall through to the last branch
+const uint8_t kSkeletonRGB[21][3] = {
+    {230, 230, 0}, {255, 51, 51},  {255, 102, 102}, {255, 153, 153}, {230, 230, 0}, {51, 255, 51},   {102, 255, 102},
+    {153, 255, 153}, {230, 230, 0}, {255, 153, 51}, {255, 178, 102}, {255, 204, 153}, {230, 230, 0}, {51, 153, 255},
+    {102, 178, 255}, {153, 204, 255}, {230, 230, 0}, {255, 51, 255}, {255, 102, 255}, {255, 153, 255}, {230, 230, 0}};
+
+void skeleton_default_colors(bool bgr, uint8_t* out63) {
+  for (int i = 0; i < 21; ++i)
+    for (int c = 0; c < 3; ++c) out63[i * 3 + c] = kSkeletonRGB[i][bgr ? 2 - c : c];
+}
+
+// The piece-wise linear "jet": with t = i / 255, red = clamp(1.5 - |4 t - 3|), green = clamp(1.5 - |4 t - 2|), blue =
+// clamp(1.5 - |4 t - 1|), clamped to [0, 1] and scaled to bytes by floor(255 v + 0.5).  255 v + 0.5 = 383 - |4 i - 255 k|
+// (k = 3, 2, 1) is an integer, so the table is exact integer arithmetic: byte = clamp(383 - |4 i - 255 k|, 0, 255).
+void heatmap_default_lut(bool bgr, uint8_t* out768) {
+  for (int i = 0; i < 256; ++i)
+    for (int c = 0; c < 3; ++c) {
+      const int k = 3 - c, d = 4 * i - 255 * k, v = 383 - (d < 0 ? -d : d);
+      out768[i * 3 + (bgr ? 2 - c : c)] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+    }
+}
+
+static bool dword_rows(const void* p, int W) { return W % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+hipError_t launch_skeleton(const SkeletonArgs& a0, hipStream_t s) {
+  SkeletonArgs a = a0;
+  a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.img_out, a.W);
+  hipLaunchKernelGGL(skeleton_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n_frames), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_heatmap(const HeatmapArgs& a0, hipStream_t s) {
+  HeatmapArgs a = a0;
+  a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
+  hipLaunchKernelGGL(heatmap_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace acrmi

@@ -392,6 +392,12 @@ class Engine(object):
             out = {k: v.permute(0, 3, 1, 2).contiguous() for k, v in out.items()}
         return out
 
+    def center_maps(self, B):
+        """The left / right centre maps of the last program run as one fp32 tensor [B,2,h,w] (what `overlay(...,
+        'centermap')` draws straight from the head buffers; a 16-bit storage program's maps convert exactly)."""
+        hl = self.program['heads']
+        return torch.stack([self.buffer(hl.center_buf[si], B, 1)[..., 0] for si in (0, 1)], 1).float().contiguous()
+
     def decode(self, B, prior_gate=None):
         """prior_gate: int32 device tensor [B] (acrmi_decode_gated: < 0 per-frame rule, 0 no prior, 1 prior when the frame
         has both hands) - how acr.result_parser applies the reference's batch-wide prior rules; None = per frame."""
@@ -522,6 +528,49 @@ class Engine(object):
                                        float(visible_weight), _ptr(src), _ptr(dst), H, W, _ptr(ids), st), self.ctx)
         self._render_keep = (verts, slots, cam_trans, offsets, src)      # referenced until the next call has been queued
         return (dst, ids) if return_ids else dst
+
+    def overlay(self, out, images, what, offsets=None, bgr=False, dst=None, stream=None):
+        """The reference's other two views of a result over `images` (acrmi_overlay; acr/visualization.py:228-300, rules in
+        DESIGN.md "Key-point and heat-map views").  `out`: what `forward(..., project=True)` returned; images uint8 [B,H,W,3]
+        on the device - the 512 x 512 network input when offsets is None, else the original frames the `offsets` rows
+        [B,10] describe.  what = 'pj2d': the 21 projected key points of every flagged hand as a coloured skeleton, at
+        (pj2d + 1) / 2 * 512, respectively at pj2d_org -> uint8 [B,H,W,3].  what = 'centermap': the left and right centre
+        maps of the LAST program run of this context (it must be the forward that produced `out`) in false colour at
+        weight 0.7 -> uint8 [2,B,H,W,3] (left, right).  bgr: the images' channel order.  dst: tensor to draw into, shaped
+        like the result ('pj2d': may be `images` itself).  stream: as `forward`."""
+        dev = self.device
+        if what not in ('pj2d', 'centermap'):
+            raise ValueError("what: 'pj2d' or 'centermap'")
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError('images must be uint8 [B,H,W,3] on the device')
+        B, H, W, _ = images.shape
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        if offsets is not None:
+            offsets = offsets.to(dev, torch.float32).contiguous()
+            if tuple(offsets.shape) != (B, 10):
+                raise ValueError('offsets must be [B,10]')
+        src = images.contiguous()
+        shape = (B, H, W, 3) if what == 'pj2d' else (2, B, H, W, 3)
+        if dst is None:
+            dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
+        elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != src.device:
+            raise ValueError('dst must be a contiguous uint8 tensor %s on the images\' device' % (shape,))
+        slots = kps = None
+        if what == 'pj2d':
+            kps = out.get('pj2d') if offsets is None else out.get('pj2d_org')
+            if kps is None:
+                raise ValueError('out holds no %s (forward(..., project=True%s))' %
+                                 (('pj2d', '') if offsets is None else ('pj2d_org', ', offsets=offsets')))
+            if tuple(kps.shape) != (B, 2, 21, 2) or tuple(out['slots'].shape) != (B, 2, _lib.SLOT):
+                raise ValueError('out does not hold the results of %d frames' % B)
+            kps, slots = kps.contiguous(), out['slots'].contiguous()
+            _lib.check(self.L.acrmi_overlay(self.ctx, _lib.OVERLAY_SKELETON, _ptr(slots), _ptr(kps), B, _ptr(offsets),
+                                            int(bool(bgr)), _ptr(src), _ptr(dst), None, H, W, st), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_overlay(self.ctx, _lib.OVERLAY_CENTERMAP, None, None, B, _ptr(offsets), int(bool(bgr)),
+                                            _ptr(src), _ptr(dst[0]), _ptr(dst[1]), H, W, st), self.ctx)
+        self._overlay_keep = (slots, kps, offsets, src)      # referenced until the next call has been queued
+        return dst
 
     def profile_ops(self, img):
         img = self._check_img(img)
@@ -672,6 +721,25 @@ class EnginePool(object):
         # as in submit: everything the drawing touches stays referenced by the ticket until its event has completed
         ticket['event'] = done
         ticket['render'] = (res, images, offsets, self.engines[i]._render_keep)
+        return res
+
+    def overlay(self, ticket, images, what, offsets=None, **kw):
+        """Engine.overlay of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True) and collect(), like render().  Returns what Engine.overlay returns."""
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('overlay() belongs between submit() and collect() of its ticket')
+        images = images.contiguous()
+        if offsets is not None:
+            offsets = offsets.to(self.device, torch.float32).contiguous()
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        self.streams[i].wait_event(ready)
+        res = self.engines[i].overlay(ticket['out'], images, what, offsets=offsets, stream=self._raw[i].value, **kw)
+        done = torch.cuda.Event()
+        done.record(self.streams[i])
+        ticket['event'] = done
+        ticket.setdefault('overlay', []).append((res, images, offsets, self.engines[i]._overlay_keep))
         return res
 
     def _reap(self):

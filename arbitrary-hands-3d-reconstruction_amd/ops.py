@@ -412,3 +412,110 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
                                  _p(vw), float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids),
                                  C.c_void_p(ws_p), _s(src)))
     return (out, ids) if return_ids else out
+
+
+# ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------
+# mano/skeleton.txt (first 21 rows) of the reference: five fingers of four joints, tip to base, then the wrist (no parent)
+SKELETON_PARENTS = (1, 2, 3, 20, 5, 6, 7, 20, 9, 10, 11, 20, 13, 14, 15, 20, 17, 18, 19, 20, -1)
+# skeleton joint i is MANO joint MANO2INTERHAND[i] (acr/visualization.py:25)
+MANO2INTERHAND = (4, 3, 2, 1, 8, 7, 6, 5, 12, 11, 10, 9, 16, 15, 14, 13, 20, 19, 18, 17, 0)
+# get_keypoint_rgb (acr/visualization.py:331-381) for that skeleton, by skeleton joint
+SKELETON_COLORS_RGB = ((230, 230, 0), (255, 51, 51), (255, 102, 102), (255, 153, 153),
+                       (230, 230, 0), (51, 255, 51), (102, 255, 102), (153, 255, 153),
+                       (230, 230, 0), (255, 153, 51), (255, 178, 102), (255, 204, 153),
+                       (230, 230, 0), (51, 153, 255), (102, 178, 255), (153, 204, 255),
+                       (230, 230, 0), (255, 51, 255), (255, 102, 255), (255, 153, 255), (230, 230, 0))
+
+
+def overlay_tables(bgr=False):
+    """The library's default tables (acrmi_overlay_tables; pure host): (colors uint8 [21,3] by skeleton joint, lut uint8
+    [256,3] - the piece-wise linear jet of include/acrmi.h), RGB or flipped."""
+    colors, lut = np.empty((21, 3), np.uint8), np.empty((256, 3), np.uint8)
+    _lib.check(_lib.lib().acrmi_overlay_tables(int(bool(bgr)), colors.ctypes.data_as(C.c_void_p), lut.ctypes.data_as(C.c_void_p)))
+    return colors, lut
+
+
+def _check_images(images, name='images'):
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 \
+            or images.shape[0] < 1:
+        raise ValueError('%s must be a uint8 tensor [N,H,W,3]' % name)
+
+
+def _check_dst(dst, src, name='dst'):
+    if dst.dtype != torch.uint8 or tuple(dst.shape) != tuple(src.shape) or not dst.is_contiguous() or dst.device != src.device:
+        raise ValueError('%s must be a contiguous uint8 tensor shaped like images, on their device' % name)
+
+
+def draw_skeletons(kps, images, hand_frame=None, colors=None, line_width=3, circle_rad=3, bgr=False, dst=None):
+    """Draws the 21 key points of M hands as coloured skeletons over N equal-sized frames on the GPU (acrmi_draw_skeletons;
+    the reference's Visualizer 'pj2d' view, acr/visualization.py:228-278, with the integer rule of DESIGN.md "Key-point and
+    heat-map views").  kps [M,21,2] device fp32, pixels of the image, MANO joint order; images uint8 [N,H,W,3] device;
+    hand_frame [M] = the frame each hand is drawn into, -1 = not drawn (default: hand m into frame m // (M / N));
+    colors uint8 [21,3] by skeleton joint in the images' channel order (default: the reference's, flipped with bgr=True);
+    dst: uint8 tensor like images to draw into (may BE images: in place).  Returns dst."""
+    _check_images(images)
+    if not isinstance(kps, torch.Tensor) or kps.dim() != 3 or tuple(kps.shape[1:]) != (21, 2) or kps.shape[0] < 1 or \
+            kps.dtype != torch.float32:
+        raise ValueError('kps must be a float32 tensor [M,21,2]')
+    _need_cuda(kps, images, dst)
+    dev = images.device
+    M, N = kps.shape[0], images.shape[0]
+    if hand_frame is None:
+        if M % N:
+            raise ValueError('hand_frame is needed when the frames do not divide the hands')
+        hand_frame = torch.arange(M, dtype=torch.int32) // (M // N)
+    hf = torch.as_tensor(hand_frame).to(dev, torch.int32).contiguous()
+    if hf.numel() != M:
+        raise ValueError('hand_frame must hold one int per hand')
+    col = None
+    if colors is not None:
+        col = np.ascontiguousarray(np.asarray(colors.cpu() if hasattr(colors, 'cpu') else colors))
+        if col.shape != (21, 3) or col.dtype != np.uint8:
+            raise ValueError('colors must be uint8 [21,3]')
+    k = kps.to(dev).contiguous()
+    src = images.contiguous()
+    if dst is None:
+        dst = torch.empty_like(src)
+    else:
+        _check_dst(dst, src)
+    _lib.check(_lib.lib().acrmi_draw_skeletons(_p(k), _p(hf), M, None if col is None else col.ctypes.data_as(C.c_void_p),
+                                               int(bool(bgr)), int(line_width), int(circle_rad), _p(src), _p(dst), N,
+                                               src.shape[1], src.shape[2], _s(src)))
+    return dst
+
+
+def draw_heatmaps(maps, images, view=None, weight=0.7, bgr=False, lut=None):
+    """Heat maps in false colour over N frames on the GPU (acrmi_draw_heatmaps; the reference's 'centermap' view,
+    acr/visualization.py:246-300: bilinear to the frame, * 255 truncated to a byte, colour table, weight * colour +
+    (1 - weight) * frame - rule and table in DESIGN.md "Key-point and heat-map views"; the table is a piece-wise linear
+    jet, not cv2's).  maps device float [N,2,h,w] (left, right: one launch, the frames are read once) or [N,h,w];
+    images uint8 [N,H,W,3] device; view [N,4] (view_from_offsets) = where the 512 canvas the maps cover sits in the frames,
+    None = it is the whole frame.  lut: uint8 [256,3] in the images' channel order (default: the library's, flipped with
+    bgr=True).  Returns uint8 [2,N,H,W,3] for [N,2,h,w] maps, [N,H,W,3] for [N,h,w]."""
+    _check_images(images)
+    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() not in (3, 4) or \
+            (maps.dim() == 4 and maps.shape[1] != 2) or maps.shape[0] != images.shape[0]:
+        raise ValueError('maps must be a float tensor [N,2,h,w] or [N,h,w] with one row per image')
+    _need_cuda(maps, images)
+    dev = images.device
+    N, H, W, _ = images.shape
+    m = maps.to(dev, torch.float32).contiguous()      # (16-bit maps convert exactly)
+    h, w = m.shape[-2:]
+    two = m.dim() == 4
+    vw = None
+    if view is not None:
+        vw = torch.as_tensor(view, dtype=torch.float32).to(dev).contiguous()
+        if tuple(vw.shape) != (N, 4):
+            raise ValueError('view must be [N,4]')
+    tab = None
+    if lut is not None:
+        tab = np.ascontiguousarray(np.asarray(lut.cpu() if hasattr(lut, 'cpu') else lut))
+        if tab.shape != (256, 3) or tab.dtype != np.uint8:
+            raise ValueError('lut must be uint8 [256,3]')
+    src = images.contiguous()
+    out = torch.empty((2 if two else 1, N, H, W, 3), dtype=torch.uint8, device=dev)
+    right = C.c_void_p(m.data_ptr() + 4 * h * w) if two else None
+    _lib.check(_lib.lib().acrmi_draw_heatmaps(_p(m), right, (2 if two else 1) * h * w, N, h, w, _p(vw), float(weight),
+                                              None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
+                                              _p(src), _p(out[0]), _p(out[1]) if two else None, H, W, _s(src)))
+    return out if two else out[0]

@@ -434,6 +434,59 @@ int acrmi_render(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_
                  const float* offsets_dev, const float* colors_host, float focal, float visible_weight,
                  const uint8_t* img_in_dev, uint8_t* img_out_dev, int H, int W, int32_t* ids_out_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Key-point skeleton and centre heat-map views: acr/visualization.py:228-300 (Visualizer.visulize_result_live with
+ * show_items 'pj2d' / 'centermap', vis_keypoints, make_heatmaps), drawn on the device.  Nothing of PIL or cv2 is used; the
+ * rules are (DESIGN.md "Key-point and heat-map views"):
+ *  Skeleton - integer throughout.  The 21 key points of a hand are re-ordered by mano2interhand_mapper
+ *   {4,3,2,1, 8,7,6,5, 12,11,10,9, 16,15,14,13, 20,19,18,17, 0}; the tree is mano/skeleton.txt: joint i has parent i + 1,
+ *   the base of each finger (i % 4 == 3) has parent 20, the wrist, which has none.  A key point is truncated toward zero to
+ *   the pixel k; a hand with a non-finite key point is not drawn; a primitive with an end point at |k| >= 16384 is dropped.
+ *   Disc of radius r at k: (x-kx)^2 + (y-ky)^2 <= r^2 + r.  Bone a -> b of width w, d = b - a, L2 = |d|^2 > 0, u = p - a:
+ *   0 <= u.d <= L2, |u x d| < 2^18 and 4 (u x d)^2 <= w^2 L2.  Painter's order: per hand (in hand order), per joint i = 0..20
+ *   with parent p: bone(i, p) in colour[p], disc(i) in colour[i], disc(p) in colour[p] (the wrist: its disc only); the last
+ *   primitive that covers a pixel wins and its colour is written opaque, every other pixel is the input byte for byte.
+ *  Heat map - fp32, every operation rounded on its own, in this order.  Canvas coordinate of pixel (x, y):
+ *   cx = (x + 0.5 - ox) / sx with the image's view row (sx, sy, ox, oy) (the one acrmi_rasterize takes), cx = (x + 0.5) *
+ *   (512 / W) without one; a pixel with cx or cy outside [0, 512) - and every pixel of a view with sx or sy not > 0 - keeps
+ *   the input.  s = max(cx * (w / 512) - 0.5, 0), i0 = min(int(s), w - 1), i1 = min(i0 + 1, w - 1), l1 = s - i0, l0 = 1 - l1,
+ *   the same in y; v = ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d); idx = int(min(max(v * 255, 0), 255)) (truncated; NaN -> 0);
+ *   out = floor(weight * LUT[idx] + (1 - weight) * img).  Default LUT [256][3], RGB, t = i / 255: red clamp(1.5 - |4t - 3|),
+ *   green clamp(1.5 - |4t - 2|), blue clamp(1.5 - |4t - 1|), clamped to [0, 1], byte = floor(255 v + 0.5) - which is the
+ *   integer clamp(383 - |4 i - 255 k|, 0, 255), k = 3, 2, 1.  A piece-wise linear "jet", NOT cv2.COLORMAP_JET byte for byte.
+ * No atomics on global memory: deterministic; a frame drawn alone equals the frame drawn in a batch; in place = out of place.
+ * ------------------------------------------------------------------------------------- */
+#define ACRMI_OVERLAY_SKELETON 0
+#define ACRMI_OVERLAY_CENTERMAP 1
+/* Pure host: the default tables in RGB order, or flipped (bgr != 0): colors_host [21][3] by skeleton joint (the values
+ * get_keypoint_rgb yields for mano/skeleton.txt), lut_host [256][3].  Either may be NULL. */
+int acrmi_overlay_tables(int bgr, uint8_t* colors_host, uint8_t* lut_host);
+/* kps_dev fp32 [n_hands,21,2] in pixels of the image drawn into, MANO joint order; hand_frame_dev int32 [n_hands] = the frame
+ * a hand is drawn into, < 0 (or >= n_frames) = not drawn; colors_host [21][3] bytes by skeleton joint in the image's channel
+ * order, NULL = the default table (flipped when bgr != 0); line_width 1..11, circle_rad 0..255; img_in_dev / img_out_dev
+ * uint8 [n_frames,H,W,3], may be the same buffer; H, W <= 16384, n_frames <= 65535. */
+int acrmi_draw_skeletons(const float* kps_dev, const int32_t* hand_frame_dev, int n_hands, const uint8_t* colors_host, int bgr,
+                         int line_width, int circle_rad, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H,
+                         int W, void* stream);
+/* maps_l_dev / maps_r_dev fp32: the [h,w] map of image i starts at element i * frame_stride (>= h * w); maps_r_dev and
+ * out_r_dev are both NULL for one view; view_dev [n,4] or NULL; weight in [0,1] (the reference: 0.7); lut_host [256][3] bytes
+ * in the image's channel order, NULL = the default (flipped when bgr != 0); img_in_dev, out_l_dev, out_r_dev uint8
+ * [n,H,W,3] - ONE launch reads the image once and writes both views; out_l_dev may be img_in_dev. */
+int acrmi_draw_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long long frame_stride, int n, int h, int w,
+                        const float* view_dev, float weight, const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev,
+                        uint8_t* out_l_dev, uint8_t* out_r_dev, int H, int W, void* stream);
+/* The outputs of acrmi_forward in, frames out, like acrmi_render.  what = ACRMI_OVERLAY_SKELETON: slots_dev [B,2,ACRMI_SLOT]
+ * (a hand is drawn when its ACRMI_SLOT_FLAG > 0.5) and pj2d_dev [B,2,21,2] - with offsets_dev NULL the projected key points
+ * `pj2d` in [-1,1], drawn at (pj2d + 1) / 2 * 512 on the 512 x 512 network input (acr/visualization.py:241); with
+ * offsets_dev [B,10] `pj2d_org`, pixels of the original frames; default colours, line_width = circle_rad = 3; out2_dev
+ * unused.  what = ACRMI_OVERLAY_CENTERMAP: the left / right centre maps the context's head buffers hold since the last
+ * program run, which must have been at batch B (a 16-bit storage program's maps are converted to fp32 inside the kernel),
+ * over the frames at weight 0.7 -> out_dev (left), out2_dev (right); the view of frame b comes from its offsets row as in
+ * acrmi_render (NULL: the network input); slots_dev / pj2d_dev unused.  bgr != 0: the default tables flipped.
+ * ACRMI_ESTATE before a program has run (acrmi_forward / acrmi_backbone_heads / acrmi_heads). */
+int acrmi_overlay(acrmi_ctx* ctx, int what, const float* slots_dev, const float* pj2d_dev, int B, const float* offsets_dev,
+                  int bgr, const uint8_t* img_in_dev, uint8_t* out_dev, uint8_t* out2_dev, int H, int W, void* stream);
+
 /* Multi-GPU (replaces nn.DataParallel's scatter/gather, acr/main.py:61): frames are sharded by the caller, one
  * process per GPU; the only collective is ONE all-gather per batch of each rank's flat result buffer
  * [slots | verts | joints] over RCCL/xGMI.  recv_dev holds n_ranks * n_floats floats, rank-major.
