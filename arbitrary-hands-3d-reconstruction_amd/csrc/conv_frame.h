@@ -27,9 +27,7 @@ __device__ __forceinline__ float vrelu1(float x) {
 // host-side state shared by the launchers of both translation units (defined in conv_mfma.hip)
 int conv_forced_cfg();                 // acrmi_tune key 0 (-1 = automatic)
 int conv_num_cus();                    // CU count of the current device (after conv_ensure_device_info)
-int conv_current_device();
-hipError_t conv_ensure_device_info();
-long conv_pick_grid(long total);
+hipError_t conv_ensure_device_info();  // launch_conv calls it before every dispatch; launch_pair1x1 for itself
 
 // Cache policy of the residual loads (aux operand of raw.buffer.load: 0 default, 2 slc = streaming): a residual
 // element is read exactly once per launch.  Measured (batch 64): the HBM-bound 64->256 1x1 + residual layer 0.611 ->
@@ -55,6 +53,28 @@ static void set_magics(ConvWork& wk) {
 __device__ __forceinline__ int fdiv(int n, unsigned long long magic) {
   return (int)(((unsigned long long)(unsigned)n * magic) >> 40);
 }
+
+// One kernel instantiation as its launcher names it: the host handle, the instantiation's own "dynamic LDS attribute set"
+// flags (one per device) and what ACRMI_DEBUG prints.  CONV_KERNEL(conv_x_kernel<...>) creates the flags where the
+// instantiation is named: every expansion has its own, and inside a template launcher every instantiation of it.
+struct ConvKernel {
+  void (*fn)(const ConvArgs, const ConvWork);
+  unsigned char* first_use;   // [MAX_DEVICES]
+  const char* name;           // the kernel expression as written ...
+  const char* where;          // ... and the launcher that names it (a template launcher: with its arguments' values)
+};
+#define CONV_KERNEL(...)                                                    \
+  ({                                                                        \
+    static unsigned char first_use_[MAX_DEVICES] = {};                      \
+    ConvKernel{__VA_ARGS__, first_use_, #__VA_ARGS__, __PRETTY_FUNCTION__}; \
+  })
+
+// The host path of every persistent conv kernel (defined in conv_mfma.hip; the caller holds launch_mutex(), as launch_conv
+// does).  The first use on a device sets the kernel's dynamic LDS size; then the work items - tiles_x * tiles_y tiles per
+// frame x a.B frames x nblk n-blocks x a.groups - are dealt to one persistent workgroup per CU (fewer when there are fewer
+// items).  nb_inner: ConvWork::nb_inner.
+hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, int tiles_x, int tiles_y, int nblk,
+                              const ConvArgs& a, hipStream_t s, int nb_inner = 1);
 
 // Workgroup b of a launch lands on XCD b % 8 (observed dispatch order on gfx950; used for speed only, never for
 // correctness).  A persistent workgroup walks items vb, vb + grid, vb + 2*grid, ...; with vb = b the 256 items in

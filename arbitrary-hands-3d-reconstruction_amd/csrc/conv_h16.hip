@@ -419,29 +419,13 @@ static hipError_t launch_h16_impl(const ConvArgs& a, hipStream_t s) {
   constexpr int PH = (TH - 1) * S + KS, PW = (TW - 1) * S + KS;
   constexpr size_t lds = (2 * (size_t)PH * PW * (CK + 4) + (size_t)WAVES_M * WAVES_N * 32 * 36) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the epilogue tiles must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (WAVES_M * WAVES_N + NLW) * 64;
-  auto kern = conv_h16_kernel<KS, S, TH, TW, WAVES_M, MT, WAVES_N, NTW, CK, NLW, ONE, BF, OUTF32, RING>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = conv_ensure_device_info()) != hipSuccess) return e;
+  int nblk = (a.n_tiles + WAVES_N * NTW - 1) / (WAVES_N * NTW), nb_inner = 1;
+  if (ONE && nblk > 1 && conv_forced_cfg() != 901) {   // all n-blocks of a tile from one patch
+    nb_inner = nblk;
+    nblk = 1;
   }
-  ConvWork wk;
-  wk.tiles_x = (a.Wo + TW - 1) / TW;
-  wk.tiles_per_frame = wk.tiles_x * ((a.Ho + TH - 1) / TH);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.n_tiles + WAVES_N * NTW - 1) / (WAVES_N * NTW);
-  if (ONE && wk.nblk > 1 && conv_forced_cfg() != 901) {   // all n-blocks of a tile from one patch
-    wk.nb_inner = wk.nblk;
-    wk.nblk = 1;
-  }
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)conv_pick_grid(wk.total)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_h16_kernel<KS, S, TH, TW, WAVES_M, MT, WAVES_N, NTW, CK, NLW, ONE, BF, OUTF32, RING>),
+                            (WAVES_M * WAVES_N + NLW) * 64, lds, (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, nblk, a, s, nb_inner);
 }
 
 // F32OK: the shape also exists with fp32 output (the head exits); the other shapes only ever write 16-bit maps
@@ -476,10 +460,6 @@ static hipError_t launch_h16(const ConvArgs& a, hipStream_t s) {
 // on the big tiles (the layers are HBM / L2 bound: two chunks of requests in flight instead of one).
 // fp32 output (a.out_f32; output AND residual fp32) exists for 1x1 and 3x3 stride-1 shapes: the head exits.
 hipError_t launch_conv_h16(ConvArgs a, hipStream_t s) {
-  {
-    hipError_t de = conv_ensure_device_info();
-    if (de != hipSuccess) return de;
-  }
   if ((a.in_cs & 1) || (a.in_coff & 1) || (a.groups > 1 && (a.Cin & 1))) return hipErrorInvalidValue;
   a.in_cs /= 2;
   a.in_coff /= 2;

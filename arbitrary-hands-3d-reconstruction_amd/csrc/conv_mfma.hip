@@ -475,53 +475,48 @@ bool first_use_on_device(unsigned char* flags) {
 // One persistent workgroup per CU.  (Two per CU were measured: the 384-thread workgroups do not become
 // co-resident on gfx950 even when LDS and registers would allow it - the second half of the grid simply runs
 // after the first - so k = 2 only adds a second prologue/tail; PMC: profiles/r01_pmc_wino_b2.txt.)
-static long pick_grid(long total, size_t lds_bytes) {
-  (void)lds_bytes;
+static long pick_grid(long total) {
   const long grid = g_num_cus_dev[current_device()];
   return grid > total ? total : grid;
 }
 
 int conv_forced_cfg() { return g_force_cfg; }
 int conv_num_cus() { return g_num_cus_dev[current_device()]; }
-int conv_current_device() { return current_device(); }
 hipError_t conv_ensure_device_info() { return ensure_device_info(); }
-long conv_pick_grid(long total) { return pick_grid(total, 0); }
 
-template <int TH, int TW, int WAVES_M, int WAVES_N, int CK, int NLW, int ABL = 0, int MINW = 1>
+hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, int tiles_x, int tiles_y, int nblk,
+                              const ConvArgs& a, hipStream_t s, int nb_inner) {
+  if (first_use_on_device(k.first_use)) {
+    const void* fn = reinterpret_cast<const void*>(k.fn);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (getenv("ACRMI_DEBUG")) {
+      hipFuncAttributes fa;
+      (void)hipFuncGetAttributes(&fa, fn);
+      fprintf(stderr, "[acrmi] %s in %s: threads %d lds %zu regs %d scratch %zu\n", k.name, k.where, threads, lds, fa.numRegs,
+              (size_t)fa.localSizeBytes);
+    }
+  }
+  ConvWork wk;
+  wk.tiles_x = tiles_x;
+  wk.tiles_per_frame = tiles_x * tiles_y;
+  wk.n_tiles_total = wk.tiles_per_frame * a.B;
+  wk.nblk = nblk;
+  wk.nb_inner = nb_inner;
+  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
+  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
+  set_magics(wk);
+  hipLaunchKernelGGL(k.fn, dim3((unsigned)pick_grid(wk.total)), dim3(threads), lds, s, a, wk);
+  return hipGetLastError();
+}
+
+template <int TH, int TW, int WAVES_M, int WAVES_N, int CK, int NLW>
 static hipError_t launch_wino(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)(TH + 2) * (TW + 2) * (CK + 4) * sizeof(float) +
                          2 * (size_t)(WAVES_M * WAVES_N) * 2 * 1024 * sizeof(float);   // 2 patch + 2 residual areas
   static_assert(lds <= 160 * 1024, "patch and residual buffers must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (WAVES_M * WAVES_N + NLW) * 64;
-  auto kern = conv_wino_kernel<TH, TW, WAVES_M, WAVES_N, CK, NLW, ABL, MINW>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      int occ = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NTHREADS, lds);
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino<%d,%d,%d,%d,%d,%d>: threads %d lds %zu regs %d occupancy(API) %d blocks/CU\n", TH, TW,
-              WAVES_M, WAVES_N, CK, NLW, NTHREADS, lds, fa.numRegs, occ);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = (a.Wo + TW - 1) / TW;
-  wk.tiles_per_frame = wk.tiles_x * ((a.Ho + TH - 1) / TH);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.n_tiles + WAVES_N - 1) / WAVES_N;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  long grid = pick_grid(wk.total, lds);
-  if (MINW >= 3) {   // register budget allows two co-resident workgroups per CU
-    const long g2 = 2L * g_num_cus_dev[current_device()];
-    grid = g2 > wk.total ? wk.total : g2;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_wino_kernel<TH, TW, WAVES_M, WAVES_N, CK, NLW>), (WAVES_M * WAVES_N + NLW) * 64, lds,
+                            (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, (a.n_tiles + WAVES_N - 1) / WAVES_N, a, s);
 }
 
 #include "conv_wino2.inc"

@@ -410,37 +410,16 @@ static bool pp2_ok(const ConvArgs& a) {
          (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
 }
 
-static hipError_t launch_pp2_impl(const ConvArgs& a, hipStream_t s, int NT, void (*kern)(const ConvArgs, const ConvWork),
-                                  unsigned char* init) {
-  const int ntr = NT >= 2 ? 2 : 1;
-  const size_t lds = (2 * (size_t)41 * 64 * 4 + 9 * (size_t)ntr * 32 * 32) * sizeof(float);
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_pp2<%d>: lds %zu regs %d scratch %zu\n", NT, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / 16;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / 8);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.Cout / 32) / NT;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+static constexpr size_t pp2_lds(int NT) {      // two patches + the exchange area (nine tiles per n-tile)
+  return (2 * (size_t)41 * 64 * 4 + 9 * (size_t)(NT >= 2 ? 2 : 1) * 32 * 32) * sizeof(float);
 }
-static_assert((2 * (size_t)41 * 64 * 4 + 9 * (size_t)2 * 32 * 32) * sizeof(float) <= 160 * 1024, "patches + exchange area must fit the 160 KiB LDS");
+static_assert(pp2_lds(2) <= 160 * 1024, "patches + exchange area must fit the 160 KiB LDS");
+static hipError_t launch_pp2_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
+  return launch_conv_kernel(k, 256, pp2_lds(NT), a.Wo / 16, a.Ho / 8, (a.Cout / 32) / NT, a, s);
+}
 static hipError_t launch_pp2(const ConvArgs& a, hipStream_t s) {
-  static unsigned char i2[MAX_DEVICES] = {}, i1[MAX_DEVICES] = {}, ix[MAX_DEVICES] = {}, ix2[MAX_DEVICES] = {};
   if (!pp2_ok(a)) return hipErrorInvalidValue;
   if (a.nxt > 0)      // + extra residual terms (HR fuse)
-    return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, conv_pp2_kernel<2, true>, ix2) : launch_pp2_impl(a, s, 1, conv_pp2_kernel<1, true>, ix);
-  return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, conv_pp2_kernel<2, false>, i2) : launch_pp2_impl(a, s, 1, conv_pp2_kernel<1, false>, i1);
+    return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, CONV_KERNEL(conv_pp2_kernel<2, true>)) : launch_pp2_impl(a, s, 1, CONV_KERNEL(conv_pp2_kernel<1, true>));
+  return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, CONV_KERNEL(conv_pp2_kernel<2, false>)) : launch_pp2_impl(a, s, 1, CONV_KERNEL(conv_pp2_kernel<1, false>));
 }

@@ -518,31 +518,9 @@ template <int NT, int CK, int NLW, bool ONE, bool ODD = false, bool DMA = false,
 static hipError_t launch_wino2_impl(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)10 * 18 * (CK + 4) + (NT == 1 ? 2 : 1) * 4 * (size_t)2 * NT * 32 * 36) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the exchange area must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (4 + NLW) * 64;
-  auto kern = conv_wino2_kernel<NT, CK, NLW, ONE, ODD, DMA, SPLIT>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino2<%d,%d,%d,%d>: threads %d lds %zu regs %d scratch %zu\n", NT, CK, NLW, (int)ONE,
-              NTHREADS, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = (a.Wo + 15) / 16;
-  wk.tiles_per_frame = wk.tiles_x * ((a.Ho + 7) / 8);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = ODD ? 1 : (a.n_tiles + NT - 1) / NT;   // ODD: the item's one regular tile carries the 33rd channel along
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  // ODD: the item's one regular tile carries the 33rd channel along
+  return launch_conv_kernel(CONV_KERNEL(conv_wino2_kernel<NT, CK, NLW, ONE, ODD, DMA, SPLIT>), (4 + NLW) * 64, lds, (a.Wo + 15) / 16,
+                            (a.Ho + 7) / 8, ODD ? 1 : (a.n_tiles + NT - 1) / NT, a, s);
 }
 
 // LDS-DMA loader waves where the input allows it (channel quads wholly inside / outside Cin); ACRMI_CONV_DMA=0 keeps the

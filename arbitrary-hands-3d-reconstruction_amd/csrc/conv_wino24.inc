@@ -366,23 +366,5 @@ static hipError_t launch_wino24(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)10 * 34 * 36 + 4 * (size_t)2 * 32 * 36) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the exchange area must fit the 160 KiB LDS");
   if (a.ks != 3 || a.stride != 1 || (a.cin8 * 8 + 31) / 32 < 2) return hipErrorInvalidValue;
-  constexpr int NTHREADS = (4 + NLW) * 64;
-  auto kern = conv_wino24_kernel<NLW>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-  }
-  ConvWork wk;
-  wk.tiles_x = (a.Wo + 31) / 32;
-  wk.tiles_per_frame = wk.tiles_x * ((a.Ho + 7) / 8);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = a.n_tiles;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_wino24_kernel<NLW>), (4 + NLW) * 64, lds, (a.Wo + 31) / 32, (a.Ho + 7) / 8, a.n_tiles, a, s);
 }

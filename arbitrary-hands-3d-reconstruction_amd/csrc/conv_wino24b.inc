@@ -528,44 +528,24 @@ static int wino24b_ok(const ConvArgs& a) {
   return 0;
 }
 
-static hipError_t launch_wino24b_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, void (*kern)(const ConvArgs, const ConvWork),
-                                      unsigned char* init) {
-  const int TH = TW == 32 ? 8 : 16, RS = TW == 32 ? 300 : 170;
-  const size_t lds = (2 * (size_t)(((TH + 2) * RS + 63) / 64) * 64 * 4 + 4 * (size_t)2 * NT * 32 * 32) * sizeof(float);
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino24b<%d,%d>: lds %zu regs %d scratch %zu\n", NT, TW, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / TW;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / TH);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.Cout / 32) / NT;      // (the packed weights pad Cout to whole 64-cout blocks: a.n_tiles may count a tile of zeros)
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+static constexpr int wino24b_th(int TW) { return TW == 32 ? 8 : 16; }
+static constexpr size_t wino24b_lds(int NT, int TW) {      // two patches (row stride 300 / 170 floats) + the exchange area
+  return (2 * (size_t)(((wino24b_th(TW) + 2) * (TW == 32 ? 300 : 170) + 63) / 64) * 64 * 4 + 4 * (size_t)2 * NT * 32 * 32) * sizeof(float);
 }
+static_assert(wino24b_lds(2, 32) <= 160 * 1024 && wino24b_lds(2, 16) <= 160 * 1024, "patches + exchange area must fit the 160 KiB LDS");
 // (plain functions, not a template over NT / TW: referenced only from a function template, hipcc left the host-side handles
 //  of the kernel instantiations undefined)
-static_assert((2 * (size_t)48 * 64 * 4 + 4 * (size_t)2 * 2 * 32 * 32) * sizeof(float) <= 160 * 1024, "patches + exchange area must fit the 160 KiB LDS");
+static hipError_t launch_wino24b_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, const ConvKernel& k) {
+  // (the packed weights pad Cout to whole 64-cout blocks: a.n_tiles may count a tile of zeros)
+  return launch_conv_kernel(k, 256, wino24b_lds(NT, TW), a.Wo / TW, a.Ho / wino24b_th(TW), (a.Cout / 32) / NT, a, s);
+}
 static hipError_t launch_wino24b(const ConvArgs& a, int tw, hipStream_t s) {
-  static unsigned char i232[MAX_DEVICES] = {}, i216[MAX_DEVICES] = {}, i132[MAX_DEVICES] = {}, i232o[MAX_DEVICES] = {},
-                       i132o[MAX_DEVICES] = {};
   const bool one = a.Cin == 32;
   if (a.Cout % 64 == 0) {
-    if (tw == 16) return one ? hipErrorInvalidValue : launch_wino24b_impl(a, s, 2, 16, conv_wino24b_kernel<2, 16>, i216);
-    return one ? launch_wino24b_impl(a, s, 2, 32, conv_wino24b_kernel<2, 32, true>, i232o)
-               : launch_wino24b_impl(a, s, 2, 32, conv_wino24b_kernel<2, 32>, i232);
+    if (tw == 16) return one ? hipErrorInvalidValue : launch_wino24b_impl(a, s, 2, 16, CONV_KERNEL(conv_wino24b_kernel<2, 16>));
+    return one ? launch_wino24b_impl(a, s, 2, 32, CONV_KERNEL(conv_wino24b_kernel<2, 32, true>))
+               : launch_wino24b_impl(a, s, 2, 32, CONV_KERNEL(conv_wino24b_kernel<2, 32>));
   }
-  return one ? launch_wino24b_impl(a, s, 1, 32, conv_wino24b_kernel<1, 32, true>, i132o)
-             : launch_wino24b_impl(a, s, 1, 32, conv_wino24b_kernel<1, 32>, i132);
+  return one ? launch_wino24b_impl(a, s, 1, 32, CONV_KERNEL(conv_wino24b_kernel<1, 32, true>))
+             : launch_wino24b_impl(a, s, 1, 32, CONV_KERNEL(conv_wino24b_kernel<1, 32>));
 }

@@ -458,26 +458,5 @@ static bool wino24c_ok(const ConvArgs& a) {
 static hipError_t launch_wino24c(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)47 * 64 * 4 + 2 * (size_t)24 * 256) * sizeof(float);
   static_assert(lds <= 160 * 1024, "patches + fragment buffers must fit the 160 KiB LDS");
-  static unsigned char init[MAX_DEVICES] = {};
-  auto kern = conv_wino24c_kernel;
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino24c: lds %zu regs %d scratch %zu\n", lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / 32;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / 8);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = a.Cout / 64;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_wino24c_kernel), 256, lds, a.Wo / 32, a.Ho / 8, a.Cout / 64, a, s);
 }

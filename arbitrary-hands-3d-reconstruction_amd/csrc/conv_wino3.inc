@@ -624,83 +624,34 @@ template <int NLW, bool DMA, bool RES>
 static hipError_t launch_wino3b_impl(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)18 * 18 * 36 + 16 * 2 * 2 * 256) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the layer's weights must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (4 + NLW) * 64;
-  auto kern = conv_wino3b_kernel<NLW, DMA, RES>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino3b<%d,%d>: threads %d lds %zu regs %d scratch %zu\n", NLW, (int)DMA, NTHREADS, lds,
-              fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / 16;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / 16);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = 1;
-  wk.total = wk.n_tiles_total;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_wino3b_kernel<NLW, DMA, RES>), (4 + NLW) * 64, lds, a.Wo / 16, a.Ho / 16, 1, a, s);
 }
 
 template <int TH, int NLW, bool PIPE, int LPRIO = 0, bool DMA = false, int NSW = 0, bool DUAL = false>
 static hipError_t launch_wino3_impl(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)(TH + 2) * 18 * 36 + 16 * 2 * 2 * 256 + (NSW > 0 ? 2 * TH * 16 * 32 : 0)) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers, the layer's weights and the staging tiles must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (TH / 2 + NLW + NSW) * 64;
-  auto kern = conv_wino3_kernel<TH, NLW, PIPE, LPRIO, DMA, NSW, DUAL>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_wino3<%d,%d,%d,sw %d>: threads %d lds %zu regs %d scratch %zu\n", TH, NLW, (int)PIPE, NSW,
-              NTHREADS, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / 16;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / TH);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = 1;
-  wk.total = wk.n_tiles_total;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_wino3_kernel<TH, NLW, PIPE, LPRIO, DMA, NSW, DUAL>), (TH / 2 + NLW + NSW) * 64, lds,
+                            a.Wo / 16, a.Ho / TH, 1, a, s);
 }
 
 static hipError_t launch_wino3(const ConvArgs& a, hipStream_t s) {
   if (!wino3_ok(a)) return hipErrorInvalidValue;
-  hipError_t e0 = ensure_device_info();
-  if (e0 != hipSuccess) return e0;
-  const ConvArgs& az = a;
   const bool dma_ok = conv_dma_ok(a);
   if (a.out2) {      // + the full-resolution HR fuse sum as a second output (store waves)
     if (!dma_ok || a.nxt < 1 || a.nxt > 3 || a.out2_cs % 4 || a.out2_coff % 4) return hipErrorInvalidValue;
-    return launch_wino3_impl<8, 2, true, 0, true, 2, true>(az, s);
+    return launch_wino3_impl<8, 2, true, 0, true, 2, true>(a, s);
   }
   // tuning variants (tools/conv_bench.py --cfg): register-staged loader at priority 0 / 3 / 1, one LDS-DMA loader
   // wave, 16x16-pixel items on 8 compute waves (two per SIMD, 168 registers: spills)
   if (g_force_cfg == 831) return launch_wino3_impl<8, 2, true, 0>(a, s);
   if (g_force_cfg == 833) return launch_wino3_impl<8, 2, true, 3>(a, s);
   if (g_force_cfg == 834) return launch_wino3_impl<8, 2, true, 1>(a, s);
-  if (dma_ok && g_force_cfg == 836) return launch_wino3_impl<8, 1, true, 0, true>(az, s);
+  if (dma_ok && g_force_cfg == 836) return launch_wino3_impl<8, 1, true, 0, true>(a, s);
   if (g_force_cfg == 832 && a.Ho % 16 == 0) return launch_wino3_impl<16, 4, false>(a, s);
   if (g_force_cfg == 837 && a.Ho % 16 == 0) {
-    if (a.res) return dma_ok ? launch_wino3b_impl<2, true, true>(az, s) : launch_wino3b_impl<2, false, true>(a, s);
-    return dma_ok ? launch_wino3b_impl<2, true, false>(az, s) : launch_wino3b_impl<2, false, false>(a, s);
+    if (a.res) return dma_ok ? launch_wino3b_impl<2, true, true>(a, s) : launch_wino3b_impl<2, false, true>(a, s);
+    return dma_ok ? launch_wino3b_impl<2, true, false>(a, s) : launch_wino3b_impl<2, false, false>(a, s);
   }
   // measured (batch 64, 32->32 @128x128, with / without residual; conv_wino2_kernel: 0.159 / 0.149 ms):
   //   register loader prio 3: 0.144 / 0.129    prio 0: 0.146 / 0.134 (patch 1.8k cycles late)
@@ -711,7 +662,7 @@ static hipError_t launch_wino3(const ConvArgs& a, hipStream_t s) {
   // 65 launches 7.24 ms with the 16x32 tile on the residual layers, 6.77 ms with the 8x16 items + store waves everywhere
   // (tools/ab_cfg.py, former default vs this one).  conv_wino3b_kernel stays reachable as --cfg 837.
   // store waves (conv_bench --cfg 839: without): the epilogue's stores leave the compute waves
-  if (dma_ok && g_force_cfg != 839) return launch_wino3_impl<8, 2, true, 0, true, 2>(az, s);
-  if (dma_ok) return launch_wino3_impl<8, 2, true, 0, true>(az, s);
+  if (dma_ok && g_force_cfg != 839) return launch_wino3_impl<8, 2, true, 0, true, 2>(a, s);
+  if (dma_ok) return launch_wino3_impl<8, 2, true, 0, true>(a, s);
   return launch_wino3_impl<8, 2, true, 3>(a, s);
 }

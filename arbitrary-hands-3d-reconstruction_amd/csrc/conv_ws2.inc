@@ -356,30 +356,14 @@ static hipError_t launch_ws2_impl(const ConvArgs& a, hipStream_t s) {
   constexpr int PH = (TH - 1) * S + KS, PW = (TW - 1) * S + KS;
   constexpr size_t lds = (2 * (size_t)PH * PW * (CK + 4) + (size_t)WAVES_M * WAVES_N * 32 * 36) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the epilogue tiles must fit the 160 KiB LDS");
-  constexpr int NTHREADS = (WAVES_M * WAVES_N + NLW) * 64;
-  auto kern = conv_ws2_kernel<KS, S, TH, TW, WAVES_M, MT, WAVES_N, NTW, CK, NLW, ONE, XT>;
-  static unsigned char init[MAX_DEVICES] = {};
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
+  if (XT && (a.Cout % 32 || a.out_cs % 4 || a.out_coff % 4)) return hipErrorInvalidValue;      // (the vector epilogue only)
+  int nblk = (a.n_tiles + WAVES_N * NTW - 1) / (WAVES_N * NTW), nb_inner = 1;
+  if (ONE && nblk > 1 && g_force_cfg != 901) {   // all n-blocks of a tile from one patch
+    nb_inner = nblk;
+    nblk = 1;
   }
-  ConvWork wk;
-  wk.tiles_x = (a.Wo + TW - 1) / TW;
-  wk.tiles_per_frame = wk.tiles_x * ((a.Ho + TH - 1) / TH);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.n_tiles + WAVES_N * NTW - 1) / (WAVES_N * NTW);
-  if (XT && (a.Cout % 32 || a.out_cs % 4 || (a.out_coff + 0) % 4)) return hipErrorInvalidValue;      // (the vector epilogue only)
-  if (ONE && wk.nblk > 1 && g_force_cfg != 901) {   // all n-blocks of a tile from one patch
-    wk.nb_inner = wk.nblk;
-    wk.nblk = 1;
-  }
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(NTHREADS), lds, s, a, wk);
-  return hipGetLastError();
+  return launch_conv_kernel(CONV_KERNEL(conv_ws2_kernel<KS, S, TH, TW, WAVES_M, MT, WAVES_N, NTW, CK, NLW, ONE, XT>),
+                            (WAVES_M * WAVES_N + NLW) * 64, lds, (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, nblk, a, s, nb_inner);
 }
 
 template <int KS, int S, int TH, int TW, int WAVES_M, int MT, int WAVES_N, int NTW, int CK, int NLW>

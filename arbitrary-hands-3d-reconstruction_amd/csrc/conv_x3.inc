@@ -426,42 +426,20 @@ static int x3_ok(const ConvArgs& a) {
   return 0;
 }
 
-static hipError_t launch_x3_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, void (*kern)(const ConvArgs, const ConvWork),
-                                 unsigned char* init) {
-  const size_t lds = (2 * (size_t)4 * 2 * 386 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_x3<%d,%d>: lds %zu regs %d scratch %zu\n", NT, TW, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / TW;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / (TW == 32 ? 8 : 16));
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.Cout / 32) / NT;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+static hipError_t launch_x3_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, const ConvKernel& k) {
+  constexpr size_t lds = (2 * (size_t)4 * 2 * 386 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
+  return launch_conv_kernel(k, 256, lds, a.Wo / TW, a.Ho / (TW == 32 ? 8 : 16), (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3(const ConvArgs& a, bool bf, hipStream_t s) {
-  static unsigned char init[10][MAX_DEVICES] = {};
   const int tw = x3_ok(a);
   if (!tw) return hipErrorInvalidValue;
   const bool n2 = a.Cout % 64 == 0;
   if (tw == 32) {
-    if (bf && n2 && g_force_cfg != 852) return launch_x3_impl(a, s, 2, 32, conv_x3_kernel<2, true, 32, true>, init[8]);
-    if (bf) return n2 ? launch_x3_impl(a, s, 2, 32, conv_x3_kernel<2, true>, init[0]) : launch_x3_impl(a, s, 1, 32, conv_x3_kernel<1, true>, init[1]);
-    if (n2 && g_force_cfg != 852) return launch_x3_impl(a, s, 2, 32, conv_x3_kernel<2, false, 32, true>, init[9]);
-    return n2 ? launch_x3_impl(a, s, 2, 32, conv_x3_kernel<2>, init[2]) : launch_x3_impl(a, s, 1, 32, conv_x3_kernel<1>, init[3]);
+    if (bf && n2 && g_force_cfg != 852) return launch_x3_impl(a, s, 2, 32, CONV_KERNEL(conv_x3_kernel<2, true, 32, true>));
+    if (bf) return n2 ? launch_x3_impl(a, s, 2, 32, CONV_KERNEL(conv_x3_kernel<2, true>)) : launch_x3_impl(a, s, 1, 32, CONV_KERNEL(conv_x3_kernel<1, true>));
+    if (n2 && g_force_cfg != 852) return launch_x3_impl(a, s, 2, 32, CONV_KERNEL(conv_x3_kernel<2, false, 32, true>));
+    return n2 ? launch_x3_impl(a, s, 2, 32, CONV_KERNEL(conv_x3_kernel<2>)) : launch_x3_impl(a, s, 1, 32, CONV_KERNEL(conv_x3_kernel<1>));
   }
-  if (bf) return n2 ? launch_x3_impl(a, s, 2, 16, conv_x3_kernel<2, true, 16>, init[4]) : launch_x3_impl(a, s, 1, 16, conv_x3_kernel<1, true, 16>, init[5]);
-  return n2 ? launch_x3_impl(a, s, 2, 16, conv_x3_kernel<2, false, 16>, init[6]) : launch_x3_impl(a, s, 1, 16, conv_x3_kernel<1, false, 16>, init[7]);
+  if (bf) return n2 ? launch_x3_impl(a, s, 2, 16, CONV_KERNEL(conv_x3_kernel<2, true, 16>)) : launch_x3_impl(a, s, 1, 16, CONV_KERNEL(conv_x3_kernel<1, true, 16>));
+  return n2 ? launch_x3_impl(a, s, 2, 16, CONV_KERNEL(conv_x3_kernel<2, false, 16>)) : launch_x3_impl(a, s, 1, 16, CONV_KERNEL(conv_x3_kernel<1, false, 16>));
 }

@@ -302,34 +302,12 @@ static bool x3p_ok(const ConvArgs& a) {
          (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
 }
 
-static hipError_t launch_x3p_impl(const ConvArgs& a, hipStream_t s, int NT, void (*kern)(const ConvArgs, const ConvWork),
-                                  unsigned char* init) {
-  const size_t lds = (2 * (size_t)4 * 2 * 258 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_x3p<%d>: lds %zu regs %d scratch %zu\n", NT, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = 1;
-  wk.tiles_per_frame = (a.Ho * a.Wo) / 256;
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.Cout / 32) / NT;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+static hipError_t launch_x3p_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
+  constexpr size_t lds = (2 * (size_t)4 * 2 * 258 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
+  return launch_conv_kernel(k, 256, lds, 1, (a.Ho * a.Wo) / 256, (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3p(const ConvArgs& a, bool bf, hipStream_t s) {
-  static unsigned char i2[MAX_DEVICES] = {}, i1[MAX_DEVICES] = {}, j2[MAX_DEVICES] = {}, j1[MAX_DEVICES] = {};
   if (!x3p_ok(a)) return hipErrorInvalidValue;
-  if (bf) return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, conv_x3p_kernel<2, true>, j2) : launch_x3p_impl(a, s, 1, conv_x3p_kernel<1, true>, j1);
-  return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, conv_x3p_kernel<2>, i2) : launch_x3p_impl(a, s, 1, conv_x3p_kernel<1>, i1);
+  if (bf) return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, CONV_KERNEL(conv_x3p_kernel<2, true>)) : launch_x3p_impl(a, s, 1, CONV_KERNEL(conv_x3p_kernel<1, true>));
+  return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, CONV_KERNEL(conv_x3p_kernel<2>)) : launch_x3p_impl(a, s, 1, CONV_KERNEL(conv_x3p_kernel<1>));
 }

@@ -380,38 +380,16 @@ static bool x3s2_ok(const ConvArgs& a) {
          (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
 }
 
-static hipError_t launch_x3s2_impl(const ConvArgs& a, hipStream_t s, int NT, void (*kern)(const ConvArgs, const ConvWork),
-                                   unsigned char* init) {
-  const size_t lds = (2 * (size_t)2 * 2 * 1106 * 4 + 4 * (size_t)32 * 32) * sizeof(float);
-  static_assert((2 * 2 * 2 * 1106 * 4 + 4 * 32 * 32) * 4 <= 160 * 1024, "two step buffers and the transposition tiles must fit the LDS");
-  if (first_use_on_device(init)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if ((e = ensure_device_info()) != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-      fprintf(stderr, "[acrmi] conv_x3s2<%d>: lds %zu regs %d scratch %zu\n", NT, lds, fa.numRegs, (size_t)fa.localSizeBytes);
-    }
-  }
-  ConvWork wk;
-  wk.tiles_x = a.Wo / 32;
-  wk.tiles_per_frame = wk.tiles_x * (a.Ho / 8);
-  wk.n_tiles_total = wk.tiles_per_frame * a.B;
-  wk.nblk = (a.Cout / 32) / NT;
-  wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
-  set_magics(wk);
-  hipLaunchKernelGGL(kern, dim3((unsigned)pick_grid(wk.total, lds)), dim3(256), lds, s, a, wk);
-  return hipGetLastError();
+static hipError_t launch_x3s2_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
+  constexpr size_t lds = (2 * (size_t)2 * 2 * 1106 * 4 + 4 * (size_t)32 * 32) * sizeof(float);
+  static_assert(lds <= 160 * 1024, "two step buffers and the transposition tiles must fit the LDS");
+  return launch_conv_kernel(k, 256, lds, a.Wo / 32, a.Ho / 8, (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3s2(const ConvArgs& a, bool bf, hipStream_t s) {
-  static unsigned char init[4][MAX_DEVICES] = {};
   if (!x3s2_ok(a)) return hipErrorInvalidValue;
   // (single-chunk items, Cin = 32: the two-n-tile instantiation keeps ~100 values in scratch there and every scratch access
   //  waits behind the patch loads in flight - cfg 851 selects it anyway)
   const bool n2 = a.Cout % 64 == 0 && (a.Cin > 32 || g_force_cfg == 851);
-  if (bf) return n2 ? launch_x3s2_impl(a, s, 2, conv_x3s2_kernel<2, true>, init[0]) : launch_x3s2_impl(a, s, 1, conv_x3s2_kernel<1, true>, init[1]);
-  return n2 ? launch_x3s2_impl(a, s, 2, conv_x3s2_kernel<2>, init[2]) : launch_x3s2_impl(a, s, 1, conv_x3s2_kernel<1>, init[3]);
+  if (bf) return n2 ? launch_x3s2_impl(a, s, 2, CONV_KERNEL(conv_x3s2_kernel<2, true>)) : launch_x3s2_impl(a, s, 1, CONV_KERNEL(conv_x3s2_kernel<1, true>));
+  return n2 ? launch_x3s2_impl(a, s, 2, CONV_KERNEL(conv_x3s2_kernel<2>)) : launch_x3s2_impl(a, s, 1, CONV_KERNEL(conv_x3s2_kernel<1>));
 }
