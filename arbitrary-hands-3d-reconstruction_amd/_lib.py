@@ -59,7 +59,9 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_decode_gated', 'acrmi_decode_maps_gated', 'acrmi_share_weights', 'acrmi_mano_rotmat', 'acrmi_heads',
            'acrmi_backbone_channels', 'acrmi_check_range', 'acrmi_prior_gate', 'acrmi_preprocess_frames',
            'acrmi_mesh_topology', 'acrmi_render_workspace', 'acrmi_rasterize', 'acrmi_load_faces', 'acrmi_render',
-           'acrmi_overlay_tables', 'acrmi_draw_skeletons', 'acrmi_draw_heatmaps', 'acrmi_overlay']
+           'acrmi_overlay_tables', 'acrmi_draw_skeletons', 'acrmi_draw_heatmaps', 'acrmi_overlay',
+           'acrmi_streams_create', 'acrmi_streams_destroy', 'acrmi_streams_reset', 'acrmi_smooth_streams',
+           'acrmi_forward_streams']
 
 _lib = None
 
@@ -142,6 +144,12 @@ def lib():
     L.acrmi_set_option_f.argtypes = [vp, i32, C.c_float]
     L.acrmi_smooth.argtypes = [vp, f32p, i32, vp]
     L.acrmi_smooth_reset.argtypes = [vp, vp]
+    L.acrmi_streams_create.argtypes = [C.POINTER(vp), i32, i32]
+    L.acrmi_streams_destroy.argtypes = [vp]
+    L.acrmi_streams_destroy.restype = None
+    L.acrmi_streams_reset.argtypes = [vp, vp, i32, vp]
+    L.acrmi_smooth_streams.argtypes = [vp, vp, f32p, i32, vp, vp]
+    L.acrmi_forward_streams.argtypes = [vp, vp, vp, u8p, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
     L.acrmi_comm_unique_id.argtypes = [vp]
     L.acrmi_comm_init.argtypes = [vp, i32, i32, vp]
     L.acrmi_comm_destroy.argtypes = [vp]
@@ -162,7 +170,7 @@ def lib():
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
-                        'acrmi_render_workspace'):
+                        'acrmi_render_workspace', 'acrmi_streams_destroy'):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -3,6 +3,7 @@
     acr = ACR(args_set)                      # builds the model, loads the checkpoint + MANO tables
     results = acr(bgr_frame, path)           # {path: [per-hand dict of float16 arrays]}  or  {path: {}}
     results = acr.forward_batch(frames, paths)   # the batched form the reference never had
+    results = acr.forward_batch(frames, paths, streams=camera_ids)   # -t: every frame smoothed with its camera's filters
 
 Drawing (acr/visualization.py:100-218 with show_items=['mesh'], acr/renderer/*): with `renderer='hip'` the hand meshes
 are rasterised over the frames on the GPU (csrc/render.hip; conventions in DESIGN.md "Rendering") -
@@ -59,6 +60,7 @@ class ACR(object):
         self._device = device
         self.rendering = None      # renderer='hip': {'mesh_rendering_orgimgs': [frame]} of the last forward()
         self.show_items = ['mesh']      # the views `forward` leaves on `rendering` (SHOW_ITEMS); the reference's default
+        self.stream_table = None        # forward_batch(..., streams=): One-Euro state per video stream (engine.StreamTable)
         self._build_model_(state_dict, mano_tables, device, max_batch)
         if self.temporal_optimization:
             # acr/main.py:45-47: one filter set per hand type; the state lives in the engine's context
@@ -174,8 +176,35 @@ class ACR(object):
     __call__ = forward
 
     @torch.no_grad()
+    def reset_streams(self, ids=None):
+        """The listed video streams of forward_batch(..., streams=) - all of them when ids is None - start a new sequence
+        (a new video behind a camera id; the reference builds new filters per video, acr/main.py:50-53)."""
+        if self.stream_table is not None:
+            self.stream_table.reset(ids)
+
+    def close_streams(self):
+        """Frees the stream table; the next forward_batch(..., streams=) creates a new one (every stream fresh, and
+        `max_streams` may differ)."""
+        table, self.stream_table = self.stream_table, None
+        if table is not None:
+            table.close()
+
+    def _streams_for(self, streams, max_streams, B):
+        """forward_batch's `streams=`: the host ids and the table this object owns (created on first use; it is not the
+        model's, so it survives load_state_dict)."""
+        from ..engine import StreamTable, stream_ids
+        if not self.temporal_optimization:
+            raise ValueError('streams= smooths per video stream: it needs temporal_optimization (-t)')
+        ids = stream_ids(streams, B)
+        if self.stream_table is None:
+            self.stream_table = StreamTable(self._device, 256 if max_streams is None else max_streams)
+        elif max_streams is not None and int(max_streams) != self.stream_table.capacity:
+            raise ValueError('the stream table holds %d streams (max_streams=%d)' % (self.stream_table.capacity, max_streams))
+        return ids, self.stream_table
+
+    @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
-                      render_bgr=False, show_items=None):
+                      render_bgr=False, show_items=None, streams=None, max_streams=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -190,23 +219,28 @@ class ACR(object):
         The return value is then (results, rendered); `results` is what it is without `render`.
         show_items: names from SHOW_ITEMS - the views to draw over `render` instead of the meshes alone; the return value is
         then (results, {name: frames}): 'mesh' as above, 'pj2d' the key-point skeletons, 'centermap' the left and right centre
-        heat maps as [2,B,H,W,3] (a list of [2,H_i,W_i,3] for a list of frames), 'org_img' the frames themselves."""
+        heat maps as [2,B,H,W,3] (a list of [2,H_i,W_i,3] for a list of frames), 'org_img' the frames themselves.
+        streams (needs -t): the video stream (camera) of each frame, ints in [0, max_streams), -1 = do not smooth this frame -
+        every frame is smoothed with the One-Euro state of ITS stream (acr/main.py:69-83 per video) instead of the batch being
+        one video; the state lives in a table of max_streams streams (default 256, fixed when the first such call creates
+        it) that this object owns across load_state_dict; reset_streams() starts streams anew."""
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
-        eng = self.model.engine(rgb_u8_frames.shape[0])
-        semantics = batch_semantics or self.model._result_parser.batch_semantics
         B = rgb_u8_frames.shape[0]
+        ids, table = (None, None) if streams is None else self._streams_for(streams, max_streams, B)
+        eng = self.model.engine(B)
+        semantics = batch_semantics or self.model._result_parser.batch_semantics
         render_offsets = offsets
         if offsets is None:
             offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
         eng.set_point_heads(point_heads)
         # frames of the batch = one video stream, in order (smooth_coeff travels with the call: a reloaded checkpoint
-        # builds a new context)
-        eng.set_temporal(bool(self.temporal_optimization), smooth_coeff=self._args.smooth_coeff)
+        # builds a new context); with `streams` the table holds the state and the frames are not one stream
+        eng.set_temporal(bool(self.temporal_optimization) and ids is None, smooth_coeff=self._args.smooth_coeff)
         eng.set_batch_semantics(semantics)
         try:
-            out = eng.forward(rgb_u8_frames, offsets=offsets, project=True)
+            out = eng.forward(rgb_u8_frames, offsets=offsets, project=True, streams=ids, table=table)
         finally:
             eng.set_point_heads(False)
             eng.set_temporal(False)
@@ -297,18 +331,19 @@ class ACR(object):
         return drawn
 
 
-def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None):
+def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
     render=True: -> (results, frames with the hand meshes drawn over them: a tensor like the input, or a list in input order);
-    with show_items (names from SHOW_ITEMS) -> (results, {name: frames}) as forward_batch."""
+    with show_items (names from SHOW_ITEMS) -> (results, {name: frames}) as forward_batch.  streams / max_streams: as
+    forward_batch."""
     from .utils import img_preprocess_gpu
     meta = img_preprocess_gpu(bgr_frames_dev, paths)
     if show_items is not None and not render:
         raise ValueError('show_items needs render=True')
     return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=bgr_frames_dev if render else None,
-                              render_bgr=True, show_items=show_items)
+                              render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
 
 
 ACR.forward_raw_batch = _forward_raw_batch

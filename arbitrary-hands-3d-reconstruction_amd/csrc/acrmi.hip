@@ -61,7 +61,7 @@ void acrmi_destroy(acrmi_ctx* c) {
   }
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   release_weights(c);
-  if (c->smooth_state) (void)hipFree(c->smooth_state);
+  acrmi_streams_destroy(c->own_streams);
   if (c->render_ws) (void)hipFree(c->render_ws);
   for (int32_t* p : c->faces_topo)
     if (p) (void)hipFree(p);
@@ -250,35 +250,155 @@ int acrmi_set_option_f(acrmi_ctx* c, int option, float value) {
 }
 
 // ---- temporal smoothing (acr/main.py:69-83) -------------------------------------------------------------
-constexpr size_t SMOOTH_STATE_BYTES = 2 * 3 * 64 * sizeof(float) + 2 * sizeof(int);
-
-int acrmi_smooth_reset(acrmi_ctx* c, void* stream) {
-  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_smooth_reset: ctx is NULL");
-  ON_DEVICE(c);
-  if (!c->smooth_state) HIPCHK(c, hipMalloc(&c->smooth_state, SMOOTH_STATE_BYTES));
-  HIPCHK(c, hipMemsetAsync(c->smooth_state, 0, SMOOTH_STATE_BYTES, (hipStream_t)stream));
+// shared: the table carries the event that orders the launches of different contexts and is zeroed before the call returns;
+// else (a context's own table) it is zeroed on `stream`, where the context's first smoothing launch follows it.
+static int streams_create(acrmi_streams** out, int device, int capacity, bool shared, hipStream_t stream) {
+  if (!out) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: out is NULL");
+  if (capacity < 1 || capacity > SMOOTH_MAX_STREAMS)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: capacity %d outside 1..%d", capacity, SMOOTH_MAX_STREAMS);
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) return fail(nullptr, ACRMI_EHIP, "acrmi_streams_create: no HIP device (%s)", hipGetErrorString(e));
+  if (device < 0 || device >= n) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: device %d of %d", device, n);
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(g.err));
+  acrmi_streams* t = new acrmi_streams();
+  t->device = device;
+  t->capacity = capacity;
+  t->last.assign((size_t)capacity, -1);
+  const size_t state_bytes = (size_t)capacity * 2 * 3 * 64 * sizeof(float), bytes = state_bytes + (size_t)capacity * 2 * sizeof(int);
+  e = hipMalloc(&t->state, bytes);
+  if (e == hipSuccess && !shared) e = hipMemsetAsync(t->state, 0, bytes, stream);
+  if (e == hipSuccess && shared) {
+    // zeroed = every stream starts fresh; complete before the call returns: the streams that will use the table are not
+    // known here and need not be ordered behind the null stream.  Once per table.
+    e = hipMemset(t->state, 0, bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->order, hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {
+    if (t->state) (void)hipFree(t->state);
+    delete t;
+    return fail(nullptr, ACRMI_EHIP, "acrmi_streams_create: %d streams: %s", capacity, hipGetErrorString(e));
+  }
+  t->init = reinterpret_cast<int*>(reinterpret_cast<char*>(t->state) + state_bytes);
+  *out = t;
   return ACRMI_OK;
 }
 
-int acrmi_smooth(acrmi_ctx* c, float* slots, int B, void* stream) {
-  if (!c || !slots || B <= 0) return fail(c, ACRMI_EINVAL, "acrmi_smooth: bad arguments");
-  ON_DEVICE(c);
-  if (!c->smooth_state) {
-    int r = acrmi_smooth_reset(c, stream);
-    if (r) return r;
+int acrmi_streams_create(acrmi_streams** out, int device, int capacity) { return streams_create(out, device, capacity, true, nullptr); }
+
+void acrmi_streams_destroy(acrmi_streams* t) {
+  if (!t) return;
+  DeviceGuard guard_(t->device);
+  if (t->order) (void)hipEventDestroy(t->order);
+  (void)hipFree(t->state);      // (waits for the launches that still use the table)
+  delete t;
+}
+
+// One call's launches on a table: the table's lock is held, `s` waits for the table's ordering event before them and
+// done() records it behind them - also behind a call that failed midway, so that the next context still queues behind
+// whatever that call launched.
+struct TableOrder {
+  acrmi_streams* t;
+  hipStream_t s;
+  std::lock_guard<std::mutex> lock;
+  hipError_t err;
+  TableOrder(acrmi_streams* table, hipStream_t stream)
+      : t(table), s(stream), lock(table->mu), err(table->order ? hipStreamWaitEvent(stream, table->order, 0) : hipSuccess) {}
+  hipError_t done(hipError_t e) {
+    if (t->order && err == hipSuccess) {
+      const hipError_t r = hipEventRecord(t->order, s);
+      if (e == hipSuccess) e = r;
+    }
+    return e;
   }
+};
+
+int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids, int n, void* stream) {
+  if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_reset: bad arguments");
+  if (ids) {
+    const int bad = smooth_bad_id(ids, n, t->capacity, 0);
+    if (bad >= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_reset: ids[%d] = %d outside 0..%d", bad, ids[bad], t->capacity - 1);
+  }
+  DeviceGuard guard_(t->device);
+  if (guard_.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice(%d): %s", t->device, hipGetErrorString(guard_.err));
+  // a stream whose init flags are clear passes its next sample through and overwrites the rest of its row with it
+  TableOrder ord(t, (hipStream_t)stream);
+  hipError_t e = ord.err;
+  if (e == hipSuccess && !ids) e = hipMemsetAsync(t->init, 0, (size_t)t->capacity * 2 * sizeof(int), (hipStream_t)stream);
+  for (int i0 = 0; ids && e == hipSuccess && i0 < n; i0 += SMOOTH_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < SMOOTH_FRAMES_PER_LAUNCH ? n - i0 : SMOOTH_FRAMES_PER_LAUNCH;
+    SmoothIds k{};
+    memcpy(k.id, ids + i0, (size_t)m * sizeof(int32_t));
+    e = launch_smooth_reset(k, m, t->init, (hipStream_t)stream);
+  }
+  e = ord.done(e);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_streams_reset: %s", hipGetErrorString(e));
+}
+
+// ids (may be null: every frame is stream 0) are valid for t.  Successive launches of SMOOTH_FRAMES_PER_LAUNCH frames on the
+// stream, in frame order: a stream's chain continues in the next launch from the row the previous one wrote.
+static int smooth_on(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, const int32_t* ids, hipStream_t stream) {
   SmoothArgs a{};
-  a.slots = slots; a.B = B;
-  a.state = c->smooth_state;
-  a.init = reinterpret_cast<int*>(c->smooth_state + 2 * 3 * 64);
+  a.state = t->state;
+  a.init = t->init;
   // create_OneEuroFilter (acr/utils.py:1472-1473): poses / global_orient (smooth_coeff, 0.7), betas (0.6, 0.7);
   // dcutoff 1.0, freq 30.  The derivative filter's alpha is a python double rounded once when it meets the tensor.
   a.mincutoff = c->smooth_coeff; a.mincutoff_betas = 0.6f; a.beta = 0.7f; a.freq = 30.f;
   const double te = 1.0 / 30.0, tau = 1.0 / (2 * M_PI * 1.0), alpha_d = 1.0 / (1.0 + tau / te);
   a.alpha_d = (float)alpha_d; a.one_minus_alpha_d = (float)(1.0 - alpha_d);
   a.two_pi = (float)(2 * M_PI); a.te = (float)te;
-  HIPCHK(c, launch_smooth(a, (hipStream_t)stream));
+  TableOrder ord(t, stream);
+  hipError_t e = ord.err;
+  for (int f0 = 0; e == hipSuccess && f0 < B; f0 += SMOOTH_FRAMES_PER_LAUNCH) {
+    const int m = B - f0 < SMOOTH_FRAMES_PER_LAUNCH ? B - f0 : SMOOTH_FRAMES_PER_LAUNCH;
+    const int n_streams = smooth_plan(ids ? ids + f0 : nullptr, m, &a.b, t->last.data());
+    if (!n_streams) continue;      // every frame of this launch is left alone
+    a.slots = slots + (size_t)f0 * 2 * ACRMI_SLOT;
+    e = launch_smooth(a, n_streams, stream);
+  }
+  e = ord.done(e);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "smoothing: %s", hipGetErrorString(e));
+}
+
+// what acrmi_smooth_streams and acrmi_forward_streams check before anything is launched
+static int check_streams(acrmi_ctx* c, const acrmi_streams* t, const int32_t* ids, int B, const char* who) {
+  if (!t || !ids || B <= 0) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (t->device != c->device) return fail(c, ACRMI_EINVAL, "%s: the table is on device %d, the context on %d", who, t->device, c->device);
+  const int bad = smooth_bad_id(ids, B, t->capacity, -1);
+  if (bad >= 0) return fail(c, ACRMI_EINVAL, "%s: ids[%d] = %d outside -1..%d", who, bad, ids[bad], t->capacity - 1);
   return ACRMI_OK;
+}
+
+int acrmi_smooth_streams(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, const int32_t* ids, void* stream) {
+  if (!c || !slots) return fail(c, ACRMI_EINVAL, "acrmi_smooth_streams: bad arguments");
+  const int r = check_streams(c, t, ids, B, "acrmi_smooth_streams");
+  if (r) return r;
+  ON_DEVICE(c);
+  return smooth_on(c, t, slots, B, ids, (hipStream_t)stream);
+}
+
+int acrmi_smooth_reset(acrmi_ctx* c, void* stream) {
+  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_smooth_reset: ctx is NULL");
+  if (!c->own_streams) {      // (a new table is zeroed, on `stream`)
+    const int r = streams_create(&c->own_streams, c->device, 1, false, (hipStream_t)stream);
+    if (r) c->err = g_err;
+    return r;
+  }
+  const int r = acrmi_streams_reset(c->own_streams, nullptr, 0, stream);
+  if (r) c->err = g_err;
+  return r;
+}
+
+int acrmi_smooth(acrmi_ctx* c, float* slots, int B, void* stream) {
+  if (!c || !slots || B <= 0) return fail(c, ACRMI_EINVAL, "acrmi_smooth: bad arguments");
+  ON_DEVICE(c);
+  if (!c->own_streams) {
+    int r = acrmi_smooth_reset(c, stream);
+    if (r) return r;
+  }
+  return smooth_on(c, c->own_streams, slots, B, nullptr, (hipStream_t)stream);
 }
 
 int acrmi_profile_ops(acrmi_ctx* c, const uint8_t* img, int B, float* ms_out, int n_ms, void* stream) {
@@ -464,7 +584,8 @@ int acrmi_backbone_channels(acrmi_ctx* c) {
 
 // decode + MANO of acrmi_forward on one stream
 static int forward_tail(acrmi_ctx* c, int B, const float* offsets, float* slots, float* verts, float* joints,
-                        float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream) {
+                        float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream, acrmi_streams* table = nullptr,
+                        const int32_t* ids = nullptr) {
   int r = acrmi_decode(c, B, slots, stream);
   if (r) return r;
   if (c->batch_prior && B > 1) {
@@ -473,7 +594,10 @@ static int forward_tail(acrmi_ctx* c, int B, const float* offsets, float* slots,
     HIPCHK(c, launch_prior_gate(slots, B, c->gate_buf, stream));
     if ((r = acrmi_decode_gated(c, B, c->gate_buf, slots, stream))) return r;
   }
-  if (c->temporal && (r = acrmi_smooth(c, slots, B, stream))) return r;   // acr/main.py:69-83, before MANO
+  // acr/main.py:69-83, before MANO: per stream of the caller's table, or (ACRMI_OPT_TEMPORAL) the frames as one stream
+  if (table) {
+    if ((r = smooth_on(c, table, slots, B, ids, stream))) return r;
+  } else if (c->temporal && (r = acrmi_smooth(c, slots, B, stream))) return r;
   ManoArgs m{};
   m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
   m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
@@ -497,6 +621,17 @@ int acrmi_forward(acrmi_ctx* c, const uint8_t* img, int B, const float* offsets,
   int r = run_program(c, img, B, stream, c->point_heads);
   if (r) return r;
   return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+}
+
+int acrmi_forward_streams(acrmi_ctx* c, acrmi_streams* t, const int32_t* ids, const uint8_t* img, int B, const float* offsets,
+                          float* slots, float* verts, float* joints, float* verts_camed, float* pj2d, float* pj2d_org, void* stream) {
+  if (!c || !slots || !verts || !joints) return fail(c, ACRMI_EINVAL, "acrmi_forward_streams: bad arguments");
+  int r = check_streams(c, t, ids, B, "acrmi_forward_streams");
+  if (r) return r;
+  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_streams: MANO tables not loaded");
+  ON_DEVICE(c);
+  if ((r = run_program(c, img, B, stream, c->point_heads))) return r;
+  return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream, t, ids);
 }
 
 // ---- mesh overlay (csrc/render.hip) --------------------------------------------------------------------------------

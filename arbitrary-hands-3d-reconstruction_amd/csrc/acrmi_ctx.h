@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,20 @@ struct Schedule {
   std::vector<std::vector<int>> wait;
   std::vector<char> signal;
 };
+// One-Euro filter state of `capacity` video streams (acrmi_streams_create), owned outside any context: the contexts of a
+// pool share one, and it outlives a context that a checkpoint reload replaces.
+struct acrmi_streams {
+  int device = 0;
+  int capacity = 0;
+  float* state = nullptr;       // [capacity][2 hands][x_raw | x_filt | dx_filt][64], then the init flags int [capacity][2]
+  int* init = nullptr;
+  // Every launch that touches the table makes its stream wait for `order` and records it again, under `mu`: contexts on
+  // different streams update the table in the order of their calls.  null: a context's own table (one stream at a time).
+  hipEvent_t order = nullptr;
+  std::mutex mu;
+  std::vector<int32_t> last;    // smooth_plan's scratch, all -1 between calls
+};
+
 struct acrmi_ctx {
   int device = 0;
   std::string err;
@@ -81,7 +96,7 @@ struct acrmi_ctx {
   int center_idx = 9;           // < 0: no root alignment
   bool temporal = false;
   float smooth_coeff = 4.0f;
-  float* smooth_state = nullptr;   // [2][3][64] floats + 2 ints (One-Euro state of one video stream)
+  acrmi_streams* own_streams = nullptr;   // acrmi_smooth / ACRMI_OPT_TEMPORAL: this context's one-row table (one video stream)
   // mesh overlay (acrmi_load_faces / acrmi_render): one topology blob per side on the device, and the scratch of a call
   // (per-mesh frame / topology index / colour, per-frame viewport, the rasteriser's workspace), grown on demand
   int32_t* faces_topo[2] = {nullptr, nullptr};

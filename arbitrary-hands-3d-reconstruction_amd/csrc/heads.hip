@@ -489,76 +489,99 @@ hipError_t launch_prior_gate(const float* slots, int B, int* gate, hipStream_t s
 
 // ------------------------------------------------------------------------------------------------
 // Temporal smoothing between decode and MANO (acr/main.py:69-83, acr/utils.py:1466-1527): one One-Euro filter set
-// per hand type (poses[3:48], betas, and the global orientation as a 3x3 rotation matrix), applied to the frames of
-// ONE video stream in order.  State (per hand: x_raw / x_filt / dx_filt of 64 elements + an init flag) lives in the
-// context.  Element e of a hand: 0..44 finger pose, 45..54 betas, 55..63 rotation-matrix entries.
+// per hand type (poses[3:48], betas, and the global orientation as a 3x3 rotation matrix) and per VIDEO STREAM.  The
+// state of a stream (per hand: x_raw / x_filt / dx_filt of 64 elements + an init flag) is one row of a stream table
+// (acrmi_streams; the context's own one-row table for acrmi_smooth).  Element e of a hand: 0..44 finger pose, 45..54
+// betas, 55..63 rotation-matrix entries.
 // Arithmetic follows torch's: python scalars meet float32 tensors as float32; the first sample passes through.
 // ------------------------------------------------------------------------------------------------
+struct SmoothState {
+  float x_raw, x_filt, dx_filt;
+  int init;
+};
+// One frame of one stream: wave = hand type h, lane = element e; rot = the workgroup's two 3x3 scratch matrices.  Called by
+// all 128 threads (three barriers).
+__device__ __forceinline__ void smooth_frame(const SmoothArgs& a, float* sl, int h, int e, float mincut, float (*rot)[9],
+                                             SmoothState& st) {
+  const bool on = sl[ACRMI_SLOT_FLAG] > 0.5f;     // block-uniform per hand (wave = hand); false for a NaN flag
+  if (on && e == 55) {      // batch_rodrigues (acr/utils.py:602-616) + quat2mat (:618-638) of the global orientation
+    const float ax = sl[ACRMI_SLOT_POSES], ay = sl[ACRMI_SLOT_POSES + 1], az = sl[ACRMI_SLOT_POSES + 2];
+    const float ex = ax + 1e-8f, ey = ay + 1e-8f, ez = az + 1e-8f;
+    const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
+    const float nx = ax / angle, ny = ay / angle, nz = az / angle;
+    const float half = angle * 0.5f;
+    const float sn = sinf(half);
+    float w = cosf(half), x = sn * nx, y = sn * ny, z = sn * nz;
+    const float qn = sqrtf(w * w + x * x + y * y + z * z);
+    w /= qn; x /= qn; y /= qn; z /= qn;
+    const float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
+    const float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
+    float* R = rot[h];
+    R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;    R[2] = 2 * wy + 2 * xz;
+    R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;  R[5] = 2 * yz - 2 * wx;
+    R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;    R[8] = w2 - x2 - y2 + z2;
+  }
+  __syncthreads();
+  if (on) {
+    const float x = e < 45 ? sl[ACRMI_SLOT_POSES + 3 + e] : (e < 55 ? sl[ACRMI_SLOT_BETAS + (e - 45)] : rot[h][e - 55]);
+    float s;
+    if (!st.init) {
+      s = x;
+      st.dx_filt = 0.f;
+    } else {
+      const float dx = (x - st.x_raw) * a.freq;
+      const float edx = a.alpha_d * dx + a.one_minus_alpha_d * st.dx_filt;
+      const float cutoff = mincut + a.beta * fabsf(edx);
+      const float tau = 1.0f / (a.two_pi * cutoff);
+      const float al = 1.0f / (1.0f + tau / a.te);
+      s = al * x + (1.0f - al) * st.x_filt;
+      st.dx_filt = edx;
+    }
+    st.x_raw = x;
+    st.x_filt = s;
+    if (e < 45) sl[ACRMI_SLOT_POSES + 3 + e] = s;
+    else if (e < 55) sl[ACRMI_SLOT_BETAS + (e - 45)] = s;
+    else rot[h][e - 55] = s;
+  }
+  __syncthreads();
+  if (on && e == 55) {      // rotation_matrix_to_angle_axis (acr/utils.py:334-360); the reference transposes first
+    const float* R = rot[h];
+    const float t[9] = {R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]};
+    float aa[3];
+    rotmat_t_to_aa(t, aa);
+    sl[ACRMI_SLOT_POSES] = aa[0]; sl[ACRMI_SLOT_POSES + 1] = aa[1]; sl[ACRMI_SLOT_POSES + 2] = aa[2];
+  }
+  if (on) st.init = 1;
+  __syncthreads();
+}
+
+// Workgroup k = the k-th stream present in the launch: its state row sits in registers while the chain of its frames is
+// walked (a.b.first / a.b.next, uniform reads of the kernel arguments) and is read and written once.  Workgroups touch
+// disjoint frames and disjoint rows: no atomics, the result does not depend on how they are scheduled.
 __global__ __launch_bounds__(128) void smooth_kernel(const SmoothArgs a) {
   const int tid = threadIdx.x, h = tid >> 6, e = tid & 63;
   __shared__ float rot[2][9];
-  float* st = a.state + h * 3 * 64;     // [x_raw | x_filt | dx_filt][64]
-  float x_raw = st[e], x_filt = st[64 + e], dx_filt = st[128 + e];
-  int init = a.init[h];
+  const size_t hand = (size_t)a.b.row[blockIdx.x] * 2 + h;
+  float* st = a.state + hand * 3 * 64;     // [x_raw | x_filt | dx_filt][64]
+  SmoothState s{st[e], st[64 + e], st[128 + e], a.init[hand]};
   const float mincut = (e >= 45 && e < 55) ? a.mincutoff_betas : a.mincutoff;
-  for (int b = 0; b < a.B; ++b) {
-    float* sl = a.slots + ((size_t)b * 2 + h) * ACRMI_SLOT;
-    const bool on = sl[ACRMI_SLOT_FLAG] > 0.5f;     // block-uniform per hand (wave = hand)
-    if (on && e == 55) {      // batch_rodrigues (acr/utils.py:602-616) + quat2mat (:618-638) of the global orientation
-      const float ax = sl[ACRMI_SLOT_POSES], ay = sl[ACRMI_SLOT_POSES + 1], az = sl[ACRMI_SLOT_POSES + 2];
-      const float ex = ax + 1e-8f, ey = ay + 1e-8f, ez = az + 1e-8f;
-      const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-      const float nx = ax / angle, ny = ay / angle, nz = az / angle;
-      const float half = angle * 0.5f;
-      const float sn = sinf(half);
-      float w = cosf(half), x = sn * nx, y = sn * ny, z = sn * nz;
-      const float qn = sqrtf(w * w + x * x + y * y + z * z);
-      w /= qn; x /= qn; y /= qn; z /= qn;
-      const float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-      const float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-      float* R = rot[h];
-      R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;    R[2] = 2 * wy + 2 * xz;
-      R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;  R[5] = 2 * yz - 2 * wx;
-      R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;    R[8] = w2 - x2 - y2 + z2;
-    }
-    __syncthreads();
-    if (on) {
-      const float x = e < 45 ? sl[ACRMI_SLOT_POSES + 3 + e] : (e < 55 ? sl[ACRMI_SLOT_BETAS + (e - 45)] : rot[h][e - 55]);
-      float s;
-      if (!init) {
-        s = x;
-        dx_filt = 0.f;
-      } else {
-        const float dx = (x - x_raw) * a.freq;
-        const float edx = a.alpha_d * dx + a.one_minus_alpha_d * dx_filt;
-        const float cutoff = mincut + a.beta * fabsf(edx);
-        const float tau = 1.0f / (a.two_pi * cutoff);
-        const float al = 1.0f / (1.0f + tau / a.te);
-        s = al * x + (1.0f - al) * x_filt;
-        dx_filt = edx;
-      }
-      x_raw = x;
-      x_filt = s;
-      if (e < 45) sl[ACRMI_SLOT_POSES + 3 + e] = s;
-      else if (e < 55) sl[ACRMI_SLOT_BETAS + (e - 45)] = s;
-      else rot[h][e - 55] = s;
-    }
-    __syncthreads();
-    if (on && e == 55) {      // rotation_matrix_to_angle_axis (acr/utils.py:334-360); the reference transposes first
-      const float* R = rot[h];
-      const float t[9] = {R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]};
-      float aa[3];
-      rotmat_t_to_aa(t, aa);
-      sl[ACRMI_SLOT_POSES] = aa[0]; sl[ACRMI_SLOT_POSES + 1] = aa[1]; sl[ACRMI_SLOT_POSES + 2] = aa[2];
-    }
-    if (on) init = 1;
-    __syncthreads();
-  }
-  st[e] = x_raw; st[64 + e] = x_filt; st[128 + e] = dx_filt;
-  if (e == 0) a.init[h] = init;
+  for (int f = a.b.first[blockIdx.x]; f != SMOOTH_END; f = a.b.next[f])
+    smooth_frame(a, a.slots + ((size_t)f * 2 + h) * ACRMI_SLOT, h, e, mincut, rot, s);
+  st[e] = s.x_raw; st[64 + e] = s.x_filt; st[128 + e] = s.dx_filt;
+  if (e == 0) a.init[hand] = s.init;
 }
-hipError_t launch_smooth(const SmoothArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(smooth_kernel, dim3(1), dim3(128), 0, s, a);
+hipError_t launch_smooth(const SmoothArgs& a, int n_streams, hipStream_t s) {
+  hipLaunchKernelGGL(smooth_kernel, dim3(n_streams), dim3(128), 0, s, a);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void smooth_reset_kernel(const SmoothIds ids, int n, int* __restrict__ init) {
+  const int i = threadIdx.x;
+  if (i < n) { init[2 * (size_t)ids.id[i]] = 0; init[2 * (size_t)ids.id[i] + 1] = 0; }
+}
+hipError_t launch_smooth_reset(const SmoothIds& ids, int n, int* init, hipStream_t s) {
+  static_assert(SMOOTH_FRAMES_PER_LAUNCH == 256, "one thread per listed stream");
+  hipLaunchKernelGGL(smooth_reset_kernel, dim3(1), dim3(256), 0, s, ids, n, init);
   return hipGetLastError();
 }
 

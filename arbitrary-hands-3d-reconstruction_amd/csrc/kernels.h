@@ -6,6 +6,8 @@
 
 #include <stdlib.h>
 
+#include "smooth_plan.h"
+
 namespace acrmi {
 
 // Environment switches of timing experiments / A-B runs (lane-sync ablation, event flags, loader and kernel-frame A/B) exist
@@ -189,17 +191,23 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 // left-detected frame and the right center of the FIRST right-detected frame are <= 32 map pixels apart; else 0.  One workgroup.
 hipError_t launch_prior_gate(const float* slots, int B, int* gate, hipStream_t s);
 
-// One-Euro smoothing of the decoded (poses, betas) of one video stream, frames in order (acr/utils.py:1466-1527)
+// One-Euro smoothing of the decoded (poses, betas) between decode and MANO (acr/utils.py:1466-1527), filter state per video
+// stream in a table: one workgroup per stream present in the launch, that stream's frames in batch order (smooth_plan.h)
 struct SmoothArgs {
-  float* slots;          // [B,2,ACRMI_SLOT], smoothed in place where the flag is set
-  int B;
-  float* state;          // [2 hands][x_raw | x_filt | dx_filt][64]
-  int* init;             // [2]
+  float* slots;          // [n frames of the launch,2,ACRMI_SLOT], smoothed in place where the flag is set
+  float* state;          // [capacity][2 hands][x_raw | x_filt | dx_filt][64]
+  int* init;             // [capacity][2]
   float mincutoff, mincutoff_betas, beta, freq;
   float alpha_d, one_minus_alpha_d;   // derivative filter: compute_alpha(dcutoff) in double, rounded once
   float two_pi, te;
+  SmoothBatch b;         // which frames belong to which stream, by value
 };
-hipError_t launch_smooth(const SmoothArgs& a, hipStream_t s);
+hipError_t launch_smooth(const SmoothArgs& a, int n_streams, hipStream_t s);
+// the n <= SMOOTH_FRAMES_PER_LAUNCH listed streams start a new sequence (their init flags are cleared)
+struct SmoothIds {
+  int32_t id[SMOOTH_FRAMES_PER_LAUNCH];
+};
+hipError_t launch_smooth_reset(const SmoothIds& ids, int n, int* init, hipStream_t s);
 
 // Point heads: the six non-center head towers evaluated only at the pixels the decode reads (heads.hip).
 // Per tower (floats): entry W [9 taps][9 cin/4][64 cout][4] + b[64]; 4 x (conv W [9][16][64][4] + b[64]);

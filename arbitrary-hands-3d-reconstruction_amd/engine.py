@@ -26,6 +26,77 @@ def torch_nccl_group_active():
         return False
 
 
+def stream_ids(ids, B):
+    """The stream id of each of B frames (any int sequence or int tensor of length B; -1 = leave the frame alone) as the
+    contiguous host int32 array the library reads.  A host sequence or CPU tensor is converted without touching the
+    device; a device tensor is copied to the host (that copy waits for the work that produces it)."""
+    if isinstance(ids, torch.Tensor):
+        if ids.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise ValueError('streams must hold integers, got %s' % ids.dtype)
+        a = ids.detach().cpu().numpy()
+    else:
+        a = np.asarray(ids)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('streams must hold integers, got %s' % a.dtype)
+    if a.ndim != 1 or a.shape[0] != B:
+        raise ValueError('streams must name one stream per frame: shape %s for %d frames' % (tuple(a.shape), B))
+    if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
+        raise ValueError('streams: an id does not fit 32 bits')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def stream_args(streams, table, B):
+    """`streams=` / `table=` of Engine.smooth and Engine.forward: both or neither.  -> host int32 ids [B], or None."""
+    if streams is None and table is None:
+        return None
+    if streams is None or table is None:
+        raise ValueError('streams= and table= go together: the ids of the frames and the StreamTable that holds their state')
+    if getattr(table, 'handle', None) is None:
+        raise ValueError('table must be an open StreamTable')
+    return stream_ids(streams, B)
+
+
+class StreamTable(object):
+    """One-Euro filter state of `capacity` video streams on one GPU (acrmi_streams; acr/main.py:50-53 keeps one filter set
+    per video): what `Engine.smooth(..., streams=, table=)` / `Engine.forward(..., streams=, table=)` update.  It belongs to
+    no Engine: the contexts of an EnginePool share one (the library orders their updates by the order of the calls), and
+    it outlives an Engine that a checkpoint reload replaces.  Every stream starts fresh."""
+
+    def __init__(self, device=0, capacity=64):
+        self.L = _lib.lib()
+        self.device = torch.device('cuda', device if isinstance(device, int) else torch.device(device).index or 0)
+        self.capacity = int(capacity)
+        self.handle = None
+        h = C.c_void_p()
+        _lib.check(self.L.acrmi_streams_create(C.byref(h), self.device.index, self.capacity))
+        self.handle = h
+
+    def reset(self, ids=None):
+        """The listed streams - every stream when ids is None - start a new sequence: their next sample passes through.
+        Queued on the current stream, ordered with the smoothing calls of every context."""
+        if self.handle is None:
+            raise ValueError('the StreamTable is closed')
+        arr, n = None, 0
+        if ids is not None:
+            a = np.atleast_1d(np.asarray(ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else ids))
+            if a.size == 0:
+                return
+            a = stream_ids(a, a.shape[0])
+            arr, n = a.ctypes.data_as(C.c_void_p), a.shape[0]
+        _lib.check(self.L.acrmi_streams_reset(self.handle, arr, n, _stream(self.device)))
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            self.L.acrmi_streams_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine(object):
     def __init__(self, device=0):
         if not torch.cuda.is_available():
@@ -230,11 +301,19 @@ class Engine(object):
         _lib.check(self.L.acrmi_prior_gate(self.ctx, _ptr(slots), slots.shape[0], _ptr(gate), _stream(self.device)), self.ctx)
         return gate
 
-    def smooth(self, slots):
-        """One-Euro smoothing of slots [B,2,176] in place (acr/utils.py:1466-1527), state resident in the context."""
+    def smooth(self, slots, streams=None, table=None):
+        """One-Euro smoothing of slots [B,2,176] in place (acr/utils.py:1466-1527), state resident in the context: the
+        frames are one video stream in order.  streams= (one id per frame, -1 = leave the frame alone) with table= (a
+        StreamTable): every frame is filtered with the state of ITS stream instead (acrmi_smooth_streams) - frames that
+        share an id are one sequence in batch order, streams never meet."""
         if not slots.is_cuda or slots.dtype != torch.float32 or not slots.is_contiguous():
             raise ValueError('slots must be a contiguous float32 device tensor')
-        _lib.check(self.L.acrmi_smooth(self.ctx, _ptr(slots), slots.shape[0], _stream(self.device)), self.ctx)
+        ids = stream_args(streams, table, slots.shape[0])
+        if ids is None:
+            _lib.check(self.L.acrmi_smooth(self.ctx, _ptr(slots), slots.shape[0], _stream(self.device)), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_smooth_streams(self.ctx, table.handle, _ptr(slots), slots.shape[0],
+                                                   ids.ctypes.data_as(C.c_void_p), _stream(self.device)), self.ctx)
         return slots
 
     def smooth_reset(self):
@@ -454,12 +533,15 @@ class Engine(object):
                                      _stream(dev)), self.ctx)
         return verts, joints, center, extra
 
-    def forward(self, img, offsets=None, project=False, out=None, stream=None):
+    def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None):
         """frames -> (slots [B,2,176], verts [B,2,778,3], joints [B,2,21,3][, verts_camed, pj2d, pj2d_org]).
         stream: raw hipStream_t (int) to queue the call on instead of torch's current stream; tensors this call
-        allocates still come from the current stream's pool."""
+        allocates still come from the current stream's pool.
+        streams= / table=: as `smooth` - the decoded poses / betas of every frame are smoothed with the state of its video
+        stream before MANO (acrmi_forward_streams), whatever set_temporal says."""
         img = self._check_img(img)
         B = img.shape[0]
+        ids = stream_args(streams, table, B)
         self.ensure_batch(B)
         dev = self.device
         if out is None:
@@ -473,10 +555,13 @@ class Engine(object):
                     out['pj2d_org'] = torch.empty(B, 2, 21, 2, dtype=torch.float32, device=dev)
         if offsets is not None:
             offsets = offsets.to(dev, torch.float32).contiguous()
-        _lib.check(self.L.acrmi_forward(self.ctx, _ptr(img), B, _ptr(offsets), _ptr(out['slots']), _ptr(out['verts']),
-                                        _ptr(out['joints']), _ptr(out.get('verts_camed')), _ptr(out.get('pj2d')),
-                                        _ptr(out.get('pj2d_org')),
-                                        _stream(dev) if stream is None else C.c_void_p(stream)), self.ctx)
+        args = (_ptr(img), B, _ptr(offsets), _ptr(out['slots']), _ptr(out['verts']), _ptr(out['joints']),
+                _ptr(out.get('verts_camed')), _ptr(out.get('pj2d')), _ptr(out.get('pj2d_org')),
+                _stream(dev) if stream is None else C.c_void_p(stream))
+        if ids is None:
+            _lib.check(self.L.acrmi_forward(self.ctx, *args), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), *args), self.ctx)
         return out
 
     def render(self, out, images, offsets=None, cam_trans=None, focal_length=1265., visible_weight=0.9, colors=None,
@@ -619,6 +704,7 @@ class EnginePool(object):
         self._turn = 0
         self._busy = [None] * n
         self._inflight = []      # released tickets whose batch may still be running: their tensors stay referenced
+        self.table = None        # stream_table(): the One-Euro state the contexts share
 
     def __len__(self):
         return len(self.engines)
@@ -629,6 +715,9 @@ class EnginePool(object):
             with torch.cuda.device(self.device):
                 torch.cuda.synchronize()
             self._inflight = []          # every batch has run: the tensors the tickets kept alive may go
+            if self.table is not None:
+                self.table.close()
+                self.table = None
             self.streams = []
             L = _lib.lib()
             for st in self._raw:
@@ -676,7 +765,21 @@ class EnginePool(object):
         for e in self.engines:
             fn(e)
 
-    def submit(self, img, offsets=None, project=False, out=None):
+    def stream_table(self, capacity):
+        """The pool's StreamTable (created on the first call): ONE table for all contexts, so a video stream's state follows
+        its frames to whichever context takes the batch; the library applies the updates in the order of the submits."""
+        if self.table is None:
+            self.table = StreamTable(self.device, capacity)
+        elif self.table.capacity != int(capacity):
+            raise ValueError('the pool holds a table of %d streams (asked for %d)' % (self.table.capacity, int(capacity)))
+        return self.table
+
+    def submit(self, img, offsets=None, project=False, out=None, streams=None):
+        """streams: the video stream of each frame (Engine.forward's `streams=`, on the pool's stream_table())."""
+        if streams is not None and self.table is None:
+            raise ValueError('streams= needs the pool\'s table: call stream_table(capacity) first')
+        if streams is not None:      # (checked before the turn moves on)
+            streams = stream_ids(streams, img.shape[0])
         i = self._turn
         if self._busy[i] is not None:
             raise RuntimeError('collect() the ticket submitted %d calls ago first' % len(self.engines))
@@ -692,13 +795,15 @@ class EnginePool(object):
         # (no `with torch.cuda.stream(st)`: tensors must not come from the caching allocator's pool of a stream that
         # close() destroys; everything this call allocates belongs to the caller's stream, which collect() orders behind
         # the batch)
-        res = self.engines[i].forward(img, offsets=offsets, project=project, out=out, stream=self._raw[i].value)
+        table = self.table if streams is not None else None
+        res = self.engines[i].forward(img, offsets=offsets, project=project, out=out, stream=self._raw[i].value,
+                                      streams=streams, table=table)
         done = torch.cuda.Event()
         done.record(st)
         # Everything the batch reads or writes stays referenced by the ticket until its event has completed: the call
         # runs on the pool's stream, so torch's caching allocator (which only knows the caller's stream) would hand a
         # dropped `img` / `offsets` block to the caller's next allocation while the kernels still read it.
-        ticket = {'slot': i, 'event': done, 'out': res, 'img': img, 'offsets': offsets}
+        ticket = {'slot': i, 'event': done, 'out': res, 'img': img, 'offsets': offsets, 'table': table}
         self._busy[i] = ticket
         return ticket
 

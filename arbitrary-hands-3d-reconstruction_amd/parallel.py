@@ -248,7 +248,9 @@ class ShardedRunner(object):
         the result is exactly the n frames, in order.  The padding rows run through whatever `local_forward` does per batch:
         with temporal smoothing switched on (Engine.set_temporal: ONE video stream per context, frames in order) a padded
         shard would feed repeated frames into the One-Euro state - sharded batches are sets of independent frames, so
-        smoothing and sharding are not combined (acr/main.py smooths a single-frame stream)."""
+        smoothing and sharding are not combined.  Per-stream state exists (engine.StreamTable, `streams=` of Engine.forward /
+        EnginePool.submit), but a table lives on one GPU: routing every video stream to the rank that holds its state is
+        not built, so `local_forward` must not smooth here either."""
         rank, world = dist.get_rank(self.group), dist.get_world_size(self.group)
         n = frames_global.shape[0]
         if n % world == 0:

@@ -390,6 +390,35 @@ int acrmi_set_option_f(acrmi_ctx* ctx, int option, float value);
 int acrmi_smooth(acrmi_ctx* ctx, float* slots_dev, int B, void* stream);
 int acrmi_smooth_reset(acrmi_ctx* ctx, void* stream);
 
+/* The same smoothing for MANY video streams in one batch (N cameras, one frame of each per call): a stream table holds the
+ * filter state the reference keeps per video in its filter_dict (acr/main.py:50-53, create_OneEuroFilter acr/utils.py:1472-1473)
+ * for `capacity` streams (1..65536, else ACRMI_EINVAL) - per stream 2 hand types x (x_raw | x_filt | dx_filt)[64] floats
+ * (element 0..44 finger pose, 45..54 betas, 55..63 rotation matrix) + an init flag per (stream, hand).  The table belongs to
+ * no context: the contexts of a pool share one, and it outlives a context that a checkpoint reload replaces.  Created
+ * zeroed: every stream starts fresh (its first sample passes through, acr/utils.py:1489-1496). */
+typedef struct acrmi_streams acrmi_streams;
+int acrmi_streams_create(acrmi_streams** out, int device, int capacity);
+void acrmi_streams_destroy(acrmi_streams* t);
+/* ids_host == NULL: every stream; else the n listed streams (each in [0, capacity)) start a new sequence - what a new video
+ * does to the reference's filters (acr/main.py:50-53).  Queued on `stream`, ordered with the smoothing calls like them. */
+int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids_host, int n, void* stream);
+/* acr/main.py:69-83 per stream: slots_dev [B,2,ACRMI_SLOT] smoothed in place with the coefficients of acrmi_smooth
+ * (ACRMI_OPT_SMOOTH_COEFF of ctx; betas 0.6, beta 0.7, dcutoff 1, 30 Hz); ids_host [B] = the stream of each frame, -1 = leave
+ * this frame alone.  Frames that carry the same id are ONE sequence, applied in batch order, wherever they stand in the batch;
+ * different streams never see each other; a hand whose flag is not set (NaN included) leaves its filter untouched
+ * (acr/main.py:78-80); nothing but poses and betas is written.  An id < -1 or >= capacity is ACRMI_EINVAL and nothing is
+ * launched.  The ids travel in the kernel arguments (256 frames per launch, longer batches as successive launches in frame
+ * order): nothing is allocated or uploaded, ids_host may be freed when the call returns.
+ * Ordering between contexts: the table carries one HIP event; every call makes `stream` wait for it before its launches and
+ * records it behind them, so calls of several contexts on several streams update a shared table in the order they were
+ * made (host threads may call concurrently; the order is then the one in which they got the table's lock). */
+int acrmi_smooth_streams(acrmi_ctx* ctx, acrmi_streams* t, float* slots_dev, int B, const int32_t* ids_host, void* stream);
+/* acrmi_forward with acrmi_smooth_streams between decode and MANO (acr/main.py:69-83 sits there), whatever
+ * ACRMI_OPT_TEMPORAL says.  The ids are checked before anything is launched. */
+int acrmi_forward_streams(acrmi_ctx* ctx, acrmi_streams* t, const int32_t* ids_host, const uint8_t* img_dev, int B,
+                          const float* offsets_dev, float* slots_dev, float* verts_dev, float* joints_dev,
+                          float* verts_camed_dev, float* pj2d_dev, float* pj2d_org_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Mesh overlay: acr/visualization.py:100-218 (Visualizer.visulize_result_live, show_items=['mesh'], settings ['put_org'])
  * + acr/renderer/renderer_pyrd.py / renderer_pt3d.py - the frame with the hand meshes drawn over it.  Nothing of those
