@@ -331,18 +331,27 @@ class ACR(object):
         return drawn
 
 
-def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None):
+def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
+                       pixel_format='bgr', matrix='cv601'):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
     render=True: -> (results, frames with the hand meshes drawn over them: a tensor like the input, or a list in input order);
     with show_items (names from SHOW_ITEMS) -> (results, {name: frames}) as forward_batch.  streams / max_streams: as
-    forward_batch."""
+    forward_batch.
+    pixel_format='nv12': the frames are NV12 surfaces as a video decoder leaves them (ops.preprocess_nv12 says which layouts),
+    converted by the integer rule `matrix` names (ops.nv12_matrix) inside the pre-processing kernel; the results are those
+    of the BGR frames ops.nv12_to_bgr makes of them, and those BGR frames - a tensor [n,H,W,3] when all sizes agree, else a
+    list - are what render=True / show_items draw over."""
     from .utils import img_preprocess_gpu
-    meta = img_preprocess_gpu(bgr_frames_dev, paths)
     if show_items is not None and not render:
         raise ValueError('show_items needs render=True')
-    return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=bgr_frames_dev if render else None,
+    meta = img_preprocess_gpu(bgr_frames_dev, paths, pixel_format=pixel_format, matrix=matrix)
+    canvas = None
+    if render:
+        from .. import ops
+        canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
+    return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                               render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
 
 

@@ -81,13 +81,18 @@ def img_preprocess(image, imgpath=None, input_size=512, single_img_input=False, 
     return data
 
 
-def img_preprocess_gpu(bgr_frames, imgpaths=None):
+def img_preprocess_gpu(bgr_frames, imgpaths=None, pixel_format='bgr', matrix='cv601'):
     """Batched device pre-processing: uint8 BGR frames [n,H,W,3] already in HBM - or a list of frames
     [H_i,W_i,3] of different sizes (acrmi_preprocess_frames) ->
     {'image': uint8 RGB [n,512,512,3] (device), 'offsets': [n,10], 'batch_ids': [n]}: one HIP kernel, no host
-    round trip."""
+    round trip.  pixel_format='nv12': the frames are NV12 surfaces as ops.preprocess_nv12 takes them (a decoder's output,
+    1.5 bytes per pixel), converted by the integer rule `matrix` names inside the same kernel (acrmi_preprocess_nv12)."""
     from .. import ops
-    if isinstance(bgr_frames, (list, tuple)):        # frames of different sizes (folder mode): per-frame geometry, one call
+    if pixel_format == 'nv12':
+        img, offsets = ops.preprocess_nv12(bgr_frames, matrix)
+    elif pixel_format != 'bgr':
+        raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
+    elif isinstance(bgr_frames, (list, tuple)):        # frames of different sizes (folder mode): per-frame geometry, one call
         img, offsets = ops.preprocess_frames(bgr_frames)
     else:
         img, offsets = ops.preprocess(bgr_frames)

@@ -208,6 +208,114 @@ int acrmi_preprocess_frames(const acrmi_frame* frames_host, int n, uint8_t* out_
   return ACRMI_OK;
 }
 
+// ---- NV12 input (csrc/nv12.hip; DESIGN.md "NV12 input") ------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// (cy, cub, cug, cvg, cvr, y_off) by ACRMI_NV12_*: OpenCV's literal ITUR_BT_601 integers, then round(x * 2^20) of the
+// textbook Kr / Kb forms (limited range: 255/219 luma and 255/224 chroma gains; full range: none)
+const int32_t kNv12Matrix[5][6] = {
+    {1220542, 2116026, -409993, -852492, 1673527, 16},     // cv601
+    {1220945, 2115221, -410793, -852458, 1673555, 16},     // bt601
+    {1048576, 1858077, -360853, -748826, 1470104, 0},      // bt601-full
+    {1220945, 2215014, -223607, -558796, 1879825, 16},     // bt709
+    {1048576, 1945738, -196424, -490864, 1651297, 0},      // bt709-full
+};
+
+// Null row = cv601.  Refused: y_off outside 0..255, or a row whose int32 sums could overflow:
+// 255 |cy| + 128 max(|cub|, |cvr|, |cug| + |cvg|) + 2^19 >= 2^31.
+int nv12_coef(const char* who, const int32_t* coef6, Nv12Coef& k) {
+  const int32_t* c = coef6 ? coef6 : kNv12Matrix[0];
+  auto mag = [](int32_t v) { return v < 0 ? -(long long)v : (long long)v; };
+  long long m = mag(c[1]);
+  if (mag(c[4]) > m) m = mag(c[4]);
+  if (mag(c[2]) + mag(c[3]) > m) m = mag(c[2]) + mag(c[3]);
+  if (c[5] < 0 || c[5] > 255)
+    return fail(nullptr, ACRMI_EINVAL, "%s: y_off %d outside 0..255", who, (int)c[5]);
+  if (255 * mag(c[0]) + 128 * m + (1LL << 19) >= (1LL << 31))
+    return fail(nullptr, ACRMI_EINVAL, "%s: coefficient row (%d, %d, %d, %d, %d) could overflow the int32 sums", who, (int)c[0],
+                (int)c[1], (int)c[2], (int)c[3], (int)c[4]);
+  k.cy = c[0]; k.cub = c[1]; k.cug = c[2]; k.cvg = c[3]; k.cvr = c[4]; k.y_off = c[5];
+  return ACRMI_OK;
+}
+
+int nv12_check_frames(const char* who, const acrmi_nv12_frame* fr, int n) {
+  for (int i = 0; i < n; ++i) {
+    const acrmi_nv12_frame& f = fr[i];
+    if (!f.y_dev || !f.uv_dev) return fail(nullptr, ACRMI_EINVAL, "%s: frame %d: null plane", who, i);
+    if (f.H < 2 || f.W < 2 || (f.H & 1) || (f.W & 1))
+      return fail(nullptr, ACRMI_EINVAL, "%s: frame %d: size %d x %d (H x W) must be even and >= 2", who, i, f.H, f.W);
+    if (f.y_pitch < f.W || f.uv_pitch < f.W)
+      return fail(nullptr, ACRMI_EINVAL, "%s: frame %d: pitch (y %d, uv %d) below the width %d", who, i, f.y_pitch, f.uv_pitch, f.W);
+  }
+  return ACRMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int acrmi_nv12_matrix(int which, int32_t coef6[6]) {
+  if (!coef6 || which < 0 || which > ACRMI_NV12_BT709_FULL)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_matrix: bad arguments (matrix %d)", which);
+  for (int i = 0; i < 6; ++i) coef6[i] = kNv12Matrix[which][i];
+  return ACRMI_OK;
+}
+
+int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, uint8_t* out_rgb_dev,
+                          float* offsets_host, void* stream) {
+  if (!frames_host || !out_rgb_dev || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_nv12: bad arguments");
+  Nv12Coef k{};
+  int rc = nv12_coef("acrmi_preprocess_nv12", coef6_host, k);
+  if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_preprocess_nv12", frames_host, n);
+  if (rc != ACRMI_OK) return rc;
+  for (int i0 = 0; i0 < n; i0 += NV12_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < NV12_FRAMES_PER_LAUNCH ? n - i0 : NV12_FRAMES_PER_LAUNCH;
+    Nv12Batch pb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_frame& fr = frames_host[i0 + i];
+      pb.f[i].y = fr.y_dev; pb.f[i].uv = fr.uv_dev; pb.f[i].H = fr.H; pb.f[i].W = fr.W;
+      pb.f[i].y_pitch = fr.y_pitch; pb.f[i].uv_pitch = fr.uv_pitch;
+      if (offsets_host) {     // the same `offsets` row acrmi_preprocess_frames writes for this H, W
+        const int H = fr.H, W = fr.W, S = H > W ? H : W;
+        int top = 0, right = 0, bottom = 0, left = 0;
+        if (W < H) { const int d = H - W; right = (d + 1) / 2; left = d / 2; }
+        else if (H < W) { const int d = W - H; top = d / 2; bottom = (d + 1) / 2; }
+        float* o = offsets_host + (size_t)(i0 + i) * 10;
+        o[0] = (float)S; o[1] = (float)S; o[2] = o[3] = o[4] = o[5] = 0.f;
+        o[6] = (float)top; o[7] = (float)right; o[8] = (float)bottom; o[9] = (float)left;
+      }
+    }
+    hipError_t e = launch_preprocess_nv12(pb, k, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_nv12: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, int bgr,
+                      uint8_t* const* dst_dev_host, void* stream) {
+  if (!frames_host || !dst_dev_host || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_to_rgb: bad arguments");
+  Nv12Coef k{};
+  int rc = nv12_coef("acrmi_nv12_to_rgb", coef6_host, k);
+  if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_nv12_to_rgb", frames_host, n);
+  if (rc != ACRMI_OK) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!dst_dev_host[i]) return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_to_rgb: frame %d: null destination", i);
+  for (int i0 = 0; i0 < n; i0 += NV12_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < NV12_FRAMES_PER_LAUNCH ? n - i0 : NV12_FRAMES_PER_LAUNCH;
+    Nv12DstBatch pb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_frame& fr = frames_host[i0 + i];
+      pb.f[i].y = fr.y_dev; pb.f[i].uv = fr.uv_dev; pb.f[i].dst = dst_dev_host[i0 + i]; pb.f[i].H = fr.H; pb.f[i].W = fr.W;
+      pb.f[i].y_pitch = fr.y_pitch; pb.f[i].uv_pitch = fr.uv_pitch;
+    }
+    hipError_t e = launch_nv12_to_rgb(pb, k, m, bgr ? 1 : 0, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "nv12_to_rgb: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream) {
   if (!img || !out || n_pixels <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_u8norm: bad arguments");
   hipError_t e = launch_u8norm(img, n_pixels, out, (hipStream_t)stream);

@@ -326,24 +326,7 @@ namespace acrmi {
 // oracle/preprocess.py is the CPU statement of the same algorithm; tests require equality.
 // One thread per output pixel; the 1080p source (6.2 MB/frame) is read once through L2.
 // ------------------------------------------------------------------------------------------------
-__device__ inline void cv_cubic_taps(int d, double scale, int& s0, int (&c)[4]) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  const float fl = floorf(f);
-  s0 = (int)fl;
-  f -= fl;
-  const float A = -0.75f;
-  float k[4];
-  k[0] = ((A * (f + 1.f) - 5.f * A) * (f + 1.f) + 8.f * A) * (f + 1.f) - 4.f * A;
-  k[1] = ((A + 2.f) * f - (A + 3.f)) * f * f + 1.f;
-  k[2] = ((A + 2.f) * (1.f - f) - (A + 3.f)) * (1.f - f) * (1.f - f) + 1.f;
-  k[3] = 1.f - k[0] - k[1] - k[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int v = (int)rintf(k[i] * 2048.f);            // saturate_cast<short>(float): cvRound, then clamp
-    c[i] = v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
-  }
-}
-
+// (cv_cubic_taps: csrc/kernels.h, shared with csrc/nv12.hip)
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ bgr, int n, int H, int W, int S,
                                                          int pad_top, int pad_left, int out_size,
                                                          uint8_t* __restrict__ out) {

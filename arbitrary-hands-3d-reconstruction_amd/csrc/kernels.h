@@ -124,6 +124,25 @@ struct FuseArgs {
   float* out;
 };
 hipError_t launch_fuse_sum(const FuseArgs& a, hipStream_t s);
+// One axis of OpenCV's uint8 INTER_CUBIC (see the pre-processing section of csrc/elementwise.hip): destination index d ->
+// source origin s0 and the four 11-bit fixed-point coefficients.  Shared by the BGR and the NV12 pre-processing kernels.
+__device__ inline void cv_cubic_taps(int d, double scale, int& s0, int (&c)[4]) {
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  const float fl = floorf(f);
+  s0 = (int)fl;
+  f -= fl;
+  const float A = -0.75f;
+  float k[4];
+  k[0] = ((A * (f + 1.f) - 5.f * A) * (f + 1.f) + 8.f * A) * (f + 1.f) - 4.f * A;
+  k[1] = ((A + 2.f) * f - (A + 3.f)) * f * f + 1.f;
+  k[2] = ((A + 2.f) * (1.f - f) - (A + 3.f)) * (1.f - f) * (1.f - f) + 1.f;
+  k[3] = 1.f - k[0] - k[1] - k[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int v = (int)rintf(k[i] * 2048.f);            // saturate_cast<short>(float): cvRound, then clamp
+    c[i] = v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
+  }
+}
 hipError_t launch_preprocess(const uint8_t* bgr, int n, int H, int W, int S, int pad_top, int pad_left, int out_size,
                              uint8_t* out, hipStream_t s);
 // frames of DIFFERENT sizes in one launch (acrmi_preprocess_frames): geometry by value, PRE_FRAMES_PER_LAUNCH per launch
@@ -136,6 +155,32 @@ struct PreBatch {
   PreFrame f[PRE_FRAMES_PER_LAUNCH];
 };
 hipError_t launch_preprocess_frames(const PreBatch& pb, int n, int out_size, uint8_t* out, hipStream_t s);
+// NV12 surfaces (csrc/nv12.hip; acrmi_preprocess_nv12 / acrmi_nv12_to_rgb): geometry by value, NV12_FRAMES_PER_LAUNCH per launch
+constexpr int NV12_FRAMES_PER_LAUNCH = 64;
+struct Nv12Coef {
+  int cy, cub, cug, cvg, cvr, y_off;
+};
+struct Nv12Frame {      // 32 bytes, the layout of acrmi_nv12_frame
+  const uint8_t* y;
+  const uint8_t* uv;
+  int H, W, y_pitch, uv_pitch;
+};
+struct Nv12Batch {
+  Nv12Frame f[NV12_FRAMES_PER_LAUNCH];
+};
+struct Nv12DstFrame {   // 40 bytes: 64 of them + the coefficient row are 2.6 KB of the 4 KB argument block
+  const uint8_t* y;
+  const uint8_t* uv;
+  uint8_t* dst;
+  int H, W, y_pitch, uv_pitch;
+};
+struct Nv12DstBatch {
+  Nv12DstFrame f[NV12_FRAMES_PER_LAUNCH];
+};
+static_assert(sizeof(Nv12Batch) + sizeof(Nv12Coef) + 24 <= 4096 && sizeof(Nv12DstBatch) + sizeof(Nv12Coef) + 8 <= 4096,
+              "NV12 kernel arguments must fit the 4 KB argument block");
+hipError_t launch_preprocess_nv12(const Nv12Batch& pb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
+hipError_t launch_nv12_to_rgb(const Nv12DstBatch& pb, const Nv12Coef& k, int n, int bgr, hipStream_t s);
 hipError_t launch_pow11(float* buf, long n_pixels, int cs, int ch, hipStream_t s);
 // fp32 NCHW [B,C,H,W] -> channels [coff, coff + C) of an NHWC buffer with channel stride cs (acrmi_heads: backbone features a
 // caller hands to head_forward, acr/model.py:47-53)

@@ -208,6 +208,127 @@ def preprocess_frames(bgr_frames):
     return out, torch.from_numpy(offsets)
 
 
+# ---- NV12 input (csrc/nv12.hip; DESIGN.md "NV12 input") -----------------------------------------------------------------
+def nv12_matrix(name_or_row='cv601'):
+    """A matrix name ('cv601', 'bt601', 'bt601-full', 'bt709', 'bt709-full': acrmi_nv12_matrix) or a row of six integers
+    (cy, cub, cug, cvg, cvr, y_off) -> the row as int32 numpy [6].  Pure host: works without a GPU."""
+    if isinstance(name_or_row, str):
+        which = _lib.NV12_MATRICES.get(name_or_row)
+        if which is None:
+            raise ValueError('unknown NV12 matrix %r: one of %s, or a row of six integers' % (name_or_row, sorted(_lib.NV12_MATRICES)))
+        row = np.zeros(6, np.int32)
+        _lib.check(_lib.lib().acrmi_nv12_matrix(which, row.ctypes.data_as(C.c_void_p)))
+        return row
+    row = np.asarray(name_or_row.cpu() if hasattr(name_or_row, 'cpu') else name_or_row)
+    if row.shape != (6,) or row.dtype.kind not in 'iu' or np.abs(row.astype(np.int64)).max() >= 2 ** 31:
+        raise ValueError('an NV12 matrix is a name or six int32 integers (cy, cub, cug, cvg, cvr, y_off)')
+    return np.ascontiguousarray(row.astype(np.int32))
+
+
+def _nv12_plane(t, what, i):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError('NV12 frame %d: %s must be a uint8 tensor' % (i, what))
+
+
+def _nv12_item(item, i):
+    """One item of `frames` -> (y_ptr, uv_ptr, H, W, y_pitch, uv_pitch, tensors to keep bound).  Strided views are taken as
+    they are (pitch = stride(0)); nothing is copied."""
+    if isinstance(item, torch.Tensor):                       # [H*3/2, W]: the Y rows, then the UV rows (OpenCV's layout)
+        _nv12_plane(item, 'the surface', i)
+        if item.dim() != 2 or item.shape[0] % 3:
+            raise ValueError('NV12 frame %d: one tensor must be [H*3/2, W], got %s' % (i, tuple(item.shape)))
+        H, W = item.shape[0] // 3 * 2, item.shape[1]
+        if H < 2 or W < 2 or H % 2 or W % 2:
+            raise ValueError('NV12 frame %d: H and W must be even and >= 2, got %d x %d' % (i, H, W))
+        if item.stride(1) != 1 or item.stride(0) < W:
+            raise ValueError('NV12 frame %d: rows must be dense (innermost stride 1, pitch >= W), got strides %s' % (i, item.stride()))
+        p = item.stride(0)
+        return item.data_ptr(), item.data_ptr() + H * p, H, W, p, p, (item,)
+    if not isinstance(item, tuple) or len(item) != 2:
+        raise ValueError('NV12 frame %d: a uint8 tensor [H*3/2, W] or a tuple (y [H,W], uv [H/2,W] or [H/2,W/2,2])' % i)
+    y, uv = item
+    _nv12_plane(y, 'y', i)
+    _nv12_plane(uv, 'uv', i)
+    if y.dim() != 2:
+        raise ValueError('NV12 frame %d: y must be [H,W], got %s' % (i, tuple(y.shape)))
+    H, W = y.shape
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError('NV12 frame %d: H and W must be even and >= 2, got %d x %d' % (i, H, W))
+    if tuple(uv.shape) not in ((H // 2, W), (H // 2, W // 2, 2)):
+        raise ValueError('NV12 frame %d: uv must be [H/2,W] or [H/2,W/2,2] for y %s, got %s' % (i, tuple(y.shape), tuple(uv.shape)))
+    if y.stride(1) != 1 or y.stride(0) < W:
+        raise ValueError('NV12 frame %d: y rows must be dense (innermost stride 1, pitch >= W), got strides %s' % (i, y.stride()))
+    inner_ok = uv.stride(-1) == 1 and (uv.dim() == 2 or W == 2 or uv.stride(1) == 2)
+    uv_pitch = uv.stride(0) if H > 2 else W                  # (a single row has no pitch to speak of)
+    if not inner_ok or uv_pitch < W:
+        raise ValueError('NV12 frame %d: uv rows must be dense interleaved U, V bytes (pitch >= W), got strides %s' % (i, uv.stride()))
+    if y.device != uv.device:
+        raise ValueError('NV12 frame %d: y and uv are on different devices' % i)
+    return y.data_ptr(), uv.data_ptr(), H, W, y.stride(0), uv_pitch, (y, uv)
+
+
+def _nv12_frames(frames):
+    """`frames` of preprocess_nv12 / nv12_to_bgr -> (acrmi_nv12_frame array, sizes [(H, W)], device, bound tensors).  Layout
+    errors are ValueErrors raised before the device is looked at."""
+    if isinstance(frames, torch.Tensor) and frames.dim() == 3:       # [n, H*3/2, W]: n surfaces of one size
+        items = list(frames.unbind(0))
+    elif isinstance(frames, (torch.Tensor, tuple)):                  # a single item: a batch of one
+        items = [frames]
+    else:
+        items = list(frames)
+    if not items:
+        raise ValueError('no frames')
+    arr = (_lib.NV12Frame * len(items))()
+    keep, sizes = [], []
+    for i, item in enumerate(items):
+        yp, uvp, H, W, ypitch, uvpitch, bound = _nv12_item(item, i)
+        if max(ypitch, uvpitch) >= 2 ** 31:
+            raise ValueError('NV12 frame %d: pitch beyond int32' % i)
+        arr[i].y_dev, arr[i].uv_dev, arr[i].H, arr[i].W, arr[i].y_pitch, arr[i].uv_pitch = yp, uvp, H, W, ypitch, uvpitch
+        keep.extend(bound)                                           # bound until the call has been queued
+        sizes.append((H, W))
+    if any(t.device != keep[0].device for t in keep):
+        raise ValueError('NV12 frames must all be on one device')
+    _need_cuda(*keep)
+    return arr, sizes, keep[0].device, keep
+
+
+def preprocess_nv12(frames, matrix='cv601'):
+    """NV12 frames in HBM -> (uint8 RGB [n,512,512,3] device, offsets [n,10] host) in one call (acrmi_preprocess_nv12): colour
+    conversion by the integer rule of include/acrmi.h, white square pad and OpenCV's cubic resize fused - byte for byte
+    preprocess_frames(nv12_to_bgr(frames)), without the full-resolution frame.
+    frames: a list whose items are each one uint8 device tensor [H*3/2, W] (the Y rows, then the interleaved UV rows: OpenCV's
+    layout) or a TUPLE (y [H,W], uv [H/2,W] or [H/2,W/2,2]); one such item alone is a batch of one, a tensor [n,H*3/2,W] is n
+    frames.  H, W even.  Rows may be strided views (innermost stride 1, pitch = stride(0)): nothing is copied.
+    matrix: a name or six integers (nv12_matrix)."""
+    coef = nv12_matrix(matrix)
+    arr, sizes, dev, keep = _nv12_frames(frames)
+    n = len(sizes)
+    out = torch.empty(n, 512, 512, 3, dtype=torch.uint8, device=dev)
+    offsets = np.zeros((n, 10), np.float32)
+    _lib.check(_lib.lib().acrmi_preprocess_nv12(arr, n, coef.ctypes.data_as(C.c_void_p), _p(out),
+                                                offsets.ctypes.data_as(C.c_void_p), _s(out)))
+    del keep
+    return out, torch.from_numpy(offsets)
+
+
+def nv12_to_bgr(frames, matrix='cv601', rgb=False):
+    """NV12 frames (as preprocess_nv12 takes them) -> the full-resolution uint8 frames, BGR (RGB with rgb=True), by the same
+    integer rule (acrmi_nv12_to_rgb): a tensor [n,H,W,3] when all sizes agree, otherwise a list of [H_i,W_i,3] in input order."""
+    coef = nv12_matrix(matrix)
+    arr, sizes, dev, keep = _nv12_frames(frames)
+    n = len(sizes)
+    if all(s == sizes[0] for s in sizes):
+        out = torch.empty(n, sizes[0][0], sizes[0][1], 3, dtype=torch.uint8, device=dev)
+        dst = [out[i] for i in range(n)]
+    else:
+        out = dst = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for H, W in sizes]
+    ptrs = (C.c_void_p * n)(*[d.data_ptr() for d in dst])
+    _lib.check(_lib.lib().acrmi_nv12_to_rgb(arr, n, coef.ctypes.data_as(C.c_void_p), 0 if rgb else 1, ptrs, _s(dst[0])))
+    del keep
+    return out
+
+
 def cam_trans(joints, pj2d, focal_length=600.0, img_size=512.0):
     """joints [n,21,3], pj2d [n,21,2] (device fp32) -> cam_trans [n,3]: the reference's closed-form least squares
     (acr/utils.py:430-472, unit confidences) on the device."""

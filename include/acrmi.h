@@ -319,6 +319,41 @@ typedef struct acrmi_frame {
   int32_t H, W;
 } acrmi_frame;
 int acrmi_preprocess_frames(const acrmi_frame* frames_host, int n, uint8_t* out_rgb_dev, float* offsets_host, void* stream);
+/* NV12 video surfaces as the input (DESIGN.md "NV12 input"): what hardware and software decoders hand out - a luma plane and a
+ * half-height plane of interleaved chroma, pitched rows, 1.5 bytes per pixel - instead of the packed BGR frame cv2 makes of it
+ * (acr/main.py:126-141 reads frames with cv2).  The colour rule is integer, chroma is nearest (each 2x2 block of luma shares one
+ * U, V pair); it is OpenCV's published cvtColor(COLOR_YUV2BGR_NV12) arithmetic with the coefficient row as a parameter.  For
+ * bytes Y, U, V and a row (cy, cub, cug, cvg, cvr, y_off):
+ *   y = max(0, Y - y_off) * cy;  u = U - 128;  v = V - 128;  r = 1 << 19
+ *   R = clamp((y + cvr v + r) >> 20);  G = clamp((y + cug u + cvg v + r) >> 20);  B = clamp((y + cub u + r) >> 20)
+ * (arithmetic shift, clamp to 0..255).  A row is refused (ACRMI_EINVAL) when y_off is outside 0..255 or when
+ * 255 |cy| + 128 max(|cub|, |cvr|, |cug| + |cvg|) + 2^19 >= 2^31: the int32 sums cannot overflow. */
+typedef struct acrmi_nv12_frame {      /* 32 bytes */
+  const uint8_t* y_dev;                /* [H, y_pitch]  */
+  const uint8_t* uv_dev;               /* [H/2, uv_pitch], U at even bytes, V at odd */
+  int32_t H, W;                        /* both even, >= 2 */
+  int32_t y_pitch, uv_pitch;           /* bytes per row, >= W; nothing beyond W bytes of a row is read */
+} acrmi_nv12_frame;
+/* The named coefficient rows.  CV601: OpenCV's literal integers (NV12 -> the BGR frame cv2 gives the reference); the others:
+ * round(x * 2^20) of the textbook Kr / Kb forms, limited range (y_off 16) or full range (y_off 0). */
+#define ACRMI_NV12_CV601 0
+#define ACRMI_NV12_BT601 1
+#define ACRMI_NV12_BT601_FULL 2
+#define ACRMI_NV12_BT709 3
+#define ACRMI_NV12_BT709_FULL 4
+int acrmi_nv12_matrix(int which, int32_t coef6[6]);   /* host only */
+/* acrmi_preprocess_frames on NV12 frames: each of the 16 cubic taps is converted to 8-bit R, G, B by the rule above before it
+ * enters the sums, so out_rgb_dev [n,512,512,3] is byte for byte what converting the whole frame and calling
+ * acrmi_preprocess_frames gives, without a full-resolution RGB frame; pad taps are white.  coef6_host: six integers, NULL =
+ * CV601.  offsets_host [n,10] (may be NULL): the rows acrmi_preprocess_frames writes for the same H, W.  Everything is checked
+ * before anything is queued (the message names the frame); geometry travels in the kernel arguments, 64 frames per launch,
+ * further frames in further launches; frames_host may be freed when the call returns. */
+int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, uint8_t* out_rgb_dev,
+                          float* offsets_host, void* stream);
+/* The plain conversion at full resolution (frames to draw over, or to look at): dst_dev_host [n] device pointers to tight
+ * [H,W,3] uint8 images, RGB, or BGR when bgr != 0. */
+int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, int bgr,
+                      uint8_t* const* dst_dev_host, void* stream);
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream);
 /* ACRMI_OP_STEM stand-alone: img uint8 RGB [B,H,W,3] (H % 16 == 0, W % 128 == 0) -> [relu](conv3x3 stride 2 pad 1 of
  * (x/255*2-1) + bias) into channels out_coff..out_coff+63 of out [B,H/2,W/2,out_cs]; w_packed = packer.pack_stem(w
