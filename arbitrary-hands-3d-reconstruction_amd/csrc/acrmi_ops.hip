@@ -1,5 +1,6 @@
 // libacrmi.so: the stand-alone operators of the C ABI (unit tests / callers with their own tensors; no context).
 #include "acrmi_ctx.h"
+#include "conv_frame.h"   // conv_shape
 
 // (poison: acrmi_decode_gated's range flag of an 'fp16x3' program; null for the stand-alone operator)
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params,
@@ -37,6 +38,24 @@ int acrmi_decode_maps(const float* l_center, const float* r_center, int center_c
 }
 
 // ---- stand-alone operators -------------------------------------------------------------------------
+}  // extern "C"
+
+// the tail of the three convolution entry points: channel ranges, derived fields, the shape rules (csrc/conv_rules.h), the launch
+static int conv_check_and_launch(const char* who, ConvArgs& a, void* stream) {
+  if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2))
+    return fail(nullptr, ACRMI_EINVAL, "%s: only 3x3 and 1x1 at stride 1 / 2 are implemented (got k%d s%d)", who, a.ks, a.stride);
+  const int og = a.splitk ? 1 : a.groups;      // the slices of a split-K conv share the output channels
+  if (a.in_coff < 0 || a.out_coff < 0 || a.res_coff < 0 || a.in_coff + a.groups * a.Cin > a.in_cs || a.out_coff + og * a.Cout > a.out_cs ||
+      (a.res && a.res_coff + og * a.Cout > a.res_cs) || a.bias_fstride < 0 || (a.bias_fstride > 0 && a.bias_fstride < a.groups * a.Cout))
+    return fail(nullptr, ACRMI_EINVAL, "%s: channel slice outside its tensor's channel stride", who);
+  conv_derive(a);
+  if (const char* why = conv_algo_reject(a.algo, conv_shape(a))) return fail(nullptr, ACRMI_EINVAL, "%s: %s", who, why);
+  hipError_t e = launch_conv(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "conv launch: %s", hipGetErrorString(e));
+}
+
+extern "C" {
+
 int acrmi_conv2d(const float* in, int B, int H, int W, int in_cs, int in_coff, int cin, const float* w_packed,
                  const float* bias, int bias_frame_stride, const float* res, int res_cs, int res_coff, float* out,
                  int out_cs, int out_coff, int cout, int ksize, int stride, int relu, int groups, int algo,
@@ -45,47 +64,18 @@ int acrmi_conv2d(const float* in, int B, int H, int W, int in_cs, int in_coff, i
     return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: bad arguments");
   const int bias_map = algo >= 0 ? (algo & ACRMI_CONV_BIAS_MAP) : 0;      // res = ONE map [Ho][Wo][res_cs] for all frames
   if (algo >= 0) algo &= ~ACRMI_CONV_BIAS_MAP;
-  if (bias_map && (!res || algo == 3))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: ACRMI_CONV_BIAS_MAP needs res (the map) and an algo other than 3");
-  const bool x3s2 = (algo == 6 || algo == 7) && ksize == 3 && stride == 2;      // conv_x3s2.inc
-  if (algo != 0 && !x3s2 && !((algo >= 1 && algo <= 7) && (ksize == 3 || (algo >= 6 && ksize == 1)) && stride == (algo == 5 ? 2 : 1)))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo %d needs a 3x3 stride-%d convolution", algo, algo == 5 ? 2 : 1);
-  if (x3s2 && (cin % 32 || cout % 32 || H % 16 || W % 64))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo 6 / 7 at stride 2 needs Cin %% 32 = 0, Cout %% 32 = 0, H %% 16 == 0, W %% 64 == 0");
-  if ((algo == 6 || algo == 7) && !x3s2 && (cin % 32 || cout % 32 || (ksize == 3 ? ((H % 8 || W % 32) && (H % 16 || W % 16)) : ((H * W) % 256 != 0))))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo 6 / 7 needs Cin %% 32 = 0, Cout %% 32 = 0, H %% 8 == 0, W %% 32 == 0");
-  if (algo == 5 && (cin % 16 || cout % 32 || H % 16 || W % 32))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo 5 needs Cin %% 16 = 0, Cout %% 32 = 0, H %% 16 == 0, W %% 32 == 0");
-  if (algo == 3 && (groups != 1 || cin > 32 || cout != 32 || bias_frame_stride != 0 || H % 8 || W % 16 || out_cs % 4 ||
-                    out_coff % 4 || (res && (res_cs % 4 || res_coff % 4))))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo 3 needs groups 1, Cin <= 32, Cout = 32, H %% 8 == 0, W %% 16 == 0");
-  if (algo == 4 && (cin < 32 || (cin == 32 && (cout % 32 || H % 8 || W % 32))))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: algo 4 needs Cin > 32 (or Cin = 32, Cout %% 32 = 0 on a map of 8x32-pixel tiles)");
-  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: only 3x3 and 1x1 at stride 1 / 2 are implemented (got k%d s%d)", ksize, stride);
-  if (in_cs % 4 || in_coff % 4 || (groups > 1 && cin % 4))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: input channel stride/offset must be multiples of 4");
-  if (in_coff < 0 || out_coff < 0 || res_coff < 0 || in_coff + groups * cin > in_cs || out_coff + groups * cout > out_cs ||
-      (res && res_coff + groups * cout > res_cs) || bias_frame_stride < 0 ||
-      (bias_frame_stride > 0 && bias_frame_stride < groups * cout))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: channel slice outside its tensor's channel stride");
+  if (bias_map && !res) return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d: ACRMI_CONV_BIAS_MAP needs res (the map)");
   ConvArgs a{};
   a.in = in; a.w = w_packed; a.bias = bias; a.res = res; a.out = out;
   a.B = B; a.H = H; a.W = W;
-  const int pad = ksize / 2;
-  a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
   a.in_cs = in_cs; a.in_coff = in_coff; a.Cin = cin;
   a.out_cs = out_cs; a.out_coff = out_coff; a.Cout = cout;
   a.res_cs = res_cs; a.res_coff = res_coff;
   a.ks = ksize; a.stride = stride; a.relu = relu; a.groups = groups;
-  a.cin8 = (cin + 7) / 8;
-  a.n_tiles = cout <= 32 ? 1 : ((cout + 63) / 64) * 2;
   a.bias_fstride = bias_frame_stride;
   a.algo = algo;
   a.res_bcast = bias_map ? 1 : 0;
-  hipError_t e = launch_conv(a, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "conv launch: %s", hipGetErrorString(e));
-  return ACRMI_OK;
+  return conv_check_and_launch("acrmi_conv2d", a, stream);
 }
 
 size_t acrmi_conv2d_splitk_workspace(int B, int H, int W, int cout, int splits) {
@@ -99,30 +89,21 @@ int acrmi_conv2d_splitk(const float* in, int B, int H, int W, int in_cs, int in_
                         int out_cs, int out_coff, int cout, int relu, void* workspace, size_t workspace_bytes, void* stream) {
   if (!in || !w_packed || !bias || !out || !workspace || B <= 0 || H <= 0 || W <= 0 || cout <= 0)
     return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_splitk: bad arguments");
-  if (splits < 2 || splits > 8 || cin_slice < 64 || cin_slice % 32 || cout == 33)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_splitk: 2..8 slices of >= 64 channels (a multiple of 32) each; Cout != 33");
-  if (in_cs % 4 || in_coff % 4 || in_coff < 0 || out_coff < 0 || res_coff < 0 || in_coff + splits * cin_slice > in_cs ||
-      out_coff + cout > out_cs || (res && res_coff + cout > res_cs))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_splitk: channel slice outside its tensor's channel stride");
   if (workspace_bytes < acrmi_conv2d_splitk_workspace(B, H, W, cout, splits) || ((uintptr_t)workspace & 15))
     return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_splitk: workspace too small (acrmi_conv2d_splitk_workspace) or unaligned");
-  ConvArgs a{};
+  ConvArgs a{};      // (2..8 slices of >= 64 channels, a multiple of 32, each; Cout != 33: conv_rules.h)
   a.in = in; a.w = w_packed; a.bias = bias; a.res = res; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Ho = H; a.Wo = W;
+  a.B = B; a.H = H; a.W = W;
   a.in_cs = in_cs; a.in_coff = in_coff; a.Cin = cin_slice;
   a.out_cs = out_cs; a.out_coff = out_coff; a.Cout = cout;
   a.res_cs = res_cs; a.res_coff = res_coff;
   a.ks = 3; a.stride = 1; a.relu = relu; a.groups = splits;
-  a.cin8 = cin_slice / 8;
-  a.n_tiles = cout <= 32 ? 1 : ((cout + 63) / 64) * 2;
   a.algo = 2;
   a.splitk = 1;
   a.split_cnt = reinterpret_cast<unsigned*>(workspace);
   a.split_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) +
                                         (conv_splitk_counters(B, H, W, cout) * sizeof(unsigned) + 255) / 256 * 256);
-  hipError_t e = launch_conv(a, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "conv launch: %s", hipGetErrorString(e));
-  return ACRMI_OK;
+  return conv_check_and_launch("acrmi_conv2d_splitk", a, stream);
 }
 
 int acrmi_conv2d_h16(const void* in, int B, int H, int W, int in_cs, int in_coff, int cin, const void* w_packed,
@@ -132,32 +113,17 @@ int acrmi_conv2d_h16(const void* in, int B, int H, int W, int in_cs, int in_coff
   if (!in || !w_packed || !bias || !out || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || groups <= 0 ||
       (dtype != ACRMI_DT_F16 && dtype != ACRMI_DT_BF16))
     return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_h16: bad arguments");
-  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || (out_f32 && stride != 1))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_h16: 3x3 and 1x1 at stride 1 / 2 (fp32 output: stride 1 only); got k%d s%d", ksize, stride);
-  const int oq = out_f32 ? 4 : 8;      // elements per 16-byte vector of the output / residual
-  if (in_cs % 8 || in_coff % 8 || (groups > 1 && cin % 8) || out_cs % oq || (res && res_cs % oq))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_h16: channel strides must be multiples of 16 bytes");
-  if (in_coff < 0 || out_coff < 0 || res_coff < 0 || in_coff + groups * cin > in_cs || out_coff + groups * cout > out_cs ||
-      (res && res_coff + groups * cout > res_cs) || bias_frame_stride < 0 ||
-      (bias_frame_stride > 0 && bias_frame_stride < groups * cout))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_h16: channel slice outside its tensor's channel stride");
   ConvArgs a{};
   a.in = reinterpret_cast<const float*>(in); a.w = reinterpret_cast<const float*>(w_packed); a.bias = bias;
   a.res = reinterpret_cast<const float*>(res); a.out = reinterpret_cast<float*>(out);
   a.B = B; a.H = H; a.W = W;
-  const int pad = ksize / 2;
-  a.Ho = (H + 2 * pad - ksize) / stride + 1; a.Wo = (W + 2 * pad - ksize) / stride + 1;
   a.in_cs = in_cs; a.in_coff = in_coff; a.Cin = cin;
   a.out_cs = out_cs; a.out_coff = out_coff; a.Cout = cout;
   a.res_cs = res_cs; a.res_coff = res_coff;
   a.ks = ksize; a.stride = stride; a.relu = relu; a.groups = groups;
-  a.cin8 = (cin + 15) / 16;
-  a.n_tiles = cout <= 32 ? 1 : ((cout + 63) / 64) * 2;
   a.bias_fstride = bias_frame_stride;
   a.algo = 0; a.dtype = dtype; a.out_f32 = out_f32 ? 1 : 0;
-  hipError_t e = launch_conv(a, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "conv launch: %s", hipGetErrorString(e));
-  return ACRMI_OK;
+  return conv_check_and_launch("acrmi_conv2d_h16", a, stream);
 }
 
 int acrmi_preprocess(const uint8_t* bgr_dev, int n, int H, int W, uint8_t* out_rgb_dev, float* offsets_host,

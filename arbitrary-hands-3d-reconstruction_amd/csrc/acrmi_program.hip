@@ -1,5 +1,6 @@
 // libacrmi.so: the op program - validation (acrmi_set_program), dependency schedule and lanes, replay.
 #include "acrmi_ctx.h"
+#include "conv_frame.h"   // conv_shape
 
 void free_program(acrmi_ctx* c) {
   for (hipEvent_t e : c->op_ev)
@@ -28,6 +29,33 @@ void free_program(acrmi_ctx* c) {
   c->last_batch = 0;
 }
 
+// The integer side of a conv op's launch arguments, from the op and its buffer descriptors: what acrmi_set_program holds against
+// the shape rules (csrc/conv_rules.h) is what run_op launches (it adds the pointers).
+static ConvArgs conv_geometry(const acrmi_op& op, const acrmi_buffer_desc* bufs, int B) {
+  const auto& di = bufs[op.in_buf];
+  const auto& dout = bufs[op.out_buf];
+  ConvArgs a{};
+  a.B = B; a.H = di.h; a.W = di.w;
+  a.in_cs = di.cs; a.in_coff = op.in_coff; a.Cin = op.cin;
+  a.out_cs = dout.cs; a.out_coff = op.out_coff; a.Cout = op.cout;
+  a.res_cs = op.res_buf >= 0 ? bufs[op.res_buf].cs : 0; a.res_coff = op.res_coff;
+  a.splitk = (op.flags & ACRMI_CONV_SPLITK) != 0;      // groups = K-slices of one convolution
+  if (op.flags & ACRMI_CONV_BIAS_MAP) {   // position-bias map in the weight blob, added to every frame
+    a.res_cs = (op.groups * op.cout + 3) / 4 * 4; a.res_coff = 0; a.res_bcast = 1;
+  }
+  a.ks = op.ksize; a.stride = op.stride; a.relu = op.relu; a.groups = op.groups;
+  a.bias_fstride = op.bias_per_frame ? bufs[op.aux_buf].cs : 0;
+  a.nxt = op.nterms;      // extra residual terms of a stride-2 convolution (the HR fuse folded into its epilogue)
+  for (int t = 0; t < op.nterms && t < 3; ++t) {
+    a.xt_cs[t] = bufs[op.term_buf[t]].cs; a.xt_coff[t] = op.term_coff[t]; a.xt_shift[t] = op.term_shift[t];
+  }
+  if (op.flags & ACRMI_CONV_DUAL) a.out2_cs = bufs[op.aux_buf].cs;      // (out2_coff = 0)
+  a.algo = op.flags & 7;
+  a.dtype = di.dtype;                                    // 16-bit input: conv_h16.hip
+  a.out_f32 = di.dtype != ACRMI_DT_F32 && dout.dtype == ACRMI_DT_F32;
+  conv_derive(a);      // (Ho, Wo = the output buffer's size: acrmi_set_program checks it)
+  return a;
+}
 
 int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane) {
   auto ptr = [&](int id) -> float* { return id >= 0 ? c->buf_ptr[id] : nullptr; };
@@ -63,40 +91,18 @@ int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStrea
       return ACRMI_OK;
     }
     case ACRMI_OP_CONV: {
-      const auto& di = desc(op.in_buf);
-      const auto& dout = desc(op.out_buf);
-      ConvArgs a{};
+      ConvArgs a = conv_geometry(op, c->bufs.data(), B);
       a.in = ptr(op.in_buf);
       a.w = c->weights + op.w_off;
       a.bias = op.bias_per_frame ? ptr(op.aux_buf) : c->weights + op.b_off;
-      a.res = ptr(op.res_buf);
+      a.res = a.res_bcast ? c->weights + op.w_off2 : ptr(op.res_buf);
       a.out = ptr(op.out_buf);
-      a.B = B; a.H = di.h; a.W = di.w; a.Ho = dout.h; a.Wo = dout.w;
-      a.in_cs = di.cs; a.in_coff = op.in_coff; a.Cin = op.cin;
-      a.out_cs = dout.cs; a.out_coff = op.out_coff; a.Cout = op.cout;
-      a.res_cs = op.res_buf >= 0 ? desc(op.res_buf).cs : 0; a.res_coff = op.res_coff;
-      if (op.flags & ACRMI_CONV_SPLITK) {     // groups = K-slices of one convolution; workspace of the lane this op runs on
-        a.splitk = 1; a.split_ws = c->split_ws[lane]; a.split_cnt = c->split_cnt[lane];
+      if (a.splitk) {     // workspace of the lane this op runs on
+        a.split_ws = c->split_ws[lane]; a.split_cnt = c->split_cnt[lane];
       }
-      if (op.flags & ACRMI_CONV_BIAS_MAP) {   // position-bias map in the weight blob, added to every frame
-        a.res = c->weights + op.w_off2; a.res_cs = (op.groups * op.cout + 3) / 4 * 4; a.res_coff = 0; a.res_bcast = 1;
-      }
-      a.ks = op.ksize; a.stride = op.stride; a.relu = op.relu; a.groups = op.groups;
-      a.cin8 = (op.cin + 7) / 8;
-      a.n_tiles = op.cout <= 32 ? 1 : ((op.cout + 63) / 64) * 2;
-      a.bias_fstride = op.bias_per_frame ? desc(op.aux_buf).cs : 0;
-      a.nxt = op.nterms;      // extra residual terms of a stride-2 convolution (the HR fuse folded into its epilogue)
-      for (int t = 0; t < op.nterms && t < 3; ++t) {
-        a.xt[t] = ptr(op.term_buf[t]);
-        a.xt_cs[t] = desc(op.term_buf[t]).cs; a.xt_coff[t] = op.term_coff[t]; a.xt_shift[t] = op.term_shift[t];
-      }
-      if (op.flags & ACRMI_CONV_DUAL) {      // the full-resolution HR fuse sum as a second output (conv_wino3's store waves)
-        a.out2 = ptr(op.aux_buf); a.out2_cs = desc(op.aux_buf).cs; a.out2_coff = 0;
-      }
-      a.algo = op.flags & 7;
+      for (int t = 0; t < op.nterms && t < 3; ++t) a.xt[t] = ptr(op.term_buf[t]);
+      if (op.flags & ACRMI_CONV_DUAL) a.out2 = ptr(op.aux_buf);      // the full-resolution HR fuse sum (conv_wino3's store waves)
       a.range_flag = a.algo == 6 ? c->range_flag : nullptr;      // f16 operand halves: |x| must stay inside the f16 range
-      a.dtype = di.dtype;                                    // 16-bit input: conv_h16.hip
-      a.out_f32 = di.dtype != ACRMI_DT_F32 && dout.dtype == ACRMI_DT_F32;
       HIPCHK(c, launch_conv(a, s));
       return ACRMI_OK;
     }
@@ -416,9 +422,6 @@ int acrmi_set_program(acrmi_ctx* c, const acrmi_buffer_desc* bufs, int n_bufs, c
       if (op.res_buf >= 0 && bufs[op.res_buf].dtype != odt)
         return fail(c, ACRMI_EINVAL, "op %d: the residual must have the type of the output", i);
       const bool splitk = (op.flags & ACRMI_CONV_SPLITK) != 0;
-      if (splitk && (algo != 2 || idt || op.groups < 2 || op.groups > 8 || op.cin % 32 || op.cin < 64 || op.cout == 33 ||
-                     op.bias_per_frame))
-        return fail(c, ACRMI_EINVAL, "op %d: split-K needs algo 2, fp32, 2..8 slices of Cin %% 32 == 0, Cin >= 64 channels each", i);
       if (op.flags & ACRMI_CONV_BIAS_MAP) {
         const long long mcs = (op.groups * op.cout + 3) / 4 * 4;
         if (splitk || op.res_buf >= 0 || idt || algo == 3 || !w_ok(op.w_off2, (long long)bufs[op.out_buf].h * bufs[op.out_buf].w * mcs))
@@ -430,13 +433,10 @@ int acrmi_set_program(acrmi_ctx* c, const acrmi_buffer_desc* bufs, int n_bufs, c
                    bufs[op.aux_buf].h != bufs[op.out_buf].h || bufs[op.aux_buf].w != bufs[op.out_buf].w || bufs[op.aux_buf].cs % 4 ||
                    bufs[op.aux_buf].cs < op.cout || op.aux_buf == op.out_buf || op.aux_buf == op.in_buf || op.aux_buf == op.res_buf))
         return fail(c, ACRMI_EINVAL, "op %d: a second output needs algo 3, 1..3 terms and an fp32 map of the output's size in aux_buf", i);
-      if (op.nterms) {      // extra residual terms (ConvArgs.xt): what conv_pp2_kernel<NT, true> / the 32-cout stride-2 kernel take
+      if (op.nterms) {      // extra residual terms (ConvArgs.xt); which convolutions take them: conv_algo_reject below
         const int ho_ = bufs[op.out_buf].h, wo_ = bufs[op.out_buf].w;
-        if (op.nterms < 0 || op.nterms > 3 || idt || (op.flags & ACRMI_CONV_BIAS_MAP) || splitk ||
-            (dual ? false : (op.ksize != 3 || op.stride != 2 || (algo != 0 && algo != 5) || op.cout % 32 || op.cin <= 16 ||
-                             op.out_coff % 4 || bufs[op.out_buf].cs % 4)))
-          return fail(c, ACRMI_EINVAL, "op %d: extra residual terms need an fp32 3x3 stride-2 convolution (algo 0 / 5) with Cin > 16, "
-                      "Cout %% 32 = 0 and 16-byte aligned output channels - or ACRMI_CONV_DUAL", i);
+        if (op.nterms < 0 || op.nterms > 3 || (op.flags & ACRMI_CONV_BIAS_MAP))
+          return fail(c, ACRMI_EINVAL, "op %d: 1..3 extra residual terms, and no position-bias map beside them", i);
         for (int t = 0; t < op.nterms; ++t) {
           const int tb = op.term_buf[t];
           if (!buf_ok(tb) || bufs[tb].dtype != ACRMI_DT_F32 || op.term_coff[t] < 0 || op.term_coff[t] % 4 || bufs[tb].cs % 4 ||
@@ -446,46 +446,25 @@ int acrmi_set_program(acrmi_ctx* c, const acrmi_buffer_desc* bufs, int n_bufs, c
             return fail(c, ACRMI_EINVAL, "op %d: residual term %d does not fit the output", i, t);
         }
       }
-      if (op.bias_per_frame && buf_ok(op.aux_buf) && bufs[op.aux_buf].dtype != ACRMI_DT_F32)
-        return fail(c, ACRMI_EINVAL, "op %d: the per-frame bias must be fp32", i);
-      if (algo != 0 && !((algo == 6 || algo == 7) && op.ksize == 3 && op.stride == 2) &&
-          !((op.ksize == 3 || (algo >= 6 && op.ksize == 1)) && op.stride == (algo == 5 ? 2 : 1)))
-        return fail(c, ACRMI_EINVAL, "op %d: algo %d needs a 3x3 stride-%d convolution", i, algo, algo == 5 ? 2 : 1);
-      if (algo == 3 && (op.groups != 1 || op.cin > 32 || op.cout != 32 || op.bias_per_frame || bufs[op.out_buf].h % 8 ||
-                        bufs[op.out_buf].w % 16 || op.out_coff % 4 || op.res_coff % 4))
-        return fail(c, ACRMI_EINVAL, "op %d: algo 3 needs groups 1, Cin <= 32, Cout = 32, a map of 8x16-pixel tiles", i);
+      if (op.bias_per_frame && (!buf_ok(op.aux_buf) || bufs[op.aux_buf].dtype != ACRMI_DT_F32 || bufs[op.aux_buf].cs < op.groups * op.cout))
+        return fail(c, ACRMI_EINVAL, "op %d: per-frame bias buffer missing, too narrow or not fp32", i);
       const int ogroups = splitk ? 1 : op.groups;      // the slices of a split-K conv share the output channels
       if (op.in_coff + op.groups * op.cin > bufs[op.in_buf].cs || op.out_coff + ogroups * op.cout > bufs[op.out_buf].cs ||
           (op.res_buf >= 0 && op.res_coff + ogroups * op.cout > bufs[op.res_buf].cs) ||
           (op.groups > 1 && op.cin % (bufs[op.in_buf].dtype == ACRMI_DT_F32 ? 4 : 8)))      // a group starts on a 16-byte vector
         return fail(c, ACRMI_EINVAL, "op %d: channel slice outside its buffer's channel stride", i);
-      const int pad = op.ksize / 2;
-      const int ho = (bufs[op.in_buf].h + 2 * pad - op.ksize) / op.stride + 1, wo = (bufs[op.in_buf].w + 2 * pad - op.ksize) / op.stride + 1;
+      const int ho = conv_out_size(bufs[op.in_buf].h, op.ksize, op.stride), wo = conv_out_size(bufs[op.in_buf].w, op.ksize, op.stride);
       if (ho != bufs[op.out_buf].h || wo != bufs[op.out_buf].w ||
           (op.res_buf >= 0 && (bufs[op.res_buf].h != ho || bufs[op.res_buf].w != wo)))
         return fail(c, ACRMI_EINVAL, "op %d: output/residual buffer geometry does not match the convolution", i);
-      const long long n_tiles = op.cout <= 32 ? 1 : ((op.cout + 63) / 64) * 2;
-      if (algo == 4 && (op.cin < 32 || (op.cin == 32 && (op.cout % 32 || ho % 8 || wo % 32))))      // (Cin = 32: conv_wino24b_kernel only)
-        return fail(c, ACRMI_EINVAL, "op %d: algo 4 needs Cin > 32, or Cin = 32 with Cout %% 32 = 0 on a map of 8x32-pixel tiles", i);
-      if ((algo == 6 || algo == 7) && op.stride == 2 &&
-          (op.ksize != 3 || ho % 8 || wo % 32 || bufs[op.in_buf].h != 2 * ho || bufs[op.in_buf].w != 2 * wo || op.nterms > 0))      // (conv_x3s2.inc x3s2_ok)
-        return fail(c, ACRMI_EINVAL, "op %d: algo 6 / 7 at stride 2 needs a 3x3 convolution onto a map of 8x32-pixel tiles, even input size, no extra residual terms", i);
-      if ((algo == 6 || algo == 7) && (idt || op.cin % 32 || op.cout % 32 || op.out_coff % 4 || op.res_coff % 4 ||
-                                       (op.ksize == 3 ? ((ho % 8 || wo % 32) && (ho % 16 || wo % 16)) : ((ho * wo) % 256 != 0))))      // (conv_x3.inc x3_ok / conv_x3p.inc x3p_ok)
-        return fail(c, ACRMI_EINVAL, "op %d: algo 6 / 7 needs fp32 storage, Cin %% 32 = 0, Cout %% 32 = 0, a map of 8x32- or 16x16-pixel tiles (3x3) / of whole 256-pixel items (1x1)", i);
-      if (algo == 5 && (idt || op.cin % 16 || op.cout % 32 || bufs[op.in_buf].h % 2 || bufs[op.in_buf].w % 2 || ho % 8 || wo % 16 ||
-                        op.out_coff % 4 || op.res_coff % 4))      // (conv_pp2.inc pp2_ok)
-        return fail(c, ACRMI_EINVAL, "op %d: algo 5 needs fp32, Cin %% 16 = 0, Cout %% 32 = 0, an output map of 8x16-pixel tiles", i);
-      const long long taps = algo >= 6 ? op.ksize * op.ksize : algo == 5 ? 28 : algo == 4 ? 24 : (algo >= 2 ? 16 : (algo == 1 ? 12 : op.ksize * op.ksize));
-      const long long ksteps = idt ? (op.cin + 15) / 16 : (op.cin + 7) / 8;      // 1 KiB weight fragments per tap and n-tile
-      const long long wn = algo == 3 ? 16384 : (long long)op.groups * taps * ksteps * n_tiles * 256 + (algo >= 6 ? 1 : 0);      // (algo 6 / 7: + the weight scale)
+      // the convolution as run_op will launch it (no pointers yet): does launch_conv have a kernel for it (csrc/conv_rules.h)?
+      ConvShape cs = conv_shape(conv_geometry(op, bufs, max_batch));
+      cs.has_res = op.res_buf >= 0 || cs.res_bcast; cs.out2 = dual;
+      if (const char* why = conv_algo_reject(algo, cs)) return fail(c, ACRMI_EINVAL, "op %d (algo %d): %s", i, algo, why);
+      const long long wn = conv_weight_floats(algo, op.groups, op.ksize, op.cin, op.cout, idt);
       if (!w_ok(op.w_off, wn)) return fail(c, ACRMI_EINVAL, "op %d: packed weights outside the blob", i);
-      if (op.bias_per_frame) {
-        if (!buf_ok(op.aux_buf) || bufs[op.aux_buf].cs < op.groups * op.cout)
-          return fail(c, ACRMI_EINVAL, "op %d: per-frame bias buffer missing or too narrow", i);
-      } else if (!w_ok(op.b_off, (long long)op.groups * n_tiles * 32)) {
+      if (!op.bias_per_frame && !w_ok(op.b_off, (long long)op.groups * conv_n_tiles(op.cout) * 32))
         return fail(c, ACRMI_EINVAL, "op %d: bias outside the blob", i);
-      }
     }
     if (op.kind == ACRMI_OP_STEM) {
       if (bufs[op.out_buf].dtype && (bufs[op.out_buf].cs % 8 || op.out_coff % 8))

@@ -54,6 +54,12 @@ __device__ __forceinline__ int fdiv(int n, unsigned long long magic) {
   return (int)(((unsigned long long)(unsigned)n * magic) >> 40);
 }
 
+// a ConvArgs as conv_rules.h sees it
+inline ConvShape conv_shape(const ConvArgs& a) {
+  return ConvShape{a.ks, a.stride, a.groups, a.Cin, a.Cout, a.H, a.W, a.Ho, a.Wo, a.in_cs, a.in_coff, a.out_cs, a.out_coff, a.res_cs, a.res_coff,
+                   a.out2_cs, a.out2_coff, a.res != nullptr, a.bias_fstride, a.nxt, a.out2 != nullptr, a.splitk, a.res_bcast, a.in_sub, a.dtype, a.out_f32};
+}
+
 // One kernel instantiation as its launcher names it: the host handle, the instantiation's own "dynamic LDS attribute set"
 // flags (one per device) and what ACRMI_DEBUG prints.  CONV_KERNEL(conv_x_kernel<...>) creates the flags where the
 // instantiation is named: every expansion has its own, and inside a template launcher every instantiation of it.

@@ -460,7 +460,7 @@ static hipError_t launch_h16(const ConvArgs& a, hipStream_t s) {
 // on the big tiles (the layers are HBM / L2 bound: two chunks of requests in flight instead of one).
 // fp32 output (a.out_f32; output AND residual fp32) exists for 1x1 and 3x3 stride-1 shapes: the head exits.
 hipError_t launch_conv_h16(ConvArgs a, hipStream_t s) {
-  if ((a.in_cs & 1) || (a.in_coff & 1) || (a.groups > 1 && (a.Cin & 1))) return hipErrorInvalidValue;
+  // (conv_algo_reject, checked by launch_conv: the input's channel stride, offset and group size are multiples of 8 elements)
   a.in_cs /= 2;
   a.in_coff /= 2;
   a.cin8 = (a.Cin + 15) / 16;

@@ -534,6 +534,7 @@ static hipError_t launch_wino(const ConvArgs& a, hipStream_t s) {
 // Tile selection.  N32: one 32-cout tile per wave (Cout <= 32); N64: two.
 // Small frames (<=16x16 outputs) take the 8x16 pixel tile so a batch still fills 256 CUs.
 hipError_t launch_conv(ConvArgs a, hipStream_t s) {
+  if (conv_algo_reject(a.algo, conv_shape(a))) return hipErrorInvalidValue;      // no kernel for this algo and shape (conv_rules.h)
   std::lock_guard<std::recursive_mutex> launch_lock(g_init_mutex);
   a.dbg = g_dbg;
   a.phase_delay = g_phase_delay;
@@ -564,9 +565,6 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s) {
   if (a.dtype != ACRMI_DT_F32) return launch_conv_h16(a, s);   // f16 / bf16 storage: conv_h16.hip
   const bool n32 = a.n_tiles == 1;
   const bool small = (a.Ho * a.Wo <= 256) || (a.Ho % 16 != 0) || (a.Wo % 16 != 0);
-  if (a.splitk && a.algo != 2) return hipErrorInvalidValue;
-  if (a.nxt > 0 && a.algo != 5 && a.algo != 0 && !(a.algo == 3 && a.out2)) return hipErrorInvalidValue;      // extra residual terms: the stride-2 kernels, or conv_wino3's second output
-  if (a.out2 && a.algo != 3) return hipErrorInvalidValue;
   if ((a.algo == 6 || a.algo == 7) && a.ks == 1) return launch_x3p(a, a.algo == 7, s);      // ... 1x1 (conv_x3p.inc)
   if ((a.algo == 6 || a.algo == 7) && a.stride == 2) return launch_x3s2(a, a.algo == 7, s);      // ... 3x3 stride 2 (conv_x3s2.inc)
   if (a.algo == 6 || a.algo == 7) return launch_x3(a, a.algo == 7, s);      // 3x3 stride 1, split f16 / bf16 operands on the 16-bit matrix pipe (conv_x3.inc)
@@ -579,7 +577,6 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s) {
     }
   if (a.algo == 3) return launch_wino3(a, s);   // F(2x2,3x3), Cin <= 32, Cout = 32: weights packed for LDS residency
   if (a.algo == 2) {   // Winograd F(2x2,3x3): 3x3 stride 1 only, weights packed with 16 taps
-    if (a.ks != 3 || a.stride != 1) return hipErrorInvalidValue;
     if (a.splitk) return launch_wino2<1, 32, 2>(a, s);      // K-slices as groups, one n-tile per item (conv_wino2.inc SPLIT)
     // two n-tiles per wave need two Cin chunks per item (single-buffered exchange area); Cin <= 32 runs one
     // n-tile per wave and one 32-cout block per work item instead
@@ -598,15 +595,12 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s) {
     return nt1 ? launch_wino2<1, 32, 2>(a, s) : launch_wino2<2, 32, 2>(a, s);
   }
   if (a.algo == 1) {   // Winograd F(2,3) along x: 3x3 stride 1 only, weights packed with 12 taps
-    if (a.ks != 3 || a.stride != 1) return hipErrorInvalidValue;
     // (the previous round's kernel; the program lowers every 3x3 stride-1 conv to algo 2 now)
     if (n32) return small ? launch_wino<8, 16, 2, 1, 32, 2>(a, s) : launch_wino<16, 16, 4, 1, 32, 2>(a, s);
     return launch_wino<8, 16, 2, 2, 32, 2>(a, s);
   }
-  if (a.nxt > 0) {      // extra residual terms (HR fuse): the polyphase kernel above, or the 32-cout stride-2 direct kernel
-    if (a.ks != 3 || a.stride != 2 || a.cin8 * 8 <= 16 || a.nxt > 3) return hipErrorInvalidValue;
+  if (a.nxt > 0)      // extra residual terms (HR fuse): the polyphase kernel above, or the 32-cout stride-2 direct kernel
     return launch_ws2_impl<3, 2, 8, 16, 4, 1, 1, 1, 16, 2, false, true>(a, s);
-  }
   // direct: template arguments <KS, S, TH, TW, WAVES_M, MT, WAVES_N, NTW, CK, NLW>
   if (a.ks == 3 && a.stride == 1) {
     if (n32) return small ? launch_ws2<3, 1, 8, 16, 4, 1, 1, 1, 32, 2>(a, s) : launch_ws2<3, 1, 16, 16, 4, 2, 1, 1, 32, 2>(a, s);

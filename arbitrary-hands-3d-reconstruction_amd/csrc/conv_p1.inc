@@ -262,14 +262,7 @@ __global__ __launch_bounds__(256, 1) void conv_p1_kernel(const ConvArgs a, const
   }
 }
 
-// shapes conv_p1_kernel takes
-static bool p1_ok(const ConvArgs& a) {
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  return a.ks == 1 && a.stride == 1 && a.algo == 0 && a.Cin % 32 == 0 && a.Cin >= 32 && a.Cout % 32 == 0 && a.H == a.Ho &&
-         a.W == a.Wo && (a.Ho * a.Wo) % 256 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 &&
-         a.out_coff % 4 == 0 && res_ok && !a.splitk && a.in_sub <= 1 && (long long)256 * a.in_cs * 4 < (1ll << 30) &&
-         (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-}
+static bool p1_ok(const ConvArgs& a) { return a.algo == 0 && takes_p1(conv_shape(a)); }
 
 static hipError_t launch_p1_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
   constexpr size_t lds = (2 * (size_t)8 * 258 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);

@@ -401,15 +401,6 @@ __global__ __launch_bounds__(256, 1) void conv_pp2_kernel(const ConvArgs a, cons
   if (stamp) a.dbg[63] = ns_;
 }
 
-// shapes conv_pp2_kernel takes (packer.polyphase2_ok mirrors this: the weights of an algo-5 op are packed for this kernel only)
-static bool pp2_ok(const ConvArgs& a) {
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  return a.ks == 3 && a.stride == 2 && a.H % 2 == 0 && a.W % 2 == 0 && a.Ho == a.H / 2 && a.Wo == a.W / 2 && a.Ho % 8 == 0 &&
-         a.Wo % 16 == 0 && a.Cin % 16 == 0 && a.Cout % 32 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 &&
-         a.out_coff % 4 == 0 && res_ok && !a.splitk && a.in_sub <= 1 && (long long)17 * a.W * a.in_cs * 4 < (1ll << 30) &&
-         (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-}
-
 static constexpr size_t pp2_lds(int NT) {      // two patches + the exchange area (nine tiles per n-tile)
   return (2 * (size_t)41 * 64 * 4 + 9 * (size_t)(NT >= 2 ? 2 : 1) * 32 * 32) * sizeof(float);
 }
@@ -418,7 +409,7 @@ static hipError_t launch_pp2_impl(const ConvArgs& a, hipStream_t s, int NT, cons
   return launch_conv_kernel(k, 256, pp2_lds(NT), a.Wo / 16, a.Ho / 8, (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_pp2(const ConvArgs& a, hipStream_t s) {
-  if (!pp2_ok(a)) return hipErrorInvalidValue;
+  if (!takes_pp2(conv_shape(a))) return hipErrorInvalidValue;
   if (a.nxt > 0)      // + extra residual terms (HR fuse)
     return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, CONV_KERNEL(conv_pp2_kernel<2, true>)) : launch_pp2_impl(a, s, 1, CONV_KERNEL(conv_pp2_kernel<1, true>));
   return a.Cout % 64 == 0 ? launch_pp2_impl(a, s, 2, CONV_KERNEL(conv_pp2_kernel<2, false>)) : launch_pp2_impl(a, s, 1, CONV_KERNEL(conv_pp2_kernel<1, false>));

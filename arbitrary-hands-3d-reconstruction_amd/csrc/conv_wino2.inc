@@ -527,7 +527,7 @@ static hipError_t launch_wino2_impl(const ConvArgs& a, hipStream_t s) {
 // register-staged loader everywhere (A/B runs)
 static bool conv_dma_ok(const ConvArgs& a) {
   static const char* env = experiment_env("ACRMI_CONV_DMA");
-  return (!env || atoi(env) != 0) && a.Cin % 4 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0;
+  return (!env || atoi(env) != 0) && takes_dma(conv_shape(a));
 }
 // conv_wino2_kernel: measured 23.3 ms (LDS-DMA) vs 22.2 ms (register loader) over the network's 157 launches - with
 // two LDS buffers only one chunk is in flight, the register loader runs two ahead.  ACRMI_CONV_DMA=2 selects it anyway.

@@ -512,20 +512,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
   if (stamp) a.dbg[63] = ns_;
 }
 
-// shapes conv_wino24b_kernel takes (everything else stays on conv_wino24_kernel); ACRMI_WINO24B=0 / cfg 840 keep the old frame.
-// Returns the item width: 32 (8x32-pixel items), 16 (16x16-pixel items, maps narrower than 32 pixels) or 0; n-tiles per wave:
-// 2 when Cout is a multiple of 64, else 1 (Cout % 32 == 0, 8x32-pixel items only).
+// item width of conv_wino24b_kernel for the shapes it takes (conv_rules.h takes_wino24b), else 0: everything else stays on
+// conv_wino24_kernel; ACRMI_WINO24B=0 / cfg 840 keep the old frame
 static int wino24b_ok(const ConvArgs& a) {
   static const char* env = experiment_env("ACRMI_WINO24B");
-  if ((env && atoi(env) == 0) || g_force_cfg == 840) return 0;
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  const bool ok = a.ks == 3 && a.stride == 1 && a.Cin % 32 == 0 && a.Cin >= 32 && a.Cout % 32 == 0 && a.H == a.Ho && a.W == a.Wo &&
-                  a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 && res_ok && !a.splitk &&
-                  a.in_sub <= 1 && (long long)10 * a.W * a.in_cs * 4 < (1ll << 30) && (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-  if (!ok) return 0;
-  if (a.Ho % 8 == 0 && a.Wo % 32 == 0) return 32;
-  if (a.Ho % 16 == 0 && a.Wo % 16 == 0 && a.Cout % 64 == 0 && a.Cin >= 64) return 16;
-  return 0;
+  return ((env && atoi(env) == 0) || g_force_cfg == 840) ? 0 : takes_wino24b(conv_shape(a));
 }
 
 static constexpr int wino24b_th(int TW) { return TW == 32 ? 8 : 16; }

@@ -442,18 +442,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino24c_kernel(const ConvArgs a, 
   if (stamp) a.dbg[63] = ns_;
 }
 
-// shapes conv_wino24c_kernel takes.  NOT routed by default: measured 7 % SLOWER than conv_wino24b_kernel on the two-chunk
+// conv_wino24c_kernel for the shapes it takes (conv_rules.h takes_wino24c).  NOT routed by default: measured 7 % SLOWER than conv_wino24b_kernel on the two-chunk
 // layers (item 41.2k vs 38.6k cycles: the epilogue drops from 8.4k to 5.9k, but the per-step fragment exchange - 24 reads,
 // 12 stores, a barrier, 24 instead of 12 weight loads - adds ~600 cycles to each of the 8 steps; profiles/r06_wino24c_ablation.txt,
 // DESIGN.md section 7).  conv_bench --cfg 842 / acrmi_tune(0, 842) selects it (A/B runs, tests/test_gpu_kernels.py).
-static bool wino24c_ok(const ConvArgs& a) {
-  if (g_force_cfg != 842) return false;
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  return a.ks == 3 && a.stride == 1 && a.Cin % 32 == 0 && a.Cin >= 64 && a.Cout % 64 == 0 && a.H == a.Ho && a.W == a.Wo &&
-         a.Ho % 8 == 0 && a.Wo % 32 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 &&
-         res_ok && !a.splitk && a.in_sub <= 1 && (long long)10 * a.W * a.in_cs * 4 < (1ll << 30) &&
-         (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-}
+static bool wino24c_ok(const ConvArgs& a) { return g_force_cfg == 842 && takes_wino24c(conv_shape(a)); }
 
 static hipError_t launch_wino24c(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)47 * 64 * 4 + 2 * (size_t)24 * 256) * sizeof(float);

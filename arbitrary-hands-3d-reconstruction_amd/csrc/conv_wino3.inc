@@ -613,13 +613,6 @@ __global__ __launch_bounds__((4 + NLW) * 64, 1) void conv_wino3b_kernel(const Co
   if (stamp) a.dbg[63] = ns_;
 }
 
-// eligibility of a convolution for conv_wino3_kernel (also what acrmi_conv2d / acrmi_set_program check for algo 3)
-static bool wino3_ok(const ConvArgs& a) {
-  return a.ks == 3 && a.stride == 1 && a.groups == 1 && a.Cin <= 32 && a.Cout == 32 && a.n_tiles == 1 &&
-         a.bias_fstride == 0 && a.Ho % 8 == 0 && a.Wo % 16 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 &&
-         a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && (!a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0));
-}
-
 template <int NLW, bool DMA, bool RES>
 static hipError_t launch_wino3b_impl(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)18 * 18 * 36 + 16 * 2 * 2 * 256) * sizeof(float);
@@ -636,7 +629,7 @@ static hipError_t launch_wino3_impl(const ConvArgs& a, hipStream_t s) {
 }
 
 static hipError_t launch_wino3(const ConvArgs& a, hipStream_t s) {
-  if (!wino3_ok(a)) return hipErrorInvalidValue;
+  if (!takes_wino3(conv_shape(a))) return hipErrorInvalidValue;
   const bool dma_ok = conv_dma_ok(a);
   if (a.out2) {      // + the full-resolution HR fuse sum as a second output (store waves)
     if (!dma_ok || a.nxt < 1 || a.nxt > 3 || a.out2_cs % 4 || a.out2_coff % 4) return hipErrorInvalidValue;

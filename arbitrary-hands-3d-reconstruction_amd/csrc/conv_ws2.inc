@@ -356,7 +356,7 @@ static hipError_t launch_ws2_impl(const ConvArgs& a, hipStream_t s) {
   constexpr int PH = (TH - 1) * S + KS, PW = (TW - 1) * S + KS;
   constexpr size_t lds = (2 * (size_t)PH * PW * (CK + 4) + (size_t)WAVES_M * WAVES_N * 32 * 36) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two patch buffers and the epilogue tiles must fit the 160 KiB LDS");
-  if (XT && (a.Cout % 32 || a.out_cs % 4 || a.out_coff % 4)) return hipErrorInvalidValue;      // (the vector epilogue only)
+  // (XT: the vector epilogue only - Cout % 32 == 0, 16-byte aligned output channels: conv_rules.h conv_algo_reject)
   int nblk = (a.n_tiles + WAVES_N * NTW - 1) / (WAVES_N * NTW), nb_inner = 1;
   if (ONE && nblk > 1 && g_force_cfg != 901) {   // all n-blocks of a tile from one patch
     nb_inner = nblk;

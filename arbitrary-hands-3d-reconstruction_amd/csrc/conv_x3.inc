@@ -412,26 +412,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3_kernel(const ConvArgs a, const
   if (!BF && a.range_flag && range_max > 65504.f) atomicOr(a.range_flag, 1u);
 }
 
-// shapes conv_x3_kernel takes: 32 (8 x 32-pixel items), 16 (16 x 16-pixel items) or 0 (packer.split16_ok mirrors this: the
-// weights of an algo-6 / 7 op are packed for this kernel only)
-static int x3_ok(const ConvArgs& a) {
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  const bool ok = a.ks == 3 && a.stride == 1 && a.Cin % 32 == 0 && a.Cin >= 32 && a.Cout % 32 == 0 && a.H == a.Ho && a.W == a.Wo &&
-                  a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 && res_ok && !a.splitk &&
-                  a.in_sub <= 1 && (long long)18 * a.W * a.in_cs * 4 < (1ll << 30) &&
-                  (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-  if (!ok) return 0;
-  if (a.Ho % 8 == 0 && a.Wo % 32 == 0) return 32;
-  if (a.Ho % 16 == 0 && a.Wo % 16 == 0) return 16;
-  return 0;
-}
-
 static hipError_t launch_x3_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, const ConvKernel& k) {
   constexpr size_t lds = (2 * (size_t)4 * 2 * 386 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
   return launch_conv_kernel(k, 256, lds, a.Wo / TW, a.Ho / (TW == 32 ? 8 : 16), (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3(const ConvArgs& a, bool bf, hipStream_t s) {
-  const int tw = x3_ok(a);
+  const int tw = takes_x3(conv_shape(a));      // 32 (8 x 32-pixel items), 16 (16 x 16-pixel items) or 0
   if (!tw) return hipErrorInvalidValue;
   const bool n2 = a.Cout % 64 == 0;
   if (tw == 32) {

@@ -293,21 +293,12 @@ __global__ __launch_bounds__(256, 1) void conv_x3p_kernel(const ConvArgs a, cons
   if (!BF && a.range_flag && range_max > 65504.f) atomicOr(a.range_flag, 1u);
 }
 
-// shapes conv_x3p_kernel takes (packer.split16_ok mirrors this)
-static bool x3p_ok(const ConvArgs& a) {
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  return a.ks == 1 && a.stride == 1 && a.Cin % 32 == 0 && a.Cin >= 32 && a.Cout % 32 == 0 && a.H == a.Ho && a.W == a.Wo &&
-         (a.Ho * a.Wo) % 256 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 &&
-         res_ok && !a.splitk && a.in_sub <= 1 && (long long)256 * a.in_cs * 4 < (1ll << 30) &&
-         (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-}
-
 static hipError_t launch_x3p_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
   constexpr size_t lds = (2 * (size_t)4 * 2 * 258 * 4 + 4 * 2 * (size_t)32 * 32) * sizeof(float);
   return launch_conv_kernel(k, 256, lds, 1, (a.Ho * a.Wo) / 256, (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3p(const ConvArgs& a, bool bf, hipStream_t s) {
-  if (!x3p_ok(a)) return hipErrorInvalidValue;
+  if (!takes_x3p(conv_shape(a))) return hipErrorInvalidValue;
   if (bf) return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, CONV_KERNEL(conv_x3p_kernel<2, true>)) : launch_x3p_impl(a, s, 1, CONV_KERNEL(conv_x3p_kernel<1, true>));
   return a.Cout % 64 == 0 ? launch_x3p_impl(a, s, 2, CONV_KERNEL(conv_x3p_kernel<2>)) : launch_x3p_impl(a, s, 1, CONV_KERNEL(conv_x3p_kernel<1>));
 }

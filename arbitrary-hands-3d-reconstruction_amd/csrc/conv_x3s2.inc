@@ -371,22 +371,13 @@ __global__ __launch_bounds__(256, 1) void conv_x3s2_kernel(const ConvArgs a, con
   if (!BF && a.range_flag && range_max > 65504.f) atomicOr(a.range_flag, 1u);
 }
 
-// shapes conv_x3s2_kernel takes (packer.split16_ok mirrors this: the weights of an algo-6 / 7 stride-2 op are packed for it)
-static bool x3s2_ok(const ConvArgs& a) {
-  const bool res_ok = !a.res || (a.res_cs % 4 == 0 && a.res_coff % 4 == 0);
-  return a.ks == 3 && a.stride == 2 && a.Cin % 32 == 0 && a.Cin >= 32 && a.Cout % 32 == 0 && a.H == 2 * a.Ho && a.W == 2 * a.Wo &&
-         a.Ho % 8 == 0 && a.Wo % 32 == 0 && a.in_cs % 4 == 0 && a.in_coff % 4 == 0 && a.out_cs % 4 == 0 && a.out_coff % 4 == 0 &&
-         res_ok && !a.splitk && a.nxt == 0 && a.in_sub <= 1 && (long long)34 * a.W * a.in_cs * 4 < (1ll << 30) &&
-         (a.bias_fstride == 0 || a.bias_fstride >= a.groups * a.n_tiles * 32);
-}
-
 static hipError_t launch_x3s2_impl(const ConvArgs& a, hipStream_t s, int NT, const ConvKernel& k) {
   constexpr size_t lds = (2 * (size_t)2 * 2 * 1106 * 4 + 4 * (size_t)32 * 32) * sizeof(float);
   static_assert(lds <= 160 * 1024, "two step buffers and the transposition tiles must fit the LDS");
   return launch_conv_kernel(k, 256, lds, a.Wo / 32, a.Ho / 8, (a.Cout / 32) / NT, a, s);
 }
 static hipError_t launch_x3s2(const ConvArgs& a, bool bf, hipStream_t s) {
-  if (!x3s2_ok(a)) return hipErrorInvalidValue;
+  if (!takes_x3s2(conv_shape(a))) return hipErrorInvalidValue;
   // (single-chunk items, Cin = 32: the two-n-tile instantiation keeps ~100 values in scratch there and every scratch access
   //  waits behind the patch loads in flight - cfg 851 selects it anyway)
   const bool n2 = a.Cout % 64 == 0 && (a.Cin > 32 || g_force_cfg == 851);

@@ -6,6 +6,7 @@
 
 #include <stdlib.h>
 
+#include "conv_rules.h"
 #include "smooth_plan.h"
 
 namespace acrmi {
@@ -36,8 +37,8 @@ struct ConvArgs {
   int n_tiles;          // 32-cout tiles per group in the packed weights (CoutP/32)
   int cin8;             // ceil(Cin/8)
   int bias_fstride;     // floats between frames' bias rows (0 = shared)
-  int algo;             // 0 direct; 1 Winograd F(2,3) along x (3x3 stride 1, weights packed with 3x4 taps);
-                        // 2 Winograd F(2x2,3x3) (3x3 stride 1, weights packed with 4x4 taps)
+  int algo;             // 0 direct, 1..7 the other kernels: which shapes each takes, its taps and the size of its packed
+                        // weights are stated in conv_rules.h (conv_algo_reject, conv_taps, conv_weight_floats)
   long long* dbg;       // optional device buffer for cycle stamps (tuning only)
   int phase_delay;      // tuning switches of the loader waves (acrmi_tune key 3): 8 = idle loader (timing ablation, wrong
                         // results), 9 = loader at priority 0; 0 = off
@@ -73,9 +74,17 @@ struct ConvArgs {
   unsigned* range_flag;   // conv_x3 / conv_x3p with f16 halves: set to 1 when an activation beyond the f16 range was split
                           // (null: not tracked - the stand-alone operator calls)
 };
+// The derived fields (Ho, Wo, cin8, n_tiles) from the primary ones (H, W, ks, stride, Cin, Cout, dtype): every ConvArgs is
+// completed here.
+inline void conv_derive(ConvArgs& a) {
+  a.Ho = conv_out_size(a.H, a.ks, a.stride);
+  a.Wo = conv_out_size(a.W, a.ks, a.stride);
+  a.cin8 = conv_ksteps(a.Cin, a.dtype);
+  a.n_tiles = conv_n_tiles(a.Cout);
+}
 // workspace of a split-K launch: (8x16-pixel tiles) x (32-cout blocks) groups of `splits` partial tiles of 4096 floats
 inline size_t conv_splitk_groups(int B, int Ho, int Wo, int cout) {
-  return (size_t)B * ((Ho + 7) / 8) * ((Wo + 15) / 16) * (cout <= 32 ? 1 : ((cout + 63) / 64) * 2);
+  return (size_t)B * ((Ho + 7) / 8) * ((Wo + 15) / 16) * conv_n_tiles(cout);
 }
 inline size_t conv_splitk_ws_floats(int B, int Ho, int Wo, int cout, int splits) { return conv_splitk_groups(B, Ho, Wo, cout) * splits * 4096; }
 inline size_t conv_splitk_counters(int B, int Ho, int Wo, int cout) { return conv_splitk_groups(B, Ho, Wo, cout) * 4; }

@@ -49,7 +49,11 @@ def check_state_dict(sd):
             raise ValueError('checkpoint tensor %s has shape %s, expected %s' % (k, tuple(_np(sd[k]).shape), shp))
 
 
+# Which kernel takes which layer is stated once, in csrc/conv_rules.h.  n_tiles_for, polyphase2_ok, split16_ok, wino24b_width and
+# conv_algo below are its pure-Python copies (lower() works without the library); tests/test_conv_rules_host.py holds them
+# against the header over a grid of shapes.
 def n_tiles_for(cout):
+    """csrc/conv_rules.h conv_n_tiles."""
     return 1 if cout <= 32 else ((cout + 63) // 64) * 2
 
 
@@ -284,9 +288,10 @@ POLYPHASE2 = __import__('os').environ.get('ACRMI_PP2', '1') != '0'
 POLYPHASE2_SMALL = __import__('os').environ.get('ACRMI_PP2_SMALL', '1') != '0'      # ... also in small-batch programs (A/B: 0)
 
 
-def polyphase2_ok(cin, cout, ho, wo):
-    """conv_pp2_kernel takes the layer (csrc/conv_pp2.inc pp2_ok; ho, wo = OUTPUT map, the input is twice that)."""
-    return cin % 16 == 0 and cout % 32 == 0 and ho % 8 == 0 and wo % 16 == 0
+def polyphase2_ok(cin, cout, ho, wo, even_input=True):
+    """conv_pp2_kernel takes the layer (csrc/conv_rules.h takes_pp2; ho, wo = OUTPUT map; even_input: the input is exactly
+    twice that)."""
+    return even_input and cin % 16 == 0 and cout % 32 == 0 and ho % 8 == 0 and wo % 16 == 0
 
 
 # Split-operand 16-bit program ('fp16x3': fp32 storage, every operand of the eligible convolutions split into two f16
@@ -296,13 +301,13 @@ def polyphase2_ok(cin, cout, ho, wo):
 SPLIT16_STRIDE2 = __import__('os').environ.get('ACRMI_X3_STRIDE2', '1') != '0'
 
 
-def split16_ok(k, stride, cin, cout, ho, wo):
-    """conv_x3_kernel (3x3) / conv_x3p_kernel (1x1) / conv_x3s2_kernel (3x3 stride 2) takes the layer (csrc/conv_x3.inc x3_ok,
-    conv_x3p.inc x3p_ok, conv_x3s2.inc x3s2_ok)."""
+def split16_ok(k, stride, cin, cout, ho, wo, even_input=True):
+    """conv_x3_kernel (3x3) / conv_x3p_kernel (1x1) / conv_x3s2_kernel (3x3 stride 2) takes the layer (csrc/conv_rules.h takes_x3,
+    takes_x3p, takes_x3s2; even_input: a stride-2 layer's input is exactly twice its output map)."""
     if not (cin % 32 == 0 and cin >= 32 and cout % 32 == 0):
         return False
     if stride == 2:
-        return SPLIT16_STRIDE2 and k == 3 and ho % 8 == 0 and wo % 32 == 0
+        return SPLIT16_STRIDE2 and even_input and k == 3 and ho % 8 == 0 and wo % 32 == 0
     if stride != 1:
         return False
     return (k == 3 and ((ho % 8 == 0 and wo % 32 == 0) or (ho % 16 == 0 and wo % 16 == 0))) or (
@@ -329,7 +334,7 @@ WINOGRAD_24 = __import__('os').environ.get('ACRMI_WINO24', '1') != '0'
 
 
 def wino24b_width(cin, cout, ho, wo):
-    """Item width of conv_wino24b_kernel for a 3x3 stride-1 conv (csrc/conv_wino24b.inc wino24b_ok): 32, 16 or 0 = not taken."""
+    """Item width of conv_wino24b_kernel for a 3x3 stride-1 conv (csrc/conv_rules.h takes_wino24b): 32, 16 or 0 = not taken."""
     if not (cin % 32 == 0 and cin >= 32 and cout % 32 == 0):
         return 0
     if ho % 8 == 0 and wo % 32 == 0:
@@ -339,20 +344,22 @@ def wino24b_width(cin, cout, ho, wo):
     return 0
 
 
-def conv_algo(k, stride, cin, cout, groups=1, ho=0, wo=0, per_frame_bias=False, wino24=None, split16=False):
+def conv_algo(k, stride, cin, cout, groups=1, ho=0, wo=0, per_frame_bias=False, wino24=None, split16=False, even_input=True):
     """0 direct, 1 Winograd F(2,3) along x, 2 Winograd F(2x2,3x3), 3 F(2x2,3x3) with LDS-resident taps, 4 F(2x4,3x3),
     5 polyphase F(2,2) (3x3 stride 2), 6 / 7 split f16 / bf16 operands on the 16-bit matrix pipe (split16 = True | 'fp16' / 'bf16':
     the 'fp16x3' / 'bf16x3' programs only).
     wino24: None = WINOGRAD_24; False keeps the F(2x2,3x3) kernels for the layers F(2x4,3x3) would take (small batches:
-    its 8x32-pixel, one-n-tile items are half as many as conv_wino2's small-batch items)."""
-    if split16 and split16_ok(k, stride, cin, cout, ho, wo):
+    its 8x32-pixel, one-n-tile items are half as many as conv_wino2's small-batch items).
+    even_input: the input map of a stride-2 layer is exactly twice (ho, wo); an odd-sized one stays on the direct kernel.
+    Every algo returned here is one csrc/conv_rules.h conv_algo_reject accepts for the layer; the algo-3 clause is takes_wino3."""
+    if split16 and split16_ok(k, stride, cin, cout, ho, wo, even_input):
         return 7 if split16 == 'bf16' else 6
     if k == 3 and stride == 2:
         # round 4 took the polyphase kernel for the large-batch lowering only; its items (8x16 output pixels x 32 or 64 couts)
         # are no fewer than the direct kernel's at small batches and run 25 products per 2x2 block instead of 36: the 24
         # stride-2 launches on a batch-1 call's dependency chain were 22.8 us each as direct convolutions (tools/critical_path.py)
         big = (WINOGRAD_24 if wino24 is None else wino24) or POLYPHASE2_SMALL
-        return 5 if (POLYPHASE2 and big and polyphase2_ok(cin, cout, ho, wo)) else 0
+        return 5 if (POLYPHASE2 and big and polyphase2_ok(cin, cout, ho, wo, even_input)) else 0
     if not (WINOGRAD and use_winograd(k, stride)):
         return 0
     if (WINOGRAD_2D and WINOGRAD_LDS and groups == 1 and cin <= 32 and cout == 32 and ho % 8 == 0 and wo % 16 == 0
@@ -560,6 +567,7 @@ class Program(object):
         cout, cin_w = wb_list[0][0].shape[:2]
         cin = cin_w if cin is None else cin
         ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (w_ + 2 * (k // 2) - k) // stride + 1
+        even = (h, w_) == (2 * ho, 2 * wo)      # (an odd-sized input of a stride-2 layer: the direct kernel, csrc/conv_rules.h)
         flop_cout = cout
         if out is None and out_c is None and len(wb_list) == 1 and k == 3 and stride == 1 and cout < 32 and res is None:
             # a Cout < 32 tile takes the Winograd kernel's element-wise epilogue (16 scalar stores per lane); padded to
@@ -594,7 +602,7 @@ class Program(object):
         else:
             # (a stride-2 conv that hosts HR fuse terms keeps the polyphase kernel: conv_x3s2_kernel has no extra residual maps)
             algo = 2 if slices > 1 else conv_algo(k, stride, cin, cout, len(wb_list), ho, wo, bias_buf is not None, self.wino24,
-                                                    False if ((terms or fp32_kernel) and stride == 2) else self.split16)
+                                                    False if ((terms or fp32_kernel) and stride == 2) else self.split16, even)
             if algo in (6, 7):
                 packed = [pack_conv_x3(wb_list, DT_BF16 if algo == 7 else DT_F16)]      # (one power-of-two weight scale for the op: trailing float)
             elif algo == 3:
@@ -633,7 +641,7 @@ class Program(object):
         self.op_info[-1]['algo'] = ('direct', 'winograd_f23x', 'winograd_f2x2_3x3', 'winograd_f2x2_3x3_lds',
                                     'winograd_f2x4_3x3', 'polyphase_f2x2_s2', 'split_f16x3', 'split_bf16x3')[algo] + ('_splitk%d' % slices if slices > 1 else '')
         # what bench.py prints next to the PMC traffic: the kernel family launch_conv picks for this op (conv_mfma.hip /
-        # conv_wino24b.inc wino24b_ok) and the op's ALGORITHMIC HBM bytes per frame - input slice + output (+ residual)
+        # csrc/conv_rules.h takes_wino24b) and the op's ALGORITHMIC HBM bytes per frame - input slice + output (+ residual)
         # once, in their storage types
         ng = len(wb_list)
         esz = lambda b: 4 if self.dtype_of(b) == DT_F32 else 2

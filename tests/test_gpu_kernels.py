@@ -824,6 +824,45 @@ def test_conv2d_rejects_unsupported(ops):
         ops.conv2d(x, torch.zeros(8, 8, 3, 3), stride=2, algo='winograd2d')
 
 
+RULE_BOUNDARIES = [
+    # (algo, tolerance of that kernel's own test above, k, stride, accepted [(Cin, Cout, H, W of the INPUT)], refused neighbour)
+    ('winograd2d_lds', 5e-5, 3, 1, [(32, 32, 8, 16)], (32, 32, 8, 24)),
+    ('winograd24', 2e-4, 3, 1, [(64, 64, 8, 32), (64, 64, 16, 16), (64, 64, 8, 24)], (32, 48, 8, 32)),   # (8x24: ragged maps fall to conv_wino24_kernel)
+    ('polyphase2', 1e-4, 3, 2, [(32, 32, 16, 32)], (32, 32, 16, 24)),
+    ('split16', 2e-5, 3, 1, [(32, 32, 8, 32)], (32, 32, 8, 24)),
+    ('split_bf16', 5e-4, 3, 1, [(32, 32, 8, 32)], (32, 32, 8, 24)),
+    ('split16', 2e-5, 1, 1, [(32, 32, 16, 16)], (32, 32, 10, 10)),
+    ('split_bf16', 5e-4, 1, 1, [(32, 32, 16, 16)], (32, 32, 10, 10)),
+    ('split16', 2e-5, 3, 2, [(32, 32, 16, 64)], (32, 32, 15, 64)),
+    ('split_bf16', 5e-4, 3, 2, [(32, 32, 16, 64)], (32, 32, 15, 64)),
+]
+
+
+@pytest.mark.parametrize('case', RULE_BOUNDARIES, ids=lambda c: '%s_k%ds%d' % (c[0], c[2], c[3]))
+def test_conv_rules_accept_and_refuse_at_their_boundaries(ops, case):
+    """csrc/conv_rules.h on both sides of a rule's boundary: for a shape the rules accept the launcher finds a kernel (result vs
+    an fp64 convolution), the refused neighbour raises ValueError from the validator and nothing runs (output still 7)."""
+    algo, tol, k, stride, accepted, refused = case
+    g = torch.Generator().manual_seed(290)
+
+    for (cin, cout, H, W) in accepted + [refused]:
+        x = torch.randn(2, cin, H, W, generator=g)
+        w = torch.randn(cout, cin, k, k, generator=g) / np.sqrt(cin * k * k)
+        b = torch.randn(cout, generator=g) * 0.1
+        ref = F.conv2d(x.double(), w.double(), b.double(), stride, k // 2)
+        dst = torch.full((2,) + tuple(ref.shape[2:]) + (cout,), 7.0, device='cuda')
+        if (cin, cout, H, W) == refused:
+            with pytest.raises(ValueError):
+                ops.conv2d(ops.to_nhwc(x), w, b, stride=stride, algo=algo, out=dst)
+            torch.cuda.synchronize()
+            assert (dst == 7).all()
+        else:
+            ops.conv2d(ops.to_nhwc(x), w, b, stride=stride, algo=algo, out=dst)
+            torch.cuda.synchronize()
+            err = (dst.permute(0, 3, 1, 2).cpu().double() - ref).abs().max().item()
+            assert err < tol, ((cin, cout, H, W), err)
+
+
 def test_u8norm_bit_exact(ops):
     img = torch.arange(256, dtype=torch.uint8).repeat(3 * 16).view(1, 16, 256, 3).contiguous()
     out = ops.u8norm(img.cuda()).cpu()
