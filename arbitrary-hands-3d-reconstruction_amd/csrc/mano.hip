@@ -6,15 +6,14 @@
 // 2397 output floats lives in LDS; the 1.46 MB of per-side tables are read coalesced
 // (blend-shape tables pre-transposed on the host) and stay L2 resident across hands.
 #include "kernels.h"
+#include "mano_plan.h"
 
 namespace acrmi {
 
 __constant__ int c_parent[16] = {-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14};
 __constant__ int c_depth[16] = {0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3};
 __constant__ int c_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int c_tips[2][5] = {{745, 317, 445, 556, 673}, {745, 317, 444, 556, 673}};  // [left, right]
-
-constexpr int NV = 778, NV3 = 2334;
+__constant__ int c_tips[2][5] = ACRMI_MANO_TIPS;  // [left, right]
 
 // H16 = ACRMI_OPT_MANO_FP16 (BASELINE.json configs[4] "fp16 MANO LBS"): the blend-shape tables (shapedirs, posedirs)
 // and the skinning weights are read as f16 copies (0.73 instead of 1.46 MB of L2 traffic per side and hand), every
@@ -23,13 +22,14 @@ constexpr int NV = 778, NV3 = 2334;
 // weights were all of r5's 6.4e-5 m; the pose blend table, 86 % of the bytes, stays plain f16.
 template <bool H16>
 __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
-  // a.slices workgroups per hand (launch_mano): at small batches a hand's 120 us - one CU streaming the 1.26 MB pose-blend
+  // a.slices workgroups per hand (mano_plan.h): at small batches a hand's 120 us - one CU streaming the 1.26 MB pose-blend
   // table - are on the call's critical path; the slices split that table by vertex range.  Every vertex and joint is
-  // computed by exactly one slice with the arithmetic of the one-workgroup form: results do not depend on a.slices.
+  // computed by exactly one slice with the arithmetic of the one-workgroup form: results do not depend on a.slices
+  // (tests/test_gpu_mano.py: every slice count, bit for bit).
   const int row = blockIdx.x / a.slices, slice = blockIdx.x - row * a.slices;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int vper = (NV + a.slices - 1) / a.slices;
-  const int v0 = slice * vper, v1 = v0 + vper < NV ? v0 + vper : NV;
+  int v0, v1;
+  mano_slice_range(slice, a.slices, &v0, &v1);
   const int side = a.side ? a.side[row] : (row & 1);
   const ManoTables& T = a.t[side];
   __shared__ float sR[16][9];
@@ -204,11 +204,7 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
 hipError_t launch_mano(const ManoArgs& a0, hipStream_t s) {
   if (a0.H <= 0) return hipSuccess;
   ManoArgs a = a0;
-  // workgroups per hand: enough to give every CU one (2 hands: 8 slices; 128 hands: 2).  A root joint that is a FINGERTIP
-  // (center_idx 4, 8, 12, 16, 20: a skinned vertex, mano/manolayer.py:241-262) is known only to the slice that skinned
-  // it: one slice then.
-  const bool tip_center = a.center_idx >= 0 && a.center_idx % 4 == 0 && a.center_idx > 0;
-  a.slices = tip_center ? 1 : (a.H >= 256 ? 1 : (256 / a.H > 8 ? 8 : 256 / a.H));
+  a.slices = mano_slices(a.H, a.center_idx);
   if (a.lbs_f16) {
     if (!a.t[0].posedirs_h || !a.t[1].posedirs_h) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mano_kernel<true>, dim3(a.H * a.slices), dim3(256), 0, s, a);

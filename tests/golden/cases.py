@@ -86,19 +86,24 @@ MANO_ROTMAT_CASES = {
 }
 
 
-def mano_rotmat_inputs(name):
-    """[n,16,3,3] float32 matrices + betas: exact rotations (fp64 Rodrigues of seeded axis-angles), plus seeded noise so that
-    batch_rotprojs' SVD projection matters, plus - in the '_reflection' case - one matrix with a negated column (det < 0:
-    the reference's reflection branch)."""
-    kw, n, seed, noise = MANO_ROTMAT_CASES[name]
-    g = rng(1700 + seed)
+def _seeded_rotmats(g, n):
+    """[n,16,3,3] float64 rotations: fp64 Rodrigues of axis-angles drawn from g."""
     aa = g.normal(0, 0.6, (n, 16, 3))
     th = np.linalg.norm(aa, axis=-1, keepdims=True)
     k = aa / th
     K = np.zeros((n, 16, 3, 3))
     K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -k[..., 2], k[..., 1], k[..., 2]
     K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -k[..., 0], -k[..., 1], k[..., 0]
-    R = np.eye(3) + np.sin(th)[..., None] * K + (1 - np.cos(th))[..., None] * (K @ K)
+    return np.eye(3) + np.sin(th)[..., None] * K + (1 - np.cos(th))[..., None] * (K @ K)
+
+
+def mano_rotmat_inputs(name):
+    """[n,16,3,3] float32 matrices + betas: exact rotations (fp64 Rodrigues of seeded axis-angles), plus seeded noise so that
+    batch_rotprojs' SVD projection matters, plus - in the '_reflection' case - one matrix with a negated column (det < 0:
+    the reference's reflection branch)."""
+    kw, n, seed, noise = MANO_ROTMAT_CASES[name]
+    g = rng(1700 + seed)
+    R = _seeded_rotmats(g, n)
     R = R + noise * g.normal(0, 1, R.shape)
     if name.endswith('_reflection'):
         R[0, 5, :, 1] *= -1
@@ -154,6 +159,52 @@ def proj_inputs(n, seed):
     cam = np.stack([g.uniform(0.5, 2.0, n), g.uniform(-0.5, 0.5, n), g.uniform(-0.5, 0.5, n)], 1).astype(np.float32)
     offsets = np.tile(np.array([[1920, 1920, 0, 0, 0, 0, 420, 0, 420, 0]], np.float32), (n, 1))
     return cam, offsets
+
+
+# ManoLayer rooted at a FINGERTIP (center_idx 4, 8, 12, 16, 20: a skinned vertex, mano/manolayer.py:241-262), which the kernel
+# launches as one workgroup per hand (csrc/mano_plan.h).  name -> (side, center_idx, n, seed); the hands are mano_inputs(n, seed):
+# a zero hand and a large pose, at the middle finger - whose tip vertex differs between the sides - a third.
+# tests/golden/make_golden_mano_tips.py -> mano_tips.npz
+MANO_TIP_CASES = {'tip_%s_c%d' % (side, c): (side, c, 3 if c == 12 else 2, 30 + 2 * c + (side == 'left'))
+                  for side in ('left', 'right') for c in (4, 8, 12, 16, 20)}
+
+
+def mano_tip_inputs(name):
+    side, center_idx, n, seed = MANO_TIP_CASES[name]
+    return mano_inputs(n, seed)
+
+
+# ---- MANO at every slice count (tests/test_gpu_mano.py) ---------------------------------------------------------------------
+# Hands per call that reach 8, 8, 8, 7, 7, 6, 5, 4, 3, 2, 1 and 1 workgroups per hand (csrc/mano_plan.h mano_slices;
+# tests/test_mano_plan_host.py fails when a retuned formula no longer gives all eight counts for this list).
+MANO_SLICE_HANDS = (1, 2, 32, 33, 36, 42, 51, 64, 85, 128, 129, 300)
+MANO_POOL_SEED = 100
+
+
+def mano_pool(n):
+    """The first n rows of mano_inputs(16, seed) for seeds 100, 101, ... concatenated (every 16 rows hold a zero hand and a
+    large pose) -> poses [n,48], betas [n,10], side int32 [n] (0 left, 1 right: seeded, so that a call mixes the two)."""
+    blocks = [mano_inputs(16, MANO_POOL_SEED + k) + (rng(800 + MANO_POOL_SEED + k).integers(0, 2, 16).astype(np.int32),)
+              for k in range((n + 15) // 16)]
+    return tuple(np.concatenate([b[i] for b in blocks])[:n] for i in range(3))
+
+
+def mano_pool_proj(n):
+    """proj_inputs' seeded scheme for the n rows of mano_pool: cam as there, block by block, and an offsets row of its own
+    per hand - padded size, crop_trbl, pad_trbl (acr/utils.py:1294-1321) - so that a row read from a neighbour shows."""
+    cam, offsets = [], []
+    for k in range((n + 15) // 16):
+        cam.append(proj_inputs(16, MANO_POOL_SEED + k)[0])
+        g = rng(1100 + MANO_POOL_SEED + k)
+        size = g.choice(np.array([512, 640, 1280, 1920], np.float32), (16, 1))
+        offsets.append(np.concatenate([size, size, g.integers(0, 421, (16, 8)).astype(np.float32)], 1))
+    return np.concatenate(cam)[:n], np.concatenate(offsets)[:n]
+
+
+def mano_pool_rotmats(n):
+    """mano_pool's hands in joint_rot_mode='rotmat': [n,16,3,3] float32 rotations as mano_rotmat_inputs builds them (no noise:
+    the kernel takes matrices that are already on SO(3)), a block of 16 per seed."""
+    return np.concatenate([_seeded_rotmats(rng(1700 + MANO_POOL_SEED + k), 16) for k in range((n + 15) // 16)])[:n].astype(np.float32)
 
 
 def sub(t, max_elems=4096):

@@ -139,6 +139,22 @@ def test_mano_rotmat_mode_matches_reference(name, mano_tables):
         assert c is None
 
 
+@pytest.mark.parametrize('name', list(cases.MANO_TIP_CASES))
+def test_mano_fingertip_roots_match_reference(name, mano_tables):
+    """center_idx 4, 8, 12, 16, 20: the root joint is a skinned VERTEX (mano/manolayer.py:241-262), per side - the middle
+    finger's is 445 on the left, 444 on the right.  The oracle against the REAL reference's ManoLayer on both sides
+    (tests/golden/mano_tips.npz, make_golden_mano_tips.py)."""
+    g = golden('mano_tips.npz')
+    side, center_idx, n, seed = cases.MANO_TIP_CASES[name]
+    poses, betas = cases.mano_tip_inputs(name)
+    v, j, c = omano.mano_forward(mano_tables[side], side, poses, betas, center_idx=center_idx)
+    assert v.shape == (n, 778, 3) and j.shape == (n, 21, 3) and c.shape == (n, 1, 3)
+    _close(v, g[name + '_verts'], 1e-5, 2e-7)
+    _close(j, g[name + '_joints'], 1e-5, 2e-7)
+    _close(c, g[name + '_center'], 1e-5, 2e-7)
+    assert np.abs(g[name + '_joints'][:, center_idx]).max() == 0 and np.abs(g[name + '_center']).min() > 1e-3
+
+
 def test_projection_matches_reference(mano_tables):
     g = golden('mano_cases.npz')
     poses, betas = cases.mano_inputs(4, 9)
