@@ -49,6 +49,10 @@ class NV12Frame(C.Structure):      # acrmi_nv12_frame
                 ('y_pitch', C.c_int32), ('uv_pitch', C.c_int32)]
 
 
+class Roi(C.Structure):      # acrmi_roi
+    _fields_ = [('frame', C.c_int32), ('l', C.c_int32), ('t', C.c_int32), ('r', C.c_int32), ('b', C.c_int32)]
+
+
 # acrmi_nv12_matrix `which` (ACRMI_NV12_*) by the name the Python layer takes
 NV12_MATRICES = {'cv601': 0, 'bt601': 1, 'bt601-full': 2, 'bt709': 3, 'bt709-full': 4}
 
@@ -70,7 +74,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_mesh_topology', 'acrmi_render_workspace', 'acrmi_rasterize', 'acrmi_load_faces', 'acrmi_render',
            'acrmi_overlay_tables', 'acrmi_draw_skeletons', 'acrmi_draw_heatmaps', 'acrmi_overlay',
            'acrmi_streams_create', 'acrmi_streams_destroy', 'acrmi_streams_reset', 'acrmi_smooth_streams',
-           'acrmi_forward_streams', 'acrmi_nv12_matrix', 'acrmi_preprocess_nv12', 'acrmi_nv12_to_rgb']
+           'acrmi_forward_streams', 'acrmi_nv12_matrix', 'acrmi_preprocess_nv12', 'acrmi_nv12_to_rgb',
+           'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12']
 
 _lib = None
 
@@ -127,6 +132,9 @@ def lib():
     L.acrmi_nv12_matrix.argtypes = [i32, vp]
     L.acrmi_preprocess_nv12.argtypes = [C.POINTER(NV12Frame), i32, vp, vp, vp, vp]
     L.acrmi_nv12_to_rgb.argtypes = [C.POINTER(NV12Frame), i32, vp, i32, C.POINTER(vp), vp]
+    L.acrmi_roi_offsets.argtypes = [i32, i32, C.POINTER(Roi), vp, vp]
+    L.acrmi_preprocess_rois.argtypes = [C.POINTER(Frame), i32, C.POINTER(Roi), i32, vp, vp, vp]
+    L.acrmi_preprocess_rois_nv12.argtypes = [C.POINTER(NV12Frame), i32, C.POINTER(Roi), i32, vp, vp, vp, vp]
     L.acrmi_forward.argtypes = [vp, u8p, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
     L.acrmi_conv2d.argtypes = [f32p, i32, i32, i32, i32, i32, i32, f32p, f32p, i32, f32p, i32, i32, f32p, i32, i32,
                                i32, i32, i32, i32, i32, i32, vp]

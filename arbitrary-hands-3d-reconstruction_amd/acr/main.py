@@ -227,11 +227,29 @@ class ACR(object):
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
+        results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
+                                                        max_streams)
+        render_offsets = offsets
+        if render is None:
+            return results
+        if show_items is None:
+            return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
+        views = {}
+        for name in show_items:
+            if name == 'mesh':
+                views[name] = self._render_batch(eng, out, render, render_offsets, render_bgr)
+            elif name == 'org_img':
+                views[name] = render
+            else:
+                views[name] = self._overlay_batch(eng, out, render, name, render_offsets, render_bgr)
+        return results, views
+
+    def _forward_batch_results(self, rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams, max_streams):
+        """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned)."""
         B = rgb_u8_frames.shape[0]
         ids, table = (None, None) if streams is None else self._streams_for(streams, max_streams, B)
         eng = self.model.engine(B)
         semantics = batch_semantics or self.model._result_parser.batch_semantics
-        render_offsets = offsets
         if offsets is None:
             offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
         eng.set_point_heads(point_heads)
@@ -269,19 +287,7 @@ class ACR(object):
                                   'pj2d_org': host['pj2d_org'][b, h].astype(np.float16),
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
             results[path] = hands if hands else {}
-        if render is None:
-            return results
-        if show_items is None:
-            return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
-        views = {}
-        for name in show_items:
-            if name == 'mesh':
-                views[name] = self._render_batch(eng, out, render, render_offsets, render_bgr)
-            elif name == 'org_img':
-                views[name] = render
-            else:
-                views[name] = self._overlay_batch(eng, out, render, name, render_offsets, render_bgr)
-        return results, views
+        return results, eng, out
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
         kw = dict(focal_length=float(self.focal_length), bgr=bgr)
@@ -332,7 +338,7 @@ class ACR(object):
 
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
-                       pixel_format='bgr', matrix='cv601'):
+                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -342,10 +348,21 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     pixel_format='nv12': the frames are NV12 surfaces as a video decoder leaves them (ops.preprocess_nv12 says which layouts),
     converted by the integer rule `matrix` names (ops.nv12_matrix) inside the pre-processing kernel; the results are those
     of the BGR frames ops.nv12_to_bgr makes of them, and those BGR frames - a tensor [n,H,W,3] when all sizes agree, else a
-    list - are what render=True / show_items draw over."""
+    list - are what render=True / show_items draw over.
+    boxes [n,4] = (l, t, r, b) with box_frame [n] (default: box i of frame i): the network sees n REGIONS of the frames at the
+    resolution the frames have (ops.preprocess_rois; a person or hand detector's boxes, or acr.utils.boxes_from_keypoints of
+    the frame before).  One path per region, results keyed by it, a stream id per region; pj2d_org is in the pixels of the
+    ORIGINAL frame.  render=True then needs show_items of 'pj2d' / 'org_img': the skeletons of all regions of a frame are drawn
+    over that frame, one drawn frame per source frame.  'mesh' and 'centermap' over regions are a ValueError (the
+    rasteriser's viewport is per frame: DESIGN.md "Regions of interest")."""
     from .utils import img_preprocess_gpu
     if show_items is not None and not render:
         raise ValueError('show_items needs render=True')
+    if boxes is not None:
+        return _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
+                                pixel_format, matrix)
+    if box_frame is not None:
+        raise ValueError('box_frame says which frame each box is of: it needs boxes=')
     meta = img_preprocess_gpu(bgr_frames_dev, paths, pixel_format=pixel_format, matrix=matrix)
     canvas = None
     if render:
@@ -353,6 +370,56 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
     return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                               render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
+
+
+def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix):
+    """forward_raw_batch with boxes."""
+    from .. import _lib as S
+    from .. import ops
+    from .utils import img_preprocess_gpu
+    items = check_show_items(show_items)
+    if render:
+        bad = [name for name in (items or ['mesh']) if name not in ('pj2d', 'org_img')]
+        if bad:
+            raise ValueError('%s over regions is not implemented (the viewport of the rasteriser and of the heat maps is one row '
+                             "per frame; two regions of a frame need two): use show_items=('pj2d',)" % ', '.join(repr(b) for b in bad))
+    meta = img_preprocess_gpu(frames, paths, pixel_format=pixel_format, matrix=matrix, boxes=boxes, box_frame=box_frame)
+    n = meta['image'].shape[0]
+    if len(paths) != n:
+        raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
+    results, eng, out = self._forward_batch_results(meta['image'], paths, meta['offsets'], True, None, streams, max_streams)
+    if not render:
+        return results
+    canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames
+    # hand h of region i goes into frame box_frame[i]; a slot without a detection is not drawn
+    frame_of = torch.arange(n) if box_frame is None else torch.as_tensor(box_frame).cpu().long()
+    flagged = (out['slots'][:, :, S.SLOT_FLAG] > 0.5).cpu()
+    hand_frame = torch.where(flagged, frame_of[:, None].expand(n, 2), torch.full((n, 2), -1)).reshape(-1)
+    kps = out['pj2d_org'].reshape(-1, 21, 2).float().contiguous()
+    views = {}
+    for name in items:
+        views[name] = canvas if name == 'org_img' else _draw_over_frames(kps, canvas, hand_frame)
+    return results, views
+
+
+def _draw_over_frames(kps, canvas, hand_frame):
+    """ops.draw_skeletons of hands [M,21,2] over a tensor of frames, or over a list of frames of different sizes (one call per
+    size, output order = input order); hand_frame [M] = the frame of each hand, -1 = not drawn."""
+    from .. import ops
+    if not isinstance(canvas, (list, tuple)):
+        return ops.draw_skeletons(kps, canvas, hand_frame=hand_frame.to(torch.int32), bgr=True)
+    groups = {}
+    for i, f in enumerate(canvas):
+        groups.setdefault(tuple(f.shape), []).append(i)
+    drawn = [None] * len(canvas)
+    for idx in groups.values():
+        place = torch.full((len(canvas),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
+        place[idx] = torch.arange(len(idx))
+        local = torch.where(hand_frame >= 0, place[hand_frame.clamp(min=0)], torch.full_like(hand_frame, -1))
+        got = ops.draw_skeletons(kps, torch.stack([canvas[i] for i in idx]), hand_frame=local.to(torch.int32), bgr=True)
+        for j, i in enumerate(idx):
+            drawn[i] = got[j]
+    return drawn
 
 
 ACR.forward_raw_batch = _forward_raw_batch

@@ -58,20 +58,24 @@ def compute_paddings_to_reach_aspect_ratio(shape, ratio=1.0):
 def img_preprocess(image, imgpath=None, input_size=512, single_img_input=False, bbox=None, device=0):
     """BGR frame (numpy HxWx3 uint8, or a uint8 tensor) -> {'image': uint8 [1,512,512,3] RGB, 'offsets': [1,10]}
     (acr/utils.py:1315-1337).  The white pad + cv2.resize(INTER_CUBIC) run in the HIP pre-processing kernel
-    (acrmi_preprocess: OpenCV's uint8 fixed-point cubic restated bit for bit); the image stays in HBM."""
+    (acrmi_preprocess: OpenCV's uint8 fixed-point cubic restated bit for bit); the image stays in HBM.
+    bbox = (l, t, r, b), r and b exclusive: the window of the frame the box leaves after clamping is pre-processed instead of
+    the frame (image_crop_pad's bbox, acr/utils.py:1287-1301, which the reference declares and never passes through; white
+    pad here as everywhere, DESIGN.md "Regions of interest"); the offsets row carries the crop."""
     if input_size != 512:
         raise ValueError('only input_size=512 is implemented')
-    if bbox is not None:
-        raise ValueError('bbox cropping is not used by the demo path (acr/main.py:130) and is not implemented')
     frame = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
     if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
         raise ValueError('frame must be uint8 HxWx3 BGR')
+    if bbox is not None:
+        from .. import ops
+        ops.roi_offsets(frame.shape[0], frame.shape[1], bbox)      # a bad box is a ValueError before the device is looked at
     if not frame.is_cuda:
         if not torch.cuda.is_available():
             from .. import _lib
             raise _lib.AcrmiError('no GPU visible: pre-processing runs in the HIP kernel (no CPU fallback)')
         frame = frame.to(torch.device('cuda', device))
-    data = img_preprocess_gpu(frame[None], None)
+    data = img_preprocess_gpu(frame[None], None, boxes=None if bbox is None else [bbox])
     img, offsets = data['image'], data['offsets']
     if not single_img_input:
         img, offsets = img[0], offsets[0]
@@ -81,14 +85,20 @@ def img_preprocess(image, imgpath=None, input_size=512, single_img_input=False, 
     return data
 
 
-def img_preprocess_gpu(bgr_frames, imgpaths=None, pixel_format='bgr', matrix='cv601'):
+def img_preprocess_gpu(bgr_frames, imgpaths=None, pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None):
     """Batched device pre-processing: uint8 BGR frames [n,H,W,3] already in HBM - or a list of frames
     [H_i,W_i,3] of different sizes (acrmi_preprocess_frames) ->
     {'image': uint8 RGB [n,512,512,3] (device), 'offsets': [n,10], 'batch_ids': [n]}: one HIP kernel, no host
     round trip.  pixel_format='nv12': the frames are NV12 surfaces as ops.preprocess_nv12 takes them (a decoder's output,
-    1.5 bytes per pixel), converted by the integer rule `matrix` names inside the same kernel (acrmi_preprocess_nv12)."""
+    1.5 bytes per pixel), converted by the integer rule `matrix` names inside the same kernel (acrmi_preprocess_nv12).
+    boxes [n,4] = (l, t, r, b) with box_frame [n] (default: box i of frame i): n regions of the frames instead of the frames
+    (ops.preprocess_rois); image, offsets and batch_ids are then per region, in region order."""
     from .. import ops
-    if pixel_format == 'nv12':
+    if boxes is not None:
+        img, offsets = ops.preprocess_rois(bgr_frames, boxes, box_frame, pixel_format=pixel_format, matrix=matrix)
+    elif box_frame is not None:
+        raise ValueError('box_frame says which frame each box is of: it needs boxes=')
+    elif pixel_format == 'nv12':
         img, offsets = ops.preprocess_nv12(bgr_frames, matrix)
     elif pixel_format != 'bgr':
         raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
@@ -100,6 +110,42 @@ def img_preprocess_gpu(bgr_frames, imgpaths=None, pixel_format='bgr', matrix='cv
     if imgpaths is not None:
         data['imgpath'] = list(imgpaths)
     return data
+
+
+def boxes_from_keypoints(pj2d_org, frame_hw, scale=1.5, min_size=64):
+    """The boxes of the NEXT frame of a video loop from the key points of this one.  pj2d_org: per item the key points of its
+    detected hands in frame pixels - an array [hands, 21, 2] (or [points, 2]; no rows = nothing detected), or a list of
+    the hand dicts forward_batch returns ({} = nothing detected).  frame_hw: (H, W) for all items or one pair per item.
+    Per item: the bounding box of the points, scaled by `scale` about its centre, made square on the longer side, at least
+    min_size wide, rounded outwards to whole pixels, then moved back inside the frame (and cut to the frame where it is larger
+    than the frame).  Nothing detected: the whole frame.  -> int32 numpy [n,4] rows (l, t, r, b), r and b exclusive.  Pure numpy."""
+    n = len(pj2d_org)
+    hw = np.asarray(frame_hw, np.int64)
+    if hw.shape not in ((2,), (n, 2)) or (hw <= 0).any():
+        raise ValueError('frame_hw must be (H, W) or one (H, W) per item, positive')
+    hw = np.broadcast_to(hw, (n, 2))
+    out = np.zeros((n, 4), np.int32)
+    for i, item in enumerate(pj2d_org):
+        H, W = int(hw[i, 0]), int(hw[i, 1])
+        if isinstance(item, dict) and not item:      # forward_batch's "nothing detected"
+            item = []
+        if isinstance(item, (list, tuple)) and len(item) and isinstance(item[0], dict):
+            item = [h['pj2d_org'] for h in item]
+        pts = np.asarray(item, np.float64).reshape(-1, 2) if len(item) else np.zeros((0, 2))
+        pts = pts[np.isfinite(pts).all(1)]
+        if not len(pts):
+            out[i] = (0, 0, W, H)
+            continue
+        lo, hi = pts.min(0), pts.max(0)
+        centre = (lo + hi) / 2
+        side = max(float((hi - lo).max()) * scale, float(min_size))
+        l, t = np.floor(centre - side / 2)
+        r, b = np.ceil(centre + side / 2)
+        # move back inside the frame, then cut what is still outside (a box larger than the frame)
+        dx = -l if l < 0 else (W - r if r > W else 0)
+        dy = -t if t < 0 else (H - b if b > H else 0)
+        out[i] = (max(0, l + dx), max(0, t + dy), min(W, r + dx), min(H, b + dy))
+    return out
 
 
 # ---- result packaging (acr/utils.py:1098-1104, 1192-1271) ----------------------------------------------

@@ -1,6 +1,9 @@
 // libacrmi.so: the stand-alone operators of the C ABI (unit tests / callers with their own tensors; no context).
 #include "acrmi_ctx.h"
 #include "conv_frame.h"   // conv_shape
+#include "roi_plan.h"
+
+#include <vector>
 
 // (poison: acrmi_decode_gated's range flag of an 'fp16x3' program; null for the stand-alone operator)
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params,
@@ -218,6 +221,24 @@ int nv12_check_frames(const char* who, const acrmi_nv12_frame* fr, int n) {
   return ACRMI_OK;
 }
 
+// Regions of interest: every region's frame index and window, before anything is queued; sizes(frame, H, W) says how large a
+// frame is.  plans[i] = the clamped window, pad and crop of region i (csrc/roi_plan.h).
+template <class Sizes>
+int roi_plans(const char* who, const acrmi_roi* rois, int n, int n_frames, const Sizes& sizes, std::vector<RoiPlan>& plans) {
+  plans.resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const acrmi_roi& q = rois[i];
+    if (q.frame < 0 || q.frame >= n_frames)
+      return fail(nullptr, ACRMI_EINVAL, "%s: region %d: frame index %d outside [0, %d)", who, i, (int)q.frame, n_frames);
+    int H, W;
+    sizes(q.frame, H, W);
+    if (!roi_plan(H, W, q.l, q.t, q.r, q.b, &plans[(size_t)i]))
+      return fail(nullptr, ACRMI_EINVAL, "%s: region %d: box (l %d, t %d, r %d, b %d) leaves no pixel of frame %d (%d x %d, H x W)",
+                  who, i, (int)q.l, (int)q.t, (int)q.r, (int)q.b, (int)q.frame, H, W);
+  }
+  return ACRMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,6 +299,77 @@ int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t*
     }
     hipError_t e = launch_nv12_to_rgb(pb, k, m, bgr ? 1 : 0, (hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "nv12_to_rgb: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+// ---- regions of interest (csrc/roi.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") --------------------------
+int acrmi_roi_offsets(int H, int W, const acrmi_roi* roi, int32_t window_ltrb[4], float offsets10[10]) {
+  if (!roi || H <= 0 || W <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_roi_offsets: bad arguments");
+  RoiPlan p;
+  if (!roi_plan(H, W, roi->l, roi->t, roi->r, roi->b, &p))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_roi_offsets: box (l %d, t %d, r %d, b %d) leaves no pixel of a %d x %d (H x W) frame",
+                (int)roi->l, (int)roi->t, (int)roi->r, (int)roi->b, H, W);
+  if (window_ltrb) { window_ltrb[0] = p.l; window_ltrb[1] = p.t; window_ltrb[2] = p.r; window_ltrb[3] = p.b; }
+  if (offsets10) roi_offsets_row(p, offsets10);
+  return ACRMI_OK;
+}
+
+int acrmi_preprocess_rois(const acrmi_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
+                          uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
+  if (!frames_host || !rois_host || !out_rgb_dev || n <= 0 || n_frames <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois: bad arguments");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames_host[i].bgr_dev || frames_host[i].H <= 0 || frames_host[i].W <= 0)
+      return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois: frame %d: null pointer or empty size (%d x %d)", i,
+                  frames_host[i].H, frames_host[i].W);
+  std::vector<RoiPlan> plans;
+  int rc = roi_plans("acrmi_preprocess_rois", rois_host, n, n_frames,
+                     [&](int f, int& H, int& W) { H = frames_host[f].H; W = frames_host[f].W; }, plans);
+  if (rc != ACRMI_OK) return rc;
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiBgrBatch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_roi& q = rois_host[i0 + i];
+      const acrmi_frame& fr = frames_host[q.frame];
+      const RoiPlan& p = plans[(size_t)(i0 + i)];
+      rb.r[i].pitch = (size_t)fr.W * 3;
+      rb.r[i].src = fr.bgr_dev + (size_t)p.t * rb.r[i].pitch + (size_t)p.l * 3;
+      rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
+      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
+    }
+    hipError_t e = launch_preprocess_rois(rb, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_rois: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
+                               const int32_t* coef6_host, uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
+  if (!frames_host || !rois_host || !out_rgb_dev || n <= 0 || n_frames <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois_nv12: bad arguments");
+  Nv12Coef k{};
+  int rc = nv12_coef("acrmi_preprocess_rois_nv12", coef6_host, k);
+  if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_preprocess_rois_nv12", frames_host, n_frames);
+  std::vector<RoiPlan> plans;
+  if (rc == ACRMI_OK)
+    rc = roi_plans("acrmi_preprocess_rois_nv12", rois_host, n, n_frames,
+                   [&](int f, int& H, int& W) { H = frames_host[f].H; W = frames_host[f].W; }, plans);
+  if (rc != ACRMI_OK) return rc;
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiNv12Batch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_roi& q = rois_host[i0 + i];
+      const acrmi_nv12_frame& fr = frames_host[q.frame];
+      const RoiPlan& p = plans[(size_t)(i0 + i)];
+      rb.r[i].y = fr.y_dev; rb.r[i].uv = fr.uv_dev; rb.r[i].y_pitch = fr.y_pitch; rb.r[i].uv_pitch = fr.uv_pitch;
+      rb.r[i].l = p.l; rb.r[i].t = p.t; rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
+      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
+    }
+    hipError_t e = launch_preprocess_rois_nv12(rb, k, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_rois_nv12: %s", hipGetErrorString(e));
   }
   return ACRMI_OK;
 }

@@ -190,6 +190,41 @@ static_assert(sizeof(Nv12Batch) + sizeof(Nv12Coef) + 24 <= 4096 && sizeof(Nv12Ds
               "NV12 kernel arguments must fit the 4 KB argument block");
 hipError_t launch_preprocess_nv12(const Nv12Batch& pb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
 hipError_t launch_nv12_to_rgb(const Nv12DstBatch& pb, const Nv12Coef& k, int n, int bgr, hipStream_t s);
+// The NV12 colour rule of one pixel (csrc/nv12.hip states it).  Shared by the NV12 kernels and the NV12 region kernel.
+__device__ inline int nv12_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ inline void nv12_pixel(const Nv12Coef& k, int Y, int U, int V, int& R, int& G, int& B) {
+  int yy = Y - k.y_off;
+  yy = (yy < 0 ? 0 : yy) * k.cy;
+  const int u = U - 128, v = V - 128, r = 1 << 19;
+  R = nv12_clamp8((yy + k.cvr * v + r) >> 20);
+  G = nv12_clamp8((yy + k.cug * u + k.cvg * v + r) >> 20);
+  B = nv12_clamp8((yy + k.cub * u + r) >> 20);
+}
+// Regions of interest (csrc/roi.hip; acrmi_preprocess_rois / acrmi_preprocess_rois_nv12): a window of a frame pre-processed
+// as a frame of its own size.  Geometry by value, ROIS_PER_LAUNCH per launch; the windows are already clamped to their
+// frames (csrc/roi_plan.h) and the kernels trust them.
+constexpr int ROIS_PER_LAUNCH = 64;
+struct RoiBgr {         // 24 bytes
+  const uint8_t* src;   // the window's first pixel: frame + (t * W + l) * 3
+  size_t pitch;         // bytes per row of the FRAME (W * 3)
+  int h, w;             // the window
+};
+struct RoiBgrBatch {
+  RoiBgr r[ROIS_PER_LAUNCH];
+};
+struct RoiNv12 {        // 40 bytes
+  const uint8_t* y;     // the planes of the FRAME: chroma is addressed in frame coordinates, so odd l and t are legal
+  const uint8_t* uv;
+  int y_pitch, uv_pitch;
+  int l, t, h, w;       // the window: rows [t, t + h), columns [l, l + w) of the frame
+};
+struct RoiNv12Batch {
+  RoiNv12 r[ROIS_PER_LAUNCH];
+};
+static_assert(sizeof(RoiBgrBatch) + 24 <= 4096 && sizeof(RoiNv12Batch) + sizeof(Nv12Coef) + 24 <= 4096,
+              "region kernel arguments must fit the 4 KB argument block");
+hipError_t launch_preprocess_rois(const RoiBgrBatch& rb, int n, int out_size, uint8_t* out, hipStream_t s);
+hipError_t launch_preprocess_rois_nv12(const RoiNv12Batch& rb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
 hipError_t launch_pow11(float* buf, long n_pixels, int cs, int ch, hipStream_t s);
 // fp32 NCHW [B,C,H,W] -> channels [coff, coff + C) of an NHWC buffer with channel stride cs (acrmi_heads: backbone features a
 // caller hands to head_forward, acr/model.py:47-53)

@@ -14,16 +14,7 @@
 
 namespace acrmi {
 
-__device__ inline int nv12_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-__device__ inline void nv12_pixel(const Nv12Coef& k, int Y, int U, int V, int& R, int& G, int& B) {
-  int yy = Y - k.y_off;
-  yy = (yy < 0 ? 0 : yy) * k.cy;
-  const int u = U - 128, v = V - 128, r = 1 << 19;
-  R = nv12_clamp8((yy + k.cvr * v + r) >> 20);
-  G = nv12_clamp8((yy + k.cug * u + k.cvg * v + r) >> 20);
-  B = nv12_clamp8((yy + k.cub * u + r) >> 20);
-}
+// (nv12_pixel, the rule for one pixel: csrc/kernels.h, shared with csrc/roi.hip)
 
 // ------------------------------------------------------------------------------------------------
 // Fused path: NV12 -> RGB -> white square pad -> OpenCV's fixed-point cubic resize to out_size^2.  This is

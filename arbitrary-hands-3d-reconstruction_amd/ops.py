@@ -267,9 +267,10 @@ def _nv12_item(item, i):
     return y.data_ptr(), uv.data_ptr(), H, W, y.stride(0), uv_pitch, (y, uv)
 
 
-def _nv12_frames(frames):
+def _nv12_frames(frames, need_cuda=True):
     """`frames` of preprocess_nv12 / nv12_to_bgr -> (acrmi_nv12_frame array, sizes [(H, W)], device, bound tensors).  Layout
-    errors are ValueErrors raised before the device is looked at."""
+    errors are ValueErrors raised before the device is looked at (need_cuda=False: the caller has more to validate first and
+    looks at the device itself)."""
     if isinstance(frames, torch.Tensor) and frames.dim() == 3:       # [n, H*3/2, W]: n surfaces of one size
         items = list(frames.unbind(0))
     elif isinstance(frames, (torch.Tensor, tuple)):                  # a single item: a batch of one
@@ -289,7 +290,8 @@ def _nv12_frames(frames):
         sizes.append((H, W))
     if any(t.device != keep[0].device for t in keep):
         raise ValueError('NV12 frames must all be on one device')
-    _need_cuda(*keep)
+    if need_cuda:
+        _need_cuda(*keep)
     return arr, sizes, keep[0].device, keep
 
 
@@ -327,6 +329,101 @@ def nv12_to_bgr(frames, matrix='cv601', rgb=False):
     _lib.check(_lib.lib().acrmi_nv12_to_rgb(arr, n, coef.ctypes.data_as(C.c_void_p), 0 if rgb else 1, ptrs, _s(dst[0])))
     del keep
     return out
+
+
+# ---- regions of interest (csrc/roi.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") ----------------------------------
+def _roi_int_box(H, W, box, i=0):
+    """(l, t, r, b), ints or floats -> the integer box with the same crop amounts: the reference turns a bbox into
+    crop_trbl = (int(max(0, t)), int(max(0, W - r)), int(max(0, H - b)), int(max(0, l))) (acr/utils.py:1289-1292), int()
+    truncating, so r = 100.7 in a 200-wide frame crops 99 on the right."""
+    vals = np.asarray(box.cpu() if hasattr(box, 'cpu') else box)
+    if vals.shape != (4,) or vals.dtype.kind not in 'iuf' or not np.isfinite(vals.astype(np.float64)).all():
+        raise ValueError('region %d: a box is four finite numbers (l, t, r, b), got %r' % (i, box))
+    l, t, r, b = (v.item() for v in vals)
+    cap = 2 ** 30      # a crop beyond the frame leaves no pixel whatever its size: keep the integers within int32
+    ct, cr, cb, cl = (min(int(max(0, v)), cap) for v in (t, W - r, H - b, l))
+    return cl, ct, W - cr, H - cb
+
+
+def roi_offsets(H, W, box):
+    """The `offsets` row float32 numpy [10] = [padded h, padded w, crop t, r, b, l, pad t, r, b, l] of the box (l, t, r, b),
+    r and b exclusive, in an H x W frame (acrmi_roi_offsets; the reference's image_crop_pad with a bbox, acr/utils.py:1287-1301).
+    A box that leaves no pixel of the frame is a ValueError.  Pure host: works without a GPU."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError('the frame must have pixels, got %d x %d' % (H, W))
+    roi = _lib.Roi(0, *_roi_int_box(H, W, box))
+    row = np.zeros(10, np.float32)
+    _lib.check(_lib.lib().acrmi_roi_offsets(H, W, C.byref(roi), None, row.ctypes.data_as(C.c_void_p)))
+    return row
+
+
+def _rois(boxes, box_frame, sizes):
+    """boxes [n,4], box_frame [n] or None, the frames' [(H, W)] -> the acrmi_roi array."""
+    boxes = boxes.cpu() if hasattr(boxes, 'cpu') else boxes
+    boxes = [np.asarray(b) for b in boxes] if isinstance(boxes, (list, tuple)) else np.asarray(boxes)
+    n = len(boxes)
+    if n == 0 or any(np.shape(b) != (4,) for b in boxes):
+        raise ValueError('boxes must be [n,4] rows (l, t, r, b), n >= 1')
+    if box_frame is None:
+        if n != len(sizes):
+            raise ValueError('box_frame is needed when there is not one box per frame (%d boxes, %d frames)' % (n, len(sizes)))
+        frame_of = list(range(n))
+    else:
+        bf = np.asarray(box_frame.cpu() if hasattr(box_frame, 'cpu') else box_frame)
+        if bf.shape != (n,) or bf.dtype.kind not in 'iu':
+            raise ValueError('box_frame must hold one integer per box')
+        frame_of = [int(f) for f in bf]
+    arr = (_lib.Roi * n)()
+    for i, f in enumerate(frame_of):
+        if not 0 <= f < len(sizes):
+            raise ValueError('region %d: frame index %d outside [0, %d)' % (i, f, len(sizes)))
+        arr[i] = _lib.Roi(f, *_roi_int_box(sizes[f][0], sizes[f][1], boxes[i], i))
+    return arr
+
+
+def preprocess_rois(frames, boxes, box_frame=None, pixel_format='bgr', matrix='cv601'):
+    """Regions of frames in HBM -> (uint8 RGB [n,512,512,3] device, offsets [n,10] host) in one call (acrmi_preprocess_rois /
+    acrmi_preprocess_rois_nv12): region i is the box boxes[i] = (l, t, r, b), r and b exclusive, of frame box_frame[i], clamped
+    to that frame, and is pre-processed as a frame of its own size - byte for byte preprocess_frames on a copy of the window,
+    without the copy.  Its offsets row carries the crop, so pj2d_org lands in the pixels of the original frame.
+    frames: what preprocess / preprocess_frames take ('bgr': a uint8 tensor [N,H,W,3] or a list of [H_i,W_i,3]) or what
+    preprocess_nv12 takes ('nv12', with `matrix`).  box_frame: integers [n], default arange(n), which needs one box per frame;
+    frames may repeat, be skipped and come in any order.  Float boxes become crop amounts by the reference's
+    int(max(0, .)) truncation.  A box that leaves no pixel of its frame is a ValueError that names the region."""
+    L = _lib.lib()
+    if pixel_format == 'nv12':
+        coef = nv12_matrix(matrix)
+        arr, sizes, dev, keep = _nv12_frames(frames, need_cuda=False)
+    elif pixel_format != 'bgr':
+        raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
+    else:
+        items = list(frames.unbind(0)) if isinstance(frames, torch.Tensor) and frames.dim() == 4 else list(frames)
+        if not items:
+            raise ValueError('no frames')
+        keep, sizes = [], []
+        arr = (_lib.Frame * len(items))()
+        for i, f in enumerate(items):
+            if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or \
+                    f.device != items[0].device:
+                raise ValueError('frames must be uint8 [H,W,3] BGR tensors on one device')
+            f = f.contiguous()
+            keep.append(f)                     # bound until the call has been queued
+            arr[i].bgr_dev, arr[i].H, arr[i].W = f.data_ptr(), f.shape[0], f.shape[1]
+            sizes.append((f.shape[0], f.shape[1]))
+        dev = items[0].device
+    rois = _rois(boxes, box_frame, sizes)      # layouts, boxes and frame indices are ValueErrors before the device is looked at
+    _need_cuda(*keep)
+    n = len(rois)
+    out = torch.empty(n, 512, 512, 3, dtype=torch.uint8, device=dev)
+    offsets = np.zeros((n, 10), np.float32)
+    if pixel_format == 'nv12':
+        _lib.check(L.acrmi_preprocess_rois_nv12(arr, len(sizes), rois, n, coef.ctypes.data_as(C.c_void_p), _p(out),
+                                                offsets.ctypes.data_as(C.c_void_p), _s(out)))
+    else:
+        _lib.check(L.acrmi_preprocess_rois(arr, len(sizes), rois, n, _p(out), offsets.ctypes.data_as(C.c_void_p), _s(out)))
+    del keep
+    return out, torch.from_numpy(offsets)
 
 
 def cam_trans(joints, pj2d, focal_length=600.0, img_size=512.0):

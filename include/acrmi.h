@@ -354,6 +354,30 @@ int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int3
  * [H,W,3] uint8 images, RGB, or BGR when bgr != 0. */
 int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, int bgr,
                       uint8_t* const* dst_dev_host, void* stream);
+/* Regions of interest (DESIGN.md "Regions of interest"): the box of a person or hand detector instead of the whole frame, the
+ * reference's image_crop_pad with a bbox (acr/utils.py:1287-1301).  A region names a frame of the call and a box in that frame's
+ * pixels, r and b exclusive.  The box is clamped to the H x W frame as crop amounts
+ *   crop_trbl = (max(0, t), max(0, W - r), max(0, H - b), max(0, l)),   window = frame[ct : H - cb, cl : W - cr]
+ * and the window is pre-processed exactly as a frame of its own size: white pad to a square, cubic resize to 512 x 512, RGB -
+ * byte for byte what acrmi_preprocess_frames gives for a copy of the window.  Filter taps beyond the window are its clamped
+ * border or the white pad, never the neighbouring pixels of the frame.  A window without pixels is ACRMI_EINVAL.
+ * The `offsets` row is [padded h, padded w, ct, cr, cb, cl, pt, pr, pb, pl]: pj2d_org lands in the pixels of the original frame. */
+typedef struct acrmi_roi {             /* 20 bytes */
+  int32_t frame;                       /* index into the call's frames */
+  int32_t l, t, r, b;                  /* columns [l, r), rows [t, b); may overhang the frame */
+} acrmi_roi;
+/* Host only: the clamped window (l, t, r, b) and the `offsets` row of one box in an H x W frame; either output may be NULL. */
+int acrmi_roi_offsets(int H, int W, const acrmi_roi* roi, int32_t window_ltrb[4], float offsets10[10]);
+/* n regions of n_frames BGR frames -> out_rgb_dev [n,512,512,3] and offsets_host [n,10] (may be NULL), in region order.  Several
+ * regions may name one frame, in any order; a frame no region names is not read.  Everything is checked before anything is
+ * queued (the message names the region); geometry travels in the kernel arguments, 64 regions per launch, further regions in
+ * further launches; both host arrays may be freed when the call returns. */
+int acrmi_preprocess_rois(const acrmi_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
+                          uint8_t* out_rgb_dev, float* offsets_host, void* stream);
+/* The same on NV12 surfaces (the frame checks and coef6_host of acrmi_preprocess_nv12): byte for byte acrmi_preprocess_frames on
+ * the window of the frame acrmi_nv12_to_rgb makes.  Chroma is addressed in frame coordinates, so odd l and t are fine. */
+int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
+                               const int32_t* coef6_host, uint8_t* out_rgb_dev, float* offsets_host, void* stream);
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream);
 /* ACRMI_OP_STEM stand-alone: img uint8 RGB [B,H,W,3] (H % 16 == 0, W % 128 == 0) -> [relu](conv3x3 stride 2 pad 1 of
  * (x/255*2-1) + bias) into channels out_coff..out_coff+63 of out [B,H/2,W/2,out_cs]; w_packed = packer.pack_stem(w

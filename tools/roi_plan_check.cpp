@@ -1,0 +1,59 @@
+// Stand-alone print-out of the host rule of region-of-interest pre-processing (csrc/roi_plan.h: the clamp of a box to its
+// frame, the emptiness check, the square pad and the `offsets` row).  No GPU, no HIP:
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/roi_plan_check.cpp -o roi_plan_check
+//   ./roi_plan_check H W l t r b [H W l t r b ...]
+// One line per case, in order: "window l t r b offsets o0 ... o9" (integers), or "empty" for a box that leaves no pixel.
+// tests/test_roi_host.py compares the lines with the numpy statement of the rule (tests/roi_ref.py).  Without arguments: a
+// built-in list.  Exit status 2 for arguments that are not groups of six integers.
+#include "../arbitrary-hands-3d-reconstruction_amd/csrc/roi_plan.h"
+
+#include <cerrno>
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+using namespace acrmi;
+
+static bool to_int(const char* s, int32_t* v) {
+  char* end = nullptr;
+  errno = 0;
+  const long long x = std::strtoll(s, &end, 10);
+  if (errno || end == s || *end || x < INT_MIN || x > INT_MAX) return false;
+  *v = (int32_t)x;
+  return true;
+}
+
+int main(int argc, char** argv) {
+  std::vector<int32_t> v;
+  if (argc == 1) {
+    v = {480, 640, 100, 50, 300, 250, 480, 640, -20, -10, 700, 500, 37, 53, 10, 5, 11, 30, 8, 8, 8, 0, 9, 8};
+  } else {
+    if ((argc - 1) % 6) {
+      std::fprintf(stderr, "usage: %s H W l t r b [H W l t r b ...]\n", argv[0]);
+      return 2;
+    }
+    v.resize((size_t)(argc - 1));
+    for (int i = 1; i < argc; ++i)
+      if (!to_int(argv[i], &v[(size_t)i - 1])) {
+        std::fprintf(stderr, "not a 32-bit integer: %s\n", argv[i]);
+        return 2;
+      }
+  }
+  for (size_t c = 0; c + 6 <= v.size(); c += 6) {
+    // a heap plan and a heap row of exactly ten floats: a write past either is a sanitizer report
+    RoiPlan* p = new RoiPlan();
+    float* row = new float[10];
+    if (!roi_plan(v[c], v[c + 1], v[c + 2], v[c + 3], v[c + 4], v[c + 5], p)) {
+      std::printf("empty\n");
+    } else {
+      roi_offsets_row(*p, row);
+      std::printf("window %d %d %d %d offsets", p->l, p->t, p->r, p->b);
+      for (int i = 0; i < 10; ++i) std::printf(" %d", (int)row[i]);
+      std::printf("\n");
+    }
+    delete[] row;
+    delete p;
+  }
+  return 0;
+}
