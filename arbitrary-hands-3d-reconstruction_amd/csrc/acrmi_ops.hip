@@ -129,55 +129,7 @@ int acrmi_conv2d_h16(const void* in, int B, int H, int W, int in_cs, int in_coff
   return conv_check_and_launch("acrmi_conv2d_h16", a, stream);
 }
 
-int acrmi_preprocess(const uint8_t* bgr_dev, int n, int H, int W, uint8_t* out_rgb_dev, float* offsets_host,
-                     void* stream) {
-  if (!bgr_dev || !out_rgb_dev || n <= 0 || H <= 0 || W <= 0)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess: bad arguments");
-  // imgaug compute_paddings_to_reach_aspect_ratio(shape, 1.0): pad the shorter side, extra pixel bottom/right
-  const int S = H > W ? H : W;
-  int top = 0, right = 0, bottom = 0, left = 0;
-  if (W < H) { const int d = H - W; right = (d + 1) / 2; left = d / 2; }
-  else if (H < W) { const int d = W - H; top = d / 2; bottom = (d + 1) / 2; }
-  if (offsets_host) {
-    for (int i = 0; i < n; ++i) {
-      float* o = offsets_host + (size_t)i * 10;
-      o[0] = (float)S; o[1] = (float)S; o[2] = o[3] = o[4] = o[5] = 0.f;
-      o[6] = (float)top; o[7] = (float)right; o[8] = (float)bottom; o[9] = (float)left;
-    }
-  }
-  hipError_t e = launch_preprocess(bgr_dev, n, H, W, S, top, left, 512, out_rgb_dev, (hipStream_t)stream);
-  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "preprocess: %s", hipGetErrorString(e));
-}
-
-int acrmi_preprocess_frames(const acrmi_frame* frames_host, int n, uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
-  if (!frames_host || !out_rgb_dev || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_frames: bad arguments");
-  for (int i = 0; i < n; ++i)
-    if (!frames_host[i].bgr_dev || frames_host[i].H <= 0 || frames_host[i].W <= 0)
-      return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_frames: frame %d: null pointer or empty size (%d x %d)", i,
-                  frames_host[i].H, frames_host[i].W);
-  for (int i0 = 0; i0 < n; i0 += PRE_FRAMES_PER_LAUNCH) {
-    const int m = n - i0 < PRE_FRAMES_PER_LAUNCH ? n - i0 : PRE_FRAMES_PER_LAUNCH;
-    PreBatch pb{};
-    for (int i = 0; i < m; ++i) {
-      const acrmi_frame& fr = frames_host[i0 + i];
-      pb.f[i].bgr = fr.bgr_dev; pb.f[i].H = fr.H; pb.f[i].W = fr.W;
-      if (offsets_host) {     // the reference's `offsets` row of this image (acr/utils.py:1276-1313)
-        const int H = fr.H, W = fr.W, S = H > W ? H : W;
-        int top = 0, right = 0, bottom = 0, left = 0;
-        if (W < H) { const int d = H - W; right = (d + 1) / 2; left = d / 2; }
-        else if (H < W) { const int d = W - H; top = d / 2; bottom = (d + 1) / 2; }
-        float* o = offsets_host + (size_t)(i0 + i) * 10;
-        o[0] = (float)S; o[1] = (float)S; o[2] = o[3] = o[4] = o[5] = 0.f;
-        o[6] = (float)top; o[7] = (float)right; o[8] = (float)bottom; o[9] = (float)left;
-      }
-    }
-    hipError_t e = launch_preprocess_frames(pb, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_frames: %s", hipGetErrorString(e));
-  }
-  return ACRMI_OK;
-}
-
-// ---- NV12 input (csrc/nv12.hip; DESIGN.md "NV12 input") ------------------------------------------------------------
+// ---- input pre-processing (csrc/preprocess.hip, csrc/nv12.hip, csrc/roi_plan.h; DESIGN.md "NV12 input", "Regions of interest")
 }  // extern "C"
 
 namespace {
@@ -239,6 +191,59 @@ int roi_plans(const char* who, const acrmi_roi* rois, int n, int n_frames, const
   return ACRMI_OK;
 }
 
+// The plan of the whole frame, the window (0, 0, W, H): what the frame entry points hand to the window path.  The sizes have
+// been checked, so every frame has a plan.
+template <class Frame>
+std::vector<RoiPlan> full_frame_plans(const Frame* frames, int n) {
+  std::vector<RoiPlan> plans((size_t)n);
+  for (int i = 0; i < n; ++i)      // (void): H, W > 0 has been checked, and the whole frame of such a size is never empty
+    (void)roi_plan(frames[i].H, frames[i].W, 0, 0, frames[i].W, frames[i].H, &plans[(size_t)i]);
+  return plans;
+}
+
+// The window path, one helper per pixel format: output image i is the window plans[i] of frames[frame_of(i)] and gets the
+// `offsets` row of its plan.  ROIS_PER_LAUNCH records per launch.  Everything has been validated by the caller.
+template <class FrameOf>
+int preprocess_windows_bgr(const char* what, const acrmi_frame* frames, const std::vector<RoiPlan>& plans, const FrameOf& frame_of,
+                           uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
+  const int n = (int)plans.size();
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiBgrBatch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_frame& fr = frames[frame_of(i0 + i)];
+      const RoiPlan& p = plans[(size_t)(i0 + i)];
+      rb.r[i].pitch = (size_t)fr.W * 3;
+      rb.r[i].src = fr.bgr_dev + (size_t)p.t * rb.r[i].pitch + (size_t)p.l * 3;
+      rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
+      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
+    }
+    hipError_t e = launch_preprocess_rois(rb, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+template <class FrameOf>
+int preprocess_windows_nv12(const char* what, const acrmi_nv12_frame* frames, const std::vector<RoiPlan>& plans,
+                            const FrameOf& frame_of, const Nv12Coef& k, uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
+  const int n = (int)plans.size();
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiNv12Batch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_frame& fr = frames[frame_of(i0 + i)];
+      const RoiPlan& p = plans[(size_t)(i0 + i)];
+      rb.r[i].y = fr.y_dev; rb.r[i].uv = fr.uv_dev; rb.r[i].y_pitch = fr.y_pitch; rb.r[i].uv_pitch = fr.uv_pitch;
+      rb.r[i].l = p.l; rb.r[i].t = p.t; rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
+      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
+    }
+    hipError_t e = launch_preprocess_rois_nv12(rb, k, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -250,6 +255,29 @@ int acrmi_nv12_matrix(int which, int32_t coef6[6]) {
   return ACRMI_OK;
 }
 
+int acrmi_preprocess(const uint8_t* bgr_dev, int n, int H, int W, uint8_t* out_rgb_dev, float* offsets_host,
+                     void* stream) {
+  if (!bgr_dev || !out_rgb_dev || n <= 0 || H <= 0 || W <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess: bad arguments");
+  if (offsets_host) {     // the reference's `offsets` row (acr/utils.py:1276-1313): that of the whole frame's plan
+    RoiPlan p{};
+    (void)roi_plan(H, W, 0, 0, W, H, &p);      // H, W > 0: never empty
+    for (int i = 0; i < n; ++i) roi_offsets_row(p, offsets_host + (size_t)i * 10);
+  }
+  hipError_t e = launch_preprocess(bgr_dev, n, H, W, 512, out_rgb_dev, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "preprocess: %s", hipGetErrorString(e));
+}
+
+int acrmi_preprocess_frames(const acrmi_frame* frames_host, int n, uint8_t* out_rgb_dev, float* offsets_host, void* stream) {
+  if (!frames_host || !out_rgb_dev || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_frames: bad arguments");
+  for (int i = 0; i < n; ++i)
+    if (!frames_host[i].bgr_dev || frames_host[i].H <= 0 || frames_host[i].W <= 0)
+      return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_frames: frame %d: null pointer or empty size (%d x %d)", i,
+                  frames_host[i].H, frames_host[i].W);
+  return preprocess_windows_bgr("preprocess_frames", frames_host, full_frame_plans(frames_host, n), [](int i) { return i; },
+                                out_rgb_dev, offsets_host, stream);
+}
+
 int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, uint8_t* out_rgb_dev,
                           float* offsets_host, void* stream) {
   if (!frames_host || !out_rgb_dev || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_nv12: bad arguments");
@@ -257,27 +285,8 @@ int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int3
   int rc = nv12_coef("acrmi_preprocess_nv12", coef6_host, k);
   if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_preprocess_nv12", frames_host, n);
   if (rc != ACRMI_OK) return rc;
-  for (int i0 = 0; i0 < n; i0 += NV12_FRAMES_PER_LAUNCH) {
-    const int m = n - i0 < NV12_FRAMES_PER_LAUNCH ? n - i0 : NV12_FRAMES_PER_LAUNCH;
-    Nv12Batch pb{};
-    for (int i = 0; i < m; ++i) {
-      const acrmi_nv12_frame& fr = frames_host[i0 + i];
-      pb.f[i].y = fr.y_dev; pb.f[i].uv = fr.uv_dev; pb.f[i].H = fr.H; pb.f[i].W = fr.W;
-      pb.f[i].y_pitch = fr.y_pitch; pb.f[i].uv_pitch = fr.uv_pitch;
-      if (offsets_host) {     // the same `offsets` row acrmi_preprocess_frames writes for this H, W
-        const int H = fr.H, W = fr.W, S = H > W ? H : W;
-        int top = 0, right = 0, bottom = 0, left = 0;
-        if (W < H) { const int d = H - W; right = (d + 1) / 2; left = d / 2; }
-        else if (H < W) { const int d = W - H; top = d / 2; bottom = (d + 1) / 2; }
-        float* o = offsets_host + (size_t)(i0 + i) * 10;
-        o[0] = (float)S; o[1] = (float)S; o[2] = o[3] = o[4] = o[5] = 0.f;
-        o[6] = (float)top; o[7] = (float)right; o[8] = (float)bottom; o[9] = (float)left;
-      }
-    }
-    hipError_t e = launch_preprocess_nv12(pb, k, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_nv12: %s", hipGetErrorString(e));
-  }
-  return ACRMI_OK;
+  return preprocess_windows_nv12("preprocess_nv12", frames_host, full_frame_plans(frames_host, n), [](int i) { return i; }, k,
+                                 out_rgb_dev, offsets_host, stream);
 }
 
 int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, int bgr,
@@ -303,7 +312,7 @@ int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t*
   return ACRMI_OK;
 }
 
-// ---- regions of interest (csrc/roi.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") --------------------------
+// ---- regions of interest (DESIGN.md "Regions of interest") ----------------------------------------------------------
 int acrmi_roi_offsets(int H, int W, const acrmi_roi* roi, int32_t window_ltrb[4], float offsets10[10]) {
   if (!roi || H <= 0 || W <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_roi_offsets: bad arguments");
   RoiPlan p;
@@ -327,22 +336,8 @@ int acrmi_preprocess_rois(const acrmi_frame* frames_host, int n_frames, const ac
   int rc = roi_plans("acrmi_preprocess_rois", rois_host, n, n_frames,
                      [&](int f, int& H, int& W) { H = frames_host[f].H; W = frames_host[f].W; }, plans);
   if (rc != ACRMI_OK) return rc;
-  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
-    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
-    RoiBgrBatch rb{};
-    for (int i = 0; i < m; ++i) {
-      const acrmi_roi& q = rois_host[i0 + i];
-      const acrmi_frame& fr = frames_host[q.frame];
-      const RoiPlan& p = plans[(size_t)(i0 + i)];
-      rb.r[i].pitch = (size_t)fr.W * 3;
-      rb.r[i].src = fr.bgr_dev + (size_t)p.t * rb.r[i].pitch + (size_t)p.l * 3;
-      rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
-      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
-    }
-    hipError_t e = launch_preprocess_rois(rb, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_rois: %s", hipGetErrorString(e));
-  }
-  return ACRMI_OK;
+  return preprocess_windows_bgr("preprocess_rois", frames_host, plans, [&](int i) { return rois_host[i].frame; }, out_rgb_dev,
+                                offsets_host, stream);
 }
 
 int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
@@ -357,21 +352,8 @@ int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames
     rc = roi_plans("acrmi_preprocess_rois_nv12", rois_host, n, n_frames,
                    [&](int f, int& H, int& W) { H = frames_host[f].H; W = frames_host[f].W; }, plans);
   if (rc != ACRMI_OK) return rc;
-  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
-    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
-    RoiNv12Batch rb{};
-    for (int i = 0; i < m; ++i) {
-      const acrmi_roi& q = rois_host[i0 + i];
-      const acrmi_nv12_frame& fr = frames_host[q.frame];
-      const RoiPlan& p = plans[(size_t)(i0 + i)];
-      rb.r[i].y = fr.y_dev; rb.r[i].uv = fr.uv_dev; rb.r[i].y_pitch = fr.y_pitch; rb.r[i].uv_pitch = fr.uv_pitch;
-      rb.r[i].l = p.l; rb.r[i].t = p.t; rb.r[i].h = p.b - p.t; rb.r[i].w = p.r - p.l;
-      if (offsets_host) roi_offsets_row(p, offsets_host + (size_t)(i0 + i) * 10);
-    }
-    hipError_t e = launch_preprocess_rois_nv12(rb, k, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "preprocess_rois_nv12: %s", hipGetErrorString(e));
-  }
-  return ACRMI_OK;
+  return preprocess_windows_nv12("preprocess_rois_nv12", frames_host, plans, [&](int i) { return rois_host[i].frame; }, k,
+                                 out_rgb_dev, offsets_host, stream);
 }
 
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream) {

@@ -315,126 +315,6 @@ hipError_t launch_coordfill_h16(void* buf, int B, int H, int W, int cs, int coff
 
 namespace acrmi {
 
-// ------------------------------------------------------------------------------------------------
-// Pre-processing (acr/utils.py:1315-1337): BGR uint8 frame [H,W,3] -> white-padded square (imgaug
-// 0.4.0 Pad: the extra pixel goes to bottom/right) -> cv2.resize(..., (512,512), INTER_CUBIC) -> RGB uint8.
-// The resize is OpenCV's uint8 path restated from its published source (modules/imgproc/src/resize.cpp), bit for bit:
-//   fx = (float)((dx + 0.5) * scale - 0.5) with scale in double, sx = floor(fx), fx -= sx;
-//   coefficients interpolateCubic(fx) with A = -0.75 in float, stored as short = round-half-even(c * 2048)
-//   (INTER_RESIZE_COEF_BITS = 11); horizontal pass in int32 over 4 border-clamped columns; vertical pass in int32
-//   over 4 border-clamped rows; dst = saturate((v + 2^21) >> 22)   (FixedPtCast<int, uchar, 22>).
-// oracle/preprocess.py is the CPU statement of the same algorithm; tests require equality.
-// One thread per output pixel; the 1080p source (6.2 MB/frame) is read once through L2.
-// ------------------------------------------------------------------------------------------------
-// (cv_cubic_taps: csrc/kernels.h, shared with csrc/nv12.hip)
-__global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ bgr, int n, int H, int W, int S,
-                                                         int pad_top, int pad_left, int out_size,
-                                                         uint8_t* __restrict__ out) {
-  const long total = (long)n * out_size * out_size;
-  const double scale = (double)S / (double)out_size;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int ox = i % out_size;
-    const int oy = (i / out_size) % out_size;
-    const int f = i / ((long)out_size * out_size);
-    int sy, sx, cy[4], cx[4];
-    cv_cubic_taps(oy, scale, sy, cy);
-    cv_cubic_taps(ox, scale, sx, cx);
-    int acc[3] = {0, 0, 0};
-    const uint8_t* src = bgr + (size_t)f * H * W * 3;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      int yy = sy - 1 + a;
-      yy = yy < 0 ? 0 : (yy >= S ? S - 1 : yy);      // border rows / columns of the padded square are clamped
-      const int iy = yy - pad_top;
-      int row[3] = {0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        int xx = sx - 1 + b;
-        xx = xx < 0 ? 0 : (xx >= S ? S - 1 : xx);
-        const int ix = xx - pad_left;
-        int v0 = 255, v1 = 255, v2 = 255;           // white padding (acr/utils.py:1303-1308)
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-          const uint8_t* p = src + ((size_t)iy * W + ix) * 3;
-          v0 = p[2]; v1 = p[1]; v2 = p[0];          // BGR -> RGB (acr/utils.py:1318)
-        }
-        row[0] += cx[b] * v0; row[1] += cx[b] * v1; row[2] += cx[b] * v2;
-      }
-      acc[0] += cy[a] * row[0]; acc[1] += cy[a] * row[1]; acc[2] += cy[a] * row[2];
-    }
-    uint8_t* o = out + (size_t)i * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int r = (acc[c] + (1 << 21)) >> 22;
-      o[c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    }
-  }
-}
-
-// The same arithmetic with PER-FRAME geometry (acr/utils.py:1315-1337 is per image; folder mode, acr/main.py:144-205, mixes
-// sizes): up to PRE_FRAMES_PER_LAUNCH frames per launch, their {pointer, H, W} by value in the kernel arguments (no device
-// table to allocate or upload).  256 consecutive output pixels never straddle a frame (512 * 512 % 256 == 0).
-__global__ __launch_bounds__(256) void preprocess_frames_kernel(const PreBatch pb, int n, int out_size, uint8_t* __restrict__ out) {
-  const long total = (long)n * out_size * out_size;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int ox = i % out_size;
-    const int oy = (i / out_size) % out_size;
-    const int f = i / ((long)out_size * out_size);
-    const int H = pb.f[f].H, W = pb.f[f].W;
-    // imgaug compute_paddings_to_reach_aspect_ratio(shape, 1.0): pad the shorter side, the extra pixel bottom / right
-    const int S = H > W ? H : W;
-    const int pad_top = H < W ? (W - H) / 2 : 0, pad_left = W < H ? (H - W) / 2 : 0;
-    const double scale = (double)S / (double)out_size;
-    int sy, sx, cy[4], cx[4];
-    cv_cubic_taps(oy, scale, sy, cy);
-    cv_cubic_taps(ox, scale, sx, cx);
-    int acc[3] = {0, 0, 0};
-    const uint8_t* src = pb.f[f].bgr;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      int yy = sy - 1 + a;
-      yy = yy < 0 ? 0 : (yy >= S ? S - 1 : yy);
-      const int iy = yy - pad_top;
-      int row[3] = {0, 0, 0};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        int xx = sx - 1 + b;
-        xx = xx < 0 ? 0 : (xx >= S ? S - 1 : xx);
-        const int ix = xx - pad_left;
-        int v0 = 255, v1 = 255, v2 = 255;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-          const uint8_t* p = src + ((size_t)iy * W + ix) * 3;
-          v0 = p[2]; v1 = p[1]; v2 = p[0];
-        }
-        row[0] += cx[b] * v0; row[1] += cx[b] * v1; row[2] += cx[b] * v2;
-      }
-      acc[0] += cy[a] * row[0]; acc[1] += cy[a] * row[1]; acc[2] += cy[a] * row[2];
-    }
-    uint8_t* o = out + (size_t)i * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int r = (acc[c] + (1 << 21)) >> 22;
-      o[c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    }
-  }
-}
-
-hipError_t launch_preprocess_frames(const PreBatch& pb, int n, int out_size, uint8_t* out, hipStream_t s) {
-  const long total = (long)n * out_size * out_size;
-  long g = (total + 255) / 256;
-  if (g > 256L * 32) g = 256L * 32;
-  hipLaunchKernelGGL(preprocess_frames_kernel, dim3((unsigned)g), dim3(256), 0, s, pb, n, out_size, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_preprocess(const uint8_t* bgr, int n, int H, int W, int S, int pad_top, int pad_left, int out_size,
-                             uint8_t* out, hipStream_t s) {
-  const long total = (long)n * out_size * out_size;
-  long g = (total + 255) / 256;
-  if (g > 256L * 32) g = 256L * 32;
-  hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)g), dim3(256), 0, s, bgr, n, H, W, S, pad_top, pad_left, out_size, out);
-  return hipGetLastError();
-}
-
 // Max pooling 3x3, stride 2, padding 1 (ResNet stem, torchvision resnet.py maxpool; padded positions do not take part):
 // NHWC, 4 floats / 8 halfs per thread.  The maximum of values of the storage type is exact in every type.
 __global__ __launch_bounds__(256) void maxpool3s2_kernel(const float* __restrict__ in, int B, int H, int W, int in_cs, int in_coff,

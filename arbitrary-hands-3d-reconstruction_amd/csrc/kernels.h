@@ -133,8 +133,8 @@ struct FuseArgs {
   float* out;
 };
 hipError_t launch_fuse_sum(const FuseArgs& a, hipStream_t s);
-// One axis of OpenCV's uint8 INTER_CUBIC (see the pre-processing section of csrc/elementwise.hip): destination index d ->
-// source origin s0 and the four 11-bit fixed-point coefficients.  Shared by the BGR and the NV12 pre-processing kernels.
+// One axis of OpenCV's uint8 INTER_CUBIC (csrc/preprocess.hip states the rule): destination index d -> source origin s0 and
+// the four 11-bit fixed-point coefficients.
 __device__ inline void cv_cubic_taps(int d, double scale, int& s0, int (&c)[4]) {
   float f = (float)(((double)d + 0.5) * scale - 0.5);
   const float fl = floorf(f);
@@ -152,30 +152,12 @@ __device__ inline void cv_cubic_taps(int d, double scale, int& s0, int (&c)[4]) 
     c[i] = v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
   }
 }
-hipError_t launch_preprocess(const uint8_t* bgr, int n, int H, int W, int S, int pad_top, int pad_left, int out_size,
-                             uint8_t* out, hipStream_t s);
-// frames of DIFFERENT sizes in one launch (acrmi_preprocess_frames): geometry by value, PRE_FRAMES_PER_LAUNCH per launch
-constexpr int PRE_FRAMES_PER_LAUNCH = 128;
-struct PreFrame {
-  const uint8_t* bgr;
-  int H, W;
-};
-struct PreBatch {
-  PreFrame f[PRE_FRAMES_PER_LAUNCH];
-};
-hipError_t launch_preprocess_frames(const PreBatch& pb, int n, int out_size, uint8_t* out, hipStream_t s);
-// NV12 surfaces (csrc/nv12.hip; acrmi_preprocess_nv12 / acrmi_nv12_to_rgb): geometry by value, NV12_FRAMES_PER_LAUNCH per launch
+// n BGR frames of one size H x W in one allocation (csrc/preprocess.hip; acrmi_preprocess)
+hipError_t launch_preprocess(const uint8_t* bgr, int n, int H, int W, int out_size, uint8_t* out, hipStream_t s);
+// NV12 surfaces at full resolution (csrc/nv12.hip; acrmi_nv12_to_rgb): geometry by value, NV12_FRAMES_PER_LAUNCH per launch
 constexpr int NV12_FRAMES_PER_LAUNCH = 64;
 struct Nv12Coef {
   int cy, cub, cug, cvg, cvr, y_off;
-};
-struct Nv12Frame {      // 32 bytes, the layout of acrmi_nv12_frame
-  const uint8_t* y;
-  const uint8_t* uv;
-  int H, W, y_pitch, uv_pitch;
-};
-struct Nv12Batch {
-  Nv12Frame f[NV12_FRAMES_PER_LAUNCH];
 };
 struct Nv12DstFrame {   // 40 bytes: 64 of them + the coefficient row are 2.6 KB of the 4 KB argument block
   const uint8_t* y;
@@ -186,11 +168,9 @@ struct Nv12DstFrame {   // 40 bytes: 64 of them + the coefficient row are 2.6 KB
 struct Nv12DstBatch {
   Nv12DstFrame f[NV12_FRAMES_PER_LAUNCH];
 };
-static_assert(sizeof(Nv12Batch) + sizeof(Nv12Coef) + 24 <= 4096 && sizeof(Nv12DstBatch) + sizeof(Nv12Coef) + 8 <= 4096,
-              "NV12 kernel arguments must fit the 4 KB argument block");
-hipError_t launch_preprocess_nv12(const Nv12Batch& pb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
+static_assert(sizeof(Nv12DstBatch) + sizeof(Nv12Coef) + 8 <= 4096, "NV12 kernel arguments must fit the 4 KB argument block");
 hipError_t launch_nv12_to_rgb(const Nv12DstBatch& pb, const Nv12Coef& k, int n, int bgr, hipStream_t s);
-// The NV12 colour rule of one pixel (csrc/nv12.hip states it).  Shared by the NV12 kernels and the NV12 region kernel.
+// The NV12 colour rule of one pixel (csrc/nv12.hip states it).  Shared by nv12_to_rgb_kernel and the NV12 window kernel.
 __device__ inline int nv12_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ inline void nv12_pixel(const Nv12Coef& k, int Y, int U, int V, int& R, int& G, int& B) {
   int yy = Y - k.y_off;
@@ -200,9 +180,10 @@ __device__ inline void nv12_pixel(const Nv12Coef& k, int Y, int U, int V, int& R
   G = nv12_clamp8((yy + k.cug * u + k.cvg * v + r) >> 20);
   B = nv12_clamp8((yy + k.cub * u + r) >> 20);
 }
-// Regions of interest (csrc/roi.hip; acrmi_preprocess_rois / acrmi_preprocess_rois_nv12): a window of a frame pre-processed
-// as a frame of its own size.  Geometry by value, ROIS_PER_LAUNCH per launch; the windows are already clamped to their
-// frames (csrc/roi_plan.h) and the kernels trust them.
+// Windows of frames (csrc/preprocess.hip): a window of a frame pre-processed as a frame of its own size - a region of
+// interest (acrmi_preprocess_rois / acrmi_preprocess_rois_nv12) or the whole frame (acrmi_preprocess_frames /
+// acrmi_preprocess_nv12).  Geometry by value, ROIS_PER_LAUNCH per launch; the windows are already clamped to their frames
+// (csrc/roi_plan.h) and the kernels trust them.
 constexpr int ROIS_PER_LAUNCH = 64;
 struct RoiBgr {         // 24 bytes
   const uint8_t* src;   // the window's first pixel: frame + (t * W + l) * 3
@@ -222,7 +203,7 @@ struct RoiNv12Batch {
   RoiNv12 r[ROIS_PER_LAUNCH];
 };
 static_assert(sizeof(RoiBgrBatch) + 24 <= 4096 && sizeof(RoiNv12Batch) + sizeof(Nv12Coef) + 24 <= 4096,
-              "region kernel arguments must fit the 4 KB argument block");
+              "window kernel arguments must fit the 4 KB argument block");
 hipError_t launch_preprocess_rois(const RoiBgrBatch& rb, int n, int out_size, uint8_t* out, hipStream_t s);
 hipError_t launch_preprocess_rois_nv12(const RoiNv12Batch& rb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
 hipError_t launch_pow11(float* buf, long n_pixels, int cs, int ch, hipStream_t s);

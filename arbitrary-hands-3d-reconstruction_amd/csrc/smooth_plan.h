@@ -2,7 +2,7 @@
 // grouping of one launch's frames by stream.  Plain C++, no HIP: tools/smooth_plan_check.cpp compiles it alone.
 //
 // A launch carries up to SMOOTH_FRAMES_PER_LAUNCH frames.  Its SmoothBatch travels BY VALUE in the kernel arguments (like
-// PreBatch): per stream present in the launch - in the order of first appearance - the stream's row of the table and
+// RoiBgrBatch): per stream present in the launch - in the order of first appearance - the stream's row of the table and
 // its first frame, and per frame the next frame of the same stream.  One workgroup walks one stream's chain, so frames
 // that share an id are filtered in batch order and streams never meet.
 #pragma once

@@ -185,30 +185,44 @@ def preprocess(bgr_frames):
     return out, torch.from_numpy(offsets)
 
 
+def _bgr_frames(frames, need_cuda=True):
+    """`frames` of preprocess_frames / preprocess_rois (a tensor [N,H,W,3] or a list of [H_i,W_i,3]) -> (acrmi_frame array,
+    sizes [(H, W)], device, bound tensors): the counterpart of _nv12_frames.  Layout errors are ValueErrors raised before the
+    device is looked at, for preprocess_frames too, which used to look at the device first (need_cuda=False: the caller has
+    more to validate first and looks at the device itself)."""
+    items = list(frames.unbind(0)) if isinstance(frames, torch.Tensor) and frames.dim() == 4 else list(frames)
+    if not items:
+        raise ValueError('no frames')
+    keep, sizes = [], []
+    arr = (_lib.Frame * len(items))()
+    for i, f in enumerate(items):
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or \
+                f.device != items[0].device:
+            raise ValueError('frames must be uint8 [H,W,3] BGR tensors on one device')
+        f = f.contiguous()
+        keep.append(f)                     # bound until the call has been queued
+        H, W, _ = f.shape
+        arr[i].bgr_dev, arr[i].H, arr[i].W = f.data_ptr(), H, W
+        sizes.append((H, W))
+    if need_cuda:
+        _need_cuda(*keep)
+    return arr, sizes, keep[0].device, keep
+
+
 def preprocess_frames(bgr_frames):
     """A list of uint8 BGR device frames [H_i,W_i,3] of ANY sizes -> (uint8 RGB [n,512,512,3] device, offsets [n,10] host) in
     one call (acrmi_preprocess_frames: per-frame geometry in the kernel arguments).  img_preprocess is per image on the
     reference (acr/utils.py:1315-1337); folder mode mixes sizes (acr/main.py:144-205)."""
-    frames = list(bgr_frames)
-    if not frames:
-        raise ValueError('no frames')
-    _need_cuda(*frames)
-    keep = []
-    arr = (_lib.Frame * len(frames))()
-    for i, f in enumerate(frames):
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or f.device != frames[0].device:
-            raise ValueError('frames must be uint8 [H,W,3] BGR tensors on one device')
-        f = f.contiguous()
-        keep.append(f)                     # bound until the call has been queued
-        arr[i].bgr_dev, arr[i].H, arr[i].W = f.data_ptr(), f.shape[0], f.shape[1]
-    n = len(frames)
-    out = torch.empty(n, 512, 512, 3, dtype=torch.uint8, device=frames[0].device)
+    arr, sizes, dev, keep = _bgr_frames(bgr_frames)
+    n = len(sizes)
+    out = torch.empty(n, 512, 512, 3, dtype=torch.uint8, device=dev)
     offsets = np.zeros((n, 10), np.float32)
     _lib.check(_lib.lib().acrmi_preprocess_frames(arr, n, _p(out), offsets.ctypes.data_as(C.c_void_p), _s(out)))
+    del keep                               # (held until here: arr holds bare pointers into these tensors)
     return out, torch.from_numpy(offsets)
 
 
-# ---- NV12 input (csrc/nv12.hip; DESIGN.md "NV12 input") -----------------------------------------------------------------
+# ---- NV12 input (csrc/preprocess.hip, csrc/nv12.hip; DESIGN.md "NV12 input") ---------------------------------------------
 def nv12_matrix(name_or_row='cv601'):
     """A matrix name ('cv601', 'bt601', 'bt601-full', 'bt709', 'bt709-full': acrmi_nv12_matrix) or a row of six integers
     (cy, cub, cug, cvg, cvr, y_off) -> the row as int32 numpy [6].  Pure host: works without a GPU."""
@@ -331,7 +345,7 @@ def nv12_to_bgr(frames, matrix='cv601', rgb=False):
     return out
 
 
-# ---- regions of interest (csrc/roi.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") ----------------------------------
+# ---- regions of interest (csrc/preprocess.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") ---------------------
 def _roi_int_box(H, W, box, i=0):
     """(l, t, r, b), ints or floats -> the integer box with the same crop amounts: the reference turns a bbox into
     crop_trbl = (int(max(0, t)), int(max(0, W - r)), int(max(0, H - b)), int(max(0, l))) (acr/utils.py:1289-1292), int()
@@ -398,20 +412,7 @@ def preprocess_rois(frames, boxes, box_frame=None, pixel_format='bgr', matrix='c
     elif pixel_format != 'bgr':
         raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
     else:
-        items = list(frames.unbind(0)) if isinstance(frames, torch.Tensor) and frames.dim() == 4 else list(frames)
-        if not items:
-            raise ValueError('no frames')
-        keep, sizes = [], []
-        arr = (_lib.Frame * len(items))()
-        for i, f in enumerate(items):
-            if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != 3 or \
-                    f.device != items[0].device:
-                raise ValueError('frames must be uint8 [H,W,3] BGR tensors on one device')
-            f = f.contiguous()
-            keep.append(f)                     # bound until the call has been queued
-            arr[i].bgr_dev, arr[i].H, arr[i].W = f.data_ptr(), f.shape[0], f.shape[1]
-            sizes.append((f.shape[0], f.shape[1]))
-        dev = items[0].device
+        arr, sizes, dev, keep = _bgr_frames(frames, need_cuda=False)
     rois = _rois(boxes, box_frame, sizes)      # layouts, boxes and frame indices are ValueErrors before the device is looked at
     _need_cuda(*keep)
     n = len(rois)

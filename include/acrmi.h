@@ -312,7 +312,7 @@ int acrmi_preprocess(const uint8_t* bgr_dev, int n, int H, int W, uint8_t* out_r
 /* The same for frames of DIFFERENT sizes in one call (img_preprocess is per image, acr/utils.py:1315-1337; folder mode,
  * acr/main.py:144-205, mixes sizes): frames_host [n] = where each BGR uint8 frame [H,W,3] lives on the device and its size -
  * frames need not share an allocation.  Same arithmetic, bit for bit; out_rgb_dev [n,512,512,3]; offsets_host [n,10] (may be
- * NULL) = each image's own `offsets` row.  The geometry travels in the kernel arguments (128 frames per launch): nothing is
+ * NULL) = each image's own `offsets` row.  The geometry travels in the kernel arguments (64 frames per launch): nothing is
  * allocated or uploaded, the host array may be freed when the call returns. */
 typedef struct acrmi_frame {
   const uint8_t* bgr_dev;

@@ -422,7 +422,8 @@ def test_gpu_preprocess_is_bit_exact_to_the_opencv_restatement():
 def test_gpu_preprocess_of_mixed_size_frames_in_one_call():
     """acrmi_preprocess_frames - per-frame geometry, ONE call for a folder of images of different sizes
     (img_preprocess is per image, acr/utils.py:1315-1337; acr/main.py:144-205 mixes sizes) - bit-exact to oracle/preprocess.py
-    frame by frame, offsets rows included; frames live in separate allocations; > 128 frames take several launches."""
+    frame by frame, offsets rows included; frames live in separate allocations; more than 64 frames take several launches
+    (130 take three), and every one of them is compared."""
     from oracle import preprocess as opre
     ops, u = pkg('ops'), pkg('acr.utils')
     rs = np.random.RandomState(11)
@@ -438,12 +439,14 @@ def test_gpu_preprocess_of_mixed_size_frames_in_one_call():
     # the equal-size entry point computes the same bytes
     same, _ = ops.preprocess(dev[0][None])
     assert torch.equal(same[0], img[0])
-    # 130 small frames: two launches (128 geometry records per launch), every frame its own size
+    # 130 small frames: three launches (64 geometry records per launch), every frame its own size
     many = [rs.randint(0, 256, (20 + i % 7, 31 + i % 5, 3)).astype(np.uint8) for i in range(130)]
     img2, off2 = ops.preprocess_frames([torch.from_numpy(f).cuda() for f in many])
-    for i in (0, 1, 127, 128, 129):
+    assert img2.shape[0] == 130
+    got2 = img2.cpu().numpy()
+    for i in range(130):      # every frame: the last of a launch and the first of the next (63, 64, 127, 128) among them
         want_img, want_off = opre.img_preprocess(many[i])
-        assert torch.equal(img2[i].cpu(), torch.from_numpy(want_img)), i
+        assert (got2[i] == want_img).all(), i
         assert torch.equal(off2[i], torch.from_numpy(want_off)), i
     meta = u.img_preprocess_gpu(dev[:3], ['a', 'b', 'c'])                 # the acr.utils surface takes the list form
     assert torch.equal(meta['image'], img[:3]) and meta['imgpath'] == ['a', 'b', 'c']
@@ -451,6 +454,41 @@ def test_gpu_preprocess_of_mixed_size_frames_in_one_call():
         ops.preprocess_frames([])
     with pytest.raises(ValueError):
         ops.preprocess_frames([torch.zeros(4, 4, 4, dtype=torch.uint8).cuda()])
+
+
+# H x W: 1 x 1; an odd pad of 3 + 3 on one axis only; a one-pixel pad, bottom or right; an even pad of 2 + 2
+SMALLEST = ((1, 1), (1, 7), (7, 1), (2, 3), (3, 2), (5, 9), (9, 5))
+SMALLEST_ROWS = {(2, 3): [3, 3, 0, 0, 0, 0, 0, 0, 1, 0], (1, 7): [7, 7, 0, 0, 0, 0, 3, 0, 3, 0]}      # by hand
+
+
+@pytest.mark.parametrize('H,W', SMALLEST)
+def test_gpu_preprocess_entry_points_agree_at_the_smallest_sizes(H, W):
+    """The three BGR entry points - the uniform kernel, the frame path and the region path with the box of the whole frame,
+    which share one pixel body and one host rule - against oracle/preprocess.py in bytes and offsets rows, at the sizes where
+    the pad, the clamp and the extra pixel can go wrong; and the uniform kernel on a stack of three frames, per frame."""
+    from oracle import preprocess as opre
+    ops = pkg('ops')
+    frames = np.random.RandomState(1000 * H + W).randint(0, 256, (3, H, W, 3)).astype(np.uint8)
+    want = [opre.img_preprocess(f) for f in frames]
+    if (H, W) in SMALLEST_ROWS:
+        assert want[0][1].tolist() == SMALLEST_ROWS[(H, W)]
+    dev = torch.from_numpy(frames).cuda()
+    calls = (('preprocess', lambda: ops.preprocess(dev[:1])),
+             ('preprocess_frames', lambda: ops.preprocess_frames([dev[0]])),
+             ('preprocess_rois', lambda: ops.preprocess_rois([dev[0]], [(0, 0, W, H)])))
+    for name, call in calls:
+        img, off = call()
+        assert tuple(img.shape) == (1, 512, 512, 3) and img.dtype == torch.uint8 and tuple(off.shape) == (1, 10)
+        bad = int((img[0].cpu().numpy() != want[0][0]).sum())
+        print('%d x %d %s: %d differing bytes, offsets %s' % (H, W, name, bad, off[0].tolist()))
+        assert bad == 0, name
+        assert (off[0].numpy() == want[0][1]).all(), (name, off[0], want[0][1])
+    img, off = ops.preprocess(dev)
+    got = img.cpu().numpy()
+    for i in range(3):
+        assert (got[i] == want[i][0]).all(), 'frame %d of the stack' % i
+        assert (off[i].numpy() == want[i][1]).all()
+    assert not (got[0] == got[1]).all(), 'the frames of the stack must differ'
 
 
 def test_magic_jpg_end_to_end_matches_reference(synth_sd, mano_tables):

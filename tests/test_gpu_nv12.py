@@ -1,6 +1,8 @@
-"""GPU tests of the NV12 input path (csrc/nv12.hip, DESIGN.md "NV12 input") against the numpy statement of its rule in
-tests/nv12_ref.py and the pre-processing oracle: everything is integer, so everything is compared byte for byte.  All
-inputs are seeded random bytes over the full 0..255 range: both clamps and the negative-shift path are hit."""
+"""GPU tests of the NV12 input path (preprocess_rois_nv12_kernel of csrc/preprocess.hip, which ops.preprocess_nv12 runs with
+the window (0, 0, W, H) of each surface, and nv12_to_rgb_kernel of csrc/nv12.hip; DESIGN.md "NV12 input") against the numpy
+statement of its rule in tests/nv12_ref.py and the pre-processing oracle: everything is integer, so everything is compared
+byte for byte.  All inputs are seeded random bytes over the full 0..255 range: both clamps and the negative-shift path are
+hit."""
 import numpy as np
 import pytest
 import torch
@@ -107,6 +109,46 @@ def test_more_frames_than_one_launch_holds():
         assert (got[i] == want).all(), 'frame %d' % i
         assert (offsets[i].numpy() == off).all()
         assert (bgr[i].cpu().numpy() == N.nv12_to_bgr(y, uv)).all(), 'frame %d' % i
+
+
+def _pitched(plane, pitch, fill):
+    """A strided device view of `plane` inside a buffer whose bytes between the width and the pitch hold `fill`."""
+    buf = np.full((plane.shape[0], pitch), fill, np.uint8)
+    buf[:, :plane.shape[1]] = plane
+    return torch.from_numpy(buf).cuda()[:, :plane.shape[1]]
+
+
+def test_frames_through_the_window_path_at_the_smallest_sizes():
+    """acrmi_preprocess_nv12 hands the plan of the whole frame to the window path: the smallest surfaces with a pad on either
+    axis, 10 x 4 once tight and once with y_pitch 11, uv_pitch 13 and a filler that would show, in one call."""
+    ops = pkg('ops')
+    sizes = [(2, 2), (2, 6), (6, 2), (10, 4)]
+    host = [_host_frame(H, W) for H, W in sizes]
+    y, uv = host[3]
+    view = (_pitched(y, 11, 255), _pitched(uv, 13, 255))
+    assert view[0].stride() == (11, 1) and view[1].stride() == (13, 1)
+    rgb, offsets = ops.preprocess_nv12([_device_frame(*f) for f in host] + [view])
+    assert tuple(rgb.shape) == (5, 512, 512, 3) and tuple(offsets.shape) == (5, 10)
+    got = rgb.cpu().numpy()
+    for i, (H, W) in enumerate(sizes + [(10, 4)]):
+        want, off = _reference(H, W)
+        bad = int((got[i] != want).sum())
+        print('%dx%d: %d differing bytes, offsets %s' % (H, W, bad, offsets[i].tolist()))
+        assert bad == 0, 'surface %d (%dx%d)' % (i, H, W)
+        assert (offsets[i].numpy() == off).all()
+    assert torch.equal(rgb[4], rgb[3]) and torch.equal(offsets[4], offsets[3])      # pitched and tight: equal bytes
+    # 65 surfaces: the first, the last of the first launch and the one of the second against the reference, all against
+    # the conversion followed by the BGR frame path
+    many = [_host_frame(4, 4, seed=100 + i) for i in range(65)]
+    frames = [_device_frame(*f) for f in many]
+    rgb, offsets = ops.preprocess_nv12(frames)
+    assert rgb.shape[0] == 65
+    for i in (0, 63, 64):
+        want, off = N.preprocess(*many[i])
+        assert (rgb[i].cpu().numpy() == want).all(), 'surface %d' % i
+        assert (offsets[i].numpy() == off).all()
+    two, off2 = ops.preprocess_frames(ops.nv12_to_bgr(frames))
+    assert torch.equal(rgb, two) and torch.equal(offsets, off2)
 
 
 def test_plain_conversion_equals_reference():

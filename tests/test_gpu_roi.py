@@ -1,8 +1,10 @@
-"""GPU tests of region-of-interest pre-processing (csrc/roi.hip, DESIGN.md "Regions of interest").  Everything is integer, so
-every image is compared byte for byte.  The yardstick is never the new code: it is the existing operator on a crop made on
-the host side (ops.preprocess_frames on frame[t:b, l:r].contiguous()), and for BGR also the numpy statement of the rule
-(tests/roi_ref.py over the pre-processing oracle).  All frames are seeded random bytes, so a tap that read a neighbouring
-pixel of the frame instead of the window's border or the white pad would change the result."""
+"""GPU tests of region-of-interest pre-processing (the window kernels of csrc/preprocess.hip, DESIGN.md "Regions of
+interest").  Everything is integer, so every image is compared byte for byte.  For BGR the yardstick is the numpy statement
+of the rule (tests/roi_ref.py over the pre-processing oracle); ops.preprocess_frames runs the same kernel, so equality with
+it on a crop made on the host side (frame[t:b, l:r].contiguous()) is an additional property: no neighbouring pixel of the
+frame is read.  For NV12 the comparator is nv12_to_rgb_kernel followed by the BGR window kernel on the crop, both other
+kernels than the one under test.  All frames are seeded random bytes, so a tap that read a neighbouring pixel of the frame
+instead of the window's border or the white pad would change the result."""
 import os
 import re
 
@@ -109,7 +111,8 @@ def test_one_region_more_than_a_launch_holds():
     per_launch = int(re.search(r'constexpr int ROIS_PER_LAUNCH = (\d+);', src).group(1))
     n = per_launch + 1
     g = np.random.default_rng(7)
-    frames = [torch.from_numpy(g.integers(0, 256, (8, 8, 3), dtype=np.uint8)).cuda() for _ in range(5)]
+    host = [g.integers(0, 256, (8, 8, 3), dtype=np.uint8) for _ in range(5)]
+    frames = [torch.from_numpy(f).cuda() for f in host]
     box_frame = [int(v) for v in g.integers(0, 5, n)]
     boxes = []
     for _ in range(n):
@@ -119,9 +122,10 @@ def test_one_region_more_than_a_launch_holds():
     want, _ = ops.preprocess_frames([_crop(frames[f], box) for f, box in zip(box_frame, boxes)])
     assert rgb.shape[0] == n
     for i in (0, per_launch - 1, per_launch):      # the first, the last of the first launch, the one of the second launch
-        assert torch.equal(rgb[i], want[i]), 'region %d' % i
-        assert (offsets[i].numpy() == R.offsets(8, 8, boxes[i])).all()
-    assert torch.equal(rgb, want)
+        ref, row = R.preprocess(host[box_frame[i]], boxes[i])      # the yardstick: the numpy statement of the rule
+        assert (rgb[i].cpu().numpy() == ref).all(), 'region %d' % i
+        assert (offsets[i].numpy() == row).all() and (row == R.offsets(8, 8, boxes[i])).all()
+    assert torch.equal(rgb, want)      # and no region reads a neighbouring pixel of its frame: the bytes of the crops
     nv12 = [torch.from_numpy(np.concatenate(N.random_nv12(8, 8, s), 0)).cuda() for s in range(5)]
     got, _ = ops.preprocess_rois(nv12, boxes, box_frame, pixel_format='nv12')
     bgr = ops.nv12_to_bgr(nv12)

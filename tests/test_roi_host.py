@@ -272,11 +272,41 @@ def _check_program_rows(exe):
     assert subprocess.run([exe, '8', '8', '0', '0', '4', 'x'], capture_output=True).returncode == 2
 
 
+# the sizes at which the pad rule can go wrong (an odd pad on one axis, a one-pixel pad, an even pad), and 1080p both ways
+FRAME_SIZES = [(1, 1), (1, 7), (7, 1), (2, 3), (3, 2), (5, 9), (9, 5), (1080, 1920), (1920, 1080)]
+
+
+def _check_full_frame_rows(exe):
+    """`frames`: the plan of the whole frame, which acrmi_preprocess, acrmi_preprocess_frames and acrmi_preprocess_nv12 take
+    their offsets rows from, against the offsets of oracle.preprocess.img_preprocess for a frame of that size."""
+    from oracle import preprocess as opre
+    run = subprocess.run([exe, 'frames'], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    lines = run.stdout.strip().split('\n')
+    assert len(lines) == len(FRAME_SIZES)
+    for line, (Hf, Wf) in zip(lines, FRAME_SIZES):
+        words = line.split()
+        assert [words[i] for i in (0, 3, 8, 13, 18, 20)] == ['frame', 'window', 'crop', 'pad', 'side', 'offsets'] and len(words) == 31, line
+        nums = {k: [int(w) for w in words[i:j]] for k, i, j in (('frame', 1, 3), ('window', 4, 8), ('crop', 9, 13), ('pad', 14, 18),
+                                                               ('side', 19, 20), ('offsets', 21, 31))}
+        _, want = opre.img_preprocess(np.zeros((Hf, Wf, 3), np.uint8))
+        want = want.astype(int).tolist()
+        assert nums['offsets'] == want, (Hf, Wf, line, want)
+        assert nums['frame'] == [Hf, Wf] and nums['window'] == [0, 0, Wf, Hf] and nums['crop'] == [0, 0, 0, 0] == want[2:6]
+        assert nums['pad'] == want[6:] and nums['side'] == [max(Hf, Wf)] == want[:1]
+    assert want == [1920, 1920, 0, 0, 0, 0, 0, 420, 0, 420]      # 1920 x 1080 (H x W), by hand
+    given = subprocess.run([exe, 'frames', '2', '3', '1', '7'], capture_output=True, text=True)
+    assert given.returncode == 0 and [l.split()[21:] for l in given.stdout.strip().split('\n')] == \
+        ['3 3 0 0 0 0 0 0 1 0'.split(), '7 7 0 0 0 0 3 0 3 0'.split()]
+    assert subprocess.run([exe, 'frames', '8'], capture_output=True).returncode == 2
+
+
 def test_roi_plan_stand_alone_program(tmp_path):
     """tools/roi_plan_check.cpp: csrc/roi_plan.h as a program of its own, its rows against tests/roi_ref.py - once as a plain
     build and once built with the address and undefined-behaviour sanitizers.  How this compiler links a sanitized program
     that starts (runtimes static or shared) is found with an empty program first; the check program must then build and
-    pass that way, and nothing here skips."""
+    pass that way, and nothing here skips.  Both builds also print the plans of whole frames (`frames`), which are compared
+    with the pre-processing oracle's offsets rows."""
     cxx = shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
     if cxx is None:
         hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -289,6 +319,7 @@ def test_roi_plan_stand_alone_program(tmp_path):
     plain = str(tmp_path / 'roi_plan_check')
     subprocess.run(base + [src, '-o', plain], check=True, capture_output=True)
     _check_program_rows(plain)
+    _check_full_frame_rows(plain)
     assert subprocess.run([plain], capture_output=True, text=True).stdout.count('\n') == 4      # the built-in list
     # the toolchain question, asked of a program without the code under test
     empty = tmp_path / 'empty.cpp'
@@ -307,6 +338,7 @@ def test_roi_plan_stand_alone_program(tmp_path):
     built = subprocess.run(base + [src, '-o', checked] + flags, capture_output=True, text=True)
     assert built.returncode == 0, built.stderr
     _check_program_rows(checked)
+    _check_full_frame_rows(checked)
 
 
 def _hand(x0, y0, x1, y1):

@@ -1,5 +1,5 @@
-"""Cost of NV12 input (csrc/nv12.hip; DESIGN.md "NV12 input") next to the BGR pre-processing it stands beside, on one GPU,
-one JSON line.
+"""Cost of NV12 input (csrc/preprocess.hip, csrc/nv12.hip; DESIGN.md "NV12 input") next to the BGR pre-processing it stands
+beside, on one GPU, one JSON line.
 
     python tools/nv12_bench.py [--repeats 30] [--warmup 5] [--frames 64] [--timeout 600] [--out FILE]
 

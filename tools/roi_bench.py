@@ -1,5 +1,5 @@
-"""Cost of region-of-interest pre-processing (csrc/roi.hip; DESIGN.md "Regions of interest") next to what a caller had to do
-before it existed, on one GPU, one JSON line.
+"""Cost of region-of-interest pre-processing (csrc/preprocess.hip; DESIGN.md "Regions of interest") next to what a caller had
+to do before it existed, on one GPU, one JSON line.
 
     python tools/roi_bench.py [--repeats 30] [--warmup 5] [--frames 64] [--size 480] [--timeout 600] [--out FILE]
 

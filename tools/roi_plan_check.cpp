@@ -5,12 +5,17 @@
 // One line per case, in order: "window l t r b offsets o0 ... o9" (integers), or "empty" for a box that leaves no pixel.
 // tests/test_roi_host.py compares the lines with the numpy statement of the rule (tests/roi_ref.py).  Without arguments: a
 // built-in list.  Exit status 2 for arguments that are not groups of six integers.
+//   ./roi_plan_check frames [H W ...]
+// The plan of the whole frame, the box (0, 0, W, H), which the frame entry points hand to the window path: one line per size,
+// "frame H W window l t r b crop t r b l pad t r b l side S offsets o0 ... o9".  Without sizes: 1x1, 1x7, 7x1, 2x3, 3x2, 5x9,
+// 9x5, 1080x1920 and 1920x1080.  tests/test_roi_host.py compares the rows with the pre-processing oracle's.
 #include "../arbitrary-hands-3d-reconstruction_amd/csrc/roi_plan.h"
 
 #include <cerrno>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 using namespace acrmi;
@@ -24,7 +29,42 @@ static bool to_int(const char* s, int32_t* v) {
   return true;
 }
 
+static int full_frames(int argc, char** argv) {
+  std::vector<int32_t> v = {1, 1, 1, 7, 7, 1, 2, 3, 3, 2, 5, 9, 9, 5, 1080, 1920, 1920, 1080};
+  if (argc > 2) {
+    if (argc % 2) {
+      std::fprintf(stderr, "usage: %s frames [H W ...]\n", argv[0]);
+      return 2;
+    }
+    v.resize((size_t)(argc - 2));
+    for (int i = 2; i < argc; ++i)
+      if (!to_int(argv[i], &v[(size_t)i - 2])) {
+        std::fprintf(stderr, "not a 32-bit integer: %s\n", argv[i]);
+        return 2;
+      }
+  }
+  for (size_t c = 0; c + 2 <= v.size(); c += 2) {
+    const int32_t H = v[c], W = v[c + 1];
+    // a heap plan and a heap row of exactly ten floats, as below: a write past either is a sanitizer report
+    RoiPlan* p = new RoiPlan();
+    float* row = new float[10];
+    if (!roi_plan(H, W, 0, 0, W, H, p)) {
+      std::printf("empty\n");
+    } else {
+      roi_offsets_row(*p, row);
+      std::printf("frame %d %d window %d %d %d %d crop %d %d %d %d pad %d %d %d %d side %d offsets", H, W, p->l, p->t, p->r, p->b,
+                  p->crop[0], p->crop[1], p->crop[2], p->crop[3], p->pad[0], p->pad[1], p->pad[2], p->pad[3], p->S);
+      for (int i = 0; i < 10; ++i) std::printf(" %d", (int)row[i]);
+      std::printf("\n");
+    }
+    delete[] row;
+    delete p;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "frames")) return full_frames(argc, argv);
   std::vector<int32_t> v;
   if (argc == 1) {
     v = {480, 640, 100, 50, 300, 250, 480, 640, -20, -10, 700, 500, 37, 53, 10, 5, 11, 30, 8, 8, 8, 0, 9, 8};
