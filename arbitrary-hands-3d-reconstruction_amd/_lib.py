@@ -75,7 +75,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_overlay_tables', 'acrmi_draw_skeletons', 'acrmi_draw_heatmaps', 'acrmi_overlay',
            'acrmi_streams_create', 'acrmi_streams_destroy', 'acrmi_streams_reset', 'acrmi_smooth_streams',
            'acrmi_forward_streams', 'acrmi_nv12_matrix', 'acrmi_preprocess_nv12', 'acrmi_nv12_to_rgb',
-           'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12']
+           'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12', 'acrmi_track_box', 'acrmi_track_boxes',
+           'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev']
 
 _lib = None
 
@@ -135,6 +136,10 @@ def lib():
     L.acrmi_roi_offsets.argtypes = [i32, i32, C.POINTER(Roi), vp, vp]
     L.acrmi_preprocess_rois.argtypes = [C.POINTER(Frame), i32, C.POINTER(Roi), i32, vp, vp, vp]
     L.acrmi_preprocess_rois_nv12.argtypes = [C.POINTER(NV12Frame), i32, C.POINTER(Roi), i32, vp, vp, vp, vp]
+    L.acrmi_track_box.argtypes = [f32p, i32, i32, i32, C.c_double, i32, vp]
+    L.acrmi_track_boxes.argtypes = [f32p, f32p, vp, i32, C.c_double, i32, vp, vp]
+    L.acrmi_preprocess_rois_dev.argtypes = [C.POINTER(Frame), i32, vp, vp, i32, vp, vp, vp, vp]
+    L.acrmi_preprocess_rois_nv12_dev.argtypes = [C.POINTER(NV12Frame), i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.acrmi_forward.argtypes = [vp, u8p, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
     L.acrmi_conv2d.argtypes = [f32p, i32, i32, i32, i32, i32, i32, f32p, f32p, i32, f32p, i32, i32, f32p, i32, i32,
                                i32, i32, i32, i32, i32, i32, vp]

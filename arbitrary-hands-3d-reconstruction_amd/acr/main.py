@@ -422,7 +422,31 @@ def _draw_over_frames(kps, canvas, hand_frame):
     return drawn
 
 
+def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=None, max_streams=None, pixel_format='bgr',
+                     matrix='cv601', scale=1.5, min_size=64):
+    """One step of a video loop on regions whose boxes stay on the device (DESIGN.md "Tracking on the device") ->
+    (results, next_boxes).  frames, paths, box_frame, streams, pixel_format, matrix: as forward_raw_batch(boxes=); boxes: the
+    int32 device tensor [n,4] the call before returned as next_boxes, or None for the first frames of a video: the whole
+    frames.  results: the dicts forward_raw_batch(boxes=) gives for those boxes.  next_boxes: the regions of the next frames
+    (ops.track_boxes: acr.utils.boxes_from_keypoints on the fp32 key points, scale and min_size as there), int32 on the
+    device.  Packaging the dicts waits for the device, as it always has; the boxes never pass through the host."""
+    from .. import ops
+    scale, min_size = ops.check_track_args(scale, min_size)
+    frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)
+    if boxes is None:
+        if box_frame is not None:
+            raise ValueError('box_frame says which frame each box is of: it needs boxes=')
+        boxes = ops.whole_frame_boxes(frames, pixel_format)
+    rgb, offsets, _ = ops.preprocess_rois_device(frames, boxes, box_frame, pixel_format=pixel_format, matrix=matrix)
+    n = rgb.shape[0]
+    if len(paths) != n:
+        raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
+    results, _, out = self._forward_batch_results(rgb, paths, offsets, True, None, streams, max_streams)
+    return results, ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size)
+
+
 ACR.forward_raw_batch = _forward_raw_batch
+ACR.track_raw_batch = _track_raw_batch
 
 
 def main(argv=None):

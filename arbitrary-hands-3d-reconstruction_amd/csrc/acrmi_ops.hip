@@ -2,6 +2,7 @@
 #include "acrmi_ctx.h"
 #include "conv_frame.h"   // conv_shape
 #include "roi_plan.h"
+#include "track_plan.h"
 
 #include <vector>
 
@@ -244,6 +245,61 @@ int preprocess_windows_nv12(const char* what, const acrmi_nv12_frame* frames, co
   return ACRMI_OK;
 }
 
+// The window path with the boxes in device memory (DESIGN.md "Tracking on the device"): the loop of the helpers above, but a
+// record holds the frame and the index of its region's box, and the kernel makes the plan.  Nothing is copied, awaited or
+// allocated.  Everything has been validated by the caller.
+template <class FrameOf>
+int preprocess_windows_bgr_dev(const char* what, const acrmi_frame* frames, const FrameOf& frame_of, const int32_t* boxes_dev, int n,
+                               uint8_t* out_rgb_dev, float* offsets_dev, int32_t* status_dev, void* stream) {
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiBgrDevBatch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_frame& fr = frames[frame_of(i0 + i)];
+      rb.r[i].frame = fr.bgr_dev; rb.r[i].H = fr.H; rb.r[i].W = fr.W; rb.r[i].box = i0 + i;
+    }
+    hipError_t e = launch_preprocess_rois_dev(rb, boxes_dev, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, offsets_dev, status_dev,
+                                              (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+template <class FrameOf>
+int preprocess_windows_nv12_dev(const char* what, const acrmi_nv12_frame* frames, const FrameOf& frame_of, const Nv12Coef& k,
+                                const int32_t* boxes_dev, int n, uint8_t* out_rgb_dev, float* offsets_dev, int32_t* status_dev,
+                                void* stream) {
+  for (int i0 = 0; i0 < n; i0 += ROIS_PER_LAUNCH) {
+    const int m = n - i0 < ROIS_PER_LAUNCH ? n - i0 : ROIS_PER_LAUNCH;
+    RoiNv12DevBatch rb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_frame& fr = frames[frame_of(i0 + i)];
+      rb.r[i].y = fr.y_dev; rb.r[i].uv = fr.uv_dev; rb.r[i].y_pitch = fr.y_pitch; rb.r[i].uv_pitch = fr.uv_pitch;
+      rb.r[i].H = fr.H; rb.r[i].W = fr.W; rb.r[i].box = i0 + i;
+    }
+    hipError_t e = launch_preprocess_rois_nv12_dev(rb, k, boxes_dev, m, 512, out_rgb_dev + (size_t)i0 * 512 * 512 * 3, offsets_dev,
+                                                   status_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+// the frame of every region, before anything is queued: roi_frame_host[i] in [0, n_frames), or - NULL - frame i of n frames
+int roi_frames_check(const char* who, const int32_t* roi_frame_host, int n, int n_frames) {
+  if (!roi_frame_host) {
+    if (n != n_frames)
+      return fail(nullptr, ACRMI_EINVAL, "%s: %d regions of %d frames: without roi_frame_host there is one region per frame", who, n,
+                  n_frames);
+    return ACRMI_OK;
+  }
+  for (int i = 0; i < n; ++i)
+    if (roi_frame_host[i] < 0 || roi_frame_host[i] >= n_frames)
+      return fail(nullptr, ACRMI_EINVAL, "%s: region %d: frame index %d outside [0, %d)", who, i, (int)roi_frame_host[i], n_frames);
+  return ACRMI_OK;
+}
+
+bool track_args_ok(double scale, int min_size) { return scale > 0 && scale <= DBL_MAX && min_size >= 1; }
+
 }  // namespace
 
 extern "C" {
@@ -354,6 +410,56 @@ int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames
   if (rc != ACRMI_OK) return rc;
   return preprocess_windows_nv12("preprocess_rois_nv12", frames_host, plans, [&](int i) { return rois_host[i].frame; }, k,
                                  out_rgb_dev, offsets_host, stream);
+}
+
+// ---- tracking on the device (csrc/track_plan.h, csrc/track.hip; DESIGN.md "Tracking on the device") ------------------
+int acrmi_track_box(const float* pts_host, int n_pts, int H, int W, double scale, int min_size, int32_t box_ltrb[4]) {
+  if (!box_ltrb || n_pts < 0 || (n_pts > 0 && !pts_host) || H <= 0 || W <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_track_box: bad arguments");
+  if (!track_args_ok(scale, min_size))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_track_box: scale %g must be finite and > 0, min_size %d must be >= 1", scale, min_size);
+  track_box_of_points(pts_host, n_pts, H, W, scale, min_size, box_ltrb);
+  return ACRMI_OK;
+}
+
+int acrmi_track_boxes(const float* pj2d_org_dev, const float* slots_dev, const int32_t* frame_hw_dev, int n, double scale,
+                      int min_size, int32_t* boxes_dev, void* stream) {
+  if (!pj2d_org_dev || !slots_dev || !frame_hw_dev || !boxes_dev || n <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_track_boxes: bad arguments");
+  if (!track_args_ok(scale, min_size))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_track_boxes: scale %g must be finite and > 0, min_size %d must be >= 1", scale, min_size);
+  hipError_t e = launch_track_boxes(pj2d_org_dev, slots_dev, frame_hw_dev, n, ACRMI_SLOT, ACRMI_SLOT_FLAG, scale, min_size, boxes_dev,
+                                    (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "track_boxes: %s", hipGetErrorString(e));
+}
+
+int acrmi_preprocess_rois_dev(const acrmi_frame* frames_host, int n_frames, const int32_t* roi_frame_host, const int32_t* boxes_dev,
+                              int n, uint8_t* out_rgb_dev, float* offsets_dev, int32_t* status_dev, void* stream) {
+  if (!frames_host || !boxes_dev || !out_rgb_dev || n <= 0 || n_frames <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois_dev: bad arguments");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames_host[i].bgr_dev || frames_host[i].H <= 0 || frames_host[i].W <= 0)
+      return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois_dev: frame %d: null pointer or empty size (%d x %d)", i,
+                  frames_host[i].H, frames_host[i].W);
+  int rc = roi_frames_check("acrmi_preprocess_rois_dev", roi_frame_host, n, n_frames);
+  if (rc != ACRMI_OK) return rc;
+  return preprocess_windows_bgr_dev("preprocess_rois_dev", frames_host, [&](int i) { return roi_frame_host ? roi_frame_host[i] : i; },
+                                    boxes_dev, n, out_rgb_dev, offsets_dev, status_dev, stream);
+}
+
+int acrmi_preprocess_rois_nv12_dev(const acrmi_nv12_frame* frames_host, int n_frames, const int32_t* roi_frame_host,
+                                   const int32_t* boxes_dev, int n, const int32_t* coef6_host, uint8_t* out_rgb_dev,
+                                   float* offsets_dev, int32_t* status_dev, void* stream) {
+  if (!frames_host || !boxes_dev || !out_rgb_dev || n <= 0 || n_frames <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_preprocess_rois_nv12_dev: bad arguments");
+  Nv12Coef k{};
+  int rc = nv12_coef("acrmi_preprocess_rois_nv12_dev", coef6_host, k);
+  if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_preprocess_rois_nv12_dev", frames_host, n_frames);
+  if (rc == ACRMI_OK) rc = roi_frames_check("acrmi_preprocess_rois_nv12_dev", roi_frame_host, n, n_frames);
+  if (rc != ACRMI_OK) return rc;
+  return preprocess_windows_nv12_dev("preprocess_rois_nv12_dev", frames_host,
+                                     [&](int i) { return roi_frame_host ? roi_frame_host[i] : i; }, k, boxes_dev, n, out_rgb_dev,
+                                     offsets_dev, status_dev, stream);
 }
 
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream) {

@@ -206,6 +206,38 @@ static_assert(sizeof(RoiBgrBatch) + 24 <= 4096 && sizeof(RoiNv12Batch) + sizeof(
               "window kernel arguments must fit the 4 KB argument block");
 hipError_t launch_preprocess_rois(const RoiBgrBatch& rb, int n, int out_size, uint8_t* out, hipStream_t s);
 hipError_t launch_preprocess_rois_nv12(const RoiNv12Batch& rb, const Nv12Coef& k, int n, int out_size, uint8_t* out, hipStream_t s);
+// The same windows with the BOXES in device memory (acrmi_preprocess_rois_dev / acrmi_preprocess_rois_nv12_dev; DESIGN.md
+// "Tracking on the device"): what the host knows travels by value - the frame, its size and the index of the region's box -
+// and the kernel reads boxes[box], clamps it to the frame itself (roi_plan_or_frame, csrc/roi_plan.h: a box without pixels
+// becomes the whole frame) and writes the region's `offsets` row and status word.
+struct RoiBgrDev {      // 24 bytes
+  const uint8_t* frame; // the FRAME's first pixel
+  int H, W;             // the frame
+  int box;              // the region: row of boxes / offsets, element of status
+};
+struct RoiBgrDevBatch {
+  RoiBgrDev r[ROIS_PER_LAUNCH];
+};
+struct RoiNv12Dev {     // 40 bytes
+  const uint8_t* y;     // the planes of the FRAME
+  const uint8_t* uv;
+  int y_pitch, uv_pitch;
+  int H, W;             // the frame
+  int box;
+};
+struct RoiNv12DevBatch {
+  RoiNv12Dev r[ROIS_PER_LAUNCH];
+};
+static_assert(sizeof(RoiBgrDevBatch) + 48 <= 4096 && sizeof(RoiNv12DevBatch) + sizeof(Nv12Coef) + 48 <= 4096,
+              "window kernel arguments must fit the 4 KB argument block");
+hipError_t launch_preprocess_rois_dev(const RoiBgrDevBatch& rb, const int32_t* boxes, int n, int out_size, uint8_t* out,
+                                      float* offsets, int32_t* status, hipStream_t s);
+hipError_t launch_preprocess_rois_nv12_dev(const RoiNv12DevBatch& rb, const Nv12Coef& k, const int32_t* boxes, int n, int out_size,
+                                           uint8_t* out, float* offsets, int32_t* status, hipStream_t s);
+// csrc/track.hip (acrmi_track_boxes): pj2d_org [n,2,21,2], slots [n,2,slot_floats] with the flag at flag_at, frame_hw int32
+// [n,2] = (H, W) -> boxes int32 [n,4], the rule of csrc/track_plan.h; one wave per region, one launch for any n
+hipError_t launch_track_boxes(const float* pj2d_org, const float* slots, const int32_t* frame_hw, int n, int slot_floats,
+                              int flag_at, double scale, int min_size, int32_t* boxes, hipStream_t s);
 hipError_t launch_pow11(float* buf, long n_pixels, int cs, int ch, hipStream_t s);
 // fp32 NCHW [B,C,H,W] -> channels [coff, coff + C) of an NHWC buffer with channel stride cs (acrmi_heads: backbone features a
 // caller hands to head_forward, acr/model.py:47-53)

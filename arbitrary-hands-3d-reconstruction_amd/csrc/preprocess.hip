@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "roi_plan.h"
 
 namespace acrmi {
 
@@ -125,6 +126,77 @@ __global__ __launch_bounds__(256) void preprocess_rois_nv12_kernel(const RoiNv12
   }
 }
 
+// The two window kernels again, with the boxes in device memory (DESIGN.md "Tracking on the device").  The record holds the
+// FRAME; the kernel reads boxes[box] and makes the plan itself with the host's own functions (csrc/roi_plan.h), so whatever
+// the box holds - garbage, an inverted box, the int32 extremes - the window lies inside the frame, and one without pixels
+// is the whole frame with status 1.  The plan is a dozen integer operations against 16 taps x 3 channels, and uniform over a
+// block: the record index is made scalar (256 consecutive output pixels never straddle a window, and every trip of the
+// loop moves a block by a multiple of 256), so the box arrives through the scalar cache and the plan runs on the scalar unit.
+// The body and the tap lambdas are those of the kernels above: the same bytes.  The thread of output pixel (0, 0) of a
+// region writes that region's `offsets` row and status word.
+__device__ inline void write_roi_row(const RoiPlan& p, int st, int box, float* __restrict__ offsets, int32_t* __restrict__ status) {
+  if (offsets) {
+    float row[10];
+    roi_offsets_row(p, row);
+    float* o = offsets + (size_t)box * 10;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) o[i] = row[i];
+  }
+  if (status) status[box] = st;
+}
+
+__global__ __launch_bounds__(256) void preprocess_rois_dev_kernel(const RoiBgrDevBatch rb, const int32_t* __restrict__ boxes, int n,
+                                                                  int out_size, uint8_t* __restrict__ out,
+                                                                  float* __restrict__ offsets, int32_t* __restrict__ status) {
+  const long total = (long)n * out_size * out_size;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ox = i % out_size;
+    const int oy = (i / out_size) % out_size;
+    const int f = __builtin_amdgcn_readfirstlane((int)(i / ((long)out_size * out_size)));
+    const int box = rb.r[f].box;
+    const int32_t* __restrict__ q = boxes + (size_t)box * 4;
+    RoiPlan p{};
+    const int st = roi_plan_or_frame(rb.r[f].H, rb.r[f].W, q[0], q[1], q[2], q[3], &p);
+    const size_t pitch = (size_t)rb.r[f].W * 3;
+    const uint8_t* __restrict__ src = rb.r[f].frame + (size_t)p.t * pitch + (size_t)p.l * 3;
+    cubic_pixel(p.b - p.t, p.r - p.l, out_size, oy, ox,
+                [=](int iy, int ix, int& v0, int& v1, int& v2) {
+                  const uint8_t* c = src + (size_t)iy * pitch + (size_t)ix * 3;
+                  v0 = c[2]; v1 = c[1]; v2 = c[0];          // BGR -> RGB
+                },
+                out + (size_t)i * 3);
+    if (ox == 0 && oy == 0) write_roi_row(p, st, box, offsets, status);
+  }
+}
+
+__global__ __launch_bounds__(256) void preprocess_rois_nv12_dev_kernel(const RoiNv12DevBatch rb, const Nv12Coef k,
+                                                                       const int32_t* __restrict__ boxes, int n, int out_size,
+                                                                       uint8_t* __restrict__ out, float* __restrict__ offsets,
+                                                                       int32_t* __restrict__ status) {
+  const long total = (long)n * out_size * out_size;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int ox = i % out_size;
+    const int oy = (i / out_size) % out_size;
+    const int f = __builtin_amdgcn_readfirstlane((int)(i / ((long)out_size * out_size)));
+    const int box = rb.r[f].box;
+    const int32_t* __restrict__ q = boxes + (size_t)box * 4;
+    RoiPlan p{};
+    const int st = roi_plan_or_frame(rb.r[f].H, rb.r[f].W, q[0], q[1], q[2], q[3], &p);
+    const uint8_t* __restrict__ yp = rb.r[f].y;
+    const uint8_t* __restrict__ uvp = rb.r[f].uv;
+    const size_t y_pitch = (size_t)rb.r[f].y_pitch, uv_pitch = (size_t)rb.r[f].uv_pitch;
+    const int l = p.l, t = p.t;
+    cubic_pixel(p.b - p.t, p.r - p.l, out_size, oy, ox,
+                [=](int iy, int ix, int& v0, int& v1, int& v2) {
+                  const int fy = t + iy, fx = l + ix;
+                  const uint8_t* c = uvp + (size_t)(fy >> 1) * uv_pitch + (size_t)(fx & ~1);
+                  nv12_pixel(k, yp[(size_t)fy * y_pitch + (size_t)fx], c[0], c[1], v0, v1, v2);
+                },
+                out + (size_t)i * 3);
+    if (ox == 0 && oy == 0) write_roi_row(p, st, box, offsets, status);
+  }
+}
+
 // one thread per output pixel in blocks of 256, at most 256 * 32 blocks: the kernels loop over the rest
 static unsigned pixel_grid(int n, int out_size) {
   const long total = (long)n * out_size * out_size;
@@ -146,6 +218,20 @@ hipError_t launch_preprocess_rois(const RoiBgrBatch& rb, int n, int out_size, ui
 hipError_t launch_preprocess_rois_nv12(const RoiNv12Batch& rb, const Nv12Coef& k, int n, int out_size, uint8_t* out,
                                        hipStream_t s) {
   hipLaunchKernelGGL(preprocess_rois_nv12_kernel, dim3(pixel_grid(n, out_size)), dim3(256), 0, s, rb, k, n, out_size, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_preprocess_rois_dev(const RoiBgrDevBatch& rb, const int32_t* boxes, int n, int out_size, uint8_t* out,
+                                      float* offsets, int32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(preprocess_rois_dev_kernel, dim3(pixel_grid(n, out_size)), dim3(256), 0, s, rb, boxes, n, out_size, out, offsets,
+                     status);
+  return hipGetLastError();
+}
+
+hipError_t launch_preprocess_rois_nv12_dev(const RoiNv12DevBatch& rb, const Nv12Coef& k, const int32_t* boxes, int n, int out_size,
+                                           uint8_t* out, float* offsets, int32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(preprocess_rois_nv12_dev_kernel, dim3(pixel_grid(n, out_size)), dim3(256), 0, s, rb, k, boxes, n, out_size, out,
+                     offsets, status);
   return hipGetLastError();
 }
 

@@ -9,8 +9,18 @@
 // 0.4.0 compute_paddings_to_reach_aspect_ratio(shape, 1.0): the shorter side, the extra pixel bottom / right) and resized.
 // The row is [padded h, padded w, ct, cr, cb, cl, pt, pr, pb, pl], as image_crop_pad returns it.  A window without pixels is
 // refused (imgaug's Crop would keep one pixel).
+// The window kernels that take their boxes from device memory (csrc/preprocess.hip, DESIGN.md "Tracking on the device") run the
+// same functions on the GPU: ACRMI_HD is `__host__ __device__` when the translation unit is HIP and nothing in plain C++.
 #pragma once
 #include <stdint.h>
+
+#ifndef ACRMI_HD
+#ifdef __HIP__
+#define ACRMI_HD __host__ __device__
+#else
+#define ACRMI_HD
+#endif
+#endif
 
 namespace acrmi {
 
@@ -22,7 +32,7 @@ struct RoiPlan {
 };
 
 // The pad of an h x w image to a square: the arithmetic acrmi_preprocess_frames uses for a frame of this size.
-inline void roi_square_pad(int h, int w, int32_t pad_trbl[4]) {
+ACRMI_HD inline void roi_square_pad(int h, int w, int32_t pad_trbl[4]) {
   pad_trbl[0] = pad_trbl[1] = pad_trbl[2] = pad_trbl[3] = 0;
   if (w < h) { const int d = h - w; pad_trbl[1] = (d + 1) / 2; pad_trbl[3] = d / 2; }
   else if (h < w) { const int d = w - h; pad_trbl[0] = d / 2; pad_trbl[2] = (d + 1) / 2; }
@@ -30,7 +40,7 @@ inline void roi_square_pad(int h, int w, int32_t pad_trbl[4]) {
 
 // Clamps the box to the H x W frame and fills *p.  False - *p untouched - when H or W is not positive or the window has no
 // pixels (an inverted box, or one that lies outside the frame).  The differences are taken in 64 bits: any int32 box is fine.
-inline bool roi_plan(int H, int W, int32_t l, int32_t t, int32_t r, int32_t b, RoiPlan* p) {
+ACRMI_HD inline bool roi_plan(int H, int W, int32_t l, int32_t t, int32_t r, int32_t b, RoiPlan* p) {
   if (H <= 0 || W <= 0) return false;
   const int64_t ct = t > 0 ? (int64_t)t : 0, cl = l > 0 ? (int64_t)l : 0;
   const int64_t cr = (int64_t)W - r > 0 ? (int64_t)W - r : 0, cb = (int64_t)H - b > 0 ? (int64_t)H - b : 0;
@@ -44,12 +54,20 @@ inline bool roi_plan(int H, int W, int32_t l, int32_t t, int32_t r, int32_t b, R
   return true;
 }
 
-inline void roi_offsets_row(const RoiPlan& p, float o[10]) {
+ACRMI_HD inline void roi_offsets_row(const RoiPlan& p, float o[10]) {
   o[0] = o[1] = (float)p.S;
   for (int i = 0; i < 4; ++i) {
     o[2 + i] = (float)p.crop[i];
     o[6 + i] = (float)p.pad[i];
   }
+}
+
+// What the device does with a box, where nothing can be refused: the plan of the box and 0, or - the box leaves no pixel of the
+// frame - the plan of the whole frame (0, 0, W, H) and 1.  H and W must be positive (with either <= 0, *p is left untouched).
+ACRMI_HD inline int roi_plan_or_frame(int H, int W, int32_t l, int32_t t, int32_t r, int32_t b, RoiPlan* p) {
+  if (roi_plan(H, W, l, t, r, b, p)) return 0;
+  (void)roi_plan(H, W, 0, 0, W, H, p);
+  return 1;
 }
 
 }  // namespace acrmi

@@ -564,6 +564,25 @@ class Engine(object):
             _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), *args), self.ctx)
         return out
 
+    def track_step(self, frames, boxes, box_frame=None, frame_hw=None, streams=None, table=None, pixel_format='bgr',
+                   matrix='cv601', scale=1.5, min_size=64):
+        """One step of a video loop on regions that never visits the host (DESIGN.md "Tracking on the device"): the regions
+        `boxes` (a contiguous int32 device tensor [n,4]) of `frames` -> (out, next_boxes, status).  Three calls queued in
+        order on the current stream: ops.preprocess_rois_device, forward(project=True, offsets=<its device rows>) and
+        ops.track_boxes on out['pj2d_org'] and the flags.  next_boxes (int32 device [n,4]) are the regions of the next
+        frames; status int32 device [n] is 1 where a box left no pixel and the whole frame was taken; out also carries
+        the network input ('image') and the device `offsets` rows ('offsets': what render / overlay take).  frames, box_frame,
+        pixel_format, matrix: as ops.preprocess_rois_device; frame_hw: as ops.track_boxes, default the sizes of the
+        regions' frames; streams / table: as forward; scale, min_size: as acr.utils.boxes_from_keypoints."""
+        from . import ops
+        scale, min_size = ops.check_track_args(scale, min_size)
+        rgb, offsets, status = ops.preprocess_rois_device(frames, boxes, box_frame, pixel_format=pixel_format, matrix=matrix)
+        if frame_hw is None:
+            frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)
+        out = self.forward(rgb, offsets=offsets, project=True, streams=streams, table=table)
+        out['image'], out['offsets'] = rgb, offsets      # what the network saw, and the rows render / overlay take
+        return out, ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size), status
+
     def render(self, out, images, offsets=None, cam_trans=None, focal_length=1265., visible_weight=0.9, colors=None,
                bgr=False, dst=None, return_ids=False, stream=None):
         """The hands of `out` (what `forward(..., project=True)` returned: slots, verts, joints, pj2d) drawn over `images`
@@ -846,6 +865,35 @@ class EnginePool(object):
         ticket['event'] = done
         ticket.setdefault('overlay', []).append((res, images, offsets, self.engines[i]._overlay_keep))
         return res
+
+    def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
+        """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True and offsets) and collect(), like render().  -> the boxes of the next frames, int32 on the device.  The
+        caller's current stream is made to wait for them ON THE DEVICE, so they can go straight into
+        ops.preprocess_rois_device and the submit() of the next batch while this ticket is still outstanding; the host waits
+        for nothing."""
+        from . import ops
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('track_boxes() belongs between submit() and collect() of its ticket')
+        res = ticket['out']
+        if res.get('pj2d_org') is None:
+            raise ValueError('the ticket holds no pj2d_org (submit(..., offsets=offsets, project=True))')
+        n = res['slots'].shape[0]
+        hw = ops.frame_hw_device(frame_hw, n, self.device)      # (on the caller's stream, before `ready` is recorded)
+        if out is None:
+            out = torch.empty(n, 4, dtype=torch.int32, device=self.device)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        self.streams[i].wait_event(ready)
+        boxes = ops.track_boxes(res['pj2d_org'], res['slots'], hw, scale=scale, min_size=min_size, out=out, stream=self._raw[i].value)
+        done = torch.cuda.Event()
+        done.record(self.streams[i])
+        torch.cuda.current_stream(self.device).wait_event(done)
+        # as in submit: everything the kernel touches stays referenced by the ticket until its event has completed
+        ticket['event'] = done
+        ticket.setdefault('track', []).append((boxes, hw))
+        return boxes
 
     def _reap(self):
         self._inflight = [t for t in self._inflight if not t['event'].query()]

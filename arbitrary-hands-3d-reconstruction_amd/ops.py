@@ -427,6 +427,164 @@ def preprocess_rois(frames, boxes, box_frame=None, pixel_format='bgr', matrix='c
     return out, torch.from_numpy(offsets)
 
 
+# ---- tracking on the device (csrc/track.hip, csrc/track_plan.h, csrc/preprocess.hip; DESIGN.md "Tracking on the device") ----
+def _raw_stream(stream, device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if stream is None else C.c_void_p(stream)
+
+
+def _device_boxes(boxes):
+    """The boxes of preprocess_rois_device: a contiguous int32 tensor [n,4], n >= 1 (its device is looked at later)."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 4 or \
+            boxes.shape[0] < 1 or not boxes.is_contiguous():
+        raise ValueError('boxes must be a contiguous int32 CUDA tensor [n,4], n >= 1 (host, float or list boxes: ops.preprocess_rois)')
+    return boxes.shape[0]
+
+
+def _box_frames(box_frame, n, n_frames):
+    """box_frame (host integers [n], or None = frame i, one box per frame) -> int32 numpy [n] or None."""
+    if box_frame is None:
+        if n != n_frames:
+            raise ValueError('box_frame is needed when there is not one box per frame (%d boxes, %d frames)' % (n, n_frames))
+        return None
+    if isinstance(box_frame, torch.Tensor) and box_frame.is_cuda:
+        raise ValueError('box_frame is a host list of integers')
+    bf = np.asarray(box_frame)
+    if bf.shape != (n,) or bf.dtype.kind not in 'iu':
+        raise ValueError('box_frame must hold one integer per box')
+    for i, f in enumerate(bf):
+        if not 0 <= int(f) < n_frames:
+            raise ValueError('region %d: frame index %d outside [0, %d)' % (i, int(f), n_frames))
+    return np.ascontiguousarray(bf, dtype=np.int32)
+
+
+def _track_out(t, shape, dtype, dev, name):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise ValueError('%s must be a contiguous %s tensor %s on the frames\' device' % (name, dtype, tuple(shape)))
+    return t
+
+
+def region_frame_sizes(frames, box_frame=None, pixel_format='bgr'):
+    """(H, W) of the frame of every region, as track_boxes takes it: one pair when all frames have one size, else a list of
+    one pair per region."""
+    if pixel_format == 'nv12':
+        sizes = _nv12_frames(frames, need_cuda=False)[1]
+    elif isinstance(frames, torch.Tensor) and frames.dim() == 4:
+        sizes = [tuple(frames.shape[1:3])] * frames.shape[0]
+    else:
+        sizes = [tuple(f.shape[:2]) for f in frames]
+    if all(s == sizes[0] for s in sizes):
+        return tuple(int(v) for v in sizes[0])
+    return [sizes[int(f)] for f in (range(len(sizes)) if box_frame is None else box_frame)]
+
+
+def whole_frame_boxes(frames, pixel_format='bgr'):
+    """The box (0, 0, W, H) of every frame as the int32 device tensor [n_frames,4] preprocess_rois_device takes: the first
+    frames of a video, before there are key points to track."""
+    if pixel_format not in ('bgr', 'nv12'):
+        raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
+    _, sizes, dev, keep = (_nv12_frames if pixel_format == 'nv12' else _bgr_frames)(frames, need_cuda=False)
+    _need_cuda(*keep)
+    return torch.tensor([[0, 0, W, H] for H, W in sizes], dtype=torch.int32).to(dev)
+
+
+def preprocess_rois_device(frames, boxes, box_frame=None, pixel_format='bgr', matrix='cv601', out=None, offsets=None, status=None,
+                           stream=None):
+    """preprocess_rois with the boxes in DEVICE memory (acrmi_preprocess_rois_dev / acrmi_preprocess_rois_nv12_dev): region i
+    is the box boxes[i] of frame box_frame[i], boxes a contiguous int32 CUDA tensor [n,4] on the frames' device - what
+    track_boxes wrote, never seen by the host.  -> (uint8 RGB [n,512,512,3], offsets float32 [n,10], status int32 [n]), all on
+    the device.  The kernel clamps every box to its frame itself; a box that leaves no pixel cannot be refused here, it takes
+    the whole frame and its status is 1 (0: the box as given).  The bytes and the offsets rows are those of preprocess_rois
+    for the same boxes.  box_frame: host integers, as preprocess_rois.  out / offsets / status: tensors to write into.
+    stream: a raw hipStream_t to queue on instead of the current stream.  Nothing here waits for the device."""
+    if pixel_format == 'nv12':
+        coef = nv12_matrix(matrix)
+        arr, sizes, dev, keep = _nv12_frames(frames, need_cuda=False)
+    elif pixel_format != 'bgr':
+        raise ValueError("pixel_format must be 'bgr' or 'nv12', got %r" % (pixel_format,))
+    else:
+        arr, sizes, dev, keep = _bgr_frames(frames, need_cuda=False)
+    n = _device_boxes(boxes)
+    bf = _box_frames(box_frame, n, len(sizes))
+    if not boxes.is_cuda or boxes.device != dev:
+        raise ValueError('boxes must be a contiguous int32 CUDA tensor [n,4] on the frames\' device (host boxes: ops.preprocess_rois)')
+    _need_cuda(*keep)
+    out = _track_out(out, (n, 512, 512, 3), torch.uint8, dev, 'out')
+    offsets = _track_out(offsets, (n, 10), torch.float32, dev, 'offsets')
+    status = _track_out(status, (n,), torch.int32, dev, 'status')
+    bfp = None if bf is None else bf.ctypes.data_as(C.c_void_p)
+    L = _lib.lib()
+    if pixel_format == 'nv12':
+        _lib.check(L.acrmi_preprocess_rois_nv12_dev(arr, len(sizes), bfp, _p(boxes), n, coef.ctypes.data_as(C.c_void_p), _p(out),
+                                                    _p(offsets), _p(status), _raw_stream(stream, dev)))
+    else:
+        _lib.check(L.acrmi_preprocess_rois_dev(arr, len(sizes), bfp, _p(boxes), n, _p(out), _p(offsets), _p(status),
+                                               _raw_stream(stream, dev)))
+    del keep
+    return out, offsets, status
+
+
+def check_track_args(scale, min_size):
+    """scale: a finite number > 0; min_size: an integer >= 1 -> (float, int)."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or scale <= 0:
+        raise ValueError('scale must be a finite number > 0, got %r' % (scale,))
+    if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or min_size < 1 or min_size >= 2 ** 31:
+        raise ValueError('min_size must be an integer >= 1, got %r' % (min_size,))
+    return float(scale), int(min_size)
+
+
+def _host_frame_hw(frame_hw, n):
+    """The host forms of frame_hw -> int numpy (2,) or (n,2); a device tensor -> None.  Does not look at the device."""
+    if isinstance(frame_hw, torch.Tensor) and frame_hw.is_cuda:
+        return None
+    hw = np.asarray(frame_hw.numpy() if isinstance(frame_hw, torch.Tensor) else frame_hw)
+    if hw.shape not in ((2,), (n, 2)) or hw.dtype.kind not in 'iu' or (hw <= 0).any() or (hw >= 2 ** 31).any():
+        raise ValueError('frame_hw must be (H, W) or one (H, W) per region, positive integers')
+    return hw
+
+
+def frame_hw_device(frame_hw, n, dev):
+    """frame_hw of track_boxes -> the int32 device table [n,2]: a device tensor is used as it is; (H, W) is written by two
+    fills; one pair per region on the host goes through pinned memory.  No form waits for the device."""
+    hw = _host_frame_hw(frame_hw, n)
+    if hw is None:
+        if frame_hw.dtype != torch.int32 or tuple(frame_hw.shape) != (n, 2) or not frame_hw.is_contiguous() or frame_hw.device != dev:
+            raise ValueError('a device frame_hw must be a contiguous int32 tensor [n,2] on the key points\' device')
+        return frame_hw
+    if hw.shape == (2,):
+        t = torch.empty(n, 2, dtype=torch.int32, device=dev)
+        t[:, 0] = int(hw[0])
+        t[:, 1] = int(hw[1])
+        return t
+    return torch.from_numpy(np.ascontiguousarray(hw, dtype=np.int32)).pin_memory().to(dev, non_blocking=True)
+
+
+def track_boxes(pj2d_org, slots, frame_hw, scale=1.5, min_size=64, out=None, stream=None):
+    """The boxes of the NEXT frame from the key points of this one, on the device (acrmi_track_boxes): pj2d_org [n,2,21,2] and
+    slots [n,2,176] as Engine.forward(..., project=True, offsets=) returns them -> int32 [n,4] rows (l, t, r, b) on the device.
+    The rule is acr.utils.boxes_from_keypoints on the fp32 points of the hands whose flag is set, integer for integer, with
+    one clause more: a result without pixels is the whole frame (DESIGN.md "Tracking on the device").  frame_hw: (H, W), or one
+    pair per region on the host, or an int32 device tensor [n,2], which is used as it is.  out: the tensor to write.  stream:
+    a raw hipStream_t to queue on instead of the current stream.  Nothing here waits for the device."""
+    scale, min_size = check_track_args(scale, min_size)
+    if not isinstance(pj2d_org, torch.Tensor) or not isinstance(slots, torch.Tensor) or pj2d_org.dim() != 4 or \
+            tuple(pj2d_org.shape[1:]) != (2, 21, 2) or tuple(slots.shape) != (pj2d_org.shape[0], 2, _lib.SLOT) or \
+            pj2d_org.dtype != torch.float32 or slots.dtype != torch.float32 or pj2d_org.shape[0] < 1:
+        raise ValueError('pj2d_org must be float32 [n,2,21,2] and slots float32 [n,2,%d], n >= 1' % _lib.SLOT)
+    n = pj2d_org.shape[0]
+    dev = pj2d_org.device
+    _host_frame_hw(frame_hw, n)      # the host forms: checked before the device is looked at
+    _need_cuda(pj2d_org, slots)
+    if slots.device != dev:
+        raise ValueError('pj2d_org and slots are on different devices')
+    hw = frame_hw_device(frame_hw, n, dev)
+    out = _track_out(out, (n, 4), torch.int32, dev, 'out')
+    pj, sl = pj2d_org.contiguous(), slots.contiguous()
+    _lib.check(_lib.lib().acrmi_track_boxes(_p(pj), _p(sl), _p(hw), n, scale, min_size, _p(out), _raw_stream(stream, dev)))
+    return out
+
+
 def cam_trans(joints, pj2d, focal_length=600.0, img_size=512.0):
     """joints [n,21,3], pj2d [n,21,2] (device fp32) -> cam_trans [n,3]: the reference's closed-form least squares
     (acr/utils.py:430-472, unit confidences) on the device."""

@@ -378,6 +378,29 @@ int acrmi_preprocess_rois(const acrmi_frame* frames_host, int n_frames, const ac
  * the window of the frame acrmi_nv12_to_rgb makes.  Chroma is addressed in frame coordinates, so odd l and t are fine. */
 int acrmi_preprocess_rois_nv12(const acrmi_nv12_frame* frames_host, int n_frames, const acrmi_roi* rois_host, int n,
                                const int32_t* coef6_host, uint8_t* out_rgb_dev, float* offsets_host, void* stream);
+/* Tracking on the device (DESIGN.md "Tracking on the device"): frame k -> boxes -> frame k+1 as launches on one stream.
+ * The box rule is acr.utils.boxes_from_keypoints for fp32 points, in double, integer for integer: the points whose two
+ * coordinates are finite; centre and extent of their bounding box; side = max(longer extent * scale, min_size); the square
+ * floor / ceil'ed outwards, moved back inside the H x W frame and cut to it; no such point: the whole frame (0, 0, W, H).  One
+ * clause more: a result without pixels (r <= l or b <= t: the side was lost against a huge centre) is the whole frame too.
+ * scale finite and > 0, min_size >= 1, else ACRMI_EINVAL. */
+/* host only: the rule on n_pts fp32 points [n_pts,2] (n_pts may be 0) */
+int acrmi_track_box(const float* pts_host, int n_pts, int H, int W, double scale, int min_size, int32_t box_ltrb[4]);
+/* pj2d_org_dev [n,2,21,2], slots_dev [n,2,ACRMI_SLOT], frame_hw_dev int32 [n,2] = (H, W) -> boxes_dev int32 [n,4].  The 21 points
+ * of a hand take part when its ACRMI_SLOT_FLAG > 0.5; the coordinates of another hand are not looked at.  A frame size that
+ * is not positive gives the box (0, 0, 0, 0), which acrmi_preprocess_rois_dev turns into its frame's whole window.  One launch. */
+int acrmi_track_boxes(const float* pj2d_org_dev, const float* slots_dev, const int32_t* frame_hw_dev, int n, double scale,
+                      int min_size, int32_t* boxes_dev, void* stream);
+/* acrmi_preprocess_rois with the boxes in device memory: region i = box boxes_dev[i] of frame roi_frame_host[i] (NULL: frame i,
+ * needs n == n_frames); offsets_dev float [n,10] and status_dev int32 [n] (0 = the box as given, 1 = it left no pixel and the
+ * whole frame was taken) are written on the device; either may be NULL.  The kernel clamps the box to its frame itself, so no
+ * box, whatever it holds, makes it read outside the frame.  The same launches as acrmi_preprocess_rois for the same n; no
+ * copy, no synchronise, no allocation. */
+int acrmi_preprocess_rois_dev(const acrmi_frame* frames_host, int n_frames, const int32_t* roi_frame_host, const int32_t* boxes_dev,
+                              int n, uint8_t* out_rgb_dev, float* offsets_dev, int32_t* status_dev, void* stream);
+int acrmi_preprocess_rois_nv12_dev(const acrmi_nv12_frame* frames_host, int n_frames, const int32_t* roi_frame_host,
+                                   const int32_t* boxes_dev, int n, const int32_t* coef6_host, uint8_t* out_rgb_dev,
+                                   float* offsets_dev, int32_t* status_dev, void* stream);
 int acrmi_u8norm(const uint8_t* img, int n_pixels, float* out, void* stream);
 /* ACRMI_OP_STEM stand-alone: img uint8 RGB [B,H,W,3] (H % 16 == 0, W % 128 == 0) -> [relu](conv3x3 stride 2 pad 1 of
  * (x/255*2-1) + bias) into channels out_coff..out_coff+63 of out [B,H/2,W/2,out_cs]; w_packed = packer.pack_stem(w
