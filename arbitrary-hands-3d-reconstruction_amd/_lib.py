@@ -49,6 +49,10 @@ class NV12Frame(C.Structure):      # acrmi_nv12_frame
                 ('y_pitch', C.c_int32), ('uv_pitch', C.c_int32)]
 
 
+class NV12Surface(C.Structure):      # acrmi_nv12_surface: the same layout, writable planes
+    _fields_ = NV12Frame._fields_
+
+
 class Roi(C.Structure):      # acrmi_roi
     _fields_ = [('frame', C.c_int32), ('l', C.c_int32), ('t', C.c_int32), ('r', C.c_int32), ('b', C.c_int32)]
 
@@ -76,7 +80,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_streams_create', 'acrmi_streams_destroy', 'acrmi_streams_reset', 'acrmi_smooth_streams',
            'acrmi_forward_streams', 'acrmi_nv12_matrix', 'acrmi_preprocess_nv12', 'acrmi_nv12_to_rgb',
            'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12', 'acrmi_track_box', 'acrmi_track_boxes',
-           'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev']
+           'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev', 'acrmi_nv12_out_matrix', 'acrmi_rgb_to_nv12',
+           'acrmi_nv12_compose']
 
 _lib = None
 
@@ -133,6 +138,9 @@ def lib():
     L.acrmi_nv12_matrix.argtypes = [i32, vp]
     L.acrmi_preprocess_nv12.argtypes = [C.POINTER(NV12Frame), i32, vp, vp, vp, vp]
     L.acrmi_nv12_to_rgb.argtypes = [C.POINTER(NV12Frame), i32, vp, i32, C.POINTER(vp), vp]
+    L.acrmi_nv12_out_matrix.argtypes = [i32, vp]
+    L.acrmi_rgb_to_nv12.argtypes = [C.POINTER(vp), C.POINTER(NV12Surface), i32, vp, i32, vp]
+    L.acrmi_nv12_compose.argtypes = [C.POINTER(NV12Frame), C.POINTER(vp), C.POINTER(NV12Surface), i32, vp, vp, i32, vp]
     L.acrmi_roi_offsets.argtypes = [i32, i32, C.POINTER(Roi), vp, vp]
     L.acrmi_preprocess_rois.argtypes = [C.POINTER(Frame), i32, C.POINTER(Roi), i32, vp, vp, vp]
     L.acrmi_preprocess_rois_nv12.argtypes = [C.POINTER(NV12Frame), i32, C.POINTER(Roi), i32, vp, vp, vp, vp]

@@ -338,7 +338,7 @@ class ACR(object):
 
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
-                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None):
+                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr'):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -354,22 +354,77 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     the frame before).  One path per region, results keyed by it, a stream id per region; pj2d_org is in the pixels of the
     ORIGINAL frame.  render=True then needs show_items of 'pj2d' / 'org_img': the skeletons of all regions of a frame are drawn
     over that frame, one drawn frame per source frame.  'mesh' and 'centermap' over regions are a ValueError (the
-    rasteriser's viewport is per frame: DESIGN.md "Regions of interest")."""
+    rasteriser's viewport is per frame: DESIGN.md "Regions of interest").
+    render_format='nv12' (with render=True): the drawn views come back as NV12 surfaces for a video encoder - a tensor
+    [n,H*3/2,W] when all sizes agree, else a list; 'centermap' keeps its leading pair.  With pixel_format='nv12' every view is
+    composed onto its source surface (ops.nv12_compose: new bytes only where something was drawn) and 'org_img' is the
+    surfaces as given; `matrix` is then a name or a pair (row6, row10).  With BGR frames the views go through
+    ops.bgr_to_nv12, and `matrix` is a name, a pair or a row of ten integers; H and W must be even."""
     from .utils import img_preprocess_gpu
     if show_items is not None and not render:
         raise ValueError('show_items needs render=True')
+    if render_format not in ('bgr', 'nv12'):
+        raise ValueError("render_format: %r is not 'bgr' or 'nv12'" % (render_format,))
+    to_nv12 = None
+    if render_format == 'nv12':
+        if not render:
+            raise ValueError("render_format='nv12' needs render=True")
+        to_nv12, matrix = _nv12_views(bgr_frames_dev, pixel_format, matrix)
     if boxes is not None:
-        return _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
-                                pixel_format, matrix)
-    if box_frame is not None:
-        raise ValueError('box_frame says which frame each box is of: it needs boxes=')
-    meta = img_preprocess_gpu(bgr_frames_dev, paths, pixel_format=pixel_format, matrix=matrix)
-    canvas = None
-    if render:
-        from .. import ops
-        canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
-    return self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
-                              render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
+        got = _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
+                               pixel_format, matrix)
+    else:
+        if box_frame is not None:
+            raise ValueError('box_frame says which frame each box is of: it needs boxes=')
+        meta = img_preprocess_gpu(bgr_frames_dev, paths, pixel_format=pixel_format, matrix=matrix)
+        canvas = None
+        if render:
+            from .. import ops
+            canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
+        got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
+                                 render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
+    if to_nv12 is None:
+        return got
+    results, views = got
+    if not isinstance(views, dict):
+        return results, to_nv12('mesh', views)
+    return results, {name: to_nv12(name, view) for name, view in views.items()}
+
+
+def _nv12_views(frames, pixel_format, matrix):
+    """render_format='nv12' of forward_raw_batch -> (the function that turns one drawn BGR view into NV12 surfaces, the matrix
+    of the input side).  Everything that can be refused is refused here, before anything runs."""
+    from .. import ops
+    if pixel_format == 'nv12':
+        row6, row10 = ops._nv12_matrix_pair(matrix)
+
+        def one(drawn):
+            return ops.nv12_compose(frames, drawn, matrix=(row6, row10), bgr=True)
+    else:
+        if isinstance(matrix, str) or (isinstance(matrix, (tuple, list)) and len(matrix) == 2):
+            row10 = ops._nv12_matrix_pair(matrix)[1]
+        else:
+            row10 = ops.nv12_out_matrix(matrix)
+        row6 = 'cv601'     # BGR frames pass no input rule: the pre-processing gets the default, not the caller's output row
+        items = list(frames.unbind(0)) if isinstance(frames, torch.Tensor) and frames.dim() == 4 else list(frames)
+        for i, f in enumerate(items):
+            if f.dim() != 3 or f.shape[0] < 2 or f.shape[1] < 2 or f.shape[0] % 2 or f.shape[1] % 2:
+                raise ValueError("render_format='nv12': frame %d: NV12 needs H and W even and >= 2, got %s" % (i, tuple(f.shape)))
+
+        def one(drawn):
+            return ops.bgr_to_nv12(drawn, matrix=row10, bgr=True)
+
+    def view(name, drawn):
+        if name == 'org_img' and pixel_format == 'nv12':
+            return frames
+        if name != 'centermap':
+            return one(drawn)
+        if isinstance(drawn, (list, tuple)):      # [2,H_i,W_i,3] per frame: left and right
+            left, right = one([d[0] for d in drawn]), one([d[1] for d in drawn])
+            return [torch.stack([a, b]) for a, b in zip(left, right)]
+        return torch.stack([one(drawn[0]), one(drawn[1])])
+
+    return view, row6
 
 
 def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix):

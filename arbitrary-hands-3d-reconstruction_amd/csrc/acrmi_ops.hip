@@ -300,6 +300,28 @@ int roi_frames_check(const char* who, const int32_t* roi_frame_host, int n, int 
 
 bool track_args_ok(double scale, int min_size) { return scale > 0 && scale <= DBL_MAX && min_size >= 1; }
 
+// NV12 output (csrc/nv12_out_plan.h).  Null row = cv601; a refused row names its reason.
+int nv12_out_coef(const char* who, const int32_t* coef10, Nv12OutCoef& k) {
+  const int32_t* c = coef10 ? coef10 : kNv12OutMatrix[0];
+  const char* why = nullptr;
+  if (!nv12_out_row(c, &k, &why))
+    return fail(nullptr, ACRMI_EINVAL, "%s: output row (%d, %d, %d, %d, %d, %d, %d, %d, %d, y_off %d): %s", who, (int)c[0], (int)c[1],
+                (int)c[2], (int)c[3], (int)c[4], (int)c[5], (int)c[6], (int)c[7], (int)c[8], (int)c[9], why);
+  return ACRMI_OK;
+}
+
+int nv12_check_surfaces(const char* who, const acrmi_nv12_surface* su, int n) {
+  for (int i = 0; i < n; ++i) {
+    const acrmi_nv12_surface& f = su[i];
+    if (!f.y_dev || !f.uv_dev) return fail(nullptr, ACRMI_EINVAL, "%s: surface %d: null plane", who, i);
+    if (f.H < 2 || f.W < 2 || (f.H & 1) || (f.W & 1))
+      return fail(nullptr, ACRMI_EINVAL, "%s: surface %d: size %d x %d (H x W) must be even and >= 2", who, i, f.H, f.W);
+    if (f.y_pitch < f.W || f.uv_pitch < f.W)
+      return fail(nullptr, ACRMI_EINVAL, "%s: surface %d: pitch (y %d, uv %d) below the width %d", who, i, f.y_pitch, f.uv_pitch, f.W);
+  }
+  return ACRMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -364,6 +386,71 @@ int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t*
     }
     hipError_t e = launch_nv12_to_rgb(pb, k, m, bgr ? 1 : 0, (hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "nv12_to_rgb: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+// ---- NV12 output (csrc/nv12_out.hip, csrc/nv12_out_plan.h; DESIGN.md "NV12 output") -----------------------------------------
+int acrmi_nv12_out_matrix(int which, int32_t coef10[10]) {
+  if (!coef10 || which < 0 || which > ACRMI_NV12_BT709_FULL)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_out_matrix: bad arguments (matrix %d)", which);
+  for (int i = 0; i < 10; ++i) coef10[i] = kNv12OutMatrix[which][i];
+  return ACRMI_OK;
+}
+
+int acrmi_rgb_to_nv12(const uint8_t* const* src_dev_host, const acrmi_nv12_surface* surfaces_host, int n,
+                      const int32_t* coef10_host, int bgr, void* stream) {
+  if (!src_dev_host || !surfaces_host || n <= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_rgb_to_nv12: bad arguments");
+  Nv12OutCoef k{};
+  int rc = nv12_out_coef("acrmi_rgb_to_nv12", coef10_host, k);
+  if (rc == ACRMI_OK) rc = nv12_check_surfaces("acrmi_rgb_to_nv12", surfaces_host, n);
+  if (rc != ACRMI_OK) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!src_dev_host[i]) return fail(nullptr, ACRMI_EINVAL, "acrmi_rgb_to_nv12: frame %d: null source", i);
+  for (int i0 = 0; i0 < n; i0 += NV12_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < NV12_FRAMES_PER_LAUNCH ? n - i0 : NV12_FRAMES_PER_LAUNCH;
+    Nv12OutBatch pb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_surface& su = surfaces_host[i0 + i];
+      pb.f[i].src = src_dev_host[i0 + i]; pb.f[i].y = su.y_dev; pb.f[i].uv = su.uv_dev; pb.f[i].H = su.H; pb.f[i].W = su.W;
+      pb.f[i].y_pitch = su.y_pitch; pb.f[i].uv_pitch = su.uv_pitch;
+    }
+    hipError_t e = launch_rgb_to_nv12(pb, k, m, bgr ? 1 : 0, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "rgb_to_nv12: %s", hipGetErrorString(e));
+  }
+  return ACRMI_OK;
+}
+
+int acrmi_nv12_compose(const acrmi_nv12_frame* src_frames_host, const uint8_t* const* drawn_dev_host,
+                       const acrmi_nv12_surface* out_surfaces_host, int n, const int32_t* coef6_host, const int32_t* coef10_host,
+                       int bgr, void* stream) {
+  if (!src_frames_host || !drawn_dev_host || !out_surfaces_host || n <= 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_compose: bad arguments");
+  Nv12Coef k6{};
+  Nv12OutCoef k10{};
+  int rc = nv12_coef("acrmi_nv12_compose", coef6_host, k6);
+  if (rc == ACRMI_OK) rc = nv12_out_coef("acrmi_nv12_compose", coef10_host, k10);
+  if (rc == ACRMI_OK) rc = nv12_check_frames("acrmi_nv12_compose", src_frames_host, n);
+  if (rc == ACRMI_OK) rc = nv12_check_surfaces("acrmi_nv12_compose", out_surfaces_host, n);
+  if (rc != ACRMI_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (!drawn_dev_host[i]) return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_compose: frame %d: null drawn frame", i);
+    if (out_surfaces_host[i].H != src_frames_host[i].H || out_surfaces_host[i].W != src_frames_host[i].W)
+      return fail(nullptr, ACRMI_EINVAL, "acrmi_nv12_compose: frame %d: the output surface is %d x %d, the source %d x %d (H x W)", i,
+                  out_surfaces_host[i].H, out_surfaces_host[i].W, src_frames_host[i].H, src_frames_host[i].W);
+  }
+  for (int i0 = 0; i0 < n; i0 += NV12_COMPOSE_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < NV12_COMPOSE_FRAMES_PER_LAUNCH ? n - i0 : NV12_COMPOSE_FRAMES_PER_LAUNCH;
+    Nv12ComposeBatch pb{};
+    for (int i = 0; i < m; ++i) {
+      const acrmi_nv12_frame& fr = src_frames_host[i0 + i];
+      const acrmi_nv12_surface& su = out_surfaces_host[i0 + i];
+      Nv12ComposeFrame& c = pb.f[i];
+      c.src_y = fr.y_dev; c.src_uv = fr.uv_dev; c.drawn = drawn_dev_host[i0 + i]; c.y = su.y_dev; c.uv = su.uv_dev;
+      c.H = fr.H; c.W = fr.W; c.src_y_pitch = fr.y_pitch; c.src_uv_pitch = fr.uv_pitch; c.y_pitch = su.y_pitch; c.uv_pitch = su.uv_pitch;
+    }
+    hipError_t e = launch_nv12_compose(pb, k6, k10, m, bgr ? 1 : 0, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "nv12_compose: %s", hipGetErrorString(e));
   }
   return ACRMI_OK;
 }

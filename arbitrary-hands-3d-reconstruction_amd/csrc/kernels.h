@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "conv_rules.h"
+#include "nv12_out_plan.h"
 #include "smooth_plan.h"
 
 namespace acrmi {
@@ -180,6 +181,36 @@ __device__ inline void nv12_pixel(const Nv12Coef& k, int Y, int U, int V, int& R
   G = nv12_clamp8((yy + k.cug * u + k.cvg * v + r) >> 20);
   B = nv12_clamp8((yy + k.cub * u + r) >> 20);
 }
+// NV12 surfaces as the OUTPUT (csrc/nv12_out.hip, csrc/nv12_out_plan.h; acrmi_rgb_to_nv12, acrmi_nv12_compose): geometry by
+// value again.  A compose frame names five planes and six sizes, 64 bytes: 58 of them (3712 bytes), the two coefficient rows and
+// the flag (68 bytes) and the 256 bytes of hidden arguments hipcc appends to the kernel-argument segment make 4040 of the 4096
+// bytes; 59 would not fit.
+struct Nv12OutFrame {   // 40 bytes
+  const uint8_t* src;   // tight [H, W, 3]
+  uint8_t* y;
+  uint8_t* uv;
+  int H, W, y_pitch, uv_pitch;
+};
+struct Nv12OutBatch {
+  Nv12OutFrame f[NV12_FRAMES_PER_LAUNCH];
+};
+constexpr int NV12_COMPOSE_FRAMES_PER_LAUNCH = 58;
+struct Nv12ComposeFrame {   // 64 bytes
+  const uint8_t* src_y;
+  const uint8_t* src_uv;
+  const uint8_t* drawn;     // tight [H, W, 3]
+  uint8_t* y;               // may be src_y (then uv is src_uv and the pitches agree): a thread reads and writes its own blocks only
+  uint8_t* uv;
+  int H, W, src_y_pitch, src_uv_pitch, y_pitch, uv_pitch;
+};
+struct Nv12ComposeBatch {
+  Nv12ComposeFrame f[NV12_COMPOSE_FRAMES_PER_LAUNCH];
+};
+static_assert(sizeof(Nv12OutBatch) + sizeof(Nv12OutCoef) + 8 + 256 <= 4096 &&
+                  sizeof(Nv12ComposeBatch) + sizeof(Nv12Coef) + sizeof(Nv12OutCoef) + 8 + 256 <= 4096,
+              "NV12 output kernel arguments must fit the 4 KB argument block");
+hipError_t launch_rgb_to_nv12(const Nv12OutBatch& pb, const Nv12OutCoef& k, int n, int bgr, hipStream_t s);
+hipError_t launch_nv12_compose(const Nv12ComposeBatch& pb, const Nv12Coef& k6, const Nv12OutCoef& k10, int n, int bgr, hipStream_t s);
 // Windows of frames (csrc/preprocess.hip): a window of a frame pre-processed as a frame of its own size - a region of
 // interest (acrmi_preprocess_rois / acrmi_preprocess_rois_nv12) or the whole frame (acrmi_preprocess_frames /
 // acrmi_preprocess_nv12).  Geometry by value, ROIS_PER_LAUNCH per launch; the windows are already clamped to their frames

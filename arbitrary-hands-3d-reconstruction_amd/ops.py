@@ -345,6 +345,105 @@ def nv12_to_bgr(frames, matrix='cv601', rgb=False):
     return out
 
 
+# ---- NV12 output (csrc/nv12_out.hip, csrc/nv12_out_plan.h; DESIGN.md "NV12 output") --------------------------------------
+def nv12_out_matrix(name_or_row='cv601'):
+    """A matrix name (those of nv12_matrix: acrmi_nv12_out_matrix) or a row of ten integers (cry, cgy, cby, cru, cgu, cbu, crv,
+    cgv, cbv, y_off) -> the row as int32 numpy [10].  Pure host: works without a GPU."""
+    if isinstance(name_or_row, str):
+        which = _lib.NV12_MATRICES.get(name_or_row)
+        if which is None:
+            raise ValueError('unknown NV12 matrix %r: one of %s, or a row of ten integers' % (name_or_row, sorted(_lib.NV12_MATRICES)))
+        row = np.zeros(10, np.int32)
+        _lib.check(_lib.lib().acrmi_nv12_out_matrix(which, row.ctypes.data_as(C.c_void_p)))
+        return row
+    row = np.asarray(name_or_row.cpu() if hasattr(name_or_row, 'cpu') else name_or_row)
+    if row.shape != (10,) or row.dtype.kind not in 'iu' or int(row.min()) < -2 ** 31 or int(row.max()) >= 2 ** 31:
+        raise ValueError('an NV12 output matrix is a name or ten int32 integers (cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv, y_off)')
+    return np.ascontiguousarray(row.astype(np.int32))
+
+
+def _nv12_matrix_pair(matrix='cv601'):
+    """`matrix` of nv12_compose: a name, which selects the input and the output row, or a pair (row6, row10), each a name or a
+    row of integers -> (int32 [6], int32 [10])."""
+    if isinstance(matrix, str):
+        return nv12_matrix(matrix), nv12_out_matrix(matrix)
+    if isinstance(matrix, (tuple, list)) and len(matrix) == 2 and not all(isinstance(v, (int, np.integer)) for v in matrix):
+        return nv12_matrix(matrix[0]), nv12_out_matrix(matrix[1])
+    raise ValueError('matrix must be a name or a pair (row of six integers, row of ten integers): the input and the output rule')
+
+
+def _nv12_surfaces(out, sizes, dev, what):
+    """`out=` of bgr_to_nv12 / nv12_compose (surfaces to write into, in the layouts of _nv12_frames), or None: new tight
+    surfaces - one tensor [n, H*3/2, W] when all sizes agree, else a list -> (what the call returns, acrmi_nv12_surface array,
+    bound tensors)."""
+    n = len(sizes)
+    if out is None:
+        if all(s == sizes[0] for s in sizes):
+            out = torch.empty(n, sizes[0][0] * 3 // 2, sizes[0][1], dtype=torch.uint8, device=dev)
+        else:
+            out = [torch.empty(H * 3 // 2, W, dtype=torch.uint8, device=dev) for H, W in sizes]
+    arr, out_sizes, out_dev, keep = _nv12_frames(out, need_cuda=False)
+    if out_sizes != sizes:
+        raise ValueError('%s: out= holds surfaces of %s (H, W), the frames are %s' % (what, out_sizes, sizes))
+    if out_dev != dev:
+        raise ValueError('%s: out= is on another device than the frames' % what)
+    su = (_lib.NV12Surface * n)()
+    for i in range(n):
+        su[i].y_dev, su[i].uv_dev, su[i].H, su[i].W = arr[i].y_dev, arr[i].uv_dev, arr[i].H, arr[i].W
+        su[i].y_pitch, su[i].uv_pitch = arr[i].y_pitch, arr[i].uv_pitch
+    return out, su, keep
+
+
+def _even_sizes(sizes, what):
+    for i, (H, W) in enumerate(sizes):
+        if H < 2 or W < 2 or H % 2 or W % 2:
+            raise ValueError('%s: frame %d: NV12 needs H and W even and >= 2, got %d x %d' % (what, i, H, W))
+
+
+def bgr_to_nv12(frames, matrix='cv601', bgr=True, out=None):
+    """Packed uint8 device frames - a tensor [n,H,W,3] or a list of [H_i,W_i,3] of different sizes, BGR (RGB with bgr=False) -> NV12
+    surfaces by the integer rule of include/acrmi.h (acrmi_rgb_to_nv12): luma per pixel, chroma from the mean of each 2x2 block.
+    H, W even.  matrix: a name, a row of ten integers, or the pair nv12_compose takes (its output row is used).
+    -> one uint8 tensor [n, H*3/2, W] (the Y rows, then the interleaved UV rows: what preprocess_nv12 takes) when all sizes
+    agree, else a list of [H_i*3/2, W_i] in input order; or `out`: surfaces to write into, in any layout preprocess_nv12
+    accepts (strided views are taken as they are, pitch = stride(0); nothing beyond W bytes of a row is written)."""
+    if isinstance(matrix, str) or (isinstance(matrix, (tuple, list)) and len(matrix) == 2):
+        coef = _nv12_matrix_pair(matrix)[1]
+    else:
+        coef = nv12_out_matrix(matrix)
+    src, sizes, dev, keep = _bgr_frames(frames, need_cuda=False)
+    _even_sizes(sizes, 'bgr_to_nv12')
+    out, su, keep_out = _nv12_surfaces(out, sizes, dev, 'bgr_to_nv12')
+    _need_cuda(*keep)
+    n = len(sizes)
+    ptrs = (C.c_void_p * n)(*[src[i].bgr_dev for i in range(n)])
+    _lib.check(_lib.lib().acrmi_rgb_to_nv12(ptrs, su, n, coef.ctypes.data_as(C.c_void_p), 1 if bgr else 0, _s(keep[0])))
+    del keep, keep_out
+    return out
+
+
+def nv12_compose(surfaces, drawn, matrix='cv601', bgr=True, out=None):
+    """The drawn frames `drawn` (as bgr_to_nv12 takes them) over the NV12 surfaces they were drawn from (as preprocess_nv12
+    takes them): new bytes only where a drawn pixel differs from what nv12_to_bgr makes of the surface, the surface's own bytes
+    everywhere else (acrmi_nv12_compose) - nv12_compose(s, nv12_to_bgr(s)) is s, byte for byte.  matrix: a name, or a pair
+    (row6, row10) of the input and the output rule.  -> as bgr_to_nv12; out= may be `surfaces` itself (in place)."""
+    coef6, coef10 = _nv12_matrix_pair(matrix)
+    arr, sizes, dev, keep = _nv12_frames(surfaces, need_cuda=False)
+    src, drawn_sizes, drawn_dev, keep_drawn = _bgr_frames(drawn, need_cuda=False)
+    if drawn_sizes != sizes:
+        raise ValueError('nv12_compose: the drawn frames are %s (H, W), the surfaces %s' % (drawn_sizes, sizes))
+    if drawn_dev != dev:
+        raise ValueError('nv12_compose: the drawn frames are on another device than the surfaces')
+    out, su, keep_out = _nv12_surfaces(out, sizes, dev, 'nv12_compose')
+    _need_cuda(*keep)
+    n = len(sizes)
+    ptrs = (C.c_void_p * n)(*[src[i].bgr_dev for i in range(n)])
+    _lib.check(_lib.lib().acrmi_nv12_compose(arr, ptrs, su, n, coef6.ctypes.data_as(C.c_void_p), coef10.ctypes.data_as(C.c_void_p),
+                                            1 if bgr else 0, _s(keep[0])))
+    del keep, keep_drawn, keep_out
+    return out
+
+
 # ---- regions of interest (csrc/preprocess.hip, csrc/roi_plan.h; DESIGN.md "Regions of interest") ---------------------
 def _roi_int_box(H, W, box, i=0):
     """(l, t, r, b), ints or floats -> the integer box with the same crop amounts: the reference turns a bbox into

@@ -354,6 +354,45 @@ int acrmi_preprocess_nv12(const acrmi_nv12_frame* frames_host, int n, const int3
  * [H,W,3] uint8 images, RGB, or BGR when bgr != 0. */
 int acrmi_nv12_to_rgb(const acrmi_nv12_frame* frames_host, int n, const int32_t* coef6_host, int bgr,
                       uint8_t* const* dst_dev_host, void* stream);
+/* NV12 surfaces as the OUTPUT (DESIGN.md "NV12 output"): drawn frames handed to a video encoder.  All arithmetic is int32, the
+ * shift is arithmetic, results clamp to 0..255.  For a row (cry, cgy, cby, cru, cgu, cbu, crv, cgv, cbv, y_off):
+ *   per pixel:      Y = clamp((cry R + cgy G + cby B + (y_off << 20) + (1 << 19)) >> 20)
+ *   per 2x2 block:  R4, G4, B4 = the sums of the four pixels' R, G, B   (0..1020)
+ *                   U = clamp((cru R4 + cgu G4 + cbu B4 + (128 << 22) + (1 << 21)) >> 22)
+ *                   V = clamp((crv R4 + cgv G4 + cbv B4 + (128 << 22) + (1 << 21)) >> 22)
+ * Chroma is the mean of the block folded into the shift: for four equal pixels it is the per-pixel value, the counterpart of the
+ * input rule's nearest chroma.  The named rows go by ACRMI_NV12_*, so a name selects the input and the output row: the four BT
+ * rows are round(x * 2^20) of the textbook forms; CV601 holds the constants of OpenCV's RGB -> YUV 4:2:0 code as remembered,
+ * NOT verified against its source.  No row is claimed to equal cv2: it writes no NV12, and its I420 path takes chroma from one
+ * pixel of the block.  A row is refused (ACRMI_EINVAL) when y_off is outside 0..255, when
+ * 255 (|cry| + |cgy| + |cby|) + (y_off << 20) + 2^19 >= 2^31, or when
+ * 1020 max(|cru| + |cgu| + |cbu|, |crv| + |cgv| + |cbv|) + (128 << 22) + 2^21 >= 2^31: the int32 sums cannot overflow. */
+int acrmi_nv12_out_matrix(int which, int32_t coef10[10]);   /* host only */
+typedef struct acrmi_nv12_surface {    /* 32 bytes: acrmi_nv12_frame with writable planes */
+  uint8_t* y_dev;                      /* [H, y_pitch]  */
+  uint8_t* uv_dev;                     /* [H/2, uv_pitch], U at even bytes, V at odd */
+  int32_t H, W;                        /* both even, >= 2 */
+  int32_t y_pitch, uv_pitch;           /* bytes per row, >= W; nothing beyond W bytes of a row is written */
+} acrmi_nv12_surface;
+/* The plain conversion: src_dev_host [n] device pointers to tight [H,W,3] uint8 frames (RGB, or BGR when bgr != 0) of the sizes
+ * surfaces_host [n] name -> those surfaces.  coef10_host: ten integers, NULL = CV601.  Everything is checked before anything is
+ * queued (even sizes >= 2, pitches >= W, null pointers, the row); geometry travels in the kernel arguments, 64 frames per launch,
+ * further frames in further launches on the same stream; the host arrays may be freed when the call returns.  A surface must
+ * not overlap its source or another surface: that is the caller's duty. */
+int acrmi_rgb_to_nv12(const uint8_t* const* src_dev_host, const acrmi_nv12_surface* surfaces_host, int n,
+                      const int32_t* coef10_host, int bgr, void* stream);
+/* Compose: the drawn frame drawn_dev_host[i] (tight [H,W,3], RGB or BGR) over the source surface it was drawn from.  A pixel is
+ * CHANGED when its drawn triple differs from what the input rule (coef6_host, NULL = CV601) makes of the source's Y, U, V.
+ *   out Y    = Y(drawn triple) for a changed pixel, else the source byte
+ *   out U, V = U, V(sums of the block's four drawn triples) when any pixel of the block is changed, else the source bytes
+ * so composing the frame acrmi_nv12_to_rgb made of a surface gives that surface back byte for byte, whatever its bytes, and one
+ * drawn pixel changes one Y byte and one U, V pair.  The output surface must have the source's size (ACRMI_EINVAL otherwise).  It
+ * may BE the source surface - the same plane pointers and pitches: a thread reads and writes only its own blocks.  Otherwise the
+ * output planes must overlap neither the source planes, nor the drawn frame, nor each other; guaranteeing that is the caller's
+ * duty, nothing checks it.  58 frames per launch (what fits the 4 KB argument block); otherwise as acrmi_rgb_to_nv12. */
+int acrmi_nv12_compose(const acrmi_nv12_frame* src_frames_host, const uint8_t* const* drawn_dev_host,
+                       const acrmi_nv12_surface* out_surfaces_host, int n, const int32_t* coef6_host, const int32_t* coef10_host,
+                       int bgr, void* stream);
 /* Regions of interest (DESIGN.md "Regions of interest"): the box of a person or hand detector instead of the whole frame, the
  * reference's image_crop_pad with a bbox (acr/utils.py:1287-1301).  A region names a frame of the call and a box in that frame's
  * pixels, r and b exclusive.  The box is clamped to the H x W frame as crop amounts
