@@ -81,7 +81,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_forward_streams', 'acrmi_nv12_matrix', 'acrmi_preprocess_nv12', 'acrmi_nv12_to_rgb',
            'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12', 'acrmi_track_box', 'acrmi_track_boxes',
            'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev', 'acrmi_nv12_out_matrix', 'acrmi_rgb_to_nv12',
-           'acrmi_nv12_compose']
+           'acrmi_nv12_compose', 'acrmi_rasterize_views', 'acrmi_draw_region_heatmaps', 'acrmi_render_regions',
+           'acrmi_overlay_regions']
 
 _lib = None
 
@@ -200,6 +201,12 @@ def lib():
     L.acrmi_draw_heatmaps.argtypes = [f32p, f32p, C.c_longlong, i32, i32, i32, f32p, C.c_float, u8p, i32, u8p, u8p, u8p, i32,
                                       i32, vp]
     L.acrmi_overlay.argtypes = [vp, i32, f32p, f32p, i32, f32p, i32, u8p, u8p, u8p, i32, i32, vp]
+    L.acrmi_rasterize_views.argtypes = list(L.acrmi_rasterize.argtypes)
+    L.acrmi_draw_region_heatmaps.argtypes = [f32p, f32p, C.c_longlong, i32, i32, i32, f32p, vp, C.c_float, u8p, i32, u8p, u8p,
+                                             u8p, i32, i32, i32, vp]
+    L.acrmi_render_regions.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, vp, C.c_float, C.c_float, u8p, u8p, i32, i32, i32,
+                                       vp, vp]
+    L.acrmi_overlay_regions.argtypes = [vp, i32, f32p, f32p, i32, f32p, vp, i32, u8p, u8p, u8p, i32, i32, i32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',

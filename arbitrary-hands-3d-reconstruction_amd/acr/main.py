@@ -338,7 +338,7 @@ class ACR(object):
 
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
-                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr'):
+                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -354,7 +354,9 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     the frame before).  One path per region, results keyed by it, a stream id per region; pj2d_org is in the pixels of the
     ORIGINAL frame.  render=True then needs show_items of 'pj2d' / 'org_img': the skeletons of all regions of a frame are drawn
     over that frame, one drawn frame per source frame.  'mesh' and 'centermap' over regions are a ValueError (the
-    rasteriser's viewport is per frame: DESIGN.md "Regions of interest").
+    rasteriser's viewport is per frame: DESIGN.md "Regions of interest") - unless region_views=True: then every view of
+    SHOW_ITEMS is drawn over the source frames with one view per REGION (Engine.render_regions / overlay_regions, DESIGN.md
+    "Views over regions"), the default view is 'mesh' as without boxes, and 'centermap' is [2,N,H,W,3] over the N frames.
     render_format='nv12' (with render=True): the drawn views come back as NV12 surfaces for a video encoder - a tensor
     [n,H*3/2,W] when all sizes agree, else a list; 'centermap' keeps its leading pair.  With pixel_format='nv12' every view is
     composed onto its source surface (ops.nv12_compose: new bytes only where something was drawn) and 'org_img' is the
@@ -370,9 +372,11 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         if not render:
             raise ValueError("render_format='nv12' needs render=True")
         to_nv12, matrix = _nv12_views(bgr_frames_dev, pixel_format, matrix)
+    if region_views and boxes is None:
+        raise ValueError('region_views=True draws the views of regions: it needs boxes=')
     if boxes is not None:
         got = _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
-                               pixel_format, matrix)
+                               pixel_format, matrix, region_views)
     else:
         if box_frame is not None:
             raise ValueError('box_frame says which frame each box is of: it needs boxes=')
@@ -427,13 +431,49 @@ def _nv12_views(frames, pixel_format, matrix):
     return view, row6
 
 
-def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix):
+def _region_views(self, eng, out, canvas, offsets, box_frame, items):
+    """The views `items` (None: the meshes alone, not in a dict) of the n regions of `out` over their BGR frames `canvas` - a
+    tensor [N,H,W,3], or a list of frames of different sizes, drawn per size and returned in input order; 'centermap' is
+    [2,N,H,W,3], respectively a list of [2,H_i,W_i,3].  offsets: the regions' rows, on the host or on the device."""
+    n = out['slots'].shape[0]
+    frame_of = torch.arange(n) if box_frame is None else torch.as_tensor(np.asarray(box_frame)).long()
+    kw = dict(bgr=True)
+
+    def draw(name, imgs, region_frame):
+        if name == 'mesh':
+            return eng.render_regions(out, imgs, offsets, region_frame, focal_length=float(self.focal_length), **kw)
+        return eng.overlay_regions(out, imgs, name, offsets, region_frame, **kw)
+
+    def one(name):
+        if name == 'org_img':
+            return canvas
+        if not isinstance(canvas, (list, tuple)):
+            return draw(name, canvas, frame_of.to(torch.int32))
+        groups = {}
+        for i, f in enumerate(canvas):
+            groups.setdefault(tuple(f.shape), []).append(i)
+        drawn = [None] * len(canvas)
+        for idx in groups.values():
+            place = torch.full((len(canvas),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
+            place[idx] = torch.arange(len(idx))
+            got = draw(name, torch.stack([canvas[i] for i in idx]), place[frame_of].to(torch.int32))
+            for j, i in enumerate(idx):
+                drawn[i] = got[:, j] if name == 'centermap' else got[j]
+        return drawn
+
+    if items is None:
+        return one('mesh')
+    return {name: one(name) for name in items}
+
+
+def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix,
+                     region_views=False):
     """forward_raw_batch with boxes."""
     from .. import _lib as S
     from .. import ops
     from .utils import img_preprocess_gpu
     items = check_show_items(show_items)
-    if render:
+    if render and not region_views:
         bad = [name for name in (items or ['mesh']) if name not in ('pj2d', 'org_img')]
         if bad:
             raise ValueError('%s over regions is not implemented (the viewport of the rasteriser and of the heat maps is one row '
@@ -446,6 +486,8 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     if not render:
         return results
     canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames
+    if region_views:
+        return results, _region_views(self, eng, out, canvas, meta['offsets'], box_frame, items)
     # hand h of region i goes into frame box_frame[i]; a slot without a detection is not drawn
     frame_of = torch.arange(n) if box_frame is None else torch.as_tensor(box_frame).cpu().long()
     flagged = (out['slots'][:, :, S.SLOT_FLAG] > 0.5).cpu()
@@ -478,14 +520,28 @@ def _draw_over_frames(kps, canvas, hand_frame):
 
 
 def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=None, max_streams=None, pixel_format='bgr',
-                     matrix='cv601', scale=1.5, min_size=64):
+                     matrix='cv601', scale=1.5, min_size=64, render=False, show_items=None, render_format='bgr'):
     """One step of a video loop on regions whose boxes stay on the device (DESIGN.md "Tracking on the device") ->
     (results, next_boxes).  frames, paths, box_frame, streams, pixel_format, matrix: as forward_raw_batch(boxes=); boxes: the
     int32 device tensor [n,4] the call before returned as next_boxes, or None for the first frames of a video: the whole
     frames.  results: the dicts forward_raw_batch(boxes=) gives for those boxes.  next_boxes: the regions of the next frames
     (ops.track_boxes: acr.utils.boxes_from_keypoints on the fp32 key points, scale and min_size as there), int32 on the
-    device.  Packaging the dicts waits for the device, as it always has; the boxes never pass through the host."""
+    device.  Packaging the dicts waits for the device, as it always has; the boxes never pass through the host.
+    render=True: -> (results, next_boxes, views): the regions' views drawn over their source frames from the device `offsets`
+    rows (DESIGN.md "Views over regions") - the frames with the meshes, or with show_items (names from SHOW_ITEMS)
+    {name: frames} as forward_raw_batch(boxes=, region_views=True); a list of frames of different sizes is drawn per size
+    and returned in input order.  render_format='nv12': as forward_raw_batch."""
     from .. import ops
+    items = check_show_items(show_items)
+    if items is not None and not render:
+        raise ValueError('show_items needs render=True')
+    if render_format not in ('bgr', 'nv12'):
+        raise ValueError("render_format: %r is not 'bgr' or 'nv12'" % (render_format,))
+    to_nv12 = None
+    if render_format == 'nv12':
+        if not render:
+            raise ValueError("render_format='nv12' needs render=True")
+        to_nv12, matrix = _nv12_views(frames, pixel_format, matrix)
     scale, min_size = ops.check_track_args(scale, min_size)
     frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)
     if boxes is None:
@@ -496,8 +552,15 @@ def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=No
     n = rgb.shape[0]
     if len(paths) != n:
         raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
-    results, _, out = self._forward_batch_results(rgb, paths, offsets, True, None, streams, max_streams)
-    return results, ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size)
+    results, eng, out = self._forward_batch_results(rgb, paths, offsets, True, None, streams, max_streams)
+    next_boxes = ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size)
+    if not render:
+        return results, next_boxes
+    canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames
+    views = _region_views(self, eng, out, canvas, offsets, box_frame, items)
+    if to_nv12 is not None:
+        views = to_nv12('mesh', views) if items is None else {name: to_nv12(name, view) for name, view in views.items()}
+    return results, next_boxes, views
 
 
 ACR.forward_raw_batch = _forward_raw_batch

@@ -63,6 +63,7 @@ void acrmi_destroy(acrmi_ctx* c) {
   release_weights(c);
   acrmi_streams_destroy(c->own_streams);
   if (c->render_ws) (void)hipFree(c->render_ws);
+  if (c->region_hand_frame) (void)hipFree(c->region_hand_frame);
   for (int32_t* p : c->faces_topo)
     if (p) (void)hipFree(p);
   for (auto& side : c->mano_allocs)
@@ -660,6 +661,27 @@ int acrmi_load_faces(acrmi_ctx* c, int side, const int32_t* faces_host, int n_fa
   return ACRMI_OK;
 }
 
+// The context's render scratch for B frames (or regions) of two hands: [mesh_frame | mesh_topo | rgb | view rows] and the
+// rasteriser's workspace behind them.  The head is sized for one view row per MESH, the larger of the two layouts.  Allocates
+// at the first call and when B grows: the one place the render calls allocate.
+static size_t render_head_bytes(int B, bool per_mesh) {
+  const size_t M = 2 * (size_t)B;
+  return (M * 4 * 2 + M * 3 * 4 + (per_mesh ? M : (size_t)B) * 4 * 4 + 255) / 256 * 256;
+}
+
+static int render_ws_reserve(acrmi_ctx* c, int B) {
+  if (B <= c->render_ws_frames) return ACRMI_OK;
+  if (c->render_ws) {
+    HIPCHK(c, hipDeviceSynchronize());
+    (void)hipFree(c->render_ws);
+    c->render_ws = nullptr;
+    c->render_ws_frames = 0;
+  }
+  HIPCHK(c, hipMalloc(&c->render_ws, render_head_bytes(B, true) + render_workspace_bytes(2 * B, c->n_faces[0])));
+  c->render_ws_frames = B;
+  return ACRMI_OK;
+}
+
 int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
                  const float* colors_host, float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out, int H,
                  int W, int32_t* ids_out, void* stream) {
@@ -671,16 +693,7 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
   const int M = 2 * B, F = c->n_faces[0];
   const size_t head = (size_t)M * 4 * 2 + (size_t)M * 3 * 4 + (size_t)B * 4 * 4;      // mesh_frame, mesh_topo, rgb, view
   const size_t head_al = (head + 255) / 256 * 256;
-  if (B > c->render_ws_frames) {      // (first call / a larger batch: the one place this call allocates)
-    if (c->render_ws) {
-      HIPCHK(c, hipDeviceSynchronize());
-      (void)hipFree(c->render_ws);
-      c->render_ws = nullptr;
-      c->render_ws_frames = 0;
-    }
-    HIPCHK(c, hipMalloc(&c->render_ws, head_al + render_workspace_bytes(M, F)));
-    c->render_ws_frames = B;
-  }
+  if (int r = render_ws_reserve(c, B)) return r;
   int32_t* mesh_frame = (int32_t*)c->render_ws;
   int32_t* mesh_topo = mesh_frame + M;
   float* rgb = (float*)(mesh_topo + M);
@@ -734,6 +747,87 @@ int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d,
     e = launch_heatmap(a, (hipStream_t)stream);
   }
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay: %s", hipGetErrorString(e));
+}
+
+// ---- views over regions (DESIGN.md "Views over regions") ------------------------------------------------------------------
+static const float kHandColors[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};      // acr/visualization.py:76, as RGB
+
+int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int n, const float* offsets,
+                         const int32_t* region_frame, const float* colors_host, float focal, float visible_weight,
+                         const uint8_t* img_in, uint8_t* img_out, int n_frames, int H, int W, int32_t* ids_out, void* stream) {
+  if (!c || !verts || !cam_trans || !slots || !offsets || !region_frame || !img_in || !img_out || n <= 0 || n_frames <= 0 ||
+      n_frames > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM || !(focal > 0.f) ||
+      !(visible_weight >= 0.f && visible_weight <= 1.f) || n > 0x3fffffff || (c->n_faces[0] > 0 && 2ll * n * c->n_faces[0] > 0x7fffffffll))
+    return fail(c, ACRMI_EINVAL, "acrmi_render_regions: bad arguments");
+  if (!c->faces_topo[0] || !c->faces_topo[1])
+    return fail(c, ACRMI_ESTATE, "acrmi_render_regions: MANO faces not loaded (acrmi_load_faces)");
+  ON_DEVICE(c);
+  const int M = 2 * n, F = c->n_faces[0];
+  if (int r = render_ws_reserve(c, n)) return r;
+  int32_t* mesh_frame = (int32_t*)c->render_ws;
+  int32_t* mesh_topo = mesh_frame + M;
+  float* rgb = (float*)(mesh_topo + M);
+  float* mesh_view = rgb + 3 * M;
+  hipError_t e = launch_render_region_prep(slots, offsets, region_frame, n, n_frames, H, W, ACRMI_SLOT, ACRMI_SLOT_FLAG,
+                                           colors_host ? colors_host : kHandColors, mesh_frame, mesh_topo, rgb, mesh_view,
+                                           (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render region prep: %s", hipGetErrorString(e));
+  RenderArgs a{};
+  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
+  a.mesh_topo = mesh_topo; a.mesh_frame = mesh_frame; a.rgb = rgb; a.mesh_view = mesh_view;
+  a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
+  a.ws = c->render_ws + render_head_bytes(n, true);
+  a.n_meshes = M; a.n_verts = 778; a.n_faces = F; a.n_frames = n_frames; a.H = H; a.W = W;
+  e = launch_render(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render regions: %s", hipGetErrorString(e));
+}
+
+int acrmi_overlay_regions(acrmi_ctx* c, int what, const float* slots, const float* pj2d_org, int n, const float* offsets,
+                          const int32_t* region_frame, int bgr, const uint8_t* img_in, uint8_t* out, uint8_t* out2, int n_frames,
+                          int H, int W, void* stream) {
+  if (!c || !offsets || !region_frame || !img_in || !out || n <= 0 || n > 0x3fffffff || n_frames <= 0 ||
+      n_frames > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM ||
+      (what != ACRMI_OVERLAY_SKELETON && what != ACRMI_OVERLAY_CENTERMAP))
+    return fail(c, ACRMI_EINVAL, "acrmi_overlay_regions: bad arguments");
+  if (what == ACRMI_OVERLAY_SKELETON ? (!slots || !pj2d_org) : (!out2 || out2 == out || out2 == img_in))
+    return fail(c, ACRMI_EINVAL, "acrmi_overlay_regions: bad arguments");
+  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "acrmi_overlay_regions: no program has run");
+  ON_DEVICE(c);
+  hipError_t e;
+  if (what == ACRMI_OVERLAY_SKELETON) {
+    if (n > c->region_hand_cap) {      // (first call / more regions: the one place this call allocates)
+      if (c->region_hand_frame) {
+        HIPCHK(c, hipDeviceSynchronize());
+        (void)hipFree(c->region_hand_frame);
+        c->region_hand_frame = nullptr;
+        c->region_hand_cap = 0;
+      }
+      HIPCHK(c, hipMalloc(&c->region_hand_frame, sizeof(int32_t) * 2 * (size_t)n));
+      c->region_hand_cap = n;
+    }
+    e = launch_render_region_prep(slots, offsets, region_frame, n, n_frames, H, W, ACRMI_SLOT, ACRMI_SLOT_FLAG, nullptr,
+                                  c->region_hand_frame, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(c, ACRMI_EHIP, "overlay region prep: %s", hipGetErrorString(e));
+    SkeletonArgs a{};
+    a.kps = pj2d_org; a.hand_frame = c->region_hand_frame; a.n_hands = 2 * n; a.n_frames = n_frames; a.H = H; a.W = W;
+    a.line_width = 3; a.circle_rad = 3; a.img_in = img_in; a.img_out = out;
+    skeleton_default_colors(bgr != 0, a.colors);
+    e = launch_skeleton(a, (hipStream_t)stream);
+  } else {
+    if (n != c->last_batch)
+      return fail(c, ACRMI_ESTATE, "acrmi_overlay_regions: the resident centre maps are those of a batch of %d, not %d",
+                  c->last_batch, n);
+    const acrmi_head_layout& hl = c->heads;
+    const acrmi_buffer_desc& d = c->bufs[hl.center_buf[0]];
+    RegionHeatmapArgs a{};
+    a.maps[0] = c->buf_ptr[hl.center_buf[0]]; a.maps[1] = c->buf_ptr[hl.center_buf[1]];
+    a.pix_stride = d.cs; a.frame_stride = (long long)d.h * d.w * d.cs; a.dtype = d.dtype;
+    a.n = n; a.h = d.h; a.w = d.w; a.n_frames = n_frames; a.H = H; a.W = W; a.offsets = offsets; a.region_frame = region_frame;
+    a.weight = 0.7f; a.img_in = img_in; a.out[0] = out; a.out[1] = out2;
+    heatmap_default_lut(bgr != 0, a.lut);
+    e = launch_region_heatmap(a, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay regions: %s", hipGetErrorString(e));
 }
 
 // Plain HIP streams for hosts that have no stream API of their own at hand (Python: torch.cuda.Stream() instantiates

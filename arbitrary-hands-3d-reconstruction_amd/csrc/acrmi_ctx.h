@@ -103,6 +103,8 @@ struct acrmi_ctx {
   int n_faces[2] = {0, 0};
   char* render_ws = nullptr;
   int render_ws_frames = 0;
+  int32_t* region_hand_frame = nullptr;   // acrmi_overlay_regions: the frame of each hand, derived on the device
+  int region_hand_cap = 0;                // regions it holds
   int last_batch = 0;          // batch of the last program run: whose centre maps the head buffers hold (acrmi_overlay)
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;

@@ -626,23 +626,45 @@ size_t acrmi_render_workspace(int n_meshes, int n_faces) {
   return n_meshes > 0 && n_faces > 0 ? render_workspace_bytes(n_meshes, n_faces) : 0;
 }
 
+static int rasterize(const char* who, bool per_mesh, const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts,
+                     int n_faces, const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                     const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
+                     float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                     int32_t* ids_out_dev, void* ws_dev, void* stream) {
+  if ((per_mesh && !view_dev) ||
+      !verts_dev || !topo_dev || !mesh_frame_dev || !rgb_dev || !img_in_dev || !img_out_dev || !ws_dev || n_meshes <= 0 ||
+      n_verts <= 0 || n_verts > RENDER_MAX_VERTS || n_faces <= 0 || n_frames <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384 ||
+      (long long)n_meshes * n_faces > 0x7fffffffll || n_frames > 65535 || !(focal > 0.f) ||
+      !(visible_weight >= 0.f && visible_weight <= 1.f))
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad arguments", who);
+  RenderArgs a{};
+  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
+  a.mesh_frame = mesh_frame_dev; a.rgb = rgb_dev; a.view = per_mesh ? nullptr : view_dev; a.mesh_view = per_mesh ? view_dev : nullptr;
+  a.focal = focal; a.visible_weight = visible_weight;
+  a.img_in = img_in_dev; a.img_out = img_out_dev; a.ids_out = ids_out_dev; a.ws = (char*)ws_dev;
+  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_frames = n_frames; a.H = H; a.W = W;
+  hipError_t e = launch_render(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "rasterize: %s", hipGetErrorString(e));
+}
+
 int acrmi_rasterize(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
                     const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
                     const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
                     float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
                     int32_t* ids_out_dev, void* ws_dev, void* stream) {
-  if (!verts_dev || !topo_dev || !mesh_frame_dev || !rgb_dev || !img_in_dev || !img_out_dev || !ws_dev || n_meshes <= 0 ||
-      n_verts <= 0 || n_verts > RENDER_MAX_VERTS || n_faces <= 0 || n_frames <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384 ||
-      (long long)n_meshes * n_faces > 0x7fffffffll || n_frames > 65535 || !(focal > 0.f) ||
-      !(visible_weight >= 0.f && visible_weight <= 1.f))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_rasterize: bad arguments");
-  RenderArgs a{};
-  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
-  a.mesh_frame = mesh_frame_dev; a.rgb = rgb_dev; a.view = view_dev; a.focal = focal; a.visible_weight = visible_weight;
-  a.img_in = img_in_dev; a.img_out = img_out_dev; a.ids_out = ids_out_dev; a.ws = (char*)ws_dev;
-  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_frames = n_frames; a.H = H; a.W = W;
-  hipError_t e = launch_render(a, (hipStream_t)stream);
-  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "rasterize: %s", hipGetErrorString(e));
+  return rasterize("acrmi_rasterize", false, verts_dev, trans_dev, n_meshes, n_verts, n_faces, topo_dev, topo2_dev, mesh_topo_dev,
+                   mesh_frame_dev, rgb_dev, view_dev, focal, visible_weight, img_in_dev, img_out_dev, n_frames, H, W, ids_out_dev,
+                   ws_dev, stream);
+}
+
+int acrmi_rasterize_views(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                          const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                          const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
+                          float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                          int32_t* ids_out_dev, void* ws_dev, void* stream) {
+  return rasterize("acrmi_rasterize_views", true, verts_dev, trans_dev, n_meshes, n_verts, n_faces, topo_dev, topo2_dev,
+                   mesh_topo_dev, mesh_frame_dev, rgb_dev, view_dev, focal, visible_weight, img_in_dev, img_out_dev, n_frames, H, W,
+                   ids_out_dev, ws_dev, stream);
 }
 
 // ---- key-point skeleton and heat-map views (csrc/overlay.hip) ----
@@ -687,6 +709,25 @@ int acrmi_draw_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long l
   else heatmap_default_lut(bgr != 0, a.lut);
   hipError_t e = launch_heatmap(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_heatmaps: %s", hipGetErrorString(e));
+}
+
+int acrmi_draw_region_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long long frame_stride, int n, int h, int w,
+                               const float* offsets_dev, const int32_t* region_frame_dev, float weight,
+                               const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev, uint8_t* out_l_dev,
+                               uint8_t* out_r_dev, int n_frames, int H, int W, void* stream) {
+  if (!maps_l_dev || !offsets_dev || !region_frame_dev || !img_in_dev || !out_l_dev ||
+      (maps_r_dev != nullptr) != (out_r_dev != nullptr) || out_l_dev == out_r_dev || (out_r_dev && out_r_dev == img_in_dev) ||
+      n <= 0 || !overlay_image_ok(n_frames, H, W) || h <= 0 || w <= 0 || h > OVERLAY_MAX_DIM || w > OVERLAY_MAX_DIM ||
+      frame_stride < (long long)h * w || !(weight >= 0.f && weight <= 1.f))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_draw_region_heatmaps: bad arguments");
+  RegionHeatmapArgs a{};
+  a.maps[0] = maps_l_dev; a.maps[1] = maps_r_dev; a.frame_stride = frame_stride; a.pix_stride = 1; a.dtype = ACRMI_DT_F32;
+  a.n = n; a.h = h; a.w = w; a.n_frames = n_frames; a.H = H; a.W = W; a.offsets = offsets_dev; a.region_frame = region_frame_dev;
+  a.weight = weight; a.img_in = img_in_dev; a.out[0] = out_l_dev; a.out[1] = out_r_dev;
+  if (lut_host) std::memcpy(a.lut, lut_host, 768);
+  else heatmap_default_lut(bgr != 0, a.lut);
+  hipError_t e = launch_region_heatmap(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_region_heatmaps: %s", hipGetErrorString(e));
 }
 
 }  // extern "C"

@@ -413,6 +413,8 @@ struct RenderArgs {
   const int32_t* mesh_frame;     // [M] frame the mesh is drawn into, < 0 = not drawn
   const float* rgb;              // [M, 3] base colour, channel order of the image
   const float* view;             // [N, 4] scale x, scale y, shift x, shift y of the 512 canvas, or null (identity)
+  const float* mesh_view;        // [M, 4] the same per MESH (views over regions), exclusive with `view`: the depth value is then
+                                 // sx / Z, one virtual camera per frame (csrc/region_view_plan.h)
   float focal, visible_weight;
   const uint8_t* img_in;         // [N, H, W, 3]
   uint8_t* img_out;              // may be img_in
@@ -428,6 +430,11 @@ size_t render_workspace_bytes(int n_meshes, int n_faces);
 hipError_t launch_render(const RenderArgs& a, hipStream_t s);
 hipError_t launch_render_prep(const float* slots, const float* offsets, int B, int slot_stride, int flag_at, const float* colors,
                               int32_t* mesh_frame, int32_t* mesh_topo, float* rgb, float* view, hipStream_t s);
+// views over regions: slots [n,2,slot_stride], offsets [n,10] and region_frame [n] on the device -> mesh_frame [2n] (-1: not
+// drawn), and where not null mesh_topo [2n], rgb [2n,3], mesh_view [2n,4]; colors may be null when rgb is
+hipError_t launch_render_region_prep(const float* slots, const float* offsets, const int32_t* region_frame, int n, int n_frames,
+                                     int H, int W, int slot_stride, int flag_at, const float* colors, int32_t* mesh_frame,
+                                     int32_t* mesh_topo, float* rgb, float* mesh_view, hipStream_t s);
 
 // Key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views").
 struct SkeletonArgs {
@@ -461,5 +468,22 @@ void skeleton_default_colors(bool bgr, uint8_t* out63);
 void heatmap_default_lut(bool bgr, uint8_t* out768);
 hipError_t launch_skeleton(const SkeletonArgs& a, hipStream_t s);
 hipError_t launch_heatmap(const HeatmapArgs& a, hipStream_t s);
+// Heat maps of REGIONS composed over their frames (DESIGN.md "Views over regions"): region i's maps tint the pixels of its
+// window in frame region_frame[i]; where windows overlap the larger colour index wins.
+struct RegionHeatmapArgs {
+  const void* maps[2];           // as HeatmapArgs, one pair per region
+  long long frame_stride;
+  int pix_stride, dtype;
+  int n, h, w;                   // regions, map size
+  int n_frames, H, W;
+  const float* offsets;          // [n, 10]
+  const int32_t* region_frame;   // [n]
+  float weight;
+  const uint8_t* img_in;         // [n_frames, H, W, 3]
+  uint8_t* out[2];
+  int wide;                      // (launch_region_heatmap fills this)
+  uint8_t lut[768];
+};
+hipError_t launch_region_heatmap(const RegionHeatmapArgs& a, hipStream_t s);
 
 }  // namespace acrmi

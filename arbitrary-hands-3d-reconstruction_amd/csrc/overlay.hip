@@ -11,10 +11,16 @@
 //                     is staged in LDS - 16-bit maps of a 16-bit storage program are converted to fp32 there - and every
 //                     thread samples, colours and blends its pixels in fp32, each operation rounded on its own.  One read
 //                     of the image, two writes.
+//   region_heatmap_kernel  the same tiling, for regions of interest (DESIGN.md "Views over regions"): the regions of the
+//                     frame whose window meets the tile are found in region order (the skeleton's compaction), one after the
+//                     other the part of their two maps the tile's share of the window samples is staged, and every thread
+//                     keeps the LARGEST colour index of each of its pixels per side in registers; after the last region
+//                     the image is read once, blended once and written to both outputs.
 // Pixels move as 4 pixels = 3 dwords per thread and row when the row length is a multiple of 4 and the buffers are dword
 // aligned, byte by byte otherwise.  A thread reads and writes only its own pixels, so drawing in place is safe; there are
 // no atomics on global memory, so the result is deterministic.
 #include "kernels.h"
+#include "region_view_plan.h"
 
 #include <hip/hip_fp16.h>
 
@@ -273,8 +279,9 @@ __global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
   if (a.view) {
     sx = a.view[f * 4]; sy = a.view[f * 4 + 1]; ox = a.view[f * 4 + 2]; oy = a.view[f * 4 + 3];
   } else if (a.offsets) {      // as ops.view_from_offsets / render_prep_kernel
-    const float* of = a.offsets + (size_t)f * 10;
-    sx = of[0] / 512.f; sy = of[1] / 512.f; ox = of[5] - of[9]; oy = of[2] - of[6];
+    float row[4];
+    region_view_row(a.offsets + (size_t)f * 10, row);
+    sx = row[0]; sy = row[1]; ox = row[2]; oy = row[3];
   }
   const float kx = 512.f / (float)a.W, ky = 512.f / (float)a.H;
   const float mx = (float)a.w / 512.f, my = (float)a.h / 512.f;
@@ -355,6 +362,146 @@ __global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
   }
 }
 
+// ---- heat maps of regions -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void region_heatmap_kernel(RegionHeatmapArgs a) {
+  __shared__ float s_map[2][MAP_CAP];
+  __shared__ uint32_t s_lut[768];
+  __shared__ int s_list[256];
+  __shared__ int s_cnt[4];
+  const int tid = threadIdx.x, f = blockIdx.z;
+  const int X0 = blockIdx.x * TW, Y0 = blockIdx.y * TH;
+  const int X1 = min(X0 + TW, a.W), Y1 = min(Y0 + TH, a.H);      // exclusive
+  const int xt = X0 + PX * (tid & 31), yt = Y0 + (tid >> 5);
+  const int views = a.maps[1] ? 2 : 1;
+  for (int t = tid; t < 768; t += 256) s_lut[t] = a.lut[t];
+  const float mx = (float)a.w / 512.f, my = (float)a.h / 512.f;
+  int best[2][ROWS][PX];      // the largest colour index of a covering region, -1: no region covers the pixel
+#pragma unroll
+  for (int v = 0; v < 2; ++v)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int j = 0; j < PX; ++j) best[v][r][j] = -1;
+
+  for (int base = 0; base < a.n; base += 256) {
+    // the regions of this frame that draw and whose window meets the tile, in region order
+    const int reg = base + tid;
+    bool mine = false;
+    if (reg < a.n && a.region_frame[reg] == f) {
+      const RegionView rv = region_view(a.offsets + (size_t)reg * 10, f, a.n_frames, a.H, a.W);
+      mine = rv.draws && rv.x0 < X1 && rv.x1 > X0 && rv.y0 < Y1 && rv.y1 > Y0;
+    }
+    const unsigned long long mask = __ballot(mine);
+    const int wave = tid >> 6;
+    if ((tid & 63) == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int off = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_cnt[w];
+      off += w < wave ? c : 0;
+      total += c;
+    }
+    if (mine) s_list[off + lane_rank(mask)] = reg;
+    __syncthreads();
+    for (int k = 0; k < total; ++k) {      // (everything up to the per-pixel part is the same for every thread)
+      const int i = __builtin_amdgcn_readfirstlane(s_list[k]);
+      const RegionView rv = region_view(a.offsets + (size_t)i * 10, f, a.n_frames, a.H, a.W);
+      // the tile's share of the window: not empty, and inside the frame (region_view_plan.h)
+      const int wx0 = max(X0, rv.x0), wx1 = min(X1, rv.x1), wy0 = max(Y0, rv.y0), wy1 = min(Y1, rv.y1);
+      auto canvas_x = [&](int x) { return ((float)x + 0.5f - rv.ox) / rv.sx; };
+      auto canvas_y = [&](int y) { return ((float)y + 0.5f - rv.oy) / rv.sy; };
+      // what it samples: as heatmap_kernel, the taps of its first and last pixel bound those of every pixel between them
+      const float cx_a = canvas_x(wx0), cx_b = canvas_x(wx1 - 1), cy_a = canvas_y(wy0), cy_b = canvas_y(wy1 - 1);
+      const bool tile_ok = cx_b >= 0.f && cx_a < 512.f && cy_b >= 0.f && cy_a < 512.f;      // (false for NaN)
+      const size_t fb = (size_t)i * a.frame_stride;
+      int ix_lo = 0, iy_lo = 0, fw = 0, fh = 0;
+      bool staged = false;
+      if (tile_ok) {
+        ix_lo = map_tap(fminf(fmaxf(cx_a, 0.f), 512.f), mx, a.w).i0;
+        iy_lo = map_tap(fminf(fmaxf(cy_a, 0.f), 512.f), my, a.h).i0;
+        fw = map_tap(fminf(fmaxf(cx_b, 0.f), 512.f), mx, a.w).i1 - ix_lo + 1;
+        fh = map_tap(fminf(fmaxf(cy_b, 0.f), 512.f), my, a.h).i1 - iy_lo + 1;
+        staged = fw * fh <= MAP_CAP;
+        if (staged) {
+          for (int v = 0; v < views; ++v)
+            for (int t = tid; t < fw * fh; t += 256) {
+              const int r = t / fw, c = t - r * fw;
+              s_map[v][t] = map_load(a.maps[v], a.dtype, fb + ((size_t)(iy_lo + r) * a.w + ix_lo + c) * a.pix_stride);
+            }
+        }
+      }
+      __syncthreads();
+      if (tile_ok) {
+#pragma unroll
+        for (int rr = 0; rr < ROWS; ++rr) {
+          const int y = yt + ROW_STEP * rr;
+          if (y < wy0 || y >= wy1) continue;
+          const float cy = canvas_y(y);
+          if (!(cy >= 0.f && cy < 512.f)) continue;
+          const Tap ty = map_tap(cy, my, a.h);
+#pragma unroll
+          for (int j = 0; j < PX; ++j) {
+            const int x = xt + j;
+            if (x < wx0 || x >= wx1) continue;
+            const float cx = canvas_x(x);
+            if (!(cx >= 0.f && cx < 512.f)) continue;
+            const Tap tx = map_tap(cx, mx, a.w);
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+              if (v >= views) continue;
+              float p00, p01, p10, p11;
+              if (staged) {
+                const float* m = s_map[v];
+                const int r0 = (ty.i0 - iy_lo) * fw - ix_lo, r1 = (ty.i1 - iy_lo) * fw - ix_lo;
+                p00 = m[r0 + tx.i0]; p01 = m[r0 + tx.i1]; p10 = m[r1 + tx.i0]; p11 = m[r1 + tx.i1];
+              } else {
+                const size_t r0 = (size_t)ty.i0 * a.w, r1 = (size_t)ty.i1 * a.w;
+                p00 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i0) * a.pix_stride);
+                p01 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i1) * a.pix_stride);
+                p10 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i0) * a.pix_stride);
+                p11 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i1) * a.pix_stride);
+              }
+              const float val = ty.l0 * (tx.l0 * p00 + tx.l1 * p01) + ty.l1 * (tx.l0 * p10 + tx.l1 * p11);
+              const int idx = (int)fminf(fmaxf(val * 255.f, 0.f), 255.f);      // truncates, as .byte() does; NaN -> 0
+              best[v][rr][j] = max(best[v][rr][j], idx);
+            }
+          }
+        }
+      }
+      __syncthreads();      // s_map (and, after the last region, s_list) is rewritten
+    }
+  }
+
+  if (xt >= a.W) return;
+  const int n = min(PX, a.W - xt);
+  const float wgt = a.weight, iw = 1.f - a.weight;
+#pragma unroll
+  for (int rr = 0; rr < ROWS; ++rr) {
+    const int y = yt + ROW_STEP * rr;
+    if (y >= a.H) continue;
+    const size_t at = (((size_t)f * a.H + y) * a.W + xt) * 3;
+    uint32_t d[3], o[2][3];
+    load_px(a.img_in + at, a.wide, n, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[0][k] = o[1][k] = d[k];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        const int idx = best[v][rr][j];
+        if (idx < 0) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float img = (float)get_byte(d, 3 * j + c);
+          set_byte(o[v], 3 * j + c, (uint32_t)floorf(wgt * (float)s_lut[idx * 3 + c] + iw * img));
+        }
+      }
+    store_px(a.out[0] + at, a.wide, n, o[0]);
+    if (views == 2) store_px(a.out[1] + at, a.wide, n, o[1]);
+  }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------
 // get_keypoint_rgb (acr/visualization.py:331-381) over mano/skeleton.txt, in skeleton order, RGB: finger tips and the wrist
 // fall through to the last branch
@@ -392,6 +539,13 @@ hipError_t launch_heatmap(const HeatmapArgs& a0, hipStream_t s) {
   HeatmapArgs a = a0;
   a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
   hipLaunchKernelGGL(heatmap_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_region_heatmap(const RegionHeatmapArgs& a0, hipStream_t s) {
+  RegionHeatmapArgs a = a0;
+  a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
+  hipLaunchKernelGGL(region_heatmap_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n_frames), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // frame with pyrender / pytorch3d (acr/visualization.py:108-218, acr/renderer/*); nothing of those is used here, only
 // their conventions: the pinhole camera at cam_trans, visible_weight, the base colours.
 //
-//   render_setup_kernel  one block per mesh: project + snap the vertices to 1/256 pixel, vertex normals through the
+//   render_setup_kernel  one block per mesh: project + snap the vertices to 1/256 pixel (through the frame's viewport, or the
+//                        mesh's own: DESIGN.md "Views over regions"), vertex normals through the
 //                        vertex->faces table (fixed summation order), one record per triangle (integer edge functions with
 //                        the top-left rule folded into the constant, 1/Z and shade/Z at the vertices), its pixel box, and
 //                        the mesh's pixel box.
@@ -12,6 +13,7 @@
 //                        larger wins, strict > so the lower global face id wins a tie), shade, blend, store.
 // The depth buffer is a register per pixel; there are no atomics on global memory, so the result is deterministic.
 #include "kernels.h"
+#include "region_view_plan.h"
 
 #include <cstring>
 #include <vector>
@@ -64,7 +66,7 @@ __device__ inline int block_compact(bool pred, int (*cnt)[4], int& phase, int& t
 }  // namespace
 
 // ---- setup ------------------------------------------------------------------------------------------------------------
-// LDS per vertex: snapped x, y (int), 1/Z (<= 0: the vertex cannot be drawn), shade.
+// LDS per vertex: snapped x, y (int), the depth value 1/Z (sx/Z with a per-mesh view; not > 0: the vertex cannot be drawn), shade.
 __global__ __launch_bounds__(256) void render_setup_kernel(RenderArgs a) {
   extern __shared__ int s_dyn[];
   int* sx = s_dyn;
@@ -87,7 +89,15 @@ __global__ __launch_bounds__(256) void render_setup_kernel(RenderArgs a) {
   float tx = 0.f, ty = 0.f, tz = 0.f;
   if (a.trans) { tx = a.trans[m * 3]; ty = a.trans[m * 3 + 1]; tz = a.trans[m * 3 + 2]; }
   float vsx = 1.f, vsy = 1.f, vox = 0.f, voy = 0.f;
-  if (a.view) { vsx = a.view[frame * 4]; vsy = a.view[frame * 4 + 1]; vox = a.view[frame * 4 + 2]; voy = a.view[frame * 4 + 3]; }
+  // the viewport of the mesh's frame, or - views over regions - the mesh's own; with its own the depths of two cameras of
+  // different scale are compared, so they are put into one virtual camera of the frame: sx / Z instead of 1 / Z
+  float depth_num = 1.f;
+  if (a.mesh_view) {
+    vsx = a.mesh_view[m * 4]; vsy = a.mesh_view[m * 4 + 1]; vox = a.mesh_view[m * 4 + 2]; voy = a.mesh_view[m * 4 + 3];
+    depth_num = vsx;
+  } else if (a.view) {
+    vsx = a.view[frame * 4]; vsy = a.view[frame * 4 + 1]; vox = a.view[frame * 4 + 2]; voy = a.view[frame * 4 + 3];
+  }
   if (tid < 4) s_box[tid] = (tid & 1) ? -32768 : 32767;      // x0, x1, y0, y1
   for (int v = tid; v < a.n_verts; v += 256) {
     const float X = V[v * 3] + tx, Y = V[v * 3 + 1] + ty, Z = V[v * 3 + 2] + tz;
@@ -98,7 +108,7 @@ __global__ __launch_bounds__(256) void render_setup_kernel(RenderArgs a) {
     const bool ok = Z > Z_NEAR && fabsf(xs) <= SNAP_MAX && fabsf(ys) <= SNAP_MAX;      // (false for NaN)
     sx[v] = ok ? (int)rintf(xs) : 0;
     sy[v] = ok ? (int)rintf(ys) : 0;
-    siz[v] = ok ? 1.f / Z : -1.f;
+    siz[v] = ok ? depth_num / Z : -1.f;      // (not > 0, NaN included: the vertex is not drawn)
     // vertex normal: sum of the un-normalised face normals, in the table's order
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int e = row[v]; e < row[v + 1]; ++e) {
@@ -323,11 +333,38 @@ __global__ void render_prep_kernel(const float* __restrict__ slots, const float*
   rgb[m * 3] = h ? r1 : r0; rgb[m * 3 + 1] = h ? g1 : g0; rgb[m * 3 + 2] = h ? b1 : b0;
   if (h == 0 && view) {
     const float* of = offsets + (size_t)b * 10;
-    view[b * 4] = of[0] / 512.f;
-    view[b * 4 + 1] = of[1] / 512.f;
-    view[b * 4 + 2] = of[5] - of[9];
-    view[b * 4 + 3] = of[2] - of[6];
+    region_view_row(of, view + b * 4);
   }
+}
+
+// acrmi_render_regions / acrmi_overlay_regions: mesh (hand) 2 i + h belongs to region i; it goes into the region's frame
+// when its flag is set and the region draws (csrc/region_view_plan.h), and is mapped by its region's view.  mesh_topo, rgb
+// and mesh_view may be null (the skeleton needs the frames only).
+__global__ void render_region_prep_kernel(const float* __restrict__ slots, const float* __restrict__ offsets,
+                                          const int32_t* __restrict__ region_frame, int n, int n_frames, int H, int W,
+                                          int slot_stride, int flag_at, float r0, float g0, float b0, float r1, float g1,
+                                          float b1, int32_t* __restrict__ mesh_frame, int32_t* __restrict__ mesh_topo,
+                                          float* __restrict__ rgb, float* __restrict__ mesh_view) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= 2 * n) return;
+  const int i = m >> 1, h = m & 1;
+  const int frame = region_frame[i];
+  const RegionView rv = region_view(offsets + (size_t)i * 10, frame, n_frames, H, W);
+  mesh_frame[m] = (rv.draws && slots[(size_t)m * slot_stride + flag_at] > 0.5f) ? frame : -1;
+  if (mesh_topo) mesh_topo[m] = h;
+  if (rgb) { rgb[m * 3] = h ? r1 : r0; rgb[m * 3 + 1] = h ? g1 : g0; rgb[m * 3 + 2] = h ? b1 : b0; }
+  if (mesh_view) { mesh_view[m * 4] = rv.sx; mesh_view[m * 4 + 1] = rv.sy; mesh_view[m * 4 + 2] = rv.ox; mesh_view[m * 4 + 3] = rv.oy; }
+}
+
+hipError_t launch_render_region_prep(const float* slots, const float* offsets, const int32_t* region_frame, int n, int n_frames,
+                                     int H, int W, int slot_stride, int flag_at, const float* colors, int32_t* mesh_frame,
+                                     int32_t* mesh_topo, float* rgb, float* mesh_view, hipStream_t s) {
+  static const float kNone[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const float* c = colors ? colors : kNone;
+  hipLaunchKernelGGL(render_region_prep_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, s, slots, offsets, region_frame, n,
+                     n_frames, H, W, slot_stride, flag_at, c[0], c[1], c[2], c[3], c[4], c[5], mesh_frame, mesh_topo, rgb,
+                     mesh_view);
+  return hipGetLastError();
 }
 
 hipError_t launch_render_prep(const float* slots, const float* offsets, int B, int slot_stride, int flag_at, const float* colors,

@@ -676,6 +676,95 @@ class Engine(object):
         self._overlay_keep = (slots, kps, offsets, src)      # referenced until the next call has been queued
         return dst
 
+    def _regions(self, images, offsets, region_frame, n):
+        """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->
+        (src, offsets, region_frame) on the device."""
+        from . import ops
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError('frames must be uint8 [N,H,W,3] on the device')
+        _, o, rf = ops.check_regions(offsets, region_frame, n)
+        return images.contiguous(), o.to(self.device, torch.float32).contiguous(), rf.to(self.device, torch.int32).contiguous()
+
+    def render_regions(self, out, frames, offsets, region_frame, cam_trans=None, focal_length=1265., visible_weight=0.9,
+                       colors=None, bgr=False, dst=None, return_ids=False, stream=None):
+        """`render` for the results of a forward on n REGIONS of interest (acrmi_render_regions; DESIGN.md "Views over
+        regions"): the hands of region i are drawn into frame region_frame[i] of `frames` (uint8 [N,H,W,3] on the device),
+        mapped by the view of ITS `offsets` row; all hands of all regions of a frame go through one depth-tested pass.
+        offsets [n,10] and region_frame [n] may be device tensors (out['offsets'] of track_step is one): the kernels read
+        them, nothing here waits for the device.  A region whose window has no pixel, whose scale is not > 0 or whose
+        frame index is outside [0, N) draws nothing.  The other arguments as `render`; ids = (2 * region + hand) * F + face."""
+        dev = self.device
+        n = out['slots'].shape[0]
+        if tuple(out['verts'].shape) != (n, 2, 778, 3) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
+            raise ValueError('out does not hold the results of %d regions' % n)
+        src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
+        N, H, W, _ = src.shape
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        if cam_trans is None:
+            if out.get('cam_trans') is not None:
+                cam_trans = out['cam_trans']
+            else:
+                if out.get('pj2d') is None:
+                    raise ValueError('cam_trans is needed (or out from forward(..., project=True))')
+                cam_trans = torch.empty(n, 2, 3, dtype=torch.float32, device=dev)
+                _lib.check(self.L.acrmi_cam_trans(_ptr(out['joints']), _ptr(out['pj2d']), 2 * n, float(focal_length), 512.0,
+                                                  _ptr(cam_trans), st))
+        cam_trans = cam_trans.to(dev, torch.float32).contiguous()
+        col = None
+        if colors is not None or bgr:
+            c = np.asarray(colors if colors is not None else [list(reversed(x)) for x in HAND_COLORS_RGB], np.float32)
+            if c.shape != (2, 3):
+                raise ValueError('colors must be [2,3] (left, right)')
+            col = np.ascontiguousarray(c)
+        if dst is None:
+            dst = torch.empty_like(src)
+        elif dst.dtype != torch.uint8 or tuple(dst.shape) != (N, H, W, 3) or not dst.is_contiguous() or dst.device != src.device:
+            raise ValueError('dst must be a contiguous uint8 tensor shaped like frames, on their device')
+        ids = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_ids else None
+        verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
+        _lib.check(self.L.acrmi_render_regions(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), n, _ptr(offsets),
+                                               _ptr(region_frame), None if col is None else col.ctypes.data_as(C.c_void_p),
+                                               float(focal_length), float(visible_weight), _ptr(src), _ptr(dst), N, H, W,
+                                               _ptr(ids), st), self.ctx)
+        self._render_keep = (verts, slots, cam_trans, offsets, region_frame, src)      # referenced until the next call has been queued
+        return (dst, ids) if return_ids else dst
+
+    def overlay_regions(self, out, frames, what, offsets, region_frame, bgr=False, dst=None, stream=None):
+        """`overlay` for the results of a forward on n REGIONS (acrmi_overlay_regions; DESIGN.md "Views over regions").
+        what = 'pj2d': the skeletons of every flagged hand at out['pj2d_org'], hand h of region i into frame region_frame[i]
+        -> uint8 [N,H,W,3].  what = 'centermap': the centre maps of the LAST program run of this context (the forward on
+        these n regions), region i tinting the pixels of its window; where windows overlap the larger colour index wins ->
+        uint8 [2,N,H,W,3].  offsets, region_frame: as `render_regions`; the other arguments as `overlay`."""
+        dev = self.device
+        if what not in ('pj2d', 'centermap'):
+            raise ValueError("what: 'pj2d' or 'centermap'")
+        n = out['slots'].shape[0]
+        src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
+        N, H, W, _ = src.shape
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        shape = (N, H, W, 3) if what == 'pj2d' else (2, N, H, W, 3)
+        if dst is None:
+            dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
+        elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != src.device:
+            raise ValueError('dst must be a contiguous uint8 tensor %s on the frames\' device' % (shape,))
+        slots = kps = None
+        if what == 'pj2d':
+            kps = out.get('pj2d_org')
+            if kps is None:
+                raise ValueError('out holds no pj2d_org (forward(..., project=True, offsets=offsets))')
+            if tuple(kps.shape) != (n, 2, 21, 2) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
+                raise ValueError('out does not hold the results of %d regions' % n)
+            kps, slots = kps.contiguous(), out['slots'].contiguous()
+            _lib.check(self.L.acrmi_overlay_regions(self.ctx, _lib.OVERLAY_SKELETON, _ptr(slots), _ptr(kps), n, _ptr(offsets),
+                                                    _ptr(region_frame), int(bool(bgr)), _ptr(src), _ptr(dst), None, N, H, W,
+                                                    st), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_overlay_regions(self.ctx, _lib.OVERLAY_CENTERMAP, None, None, n, _ptr(offsets),
+                                                    _ptr(region_frame), int(bool(bgr)), _ptr(src), _ptr(dst[0]), _ptr(dst[1]),
+                                                    N, H, W, st), self.ctx)
+        self._overlay_keep = (slots, kps, offsets, region_frame, src)      # referenced until the next call has been queued
+        return dst
+
     def profile_ops(self, img):
         img = self._check_img(img)
         B = img.shape[0]
@@ -865,6 +954,33 @@ class EnginePool(object):
         ticket['event'] = done
         ticket.setdefault('overlay', []).append((res, images, offsets, self.engines[i]._overlay_keep))
         return res
+
+    def _on_ticket(self, ticket, name, key, keep, frames, offsets, region_frame, args, kw):
+        """render_regions / overlay_regions of the ticket's batch on the ticket's stream, behind its forward."""
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('%s() belongs between submit() and collect() of its ticket' % name)
+        # (host-side conversions run on the caller's stream: they must be queued before `ready` is recorded)
+        frames, offsets, region_frame = self.engines[i]._regions(frames, offsets, region_frame, ticket['out']['slots'].shape[0])
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        self.streams[i].wait_event(ready)
+        res = getattr(self.engines[i], name)(ticket['out'], frames, *args, offsets, region_frame, stream=self._raw[i].value, **kw)
+        done = torch.cuda.Event()
+        done.record(self.streams[i])
+        # as in submit: everything the drawing touches stays referenced by the ticket until its event has completed
+        ticket['event'] = done
+        ticket.setdefault(key, []).append((res, frames, offsets, region_frame, getattr(self.engines[i], keep)))
+        return res
+
+    def render_regions(self, ticket, frames, offsets, region_frame, **kw):
+        """Engine.render_regions of the ticket's batch (a forward on regions) on the ticket's stream, like render()."""
+        return self._on_ticket(ticket, 'render_regions', 'render_regions', '_render_keep', frames, offsets, region_frame, (), kw)
+
+    def overlay_regions(self, ticket, frames, what, offsets, region_frame, **kw):
+        """Engine.overlay_regions of the ticket's batch on the ticket's stream, like overlay()."""
+        return self._on_ticket(ticket, 'overlay_regions', 'overlay_regions', '_overlay_keep', frames, offsets, region_frame,
+                               (what,), kw)
 
     def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
         """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

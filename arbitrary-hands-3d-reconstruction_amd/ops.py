@@ -813,7 +813,8 @@ def mesh_topology(faces, n_verts):
 
 def view_from_offsets(offsets):
     """`offsets` rows [N,10] (ops.preprocess / acr.utils.img_preprocess) -> the viewport rows [N,4] render_meshes takes:
-    the 512 canvas mapped into the original frame exactly like pj2d -> pj2d_org (x_org = x_512 * padded_w / 512 + left)."""
+    the 512 canvas mapped into the original frame exactly like pj2d -> pj2d_org (x_org = x_512 * padded_w / 512 + left).
+    The rule is stated once, in csrc/region_view_plan.h (region_view_row)."""
     o = torch.as_tensor(offsets, dtype=torch.float32)
     return torch.stack([o[:, 0] / 512., o[:, 1] / 512., o[:, 5] - o[:, 9], o[:, 2] - o[:, 6]], 1)
 
@@ -829,7 +830,7 @@ def _topology_on(t, n_verts, device):
 
 
 def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None, view=None, focal_length=1265.,
-                  visible_weight=0.9, out=None, return_ids=False, topo_index=None):
+                  visible_weight=0.9, out=None, return_ids=False, topo_index=None, mesh_view=None):
     """Draws M meshes over N equal-sized frames on the GPU (acrmi_rasterize; the reference's Visualizer 'mesh' view,
     acr/visualization.py:100-218, with the conventions of DESIGN.md "Rendering").
     verts [M,V,3] device fp32 (metres, camera axes); trans [M,3] added to them (cam_trans) or None.
@@ -838,8 +839,13 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
     images uint8 [N,H,W,3] device; mesh_frame [M] = the frame each mesh is drawn into, -1 = not drawn (default: mesh m
     into frame m when M == N, into frame m // (M / N) when N divides M).  colors [M,3] or [3] in the images' channel
     order (default: the reference's right-hand colour as RGB).  view [N,4] = scale x, scale y, shift x, shift y of the 512
-    canvas (view_from_offsets) or None = the 512 network input.  out: uint8 tensor like images (may BE images: in place).
+    canvas (view_from_offsets) or None = the 512 network input.  mesh_view [M,4]: such a row per MESH instead (exclusive with
+    view; meshes of several regions of interest in one frame, DESIGN.md "Views over regions") - the depth that is compared
+    is then mesh_view[m,0] / Z, one virtual camera per frame, and a mesh whose scale is not > 0 is not drawn.
+    out: uint8 tensor like images (may BE images: in place).
     Returns out, or (out, ids int32 [N,H,W]: mesh * F + face of the visible triangle, -1 = none) with return_ids."""
+    if view is not None and mesh_view is not None:
+        raise ValueError('view (one row per frame) and mesh_view (one row per mesh) exclude each other')
     _need_cuda(verts, images, out)
     if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
         raise ValueError('verts must be [M,V,3]')
@@ -875,6 +881,10 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
         vw = torch.as_tensor(view, dtype=torch.float32).to(dev).contiguous()
         if tuple(vw.shape) != (N, 4):
             raise ValueError('view must be [N,4]')
+    if mesh_view is not None:
+        vw = torch.as_tensor(mesh_view, dtype=torch.float32).to(dev).contiguous()
+        if tuple(vw.shape) != (M, 4):
+            raise ValueError('mesh_view must be [M,4]')
     src = images.contiguous()
     if out is None:
         out = torch.empty_like(src)
@@ -884,9 +894,10 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
     L = _lib.lib()
     ws = torch.empty(int(L.acrmi_render_workspace(M, F)) + 256, dtype=torch.uint8, device=dev)
     ws_p = (ws.data_ptr() + 255) // 256 * 256
-    _lib.check(L.acrmi_rasterize(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(mf), _p(c),
-                                 _p(vw), float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids),
-                                 C.c_void_p(ws_p), _s(src)))
+    call = L.acrmi_rasterize if mesh_view is None else L.acrmi_rasterize_views
+    _lib.check(call(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(mf), _p(c),
+                    _p(vw), float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids),
+                    C.c_void_p(ws_p), _s(src)))
     return (out, ids) if return_ids else out
 
 
@@ -995,3 +1006,56 @@ def draw_heatmaps(maps, images, view=None, weight=0.7, bgr=False, lut=None):
                                               None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
                                               _p(src), _p(out[0]), _p(out[1]) if two else None, H, W, _s(src)))
     return out if two else out[0]
+
+
+def check_regions(offsets, region_frame, n=None):
+    """`offsets` [n,10] and `region_frame` [n] of views over regions, checked on the host without reading them: -> (n, offsets,
+    region_frame) with lists / numpy turned into CPU tensors of the right type.  Device tensors pass as they are."""
+    o = offsets if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets, np.float32))
+    if o.dim() != 2 or o.shape[1] != 10 or o.shape[0] < 1 or (n is not None and o.shape[0] != n):
+        raise ValueError('offsets must be [n,10], one row per region%s (got %s)' % ('' if n is None else ': n = %d' % n, tuple(o.shape)))
+    n = o.shape[0]
+    rf = region_frame if isinstance(region_frame, torch.Tensor) else torch.as_tensor(np.asarray(region_frame))
+    if rf.dim() != 1 or rf.shape[0] != n or rf.is_floating_point() or rf.dtype == torch.bool:
+        raise ValueError('region_frame must hold one integer per region: [%d] (got %s %s)' % (n, rf.dtype, tuple(rf.shape)))
+    return n, o, rf
+
+
+def draw_region_heatmaps(maps, images, offsets, region_frame, weight=0.7, bgr=False, lut=None, dst=None):
+    """Heat maps of n REGIONS of interest in false colour over the N frames they were cut from (acrmi_draw_region_heatmaps;
+    DESIGN.md "Views over regions").  maps device float [n,2,h,w] (left, right) or [n,h,w], one per region; images uint8
+    [N,H,W,3] device; offsets [n,10] = the regions' `offsets` rows and region_frame [n] = the frame of each (host values or
+    device tensors: the kernel reads them).  Region i tints the pixels of ITS window in frame region_frame[i] as
+    draw_heatmaps would with view_from_offsets(offsets[i]); where windows overlap the larger colour index wins; every other
+    pixel is the input byte for byte.  weight, bgr, lut: as draw_heatmaps.  dst: uint8 [2,N,H,W,3] (or [N,H,W,3] for [n,h,w]
+    maps) to draw into; dst[0] (dst) may BE images.  Returns uint8 [2,N,H,W,3], or [N,H,W,3] for [n,h,w] maps."""
+    _check_images(images)
+    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() not in (3, 4) or \
+            (maps.dim() == 4 and maps.shape[1] != 2) or maps.shape[0] < 1:
+        raise ValueError('maps must be a float tensor [n,2,h,w] or [n,h,w] with one row per region')
+    n, o, rf = check_regions(offsets, region_frame, maps.shape[0])
+    _need_cuda(maps, images)
+    dev = images.device
+    N, H, W, _ = images.shape
+    m = maps.to(dev, torch.float32).contiguous()
+    h, w = m.shape[-2:]
+    two = m.dim() == 4
+    o = o.to(dev, torch.float32).contiguous()
+    rf = rf.to(dev, torch.int32).contiguous()
+    tab = None
+    if lut is not None:
+        tab = np.ascontiguousarray(np.asarray(lut.cpu() if hasattr(lut, 'cpu') else lut))
+        if tab.shape != (256, 3) or tab.dtype != np.uint8:
+            raise ValueError('lut must be uint8 [256,3]')
+    src = images.contiguous()
+    shape = (2, N, H, W, 3) if two else (N, H, W, 3)
+    if dst is None:
+        dst = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != dev:
+        raise ValueError('dst must be a contiguous uint8 tensor %s on the images\' device' % (shape,))
+    left, right = (dst[0], dst[1]) if two else (dst, None)
+    rp = C.c_void_p(m.data_ptr() + 4 * h * w) if two else None
+    _lib.check(_lib.lib().acrmi_draw_region_heatmaps(_p(m), rp, (2 if two else 1) * h * w, n, h, w, _p(o), _p(rf), float(weight),
+                                                     None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
+                                                     _p(src), _p(left), _p(right), N, H, W, _s(src)))
+    return dst

@@ -637,6 +637,47 @@ int acrmi_draw_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long l
 int acrmi_overlay(acrmi_ctx* ctx, int what, const float* slots_dev, const float* pj2d_dev, int B, const float* offsets_dev,
                   int bgr, const uint8_t* img_in_dev, uint8_t* out_dev, uint8_t* out2_dev, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Views over REGIONS of interest (DESIGN.md "Views over regions"; the rule once in csrc/region_view_plan.h): n regions of
+ * n_frames equal-sized frames, region i described by its `offsets` row (acrmi_roi_offsets, acrmi_preprocess_rois*) and
+ * region_frame_dev[i] int32, both in device memory - what acrmi_preprocess_rois_dev wrote goes in as it is.  fp32, every
+ * operation rounded on its own:
+ *  view   (sx, sy, ox, oy) = (o[0] / 512, o[1] / 512, o[5] - o[9], o[2] - o[6]), as acrmi_render / acrmi_overlay
+ *  window l = o[5], t = o[2], r = W - o[3], b = H - o[4], clamped into the frame (NaN -> 0); a pixel belongs to it when its
+ *         centre does.  A region whose window has no pixel, whose sx or sy is not > 0, or whose frame index is outside
+ *         [0, n_frames) draws nothing; no row, whatever it holds, makes a kernel touch memory outside the frames.
+ *  meshes hand h of region i is projected on the 512 canvas and mapped by ITS region's view; it is not clipped to the window.
+ *         All meshes of all regions of a frame go through one depth-tested pass; the depth value of a vertex is sx / Z (one
+ *         virtual camera per frame: two regions of a frame have cameras of different scale).  ids: (2 i + h) * n_faces + face.
+ *  heat   region i covers pixel (x, y) of frame f when region_frame[i] == f, the pixel is in i's window and its canvas
+ *  maps   coordinate under i's view is in [0, 512); idx_i as acrmi_draw_heatmaps; the pixel's index is the MAXIMUM of idx_i over
+ *         the covering regions; out = floor(weight * LUT[idx] + (1 - weight) * img); a pixel no region covers keeps the input.
+ * ------------------------------------------------------------------------------------- */
+/* acrmi_rasterize with one view row per MESH: view_dev [n_meshes,4] (not NULL), and the depth value view[0] / Z. */
+int acrmi_rasterize_views(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                          const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                          const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
+                          float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                          int32_t* ids_out_dev, void* ws_dev, void* stream);
+/* acrmi_draw_heatmaps for regions: the [h,w] map of REGION i starts at element i * frame_stride; offsets_dev [n,10],
+ * region_frame_dev [n]; img_in_dev, out_l_dev, out_r_dev uint8 [n_frames,H,W,3]; the rest as acrmi_draw_heatmaps. */
+int acrmi_draw_region_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long long frame_stride, int n, int h, int w,
+                               const float* offsets_dev, const int32_t* region_frame_dev, float weight,
+                               const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev, uint8_t* out_l_dev,
+                               uint8_t* out_r_dev, int n_frames, int H, int W, void* stream);
+/* acrmi_render for the outputs of a forward on n regions: verts_dev [n,2,778,3], cam_trans_dev [n,2,3], slots_dev
+ * [n,2,ACRMI_SLOT]; img_in / img_out uint8 [n_frames,H,W,3] (may alias), ids_out int32 [n_frames,H,W] or NULL. */
+int acrmi_render_regions(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int n,
+                         const float* offsets_dev, const int32_t* region_frame_dev, const float* colors_host, float focal,
+                         float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
+                         int32_t* ids_out_dev, void* stream);
+/* acrmi_overlay for n regions.  ACRMI_OVERLAY_SKELETON: pj2d_org_dev [n,2,21,2] (pixels of the frames); hand h of region i is
+ * drawn into frame region_frame[i] when its flag is set and the region draws.  ACRMI_OVERLAY_CENTERMAP: the centre maps of the
+ * last program run, which must have been at batch n -> out_dev (left), out2_dev (right), [n_frames,H,W,3] each. */
+int acrmi_overlay_regions(acrmi_ctx* ctx, int what, const float* slots_dev, const float* pj2d_org_dev, int n,
+                          const float* offsets_dev, const int32_t* region_frame_dev, int bgr, const uint8_t* img_in_dev,
+                          uint8_t* out_dev, uint8_t* out2_dev, int n_frames, int H, int W, void* stream);
+
 /* Multi-GPU (replaces nn.DataParallel's scatter/gather, acr/main.py:61): frames are sharded by the caller, one
  * process per GPU; the only collective is ONE all-gather per batch of each rank's flat result buffer
  * [slots | verts | joints] over RCCL/xGMI.  recv_dev holds n_ranks * n_floats floats, rank-major.
