@@ -18,6 +18,7 @@ OPT_BATCH_PRIOR = 9
 VERSION = 303
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 SLOT = 176
+MAX_HAND = 8      # ACRMI_MAX_HAND
 SLOT_FLAG, SLOT_FLATIND, SLOT_SCORE, SLOT_CAM, SLOT_POSES, SLOT_BETAS, SLOT_PARAMS = 0, 1, 2, 3, 6, 54, 64
 E_INVAL, E_HIP, E_STATE, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5
 OVERLAY_SKELETON, OVERLAY_CENTERMAP = 0, 1      # acrmi_overlay `what`
@@ -82,7 +83,7 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12', 'acrmi_track_box', 'acrmi_track_boxes',
            'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev', 'acrmi_nv12_out_matrix', 'acrmi_rgb_to_nv12',
            'acrmi_nv12_compose', 'acrmi_rasterize_views', 'acrmi_draw_region_heatmaps', 'acrmi_render_regions',
-           'acrmi_overlay_regions']
+           'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi']
 
 _lib = None
 
@@ -207,6 +208,9 @@ def lib():
     L.acrmi_render_regions.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, vp, C.c_float, C.c_float, u8p, u8p, i32, i32, i32,
                                        vp, vp]
     L.acrmi_overlay_regions.argtypes = [vp, i32, f32p, f32p, i32, f32p, vp, i32, u8p, u8p, u8p, i32, i32, i32, vp]
+    L.acrmi_decode_multi.argtypes = [vp, i32, i32, f32p, vp]
+    L.acrmi_decode_maps_multi.argtypes = [f32p, f32p, i32, f32p, f32p, i32, f32p, f32p, i32, i32, i32, C.c_float, f32p, vp]
+    L.acrmi_forward_multi.argtypes = [vp, u8p, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',

@@ -112,7 +112,11 @@ class ACR(object):
 
     @torch.no_grad()
     def forward(self, bgr_frame, path):
-        """acr/main.py:92-123 without the drawing: {path: [hand dicts]} or {path: {}} when nothing is detected."""
+        """acr/main.py:92-123 without the drawing: {path: [hand dicts]} or {path: {}} when nothing is detected.
+        hands_per_side > 1 in the config: the frame goes through forward_raw_batch(max_hand=hands_per_side) instead - up to
+        that many hands of each side, lefts in rank order then rights; `rendering` holds the same views."""
+        if int(getattr(self, 'hands_per_side', 1)) > 1:
+            return self._forward_multi_single(bgr_frame, path)
         outputs = self.single_image_forward(bgr_frame, path)
         if outputs is not None and outputs['detection_flag']:
             outputs, results = self.process_results(outputs)
@@ -123,6 +127,28 @@ class ACR(object):
             results = {path: {}}
         if self.renderer == 'hip':
             self.rendering = self._views_single(bgr_frame, outputs, check_show_items(self.show_items))
+        return results
+
+    def _forward_multi_single(self, bgr_frame, path):
+        """`forward` with hands_per_side > 1: one frame through the batched path."""
+        if self.temporal_optimization:
+            raise ValueError('temporal optimisation follows one hand of each side: not with hands_per_side > 1')
+        frame = torch.from_numpy(np.ascontiguousarray(np.asarray(bgr_frame, np.uint8)))[None].cuda(self._device)
+        items = check_show_items(self.show_items) if self.renderer == 'hip' else None
+        got = self.forward_raw_batch(frame, [path], render=bool(items), show_items=items or None)
+        results, views = got if items else (got, None)
+        if not results[path]:
+            print('no hand detected!')
+        elif self.save_dict_results and self.output_dir:
+            save_results(results, self.output_dir.rstrip('/') + '/results.pkl')
+        if self.renderer == 'hip':
+            self.rendering = {}
+            for name in items:
+                v = views[name]
+                if name == 'centermap':
+                    self.rendering[name] = [(v[0, 0].cpu().numpy(), v[1, 0].cpu().numpy())]
+                else:
+                    self.rendering['mesh_rendering_orgimgs' if name == 'mesh' else name] = [v[0].cpu().numpy()]
         return results
 
     def _views_single(self, bgr_frame, outputs, items):
@@ -204,7 +230,7 @@ class ACR(object):
 
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
-                      render_bgr=False, show_items=None, streams=None, max_streams=None):
+                      render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -223,10 +249,20 @@ class ACR(object):
         streams (needs -t): the video stream (camera) of each frame, ints in [0, max_streams), -1 = do not smooth this frame -
         every frame is smoothed with the One-Euro state of ITS stream (acr/main.py:69-83 per video) instead of the batch being
         one video; the state lives in a table of max_streams streams (default 256, fixed when the first such call creates
-        it) that this object owns across load_state_dict; reset_streams() starts streams anew."""
+        it) that this object owns across load_state_dict; reset_streams() starts streams anew.
+        max_hand (None = args().hands_per_side; 1..8): up to that many hands of EACH side per frame (Engine.forward's
+        max_hand).  results[path] then lists the flagged left hands in rank order, then the flagged right
+        hands in rank order.  With max_hand > 1 the dense heads run even with point_heads=True (the point heads know one
+        centre per side); batch_semantics='reference', streams= and temporal optimisation are a ValueError; 'mesh' and 'pj2d'
+        are drawn as the views of max_hand regions per frame (Engine.render_regions / overlay_regions with the frame's own
+        offsets row), 'centermap' and 'org_img' as always."""
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
+        K = int(self.hands_per_side if max_hand is None else max_hand)
+        if K != 1:
+            return self._forward_batch_multi(rgb_u8_frames, paths, offsets, batch_semantics, render, render_bgr, show_items,
+                                             streams, K)
         results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
                                                         max_streams)
         render_offsets = offsets
@@ -268,26 +304,38 @@ class ACR(object):
         from .. import ops
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(B, 2, 3)
-        slots = out['slots'].cpu().numpy()
-        host = {k: out[k].cpu().numpy() for k in ('verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans')}
-        from .. import _lib as S
-        results = {}
-        for b, path in enumerate(paths):
-            hands = []
-            for h in (0, 1):
-                if slots[b, h, S.SLOT_FLAG] > 0.5:
-                    s = slots[b, h]
-                    hands.append({'cam': s[S.SLOT_CAM:S.SLOT_CAM + 3].astype(np.float16),
-                                  'cam_trans': host['cam_trans'][b, h].astype(np.float16),
-                                  'poses': s[S.SLOT_POSES:S.SLOT_POSES + 48].astype(np.float16),
-                                  'betas': s[S.SLOT_BETAS:S.SLOT_BETAS + 10].astype(np.float16),
-                                  'j3d': host['joints'][b, h].astype(np.float16),
-                                  'verts': host['verts'][b, h].astype(np.float16),
-                                  'pj2d': host['pj2d'][b, h].astype(np.float16),
-                                  'pj2d_org': host['pj2d_org'][b, h].astype(np.float16),
-                                  'hand_type': np.int32(h), 'detection_flag_cache': True})
-            results[path] = hands if hands else {}
-        return results, eng, out
+        return results_from_out(out, paths), eng, out
+
+    def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K):
+        """forward_batch with max_hand = K > 1: Engine.forward(max_hand=K), the packaging, and the views of K regions per
+        frame."""
+        from .. import ops
+        from ..engine import check_max_hand
+        K = check_max_hand(K)
+        if streams is not None:
+            raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
+        if self.temporal_optimization:
+            raise ValueError('temporal optimisation follows one hand of each side: not with max_hand=%d' % K)
+        if (batch_semantics or self.model._result_parser.batch_semantics) != 'frame':
+            raise ValueError("batch_semantics='reference' is the reference's rule for one hand of each side (it cannot run "
+                             'more: acr/result_parser.py:134): not with max_hand=%d' % K)
+        B = frames.shape[0]
+        eng = self.model.engine(B)
+        render_offsets = offsets
+        if offsets is None:
+            offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
+        eng.set_point_heads(False)
+        eng.set_temporal(False)
+        eng.set_batch_semantics('frame')
+        out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
+        eng.check_range()
+        out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
+                                         focal_length=self.focal_length).view(B, K, 2, 3)
+        results = results_from_out(out, paths)
+        if render is None:
+            return results
+        views = _multi_views(self, eng, out, render, offsets if render_offsets is not None else None, render_bgr, items)
+        return results, views
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
         kw = dict(focal_length=float(self.focal_length), bgr=bgr)
@@ -337,8 +385,86 @@ class ACR(object):
         return drawn
 
 
+def results_from_out(out, paths):
+    """What the fused call returned -> {path: [hand dicts]} ({} for a frame without a flagged hand).  out: 'slots' [B,2,176] or
+    [B,K,2,176] and 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans' shaped alike (tensors or arrays: nothing here needs
+    a device).  A frame lists its flagged left hands in rank order, then its flagged right hands in rank order - torch.cat((l,
+    r)) of acr/result_parser.py:166-168; with one pair per frame that is left, right."""
+    from .. import _lib as S
+    host = {k: (out[k].detach().cpu().numpy() if hasattr(out[k], 'detach') else np.asarray(out[k]))
+            for k in ('slots', 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans')}
+    slots = host['slots']
+    B = slots.shape[0]
+    if slots.ndim == 3:
+        host = {k: v[:, None] for k, v in host.items()}
+        slots = host['slots']
+    if len(paths) != B:
+        raise ValueError('one path per frame: %d paths, %d frames' % (len(paths), B))
+    results = {}
+    for b, path in enumerate(paths):
+        hands = []
+        for h in (0, 1):
+            for k in range(slots.shape[1]):
+                if slots[b, k, h, S.SLOT_FLAG] > 0.5:
+                    s = slots[b, k, h]
+                    hands.append({'cam': s[S.SLOT_CAM:S.SLOT_CAM + 3].astype(np.float16),
+                                  'cam_trans': host['cam_trans'][b, k, h].astype(np.float16),
+                                  'poses': s[S.SLOT_POSES:S.SLOT_POSES + 48].astype(np.float16),
+                                  'betas': s[S.SLOT_BETAS:S.SLOT_BETAS + 10].astype(np.float16),
+                                  'j3d': host['joints'][b, k, h].astype(np.float16),
+                                  'verts': host['verts'][b, k, h].astype(np.float16),
+                                  'pj2d': host['pj2d'][b, k, h].astype(np.float16),
+                                  'pj2d_org': host['pj2d_org'][b, k, h].astype(np.float16),
+                                  'hand_type': np.int32(h), 'detection_flag_cache': True})
+        results[path] = hands if hands else {}
+    return results
+
+
+def _multi_views(self, eng, out, frames, offsets, bgr, items):
+    """The views of a forward with max_hand = K > 1 over `frames` (a tensor [B,H,W,3] or a list of B frames): pair k of frame b
+    is drawn as region b * K + k of frame b with the frame's own offsets row (offsets None: the 512 x 512 network input)."""
+    B, K = out['slots'].shape[:2]
+    if len(frames) != B:
+        raise ValueError('one frame to draw into per input frame')
+    whole = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
+    rows = (whole if offsets is None else torch.as_tensor(offsets).to(torch.float32)).repeat_interleave(K, 0)
+    flat = {k: out[k].flatten(0, 1) for k in ('slots', 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans') if out.get(k) is not None}
+    frame_of = torch.arange(B).repeat_interleave(K)
+
+    def draw(name, imgs, region_frame):
+        if name == 'mesh':
+            return eng.render_regions(flat, imgs, rows, region_frame, focal_length=float(self.focal_length), bgr=bgr)
+        if name == 'pj2d':
+            return eng.overlay_regions(flat, imgs, name, rows, region_frame, bgr=bgr)
+        raise AssertionError(name)
+
+    def one(name):
+        if name == 'org_img':
+            return frames
+        if name == 'centermap':
+            return self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, name, offsets, bgr)
+        if not isinstance(frames, (list, tuple)):
+            return draw(name, frames, frame_of.to(torch.int32))
+        groups = {}
+        for i, f in enumerate(frames):
+            groups.setdefault(tuple(f.shape), []).append(i)
+        drawn = [None] * len(frames)
+        for idx in groups.values():
+            place = torch.full((len(frames),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
+            place[idx] = torch.arange(len(idx))
+            got = draw(name, torch.stack([frames[i] for i in idx]), place[frame_of].to(torch.int32))
+            for j, i in enumerate(idx):
+                drawn[i] = got[j]
+        return drawn
+
+    if items is None:
+        return one('mesh')
+    return {name: one(name) for name in items}
+
+
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
-                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False):
+                       pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
+                       max_hand=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -361,8 +487,12 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     [n,H*3/2,W] when all sizes agree, else a list; 'centermap' keeps its leading pair.  With pixel_format='nv12' every view is
     composed onto its source surface (ops.nv12_compose: new bytes only where something was drawn) and 'org_img' is the
     surfaces as given; `matrix` is then a name or a pair (row6, row10).  With BGR frames the views go through
-    ops.bgr_to_nv12, and `matrix` is a name, a pair or a row of ten integers; H and W must be even."""
+    ops.bgr_to_nv12, and `matrix` is a name, a pair or a row of ten integers; H and W must be even.
+    max_hand: as forward_batch (None = args().hands_per_side).  With boxes= more than one hand of a side per REGION is a
+    ValueError: the box is there because the caller has found the person."""
     from .utils import img_preprocess_gpu
+    if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
+        raise ValueError('boxes= with max_hand > 1 is not implemented: a region is one person (DESIGN.md section 17)')
     if show_items is not None and not render:
         raise ValueError('show_items needs render=True')
     if render_format not in ('bgr', 'nv12'):
@@ -386,7 +516,8 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
             from .. import ops
             canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
-                                 render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams)
+                                 render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
+                                 max_hand=max_hand)
     if to_nv12 is None:
         return got
     results, views = got

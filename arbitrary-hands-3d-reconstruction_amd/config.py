@@ -23,6 +23,9 @@ DEFAULTS = dict(
     # not a reference flag: 'frame' = every frame as a batch of one (default); 'reference' = the reference's batch-wide
     # prior rules when a batch > 1 is parsed (acr/result_parser.py:42-47,131; result_parser.reference_prior_gate)
     batch_semantics='frame',
+    # not a reference flag: up to this many hands of EACH side per frame (1..8; DESIGN.md section 17: the top-K centres of
+    # each map).  max_hand above is the reference's training-time key and stays unread
+    hands_per_side=1,
 )
 
 RENDERERS = ('hip', 'none', 'pyrender', 'pytorch3d')
@@ -87,7 +90,11 @@ def validate(ns):
         # CenterMap's NMS window (acr/result_parser.py:199,207-216): the decode kernel implements the 5x5 pool only
         raise ValueError('kernel_sizes=%r: only the 5x5 center NMS (kernel_sizes=[5]) is implemented' % (ns.kernel_sizes,))
     # (max_hand is not validated: the reference reads it only under train_flag, acr/result_parser.py:221-224 -
-    # inference always takes the top-1 center per map, whatever the reference's default of 4 says)
+    # inference always takes the top-1 center per map, whatever the reference's default of 4 says; how many hands of a side
+    # THIS package decodes is hands_per_side)
+    hps = getattr(ns, 'hands_per_side', 1)
+    if isinstance(hps, bool) or not isinstance(hps, int) or not 1 <= hps <= 8:
+        raise ValueError('hands_per_side %r: an integer in 1..8' % (hps,))
     if not (isinstance(ns.align_idx, int) and 0 <= ns.align_idx <= 20):
         raise ValueError('align_idx must be a joint index 0..20')
     if getattr(ns, 'batch_semantics', 'frame') not in ('frame', 'reference'):

@@ -466,6 +466,22 @@ int acrmi_decode_gated(acrmi_ctx* c, int B, const int32_t* prior_gate, float* sl
   return r;
 }
 
+int acrmi_decode_multi(acrmi_ctx* c, int B, int max_hand, float* slots, void* stream) {
+  if (!c || !slots) return fail(c, ACRMI_EINVAL, "acrmi_decode_multi: bad arguments");
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
+    return fail(c, ACRMI_EINVAL, "acrmi_decode_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
+  if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_decode_multi: no program");
+  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
+  ON_DEVICE(c);
+  const acrmi_head_layout& h = c->heads;
+  int r = decode_maps_impl(c->buf_ptr[h.center_buf[0]], c->buf_ptr[h.center_buf[1]], c->bufs[h.center_buf[0]].cs,
+                           c->buf_ptr[h.params_buf[0]], c->buf_ptr[h.params_buf[1]], c->bufs[h.params_buf[0]].cs,
+                           c->buf_ptr[h.prior_buf[0]], c->buf_ptr[h.prior_buf[1]], c->bufs[h.prior_buf[0]].cs, B,
+                           c->conf_thresh, nullptr, c->range_flag, slots, stream, max_hand);
+  if (r) c->err = g_err;
+  return r;
+}
+
 int acrmi_prior_gate(acrmi_ctx* c, const float* slots, int B, int32_t* gate, void* stream) {
   if (!slots || !gate || B <= 0) return fail(c, ACRMI_EINVAL, "acrmi_prior_gate: bad arguments");
   if (c) {
@@ -622,6 +638,40 @@ int acrmi_forward(acrmi_ctx* c, const uint8_t* img, int B, const float* offsets,
   int r = run_program(c, img, B, stream, c->point_heads);
   if (r) return r;
   return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+}
+
+int acrmi_forward_multi(acrmi_ctx* c, const uint8_t* img, int B, int max_hand, const float* offsets, float* slots, float* verts,
+                        float* joints, float* verts_camed, float* pj2d, float* pj2d_org, void* stream) {
+  if (!c || !slots || !verts || !joints) return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: bad arguments");
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
+    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
+  // the batch-wide prior rules and the smoothing filters know one hand of each side per frame (the reference cannot run
+  // either with more: acr/result_parser.py:134, acr/main.py:77)
+  if (max_hand > 1 && c->batch_prior)
+    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: ACRMI_OPT_BATCH_PRIOR with max_hand %d > 1", max_hand);
+  if (max_hand > 1 && c->temporal)
+    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: ACRMI_OPT_TEMPORAL with max_hand %d > 1", max_hand);
+  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_multi: MANO tables not loaded");
+  ON_DEVICE(c);
+  // dense heads whatever ACRMI_OPT_POINT_HEADS says: the point heads evaluate the towers at one center per side
+  int r = run_program(c, img, B, stream, /*point=*/false);
+  if (r) return r;
+  if (max_hand == 1)      // every option of acrmi_forward keeps its meaning
+    return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+  if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
+  ManoArgs m{};
+  m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
+  m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
+  m.betas = slots + ACRMI_SLOT_BETAS; m.beta_stride = ACRMI_SLOT;
+  m.side = nullptr; m.H = 2 * max_hand * B; m.center_idx = c->center_idx;      // rows [B,K,2]: side = r & 1
+  m.verts = verts; m.joints = joints; m.center = nullptr;
+  const bool proj = verts_camed || pj2d || pj2d_org;
+  m.cam = proj ? slots + ACRMI_SLOT_CAM : nullptr; m.cam_stride = ACRMI_SLOT;
+  m.offsets = offsets; m.off_div = 2 * max_hand;
+  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
+  m.lbs_f16 = c->mano_f16;
+  HIPCHK(c, launch_mano(m, (hipStream_t)stream));
+  return ACRMI_OK;
 }
 
 int acrmi_forward_streams(acrmi_ctx* c, acrmi_streams* t, const int32_t* ids, const uint8_t* img, int B, const float* offsets,

@@ -152,4 +152,5 @@ void build_schedule(acrmi_ctx* c, bool point, bool large);
 int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op = 0);
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params, const float* r_params,
                      int params_cs, const float* l_prior, const float* r_prior, int prior_cs, int B, float conf_thresh,
-                     const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream);      // acrmi_ops.hip
+                     const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream,
+                     int max_hand = 0 /* > 0: the top-K decode, slots [B,max_hand,2,ACRMI_SLOT] */);      // acrmi_ops.hip

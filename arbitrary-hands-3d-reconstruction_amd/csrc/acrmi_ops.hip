@@ -9,7 +9,8 @@
 // (poison: acrmi_decode_gated's range flag of an 'fp16x3' program; null for the stand-alone operator)
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params,
                      const float* r_params, int params_cs, const float* l_prior, const float* r_prior, int prior_cs,
-                     int B, float conf_thresh, const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream) {
+                     int B, float conf_thresh, const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream,
+                     int max_hand) {
   if (!l_center || !r_center || !l_params || !r_params || !l_prior || !r_prior || !slots || B <= 0 || params_cs < 109 ||
       prior_cs < 106 || center_cs < 1 || !(conf_thresh == conf_thresh))
     return fail(nullptr, ACRMI_EINVAL, "acrmi_decode_maps: bad arguments");
@@ -20,7 +21,7 @@ int decode_maps_impl(const float* l_center, const float* r_center, int center_cs
   d.B = B; d.slots = slots; d.thresh = conf_thresh;
   d.prior_gate = prior_gate;
   d.poison = poison;
-  hipError_t e = launch_decode(d, (hipStream_t)stream);
+  hipError_t e = max_hand > 0 ? launch_decode_multi(d, max_hand, (hipStream_t)stream) : launch_decode(d, (hipStream_t)stream);
   if (e != hipSuccess) return fail(nullptr, ACRMI_EHIP, "decode launch: %s", hipGetErrorString(e));
   return ACRMI_OK;
 }
@@ -39,6 +40,15 @@ int acrmi_decode_maps(const float* l_center, const float* r_center, int center_c
                       int B, float conf_thresh, float* slots, void* stream) {
   return acrmi_decode_maps_gated(l_center, r_center, center_cs, l_params, r_params, params_cs, l_prior, r_prior, prior_cs, B,
                                  conf_thresh, nullptr, slots, stream);
+}
+
+int acrmi_decode_maps_multi(const float* l_center, const float* r_center, int center_cs, const float* l_params,
+                            const float* r_params, int params_cs, const float* l_prior, const float* r_prior, int prior_cs,
+                            int B, int max_hand, float conf_thresh, float* slots, void* stream) {
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_decode_maps_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
+  return decode_maps_impl(l_center, r_center, center_cs, l_params, r_params, params_cs, l_prior, r_prior, prior_cs, B, conf_thresh,
+                          nullptr, nullptr, slots, stream, max_hand);
 }
 
 // ---- stand-alone operators -------------------------------------------------------------------------

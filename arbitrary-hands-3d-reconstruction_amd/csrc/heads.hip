@@ -328,50 +328,68 @@ struct PickScratch {
   float bestv[2][4];
   int besti[2][4];
 };
+// channel 0 of the two center maps of frame b -> sc.cmap.  Called by all 256 threads; the caller's barrier follows.
+__device__ inline void load_center_maps(const float* const* center, int center_cs, int b, PickScratch& sc) {
+  const int tid = threadIdx.x;
+  // 2 x 16 strided reads per thread, ALL requested before the first one is used (a frame is one workgroup: with the loads
+  // issued one per loop trip their latencies added up to most of the kernel's 55 us)
+  float v[2][16];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[h][k] = center[h][((size_t)b * 4096 + tid + 256 * k) * center_cs];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int k = 0; k < 16; ++k) sc.cmap[h][tid + 256 * k] = v[h][k];
+}
+// 5-wide row maxima of hand h's map -> sc.rmax (the window is clipped at the border)
+__device__ inline void row_maxima(PickScratch& sc, int h) {
+  for (int i = threadIdx.x; i < 4096; i += 256) {
+    const int x = i & 63;
+    float m = sc.cmap[h][i];
+    for (int dx = -2; dx <= 2; ++dx)
+      if (dx != 0 && x + dx >= 0 && x + dx < 64) m = fmaxf(m, sc.cmap[h][i + dx]);
+    sc.rmax[i] = m;
+  }
+}
+// x * (maxpool5x5(x) == x) at pixel i of hand h (acr/result_parser.py:245-249); sc.rmax holds that hand's row maxima
+__device__ inline float nms_det(const PickScratch& sc, int h, int i) {
+  const int y = i >> 6;
+  const float v = sc.cmap[h][i];
+  float m = sc.rmax[i];
+  for (int dy = -2; dy <= 2; ++dy)
+    if (dy != 0 && y + dy >= 0 && y + dy < 64) m = fmaxf(m, sc.rmax[i + dy * 64]);
+  return (m == v) ? v : v * 0.f;
+}
+// the order of the candidates: higher value first, lower flat index on an exact tie
+__device__ inline bool ranks_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+// (value, index) of this wave's best candidate in lane 0
+__device__ inline void wave_best(float& bv, int& bi) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_down(bv, off, 64);
+    const int oi = __shfl_down(bi, off, 64);
+    if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+}
+
 __device__ inline void pick_centers(const float* const* center, int center_cs, int b, float thresh, PickScratch& sc,
                                     CenterPick& pk, const int* prior_gate = nullptr) {
   const int tid = threadIdx.x;
-  {
-    // channel 0 of the two center maps: 2 x 16 strided reads per thread, ALL requested before the first one is used (a frame
-    // is one workgroup: with the loads issued one per loop trip their latencies added up to most of the kernel's 55 us)
-    float v[2][16];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) v[h][k] = center[h][((size_t)b * 4096 + tid + 256 * k) * center_cs];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sc.cmap[h][tid + 256 * k] = v[h][k];
-  }
+  load_center_maps(center, center_cs, b, sc);
   __syncthreads();
   // 5x5 window maximum, separably (max is exact and associative: the same value as the 25-element maximum)
   for (int h = 0; h < 2; ++h) {
     if (h) __syncthreads();     // the other hand's row maxima have been read
-    for (int i = tid; i < 4096; i += 256) {
-      const int x = i & 63;
-      float m = sc.cmap[h][i];
-      for (int dx = -2; dx <= 2; ++dx)
-        if (dx != 0 && x + dx >= 0 && x + dx < 64) m = fmaxf(m, sc.cmap[h][i + dx]);
-      sc.rmax[i] = m;
-    }
+    row_maxima(sc, h);
     __syncthreads();
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = tid; i < 4096; i += 256) {
-      const int y = i >> 6;
-      const float v = sc.cmap[h][i];
-      float m = sc.rmax[i];
-      for (int dy = -2; dy <= 2; ++dy)
-        if (dy != 0 && y + dy >= 0 && y + dy < 64) m = fmaxf(m, sc.rmax[i + dy * 64]);
-      const float det = (m == v) ? v : v * 0.f;      // x * (maxpool(x) == x)  (acr/result_parser.py:245-249)
-      if (det > bv || (det == bv && i < bi)) { bv = det; bi = i; }
+      const float det = nms_det(sc, h, i);
+      if (ranks_before(det, i, bv, bi)) { bv = det; bi = i; }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_down(bv, off, 64);
-      const int oi = __shfl_down(bi, off, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
+    wave_best(bv, bi);
     if ((tid & 63) == 0) { sc.bestv[h][tid >> 6] = bv; sc.besti[h][tid >> 6] = bi; }
   }
   __syncthreads();
@@ -380,7 +398,7 @@ __device__ inline void pick_centers(const float* const* center, int center_cs, i
       float bv = sc.bestv[h][0];
       int bi = sc.besti[h][0];
       for (int w = 1; w < 4; ++w)
-        if (sc.bestv[h][w] > bv || (sc.bestv[h][w] == bv && sc.besti[h][w] < bi)) { bv = sc.bestv[h][w]; bi = sc.besti[h][w]; }
+        if (ranks_before(sc.bestv[h][w], sc.besti[h][w], bv, bi)) { bv = sc.bestv[h][w]; bi = sc.besti[h][w]; }
       pk.flag[h] = bv > thresh;                       // strict; centermap_conf_thresh (acr/result_parser.py:241)
       pk.flat[h] = pk.flag[h] ? bi : 0;               // placeholder samples pixel 0 (:106-120)
       pk.score[h] = bv;
@@ -393,6 +411,76 @@ __device__ inline void pick_centers(const float* const* center, int center_cs, i
     }
     if (prior_gate && prior_gate[b] >= 0) use = (pk.flag[0] && pk.flag[1]) ? (prior_gate[b] != 0) : 0;   // caller's batch-wide decision
     pk.prior = use;
+  }
+  __syncthreads();
+}
+
+// The K best candidates of each center map and each hand's partner: pick_centers' NMS and order, K
+// rounds of its arg-max with the winners so far left out.  Called by all 256 threads; *pk is valid after the last barrier.
+struct MultiPick {
+  int flat[2][ACRMI_MAX_HAND], flag[2][ACRMI_MAX_HAND];
+  int partner[2][ACRMI_MAX_HAND];      // flat index of the other side's center whose prior is added, -1 = no prior
+  float score[2][ACRMI_MAX_HAND];
+  float topv[2][4];                    // the four waves' candidates of a round, two rounds in flight
+  int topi[2][4];
+};
+__device__ inline void pick_centers_multi(const float* const* center, int center_cs, int b, float thresh, int K,
+                                          PickScratch& sc, MultiPick& pk) {
+  const int tid = threadIdx.x;
+  load_center_maps(center, center_cs, b, sc);
+  __syncthreads();
+  int round = 0;
+  for (int h = 0; h < 2; ++h) {
+    if (h) __syncthreads();     // the other hand's row maxima have been read
+    row_maxima(sc, h);
+    __syncthreads();
+    float det[16];              // pixel tid + 256 * k
+#pragma unroll
+    for (int k = 0; k < 16; ++k) det[k] = nms_det(sc, h, tid + 256 * k);
+    unsigned taken = 0;         // bit k: det[k] is one of the winners so far
+    for (int r = 0; r < K; ++r, ++round) {
+      float bv = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (!((taken >> k) & 1u) && ranks_before(det[k], tid + 256 * k, bv, bi)) { bv = det[k]; bi = tid + 256 * k; }
+      wave_best(bv, bi);
+      const int par = round & 1;      // a wave may be a round ahead of the readers of the round before: two buffers
+      if ((tid & 63) == 0) { pk.topv[par][tid >> 6] = bv; pk.topi[par][tid >> 6] = bi; }
+      __syncthreads();
+      bv = pk.topv[par][0];
+      bi = pk.topi[par][0];
+      for (int w = 1; w < 4; ++w)
+        if (ranks_before(pk.topv[par][w], pk.topi[par][w], bv, bi)) { bv = pk.topv[par][w]; bi = pk.topi[par][w]; }
+      // bi is a pixel unless no value of the map compares (all NaN): then bv is -inf and the flag stays clear
+      if ((bi & 255) == tid && (unsigned)bi < 4096u) taken |= 1u << (bi >> 8);
+      if (tid == 0) {
+        const int on = bv > thresh && (unsigned)bi < 4096u;      // strict; centermap_conf_thresh (acr/result_parser.py:241)
+        pk.flag[h][r] = on;
+        pk.flat[h][r] = on ? bi : 0;                             // placeholder samples pixel 0 (:106-120)
+        pk.score[h][r] = bv;
+      }
+    }
+  }
+  __syncthreads();
+  // partner = the nearest flagged center of the other side, lower rank on a tie; determine_coeff (:42-47): > 32 px -> no prior
+  if (tid < 2 * ACRMI_MAX_HAND) {
+    const int h = tid / ACRMI_MAX_HAND, k = tid % ACRMI_MAX_HAND;
+    if (k < K) {
+      int partner = -1;
+      if (pk.flag[h][k]) {
+        float bd = INFINITY;
+        for (int j = 0; j < K; ++j) {
+          if (!pk.flag[1 - h][j]) continue;
+          const float dy = (float)(pk.flat[h][k] >> 6) - (float)(pk.flat[1 - h][j] >> 6);
+          const float dx = (float)(pk.flat[h][k] & 63) - (float)(pk.flat[1 - h][j] & 63);
+          const float d = sqrtf(dy * dy + dx * dx);
+          if (partner < 0 || d < bd) { bd = d; partner = pk.flat[1 - h][j]; }
+        }
+        if (bd > 32.f) partner = -1;
+      }
+      pk.partner[h][k] = partner;
+    }
   }
   __syncthreads();
 }
@@ -444,6 +532,52 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
 }
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(decode_kernel, dim3(a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// Top-K decode, one workgroup per frame: slots [B,K,2,ACRMI_SLOT], pair k = (left rank k, right rank k); row = 2 * k + h.
+// K = 1 writes what decode_kernel writes (same picks, same add, same rot6d_to_aa).  prior_gate is not read.
+__global__ __launch_bounds__(256) void decode_multi_kernel(const DecodeArgs a, int K) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  __shared__ PickScratch sc;
+  __shared__ MultiPick pk;
+  __shared__ float pred[2 * ACRMI_MAX_HAND][112];
+  pick_centers_multi(a.center, a.center_cs, b, a.thresh, K, sc, pk);
+  const int rows = 2 * K;
+  float* slot0 = a.slots + (size_t)b * rows * ACRMI_SLOT;
+  for (int it = tid; it < rows * 109; it += 256) {
+    const int r = it / 109, c = it % 109, h = r & 1, k = r >> 1;
+    float v = a.params[h][((size_t)b * 4096 + pk.flat[h][k]) * a.params_cs + c];
+    if (pk.partner[h][k] >= 0 && c >= 3)              // own prior map at the partner's center (:141-145)
+      v += a.prior[h][((size_t)b * 4096 + pk.partner[h][k]) * a.prior_cs + (c - 3)];
+    pred[r][c] = v;
+    float* sl = slot0 + r * ACRMI_SLOT;
+    sl[ACRMI_SLOT_PARAMS + c] = v;
+    if (c < 3) sl[ACRMI_SLOT_CAM + c] = v;
+    if (c >= 99) sl[ACRMI_SLOT_BETAS + (c - 99)] = v;
+    if (c == 0) {
+      sl[ACRMI_SLOT_FLAG] = (float)pk.flag[h][k];
+      sl[ACRMI_SLOT_FLATIND] = (float)pk.flat[h][k];
+      sl[ACRMI_SLOT_SCORE] = pk.score[h][k];
+      sl[173] = 0.f; sl[174] = 0.f; sl[175] = 0.f;
+    }
+  }
+  __syncthreads();
+  for (int q = tid; q < rows * 16; q += 256) {
+    const int r = q >> 4, j = q & 15;
+    float aa[3];
+    rot6d_to_aa(&pred[r][3 + 6 * j], aa);
+    float* sl = slot0 + r * ACRMI_SLOT + ACRMI_SLOT_POSES + 3 * j;
+    sl[0] = aa[0]; sl[1] = aa[1]; sl[2] = aa[2];
+  }
+  if (a.poison && *a.poison) {      // (uniform) invalid program results: NaN everywhere instead of plausible numbers
+    __syncthreads();
+    for (int i = tid; i < rows * ACRMI_SLOT; i += 256) slot0[i] = __builtin_nanf("");
+  }
+}
+hipError_t launch_decode_multi(const DecodeArgs& a, int max_hand, hipStream_t s) {
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(decode_multi_kernel, dim3(a.B), dim3(256), 0, s, a, max_hand);
   return hipGetLastError();
 }
 

@@ -319,6 +319,10 @@ struct DecodeArgs {
                          // has applied the reference's batch-wide rules, acr/result_parser.py:42-47,131)
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
+// The max_hand (1..ACRMI_MAX_HAND) best centers of each map per frame: slots [B,max_hand,2,ACRMI_SLOT], pair k = (left rank
+// k, right rank k), the prior of a hand from its nearest flagged partner of the other side.  prior_gate
+// is not read; max_hand = 1 writes what launch_decode writes.
+hipError_t launch_decode_multi(const DecodeArgs& a, int max_hand, hipStream_t s);
 // The reference's BATCH-WIDE prior decision (acr/result_parser.py:42-47, 102-145) from a first decode's slots [B,2,ACRMI_SLOT]:
 // gate[b] = 1 when frame b has both hands AND the batch has a left and a right detection AND the left center of the FIRST
 // left-detected frame and the right center of the FIRST right-detected frame are <= 32 map pixels apart; else 0.  One workgroup.

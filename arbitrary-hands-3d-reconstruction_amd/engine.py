@@ -45,6 +45,14 @@ def stream_ids(ids, B):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def check_max_hand(max_hand):
+    """max_hand of decode / forward: an int in 1.._lib.MAX_HAND, else ValueError."""
+    k = int(max_hand)
+    if k != max_hand or not 1 <= k <= _lib.MAX_HAND:
+        raise ValueError('max_hand %r: an integer in 1..%d' % (max_hand, _lib.MAX_HAND))
+    return k
+
+
 def stream_args(streams, table, B):
     """`streams=` / `table=` of Engine.smooth and Engine.forward: both or neither.  -> host int32 ids [B], or None."""
     if streams is None and table is None:
@@ -477,9 +485,18 @@ class Engine(object):
         hl = self.program['heads']
         return torch.stack([self.buffer(hl.center_buf[si], B, 1)[..., 0] for si in (0, 1)], 1).float().contiguous()
 
-    def decode(self, B, prior_gate=None):
+    def decode(self, B, prior_gate=None, max_hand=1):
         """prior_gate: int32 device tensor [B] (acrmi_decode_gated: < 0 per-frame rule, 0 no prior, 1 prior when the frame
-        has both hands) - how acr.result_parser applies the reference's batch-wide prior rules; None = per frame."""
+        has both hands) - how acr.result_parser applies the reference's batch-wide prior rules; None = per frame.
+        max_hand > 1 (up to _lib.MAX_HAND): the max_hand best centres of each side per frame -> slots [B,max_hand,2,176]
+        (acrmi_decode_multi); the batch-wide gate knows one hand per side: a ValueError with it."""
+        max_hand = check_max_hand(max_hand)
+        if max_hand > 1:
+            if prior_gate is not None:
+                raise ValueError('prior_gate is the batch-wide rule of one hand per side: not with max_hand=%d' % max_hand)
+            slots = torch.empty(B, max_hand, 2, _lib.SLOT, dtype=torch.float32, device=self.device)
+            _lib.check(self.L.acrmi_decode_multi(self.ctx, B, max_hand, _ptr(slots), _stream(self.device)), self.ctx)
+            return slots
         slots = torch.empty(B, 2, _lib.SLOT, dtype=torch.float32, device=self.device)
         if prior_gate is None:
             _lib.check(self.L.acrmi_decode(self.ctx, B, _ptr(slots), _stream(self.device)), self.ctx)
@@ -533,12 +550,20 @@ class Engine(object):
                                      _stream(dev)), self.ctx)
         return verts, joints, center, extra
 
-    def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None):
+    def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None, max_hand=1):
         """frames -> (slots [B,2,176], verts [B,2,778,3], joints [B,2,21,3][, verts_camed, pj2d, pj2d_org]).
         stream: raw hipStream_t (int) to queue the call on instead of torch's current stream; tensors this call
         allocates still come from the current stream's pool.
         streams= / table=: as `smooth` - the decoded poses / betas of every frame are smoothed with the state of its video
-        stream before MANO (acrmi_forward_streams), whatever set_temporal says."""
+        stream before MANO (acrmi_forward_streams), whatever set_temporal says.
+        max_hand = K > 1 (up to _lib.MAX_HAND): up to K hands of each side per frame (acrmi_forward_multi; DESIGN.md
+        section 17) - every output gains a dimension, slots [B,K,2,176], verts [B,K,2,778,3], ...: pair k = (left rank k,
+        right rank k), `.flatten(0, 1)` is B * K rows of the usual shape.  The dense heads run whatever set_point_heads
+        says; streams=, set_temporal and batch_semantics 'reference' are a ValueError (no identity across frames, and the
+        batch-wide rule knows one hand per side)."""
+        max_hand = check_max_hand(max_hand)
+        if max_hand > 1:
+            return self._forward_multi(img, offsets, project, out, stream, streams, table, max_hand)
         img = self._check_img(img)
         B = img.shape[0]
         ids = stream_args(streams, table, B)
@@ -562,6 +587,34 @@ class Engine(object):
             _lib.check(self.L.acrmi_forward(self.ctx, *args), self.ctx)
         else:
             _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), *args), self.ctx)
+        return out
+
+    def _forward_multi(self, img, offsets, project, out, stream, streams, table, K):
+        if streams is not None or table is not None:
+            raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
+        img = self._check_img(img)
+        B = img.shape[0]
+        self.ensure_batch(B)
+        dev = self.device
+        if out is None:
+            out = {'slots': torch.empty(B, K, 2, _lib.SLOT, dtype=torch.float32, device=dev),
+                   'verts': torch.empty(B, K, 2, 778, 3, dtype=torch.float32, device=dev),
+                   'joints': torch.empty(B, K, 2, 21, 3, dtype=torch.float32, device=dev)}
+            if project:
+                out['verts_camed'] = torch.empty(B, K, 2, 778, 3, dtype=torch.float32, device=dev)
+                out['pj2d'] = torch.empty(B, K, 2, 21, 2, dtype=torch.float32, device=dev)
+                if offsets is not None:
+                    out['pj2d_org'] = torch.empty(B, K, 2, 21, 2, dtype=torch.float32, device=dev)
+        elif tuple(out['slots'].shape) != (B, K, 2, _lib.SLOT) or tuple(out['verts'].shape) != (B, K, 2, 778, 3):
+            raise ValueError('out does not hold %d frames of %d hand pairs' % (B, K))
+        if offsets is not None:
+            offsets = offsets.to(dev, torch.float32).contiguous()
+            if tuple(offsets.shape) != (B, 10):
+                raise ValueError('offsets must be [B,10]: one row per frame')
+        _lib.check(self.L.acrmi_forward_multi(self.ctx, _ptr(img), B, K, _ptr(offsets), _ptr(out['slots']), _ptr(out['verts']),
+                                              _ptr(out['joints']), _ptr(out.get('verts_camed')), _ptr(out.get('pj2d')),
+                                              _ptr(out.get('pj2d_org')), _stream(dev) if stream is None else C.c_void_p(stream)),
+                   self.ctx)
         return out
 
     def track_step(self, frames, boxes, box_frame=None, frame_hw=None, streams=None, table=None, pixel_format='bgr',
@@ -882,8 +935,12 @@ class EnginePool(object):
             raise ValueError('the pool holds a table of %d streams (asked for %d)' % (self.table.capacity, int(capacity)))
         return self.table
 
-    def submit(self, img, offsets=None, project=False, out=None, streams=None):
-        """streams: the video stream of each frame (Engine.forward's `streams=`, on the pool's stream_table())."""
+    def submit(self, img, offsets=None, project=False, out=None, streams=None, max_hand=1):
+        """streams: the video stream of each frame (Engine.forward's `streams=`, on the pool's stream_table());
+        max_hand: Engine.forward's."""
+        max_hand = check_max_hand(max_hand)
+        if max_hand > 1 and streams is not None:
+            raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % max_hand)
         if streams is not None and self.table is None:
             raise ValueError('streams= needs the pool\'s table: call stream_table(capacity) first')
         if streams is not None:      # (checked before the turn moves on)
@@ -905,7 +962,7 @@ class EnginePool(object):
         # the batch)
         table = self.table if streams is not None else None
         res = self.engines[i].forward(img, offsets=offsets, project=project, out=out, stream=self._raw[i].value,
-                                      streams=streams, table=table)
+                                      streams=streams, table=table, max_hand=max_hand)
         done = torch.cuda.Event()
         done.record(st)
         # Everything the batch reads or writes stays referenced by the ticket until its event has completed: the call

@@ -781,6 +781,22 @@ def decode_maps(l_center, r_center, l_params, r_params, l_prior, r_prior, conf_t
     return slots
 
 
+def decode_maps_multi(l_center, r_center, l_params, r_params, l_prior, r_prior, max_hand, conf_thresh=0.35):
+    """NHWC device maps -> slots [B,max_hand,2,176]: the max_hand (1.._lib.MAX_HAND) best centres of each map per frame, pair
+    k = (left rank k, right rank k), every hand's prior from its nearest flagged partner of the other side
+    (acrmi_decode_maps_multi).  max_hand = 1 is decode_maps with one more dimension."""
+    _need_cuda(l_center, r_center, l_params, r_params, l_prior, r_prior)
+    K = int(max_hand)
+    if K != max_hand or not 1 <= K <= _lib.MAX_HAND:
+        raise ValueError('max_hand %r: an integer in 1..%d' % (max_hand, _lib.MAX_HAND))
+    B = l_center.shape[0]
+    slots = torch.empty(B, K, 2, _lib.SLOT, dtype=torch.float32, device=l_center.device)
+    _lib.check(_lib.lib().acrmi_decode_maps_multi(_p(l_center), _p(r_center), l_center.shape[-1], _p(l_params), _p(r_params),
+                                                  l_params.shape[-1], _p(l_prior), _p(r_prior), l_prior.shape[-1], B, K,
+                                                  float(conf_thresh), _p(slots), _s(slots)))
+    return slots
+
+
 def prior_gate(slots):
     """acrmi_prior_gate (stand-alone form): slots [B,2,176] of a first decode -> int32 [B] for decode_maps(prior_gate=...):
     the reference's batch-wide prior decision (acr/result_parser.py:42-47,102-145), computed on the device."""

@@ -219,6 +219,18 @@ int acrmi_prior_gate(acrmi_ctx* ctx, const float* slots_dev, int B, int32_t* gat
  * programs without split-f16 convolutions (fp32, bf16x3: fp32's exponent range). */
 int acrmi_check_range(acrmi_ctx* ctx, void* stream);
 
+/* Several hands of each side per frame: the max_hand (1..ACRMI_MAX_HAND) best candidates of each NMS'd
+ * center map - value descending, lower flat index first on an exact tie, CenterMap.parse_centermap_heatmap_adaptive_scale_batch
+ * with K = max_hand (acr/result_parser.py:218-243) - each flagged when its score > ACRMI_OPT_CONF_THRESH (strict), else a
+ * placeholder that samples pixel 0.  slots_dev [B,max_hand,2,ACRMI_SLOT]: pair k holds (left rank k, right rank k) - a storage
+ * convention, the two hands of a pair have nothing to do with each other - and every slot field is as acrmi_decode writes
+ * it, so the result is B * max_hand rows of the [n,2,...] shape every call behind the decode takes.  The cross-hand prior
+ * (acr/result_parser.py:42-47,131-145) is decided per HAND: its own prior map at the center of its partner = the nearest
+ * flagged hand of the other side in the frame (lower rank on a tie), added unless they are more than 32 map pixels apart.
+ * max_hand = 1 writes exactly what acrmi_decode writes. */
+#define ACRMI_MAX_HAND 8
+int acrmi_decode_multi(acrmi_ctx* ctx, int B, int max_hand, float* slots_dev, void* stream);
+
 /* Same decode on caller-supplied NHWC maps (unit tests / callers with their own maps):
  * center [B,64,64,center_cs] (ch 0), params [B,64,64,params_cs] (109 ch), prior (106 ch). */
 int acrmi_decode_maps(const float* l_center, const float* r_center, int center_cs,
@@ -230,6 +242,11 @@ int acrmi_decode_maps_gated(const float* l_center, const float* r_center, int ce
                             const float* l_params, const float* r_params, int params_cs,
                             const float* l_prior, const float* r_prior, int prior_cs, int B, float conf_thresh,
                             const int32_t* prior_gate_dev /* see acrmi_decode_gated */, float* slots_dev, void* stream);
+/* acrmi_decode_multi on caller-supplied maps: slots_dev [B,max_hand,2,ACRMI_SLOT]. */
+int acrmi_decode_maps_multi(const float* l_center, const float* r_center, int center_cs,
+                            const float* l_params, const float* r_params, int params_cs,
+                            const float* l_prior, const float* r_prior, int prior_cs, int B, int max_hand,
+                            float conf_thresh, float* slots_dev, void* stream);
 
 /* mano/manolayer.py:104-276 (ManoLayer.forward, use_pca=False, flat_hand_mean=False,
  * center_idx as given; <0 = no root alignment) fused with acr/utils.py:384-412
@@ -261,6 +278,16 @@ int acrmi_cam_trans(const float* joints_dev, const float* pj2d_dev, int n, float
 int acrmi_forward(acrmi_ctx* ctx, const uint8_t* img_dev, int B, const float* offsets_dev, float* slots_dev,
                   float* verts_dev, float* joints_dev, float* verts_camed_dev, float* pj2d_dev,
                   float* pj2d_org_dev, void* stream);
+
+/* acrmi_forward for up to max_hand (1..ACRMI_MAX_HAND) hands of each side per frame: the program with its DENSE heads
+ * (whatever ACRMI_OPT_POINT_HEADS says: the point heads know one center per side), acrmi_decode_multi, one MANO launch over
+ * the 2 * max_hand * B rows (placeholders included) -> slots [B,max_hand,2,ACRMI_SLOT], verts [B,max_hand,2,778,3], joints
+ * [B,max_hand,2,21,3], the projections alike; offsets_dev [B,10] = one row per FRAME.  max_hand = 1 is acrmi_forward with
+ * dense heads.  ACRMI_EINVAL, before anything is launched, for max_hand outside 1..ACRMI_MAX_HAND and for max_hand > 1 with
+ * ACRMI_OPT_BATCH_PRIOR or ACRMI_OPT_TEMPORAL set (neither rule knows two hands of one side). */
+int acrmi_forward_multi(acrmi_ctx* ctx, const uint8_t* img_dev, int B, int max_hand, const float* offsets_dev,
+                        float* slots_dev, float* verts_dev, float* joints_dev, float* verts_camed_dev, float* pj2d_dev,
+                        float* pj2d_org_dev, void* stream);
 
 /* Stand-alone operators (same kernels the program uses; for parity tests and embedding).
  * w_packed/bias come from the Python packer (pack_conv).  algo: 0 = direct convolution;
