@@ -19,6 +19,7 @@ VERSION = 303
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 SLOT = 176
 MAX_HAND = 8      # ACRMI_MAX_HAND
+ASSOC_STATE = 41  # ACRMI_ASSOC_STATE
 SLOT_FLAG, SLOT_FLATIND, SLOT_SCORE, SLOT_CAM, SLOT_POSES, SLOT_BETAS, SLOT_PARAMS = 0, 1, 2, 3, 6, 54, 64
 E_INVAL, E_HIP, E_STATE, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5
 OVERLAY_SKELETON, OVERLAY_CENTERMAP = 0, 1      # acrmi_overlay `what`
@@ -83,7 +84,9 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_roi_offsets', 'acrmi_preprocess_rois', 'acrmi_preprocess_rois_nv12', 'acrmi_track_box', 'acrmi_track_boxes',
            'acrmi_preprocess_rois_dev', 'acrmi_preprocess_rois_nv12_dev', 'acrmi_nv12_out_matrix', 'acrmi_rgb_to_nv12',
            'acrmi_nv12_compose', 'acrmi_rasterize_views', 'acrmi_draw_region_heatmaps', 'acrmi_render_regions',
-           'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi']
+           'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi',
+           'acrmi_tracks_create', 'acrmi_tracks_destroy', 'acrmi_tracks_reset', 'acrmi_associate', 'acrmi_forward_tracks',
+           'acrmi_assoc_step']
 
 _lib = None
 
@@ -211,10 +214,17 @@ def lib():
     L.acrmi_decode_multi.argtypes = [vp, i32, i32, f32p, vp]
     L.acrmi_decode_maps_multi.argtypes = [f32p, f32p, i32, f32p, f32p, i32, f32p, f32p, i32, i32, i32, C.c_float, f32p, vp]
     L.acrmi_forward_multi.argtypes = [vp, u8p, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
+    L.acrmi_tracks_create.argtypes = [C.POINTER(vp), i32, i32, i32, i32, i32]
+    L.acrmi_tracks_destroy.argtypes = [vp]
+    L.acrmi_tracks_destroy.restype = None
+    L.acrmi_tracks_reset.argtypes = [vp, vp, i32, vp]
+    L.acrmi_associate.argtypes = [vp, vp, f32p, i32, i32, vp, i32, vp, vp, vp]
+    L.acrmi_forward_tracks.argtypes = [vp, vp, vp, i32, u8p, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp]
+    L.acrmi_assoc_step.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
-                        'acrmi_render_workspace', 'acrmi_streams_destroy'):
+                        'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy'):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -61,6 +61,7 @@ class ACR(object):
         self.rendering = None      # renderer='hip': {'mesh_rendering_orgimgs': [frame]} of the last forward()
         self.show_items = ['mesh']      # the views `forward` leaves on `rendering` (SHOW_ITEMS); the reference's default
         self.stream_table = None        # forward_batch(..., streams=): One-Euro state per video stream (engine.StreamTable)
+        self.track_table = None         # forward_batch(..., tracks=): the tracks per video stream (engine.TrackTable)
         self._build_model_(state_dict, mano_tables, device, max_batch)
         if self.temporal_optimization:
             # acr/main.py:45-47: one filter set per hand type; the state lives in the engine's context
@@ -215,6 +216,33 @@ class ACR(object):
         if table is not None:
             table.close()
 
+    @torch.no_grad()
+    def reset_tracks(self, ids=None):
+        """The listed video streams of forward_batch(..., tracks=) - all of them when ids is None - lose their tracks."""
+        if self.track_table is not None:
+            self.track_table.reset(ids)
+
+    def close_tracks(self):
+        """Frees the track table; the next forward_batch(..., tracks=) creates a new one."""
+        table, self.track_table = self.track_table, None
+        if table is not None:
+            table.close()
+
+    def _tracks_for(self, K, max_streams, gate, max_miss):
+        """forward_batch's `tracks=`: the TrackTable this object owns (created on first use with the parameters of that call;
+        like the stream table it is not the model's, so it survives load_state_dict)."""
+        from ..engine import TrackTable
+        want = (256 if max_streams is None else int(max_streams), K, 8 if gate is None else int(gate),
+                5 if max_miss is None else int(max_miss))
+        t = self.track_table
+        if t is None:
+            t = self.track_table = TrackTable(self._device, *want)
+        elif t.max_hand != K or (max_streams is not None and t.capacity != want[0]) or \
+                (gate is not None and t.gate != want[2]) or (max_miss is not None and t.max_miss != want[3]):
+            raise ValueError('the track table holds (streams, max_hand, gate, max_miss) = %s (asked for %s): close_tracks() first'
+                             % ((t.capacity, t.max_hand, t.gate, t.max_miss), want))
+        return t
+
     def _streams_for(self, streams, max_streams, B):
         """forward_batch's `streams=`: the host ids and the table this object owns (created on first use; it is not the
         model's, so it survives load_state_dict)."""
@@ -230,7 +258,8 @@ class ACR(object):
 
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
-                      render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None):
+                      render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
+                      track_gate=None, track_max_miss=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -255,14 +284,20 @@ class ACR(object):
         hands in rank order.  With max_hand > 1 the dense heads run even with point_heads=True (the point heads know one
         centre per side); batch_semantics='reference', streams= and temporal optimisation are a ValueError; 'mesh' and 'pj2d'
         are drawn as the views of max_hand regions per frame (Engine.render_regions / overlay_regions with the frame's own
-        offsets row), 'centermap' and 'org_img' as always."""
+        offsets row), 'centermap' and 'org_img' as always.
+        tracks (any max_hand): the video stream (camera) of each frame, ints in [0, max_streams), -1 =
+        leave the frame as decoded.  The hands of every frame are put into the order of their stream's TRACKS (this object owns
+        the engine.TrackTable, created by the first such call: max_streams streams, track_gate map pixels, track_max_miss
+        frames; reset_tracks() / close_tracks()), every hand dict gains 'track_id', and results[path] lists the flagged lefts
+        then the flagged rights in SLOT order, so a hand keeps its place while its rank changes.  With -t every track is smoothed
+        with its own One-Euro filter.  Not together with streams=."""
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
         K = int(self.hands_per_side if max_hand is None else max_hand)
-        if K != 1:
+        if K != 1 or tracks is not None:
             return self._forward_batch_multi(rgb_u8_frames, paths, offsets, batch_semantics, render, render_bgr, show_items,
-                                             streams, K)
+                                             streams, K, tracks, max_streams, track_gate, track_max_miss)
         results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
                                                         max_streams)
         render_offsets = offsets
@@ -306,15 +341,18 @@ class ACR(object):
                                          focal_length=self.focal_length).view(B, 2, 3)
         return results_from_out(out, paths), eng, out
 
-    def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K):
-        """forward_batch with max_hand = K > 1: Engine.forward(max_hand=K), the packaging, and the views of K regions per
-        frame."""
+    def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K, tracks=None,
+                             max_streams=None, gate=None, max_miss=None):
+        """forward_batch with max_hand = K > 1 or with tracks=: Engine.forward(max_hand=K), the packaging, and the views of K
+        regions per frame."""
         from .. import ops
         from ..engine import check_max_hand
         K = check_max_hand(K)
+        if tracks is not None and streams is not None:
+            raise ValueError('tracks= smooths every track with its own filter: not together with streams=')
         if streams is not None:
             raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
-        if self.temporal_optimization:
+        if self.temporal_optimization and tracks is None:
             raise ValueError('temporal optimisation follows one hand of each side: not with max_hand=%d' % K)
         if (batch_semantics or self.model._result_parser.batch_semantics) != 'frame':
             raise ValueError("batch_semantics='reference' is the reference's rule for one hand of each side (it cannot run "
@@ -327,7 +365,13 @@ class ACR(object):
         eng.set_point_heads(False)
         eng.set_temporal(False)
         eng.set_batch_semantics('frame')
-        out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
+        if tracks is None:
+            out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
+        else:
+            # (smooth_coeff travels with the call, as in _forward_batch_results; ACRMI_OPT_TEMPORAL itself stays off)
+            eng.set_temporal(False, smooth_coeff=self._args.smooth_coeff)
+            out = eng.forward(frames, offsets=offsets, project=True, max_hand=K, tracks=tracks,
+                              track_table=self._tracks_for(K, max_streams, gate, max_miss), smooth=bool(self.temporal_optimization))
         eng.check_range()
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(B, K, 2, 3)
@@ -398,6 +442,9 @@ def results_from_out(out, paths):
     if slots.ndim == 3:
         host = {k: v[:, None] for k, v in host.items()}
         slots = host['slots']
+    ids = out.get('track_ids')      # [B,K,2] with tracks=: every hand dict gains 'track_id'
+    if ids is not None:
+        ids = (ids.detach().cpu().numpy() if hasattr(ids, 'detach') else np.asarray(ids)).reshape(slots.shape[:3])
     if len(paths) != B:
         raise ValueError('one path per frame: %d paths, %d frames' % (len(paths), B))
     results = {}
@@ -416,6 +463,8 @@ def results_from_out(out, paths):
                                   'pj2d': host['pj2d'][b, k, h].astype(np.float16),
                                   'pj2d_org': host['pj2d_org'][b, k, h].astype(np.float16),
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
+                    if ids is not None:
+                        hands[-1]['track_id'] = np.int32(ids[b, k, h])
         results[path] = hands if hands else {}
     return results
 
@@ -464,7 +513,7 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
-                       max_hand=None):
+                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -489,8 +538,11 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     surfaces as given; `matrix` is then a name or a pair (row6, row10).  With BGR frames the views go through
     ops.bgr_to_nv12, and `matrix` is a name, a pair or a row of ten integers; H and W must be even.
     max_hand: as forward_batch (None = args().hands_per_side).  With boxes= more than one hand of a side per REGION is a
-    ValueError: the box is there because the caller has found the person."""
+    ValueError: the box is there because the caller has found the person.
+    tracks / track_gate / track_max_miss: as forward_batch; with boxes= a ValueError (ops.track_boxes follows a region)."""
     from .utils import img_preprocess_gpu
+    if boxes is not None and tracks is not None:
+        raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
         raise ValueError('boxes= with max_hand > 1 is not implemented: a region is one person (DESIGN.md section 17)')
     if show_items is not None and not render:
@@ -517,7 +569,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
             canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
-                                 max_hand=max_hand)
+                                 max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss)
     if to_nv12 is None:
         return got
     results, views = got

@@ -300,12 +300,14 @@ void acrmi_streams_destroy(acrmi_streams* t) {
 // One call's launches on a table: the table's lock is held, `s` waits for the table's ordering event before them and
 // done() records it behind them - also behind a call that failed midway, so that the next context still queues behind
 // whatever that call launched.
+extern "C++" {
+template <class Table>      // acrmi_streams or acrmi_tracks
 struct TableOrder {
-  acrmi_streams* t;
+  Table* t;
   hipStream_t s;
   std::lock_guard<std::mutex> lock;
   hipError_t err;
-  TableOrder(acrmi_streams* table, hipStream_t stream)
+  TableOrder(Table* table, hipStream_t stream)
       : t(table), s(stream), lock(table->mu), err(table->order ? hipStreamWaitEvent(stream, table->order, 0) : hipSuccess) {}
   hipError_t done(hipError_t e) {
     if (t->order && err == hipSuccess) {
@@ -315,6 +317,7 @@ struct TableOrder {
     return e;
   }
 };
+}      // extern "C++"
 
 int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids, int n, void* stream) {
   if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_reset: bad arguments");
@@ -340,16 +343,20 @@ int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids, int n, void* strea
 
 // ids (may be null: every frame is stream 0) are valid for t.  Successive launches of SMOOTH_FRAMES_PER_LAUNCH frames on the
 // stream, in frame order: a stream's chain continues in the next launch from the row the previous one wrote.
+static void smooth_coefficients(SmoothArgs& a, float smooth_coeff) {
+  // create_OneEuroFilter (acr/utils.py:1472-1473): poses / global_orient (smooth_coeff, 0.7), betas (0.6, 0.7);
+  // dcutoff 1.0, freq 30.  The derivative filter's alpha is a python double rounded once when it meets the tensor.
+  a.mincutoff = smooth_coeff; a.mincutoff_betas = 0.6f; a.beta = 0.7f; a.freq = 30.f;
+  const double te = 1.0 / 30.0, tau = 1.0 / (2 * M_PI * 1.0), alpha_d = 1.0 / (1.0 + tau / te);
+  a.alpha_d = (float)alpha_d; a.one_minus_alpha_d = (float)(1.0 - alpha_d);
+  a.two_pi = (float)(2 * M_PI); a.te = (float)te;
+}
+
 static int smooth_on(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, const int32_t* ids, hipStream_t stream) {
   SmoothArgs a{};
   a.state = t->state;
   a.init = t->init;
-  // create_OneEuroFilter (acr/utils.py:1472-1473): poses / global_orient (smooth_coeff, 0.7), betas (0.6, 0.7);
-  // dcutoff 1.0, freq 30.  The derivative filter's alpha is a python double rounded once when it meets the tensor.
-  a.mincutoff = c->smooth_coeff; a.mincutoff_betas = 0.6f; a.beta = 0.7f; a.freq = 30.f;
-  const double te = 1.0 / 30.0, tau = 1.0 / (2 * M_PI * 1.0), alpha_d = 1.0 / (1.0 + tau / te);
-  a.alpha_d = (float)alpha_d; a.one_minus_alpha_d = (float)(1.0 - alpha_d);
-  a.two_pi = (float)(2 * M_PI); a.te = (float)te;
+  smooth_coefficients(a, c->smooth_coeff);
   TableOrder ord(t, stream);
   hipError_t e = ord.err;
   for (int f0 = 0; e == hipSuccess && f0 < B; f0 += SMOOTH_FRAMES_PER_LAUNCH) {
@@ -400,6 +407,125 @@ int acrmi_smooth(acrmi_ctx* c, float* slots, int B, void* stream) {
     if (r) return r;
   }
   return smooth_on(c, c->own_streams, slots, B, nullptr, (hipStream_t)stream);
+}
+
+// ---- tracks: hand identity across frames with max_hand > 1 (assoc_plan.h) -------------------------
+int acrmi_tracks_create(acrmi_tracks** out, int device, int capacity, int max_hand, int gate, int max_miss) {
+  if (!out) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: out is NULL");
+  if (!assoc_params_ok(max_hand, gate, max_miss))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: max_hand %d outside 1..%d, gate %d outside 0..%d or max_miss %d < -1",
+                max_hand, ASSOC_MAX_HAND, gate, ASSOC_GATE_ANY, max_miss);
+  if (capacity < 1 || (long long)capacity * max_hand > ASSOC_MAX_TRACKS)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: capacity %d x max_hand %d outside 1..%d hands per side", capacity,
+                max_hand, ASSOC_MAX_TRACKS);
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) return fail(nullptr, ACRMI_EHIP, "acrmi_tracks_create: no HIP device (%s)", hipGetErrorString(e));
+  if (device < 0 || device >= n) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: device %d of %d", device, n);
+  DeviceGuard g(device);
+  if (g.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(g.err));
+  acrmi_tracks* t = new acrmi_tracks();
+  t->device = device;
+  t->capacity = capacity; t->max_hand = max_hand; t->gate = gate; t->max_miss = max_miss;
+  t->last.assign((size_t)capacity, -1);
+  const size_t hands = (size_t)capacity * max_hand * 2;
+  const size_t state_bytes = hands * 3 * 64 * sizeof(float), init_bytes = hands * sizeof(int);
+  const size_t bytes = state_bytes + init_bytes + (size_t)capacity * 2 * sizeof(AssocSide);
+  e = hipMalloc(&t->state, bytes);
+  // zeroed = every slot free, every id counter at 0; complete before the call returns (as acrmi_streams_create)
+  if (e == hipSuccess) e = hipMemset(t->state, 0, bytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->order, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    if (t->state) (void)hipFree(t->state);
+    delete t;
+    return fail(nullptr, ACRMI_EHIP, "acrmi_tracks_create: %d streams of %d hands: %s", capacity, max_hand, hipGetErrorString(e));
+  }
+  t->init = reinterpret_cast<int*>(reinterpret_cast<char*>(t->state) + state_bytes);
+  t->meta = reinterpret_cast<AssocSide*>(reinterpret_cast<char*>(t->init) + init_bytes);
+  *out = t;
+  return ACRMI_OK;
+}
+
+void acrmi_tracks_destroy(acrmi_tracks* t) {
+  if (!t) return;
+  DeviceGuard guard_(t->device);
+  if (t->order) (void)hipEventDestroy(t->order);
+  (void)hipFree(t->state);      // (waits for the launches that still use the table)
+  delete t;
+}
+
+int acrmi_tracks_reset(acrmi_tracks* t, const int32_t* ids, int n, void* stream) {
+  if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_reset: bad arguments");
+  if (ids) {
+    const int bad = smooth_bad_id(ids, n, t->capacity, 0);
+    if (bad >= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_reset: ids[%d] = %d outside 0..%d", bad, ids[bad], t->capacity - 1);
+  }
+  DeviceGuard guard_(t->device);
+  if (guard_.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice(%d): %s", t->device, hipGetErrorString(guard_.err));
+  TableOrder ord(t, (hipStream_t)stream);
+  hipError_t e = ord.err;
+  // init flags and track slots lie next to each other; a filter row behind a cleared init flag is overwritten by its next sample
+  if (e == hipSuccess && !ids)
+    e = hipMemsetAsync(t->init, 0, (size_t)t->capacity * (t->max_hand * 2 * sizeof(int) + 2 * sizeof(AssocSide)), (hipStream_t)stream);
+  for (int i0 = 0; ids && e == hipSuccess && i0 < n; i0 += SMOOTH_FRAMES_PER_LAUNCH) {
+    const int m = n - i0 < SMOOTH_FRAMES_PER_LAUNCH ? n - i0 : SMOOTH_FRAMES_PER_LAUNCH;
+    SmoothIds k{};
+    memcpy(k.id, ids + i0, (size_t)m * sizeof(int32_t));
+    e = launch_assoc_reset(k, m, t->max_hand, t->meta, t->init, (hipStream_t)stream);
+  }
+  e = ord.done(e);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_tracks_reset: %s", hipGetErrorString(e));
+}
+
+// what acrmi_associate and acrmi_forward_tracks check before anything is launched
+static int check_tracks(acrmi_ctx* c, const acrmi_tracks* t, const int32_t* ids, int B, int max_hand, const char* who) {
+  if (!t || !ids || B <= 0) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "%s: max_hand %d outside 1..%d", who, max_hand, ACRMI_MAX_HAND);
+  if (max_hand != t->max_hand) return fail(c, ACRMI_EINVAL, "%s: max_hand %d, the table holds %d slots per side", who, max_hand, t->max_hand);
+  if (c && t->device != c->device) return fail(c, ACRMI_EINVAL, "%s: the table is on device %d, the context on %d", who, t->device, c->device);
+  const int bad = smooth_bad_id(ids, B, t->capacity, -1);
+  if (bad >= 0) return fail(c, ACRMI_EINVAL, "%s: ids[%d] = %d outside -1..%d", who, bad, ids[bad], t->capacity - 1);
+  return ACRMI_OK;
+}
+
+// arguments valid for t.  Successive launches of SMOOTH_FRAMES_PER_LAUNCH frames on the stream, in frame order.
+static int associate_on(acrmi_ctx* c, acrmi_tracks* t, float* slots, int B, const int32_t* ids, int smooth, int32_t* track_ids,
+                        int32_t* perm, hipStream_t stream) {
+  AssocArgs a{};
+  a.s.state = t->state;
+  a.s.init = t->init;
+  smooth_coefficients(a.s, c ? c->smooth_coeff : 4.0f /* a new context's ACRMI_OPT_SMOOTH_COEFF */);
+  a.meta = t->meta;
+  a.K = t->max_hand; a.gate = t->gate; a.max_miss = t->max_miss; a.smooth = smooth ? 1 : 0;
+  const size_t frame_rows = (size_t)2 * t->max_hand;
+  TableOrder ord(t, stream);
+  hipError_t e = ord.err;
+  for (int f0 = 0; e == hipSuccess && f0 < B; f0 += SMOOTH_FRAMES_PER_LAUNCH) {
+    const int m = B - f0 < SMOOTH_FRAMES_PER_LAUNCH ? B - f0 : SMOOTH_FRAMES_PER_LAUNCH;
+    const int n_streams = smooth_plan(ids + f0, m, &a.s.b, t->last.data());
+    bool any_loose = false;
+    memset(a.loose, 0, sizeof a.loose);
+    for (int i = 0; i < m; ++i)
+      if (ids[f0 + i] < 0) { a.loose[i >> 5] |= 1u << (i & 31); any_loose = true; }
+    a.m = m;
+    a.s.slots = slots + (size_t)f0 * frame_rows * ACRMI_SLOT;
+    a.track_ids = track_ids + (size_t)f0 * frame_rows;
+    a.perm = perm ? perm + (size_t)f0 * frame_rows : nullptr;
+    e = launch_associate(a, n_streams, any_loose, stream);
+  }
+  e = ord.done(e);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "association: %s", hipGetErrorString(e));
+}
+
+int acrmi_associate(acrmi_ctx* c, acrmi_tracks* t, float* slots, int B, int max_hand, const int32_t* ids, int smooth,
+                    int32_t* track_ids, int32_t* perm, void* stream) {
+  if (!slots || !track_ids) return fail(c, ACRMI_EINVAL, "acrmi_associate: bad arguments");
+  const int r = check_tracks(c, t, ids, B, max_hand, "acrmi_associate");
+  if (r) return r;
+  DeviceGuard guard_(t->device);
+  if (guard_.err != hipSuccess) return fail(c, ACRMI_EHIP, "hipSetDevice(%d): %s", t->device, hipGetErrorString(guard_.err));
+  return associate_on(c, t, slots, B, ids, smooth, track_ids, perm, (hipStream_t)stream);
 }
 
 int acrmi_profile_ops(acrmi_ctx* c, const uint8_t* img, int B, float* ms_out, int n_ms, void* stream) {
@@ -599,10 +725,29 @@ int acrmi_backbone_channels(acrmi_ctx* c) {
   return c0;
 }
 
+// MANO of the 2 * max_hand * B rows of slots [B,max_hand,2,ACRMI_SLOT] (side = row & 1), placeholders included
+static int mano_multi(acrmi_ctx* c, int B, int max_hand, const float* offsets, float* slots, float* verts, float* joints,
+                      float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream) {
+  ManoArgs m{};
+  m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
+  m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
+  m.betas = slots + ACRMI_SLOT_BETAS; m.beta_stride = ACRMI_SLOT;
+  m.side = nullptr; m.H = 2 * max_hand * B; m.center_idx = c->center_idx;      // rows [B,K,2]: side = r & 1
+  m.verts = verts; m.joints = joints; m.center = nullptr;
+  const bool proj = verts_camed || pj2d || pj2d_org;
+  m.cam = proj ? slots + ACRMI_SLOT_CAM : nullptr; m.cam_stride = ACRMI_SLOT;
+  m.offsets = offsets; m.off_div = 2 * max_hand;
+  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
+  m.lbs_f16 = c->mano_f16;
+  HIPCHK(c, launch_mano(m, stream));
+  return ACRMI_OK;
+}
+
 // decode + MANO of acrmi_forward on one stream
 static int forward_tail(acrmi_ctx* c, int B, const float* offsets, float* slots, float* verts, float* joints,
                         float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream, acrmi_streams* table = nullptr,
-                        const int32_t* ids = nullptr) {
+                        const int32_t* ids = nullptr, acrmi_tracks* tracks = nullptr, int track_smooth = 0,
+                        int32_t* track_ids = nullptr) {
   int r = acrmi_decode(c, B, slots, stream);
   if (r) return r;
   if (c->batch_prior && B > 1) {
@@ -612,7 +757,9 @@ static int forward_tail(acrmi_ctx* c, int B, const float* offsets, float* slots,
     if ((r = acrmi_decode_gated(c, B, c->gate_buf, slots, stream))) return r;
   }
   // acr/main.py:69-83, before MANO: per stream of the caller's table, or (ACRMI_OPT_TEMPORAL) the frames as one stream
-  if (table) {
+  if (tracks) {      // one slot per side (acrmi_forward_tracks with max_hand 1)
+    if ((r = associate_on(c, tracks, slots, B, ids, track_smooth, track_ids, nullptr, stream))) return r;
+  } else if (table) {
     if ((r = smooth_on(c, table, slots, B, ids, stream))) return r;
   } else if (c->temporal && (r = acrmi_smooth(c, slots, B, stream))) return r;
   ManoArgs m{};
@@ -659,19 +806,26 @@ int acrmi_forward_multi(acrmi_ctx* c, const uint8_t* img, int B, int max_hand, c
   if (max_hand == 1)      // every option of acrmi_forward keeps its meaning
     return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
   if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
-  ManoArgs m{};
-  m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
-  m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
-  m.betas = slots + ACRMI_SLOT_BETAS; m.beta_stride = ACRMI_SLOT;
-  m.side = nullptr; m.H = 2 * max_hand * B; m.center_idx = c->center_idx;      // rows [B,K,2]: side = r & 1
-  m.verts = verts; m.joints = joints; m.center = nullptr;
-  const bool proj = verts_camed || pj2d || pj2d_org;
-  m.cam = proj ? slots + ACRMI_SLOT_CAM : nullptr; m.cam_stride = ACRMI_SLOT;
-  m.offsets = offsets; m.off_div = 2 * max_hand;
-  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
-  m.lbs_f16 = c->mano_f16;
-  HIPCHK(c, launch_mano(m, (hipStream_t)stream));
-  return ACRMI_OK;
+  return mano_multi(c, B, max_hand, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+}
+
+int acrmi_forward_tracks(acrmi_ctx* c, acrmi_tracks* t, const int32_t* ids, int smooth, const uint8_t* img, int B, int max_hand,
+                         const float* offsets, float* slots, float* verts, float* joints, float* verts_camed, float* pj2d,
+                         float* pj2d_org, int32_t* track_ids, void* stream) {
+  if (!c || !slots || !verts || !joints || !track_ids) return fail(c, ACRMI_EINVAL, "acrmi_forward_tracks: bad arguments");
+  int r = check_tracks(c, t, ids, B, max_hand, "acrmi_forward_tracks");
+  if (r) return r;
+  if (max_hand > 1 && c->batch_prior)
+    return fail(c, ACRMI_EINVAL, "acrmi_forward_tracks: ACRMI_OPT_BATCH_PRIOR with max_hand %d > 1", max_hand);
+  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_tracks: MANO tables not loaded");
+  ON_DEVICE(c);
+  if ((r = run_program(c, img, B, stream, /*point=*/false))) return r;      // dense heads, as acrmi_forward_multi
+  if (max_hand == 1)      // the decode of acrmi_forward with its options; the track table takes the place of the smoothing
+    return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream, nullptr, ids, t,
+                        smooth, track_ids);
+  if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
+  if ((r = associate_on(c, t, slots, B, ids, smooth, track_ids, nullptr, (hipStream_t)stream))) return r;
+  return mano_multi(c, B, max_hand, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
 }
 
 int acrmi_forward_streams(acrmi_ctx* c, acrmi_streams* t, const int32_t* ids, const uint8_t* img, int B, const float* offsets,

@@ -51,6 +51,20 @@ struct acrmi_streams {
   std::vector<int32_t> last;    // smooth_plan's scratch, all -1 between calls
 };
 
+// The tracks of `capacity` video streams with max_hand slots per side (acrmi_tracks_create; assoc_plan.h): per slot a One-Euro
+// state row in acrmi_streams' layout, per (stream, side) an AssocSide.  Owned outside any context and ordered between
+// contexts like acrmi_streams.
+struct acrmi_tracks {
+  int device = 0;
+  int capacity = 0, max_hand = 0, gate = 0, max_miss = 0;
+  float* state = nullptr;       // [capacity][max_hand][2][x_raw | x_filt | dx_filt][64], then init, then meta (one allocation)
+  int* init = nullptr;          // [capacity][max_hand][2]
+  AssocSide* meta = nullptr;    // [capacity][2]
+  hipEvent_t order = nullptr;
+  std::mutex mu;
+  std::vector<int32_t> last;    // smooth_plan's scratch, all -1 between calls
+};
+
 struct acrmi_ctx {
   int device = 0;
   std::string err;

@@ -519,6 +519,27 @@ int acrmi_track_box(const float* pts_host, int n_pts, int H, int W, double scale
   return ACRMI_OK;
 }
 
+int acrmi_assoc_step(int max_hand, int gate, int max_miss, const float* rows_host, int row_stride, int32_t* state,
+                     int32_t* track_ids, int32_t* perm, int32_t* born) {
+  static_assert(ACRMI_ASSOC_STATE == ASSOC_STATE_INTS, "the header states the size of AssocSide");
+  if (!rows_host || !state || !track_ids || !perm || row_stride < 2)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_assoc_step: bad arguments");
+  if (!assoc_params_ok(max_hand, gate, max_miss))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_assoc_step: max_hand %d outside 1..%d, gate %d outside 0..%d or max_miss %d < -1",
+                max_hand, ASSOC_MAX_HAND, gate, ASSOC_GATE_ANY, max_miss);
+  AssocSide s;
+  memcpy(&s, state, sizeof s);
+  AssocStep o;
+  assoc_step(s, max_hand, gate, max_miss, rows_host, row_stride, o);
+  memcpy(state, &s, sizeof s);
+  for (int k = 0; k < max_hand; ++k) {
+    track_ids[k] = o.track_id[k];
+    perm[k] = o.perm[k];
+    if (born) born[k] = o.born[k];
+  }
+  return ACRMI_OK;
+}
+
 int acrmi_track_boxes(const float* pj2d_org_dev, const float* slots_dev, const int32_t* frame_hw_dev, int n, double scale,
                       int min_size, int32_t* boxes_dev, void* stream) {
   if (!pj2d_org_dev || !slots_dev || !frame_hw_dev || !boxes_dev || n <= 0)

@@ -633,11 +633,10 @@ struct SmoothState {
   float x_raw, x_filt, dx_filt;
   int init;
 };
-// One frame of one stream: wave = hand type h, lane = element e; rot = the workgroup's two 3x3 scratch matrices.  Called by
-// all 128 threads (three barriers).
+// One frame of one stream: wave h = one hand, lane = element e; rot = the workgroup's 3x3 scratch matrices, one per wave; on
+// (wave-uniform): the hand takes part.  Called by all threads of the workgroup (three barriers).
 __device__ __forceinline__ void smooth_frame(const SmoothArgs& a, float* sl, int h, int e, float mincut, float (*rot)[9],
-                                             SmoothState& st) {
-  const bool on = sl[ACRMI_SLOT_FLAG] > 0.5f;     // block-uniform per hand (wave = hand); false for a NaN flag
+                                             SmoothState& st, const bool on) {
   if (on && e == 55) {      // batch_rodrigues (acr/utils.py:602-616) + quat2mat (:618-638) of the global orientation
     const float ax = sl[ACRMI_SLOT_POSES], ay = sl[ACRMI_SLOT_POSES + 1], az = sl[ACRMI_SLOT_POSES + 2];
     const float ex = ax + 1e-8f, ey = ay + 1e-8f, ez = az + 1e-8f;
@@ -699,8 +698,10 @@ __global__ __launch_bounds__(128) void smooth_kernel(const SmoothArgs a) {
   float* st = a.state + hand * 3 * 64;     // [x_raw | x_filt | dx_filt][64]
   SmoothState s{st[e], st[64 + e], st[128 + e], a.init[hand]};
   const float mincut = (e >= 45 && e < 55) ? a.mincutoff_betas : a.mincutoff;
-  for (int f = a.b.first[blockIdx.x]; f != SMOOTH_END; f = a.b.next[f])
-    smooth_frame(a, a.slots + ((size_t)f * 2 + h) * ACRMI_SLOT, h, e, mincut, rot, s);
+  for (int f = a.b.first[blockIdx.x]; f != SMOOTH_END; f = a.b.next[f]) {
+    float* sl = a.slots + ((size_t)f * 2 + h) * ACRMI_SLOT;
+    smooth_frame(a, sl, h, e, mincut, rot, s, sl[ACRMI_SLOT_FLAG] > 0.5f);     // false for a NaN flag
+  }
   st[e] = s.x_raw; st[64 + e] = s.x_filt; st[128 + e] = s.dx_filt;
   if (e == 0) a.init[hand] = s.init;
 }
@@ -716,6 +717,90 @@ __global__ __launch_bounds__(256) void smooth_reset_kernel(const SmoothIds ids, 
 hipError_t launch_smooth_reset(const SmoothIds& ids, int n, int* init, hipStream_t s) {
   static_assert(SMOOTH_FRAMES_PER_LAUNCH == 256, "one thread per listed stream");
   hipLaunchKernelGGL(smooth_reset_kernel, dim3(1), dim3(256), 0, s, ids, n, init);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tracks: which hand of this frame is which hand of the frame before (assoc_plan.h).  Workgroup g < the
+// number of streams of the launch walks stream g's chain of frames with 128 * K threads, wave w = row 2 * k + h of a frame:
+//   the frame's 2 K rows -> LDS; one thread per side runs assoc_step on the side's tracks (LDS) and writes track_ids / perm;
+//   wave (k, h) takes the row of rank perm[h][k] of its side - in LDS, where smooth_frame filters it with the slot's own state
+//   when the slot has a detection - and writes it to row (k, h) of the frame.
+// The rows of a (frame, side) are permuted as a whole; without smoothing nothing in them is edited.  Track and filter state
+// stay in LDS / registers along the chain and are read and written once.  Workgroups touch disjoint frames and disjoint
+// table rows: no atomics.  Every index into LDS, the table or the outputs comes from K, the launch plan or assoc_step's
+// integers (ranks and slots in [0, K)): nothing a slot holds is used as an index.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128 * ACRMI_MAX_HAND) void associate_kernel(const AssocArgs a) {
+  static_assert(ASSOC_MAX_HAND == ACRMI_MAX_HAND && ASSOC_SLOT_FLOATS == ACRMI_SLOT && ASSOC_FLAG == ACRMI_SLOT_FLAG &&
+                ASSOC_FLATIND == ACRMI_SLOT_FLATIND, "assoc_plan.h restates the slot layout");
+  const int tid = threadIdx.x, w = tid >> 6, e = tid & 63, k = w >> 1, h = w & 1;
+  const int K = a.K, rows = 2 * K;
+  __shared__ float row[2 * ACRMI_MAX_HAND][ACRMI_SLOT];
+  __shared__ float rot[2 * ACRMI_MAX_HAND][9];
+  __shared__ AssocSide side[2];
+  __shared__ AssocStep step[2];
+  const SmoothArgs& sa = a.s;
+  const size_t hand = ((size_t)sa.b.row[blockIdx.x] * K + k) * 2 + h;
+  float* st = sa.state + hand * 3 * 64;
+  SmoothState s{st[e], st[64 + e], st[128 + e], sa.init[hand]};
+  const float mincut = (e >= 45 && e < 55) ? sa.mincutoff_betas : sa.mincutoff;
+  int32_t* meta = reinterpret_cast<int32_t*>(a.meta + (size_t)sa.b.row[blockIdx.x] * 2);
+  for (int i = tid; i < 2 * ASSOC_STATE_INTS; i += blockDim.x) reinterpret_cast<int32_t*>(side)[i] = meta[i];
+  for (int f = sa.b.first[blockIdx.x]; f != SMOOTH_END; f = sa.b.next[f]) {
+    float* frame = sa.slots + (size_t)f * rows * ACRMI_SLOT;
+    for (int i = tid; i < rows * ACRMI_SLOT; i += blockDim.x) (&row[0][0])[i] = frame[i];
+    __syncthreads();      // (also: the tracks are in LDS before the first frame's step)
+    if (e == 0 && w < 2) {      // one thread per side, in two waves
+      assoc_step(side[w], K, a.gate, a.max_miss, &row[w][0], 2 * ACRMI_SLOT, step[w]);
+      for (int q = 0; q < K; ++q) {
+        const size_t o = ((size_t)f * K + q) * 2 + w;
+        a.track_ids[o] = step[w].track_id[q];
+        if (a.perm) a.perm[o] = step[w].perm[q];
+      }
+    }
+    __syncthreads();
+    const int src = step[h].perm[k];
+    const bool on = step[h].det[k] >= 0;
+    if (step[h].born[k]) s.init = 0;      // a new track: its first sample passes through
+    float* sl = &row[2 * src + h][0];
+    if (a.smooth) smooth_frame(sa, sl, w, e, mincut, rot, s, on);
+    float* dst = frame + (size_t)w * ACRMI_SLOT;
+    for (int i = e; i < ACRMI_SLOT; i += 64) dst[i] = sl[i];
+    __syncthreads();      // the rows are out before the next frame comes in
+  }
+  st[e] = s.x_raw; st[64 + e] = s.x_filt; st[128 + e] = s.dx_filt;
+  if (e == 0) sa.init[hand] = s.init;
+  for (int i = tid; i < 2 * ASSOC_STATE_INTS; i += blockDim.x) meta[i] = reinterpret_cast<int32_t*>(side)[i];
+}
+// the frames of the launch that belong to no stream: track_ids -1, perm the identity; the rows stay as they are
+__global__ __launch_bounds__(256) void associate_loose_kernel(const AssocArgs a) {
+  const int f = threadIdx.x;
+  if (f >= a.m || !((a.loose[f >> 5] >> (f & 31)) & 1u)) return;
+  for (int q = 0; q < 2 * a.K; ++q) {
+    a.track_ids[(size_t)f * 2 * a.K + q] = -1;
+    if (a.perm) a.perm[(size_t)f * 2 * a.K + q] = q >> 1;
+  }
+}
+hipError_t launch_associate(const AssocArgs& a, int n_streams, bool any_loose, hipStream_t s) {
+  static_assert(SMOOTH_FRAMES_PER_LAUNCH == 256, "one thread per frame of the launch");
+  if (a.K < 1 || a.K > ACRMI_MAX_HAND || a.m < 1 || a.m > SMOOTH_FRAMES_PER_LAUNCH || n_streams < 0 || n_streams > a.m)
+    return hipErrorInvalidValue;
+  if (n_streams) hipLaunchKernelGGL(associate_kernel, dim3(n_streams), dim3(128 * a.K), 0, s, a);
+  if (any_loose) hipLaunchKernelGGL(associate_loose_kernel, dim3(1), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void assoc_reset_kernel(const SmoothIds ids, int n, int K, AssocSide* __restrict__ meta,
+                                                          int* __restrict__ init) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  int32_t* m = reinterpret_cast<int32_t*>(meta + (size_t)ids.id[i] * 2);
+  for (int q = 0; q < 2 * ASSOC_STATE_INTS; ++q) m[q] = 0;
+  for (int q = 0; q < 2 * K; ++q) init[(size_t)ids.id[i] * 2 * K + q] = 0;
+}
+hipError_t launch_assoc_reset(const SmoothIds& ids, int n, int K, AssocSide* meta, int* init, hipStream_t s) {
+  hipLaunchKernelGGL(assoc_reset_kernel, dim3(1), dim3(256), 0, s, ids, n, K, meta, init);
   return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "conv_rules.h"
 #include "nv12_out_plan.h"
 #include "smooth_plan.h"
+#include "assoc_plan.h"
 
 namespace acrmi {
 
@@ -345,6 +346,21 @@ struct SmoothIds {
   int32_t id[SMOOTH_FRAMES_PER_LAUNCH];
 };
 hipError_t launch_smooth_reset(const SmoothIds& ids, int n, int* init, hipStream_t s);
+
+// Association of the hands of [n frames,K,2,ACRMI_SLOT] with the tracks of their streams, the reordering of the rows into track
+// order and (smooth) the One-Euro step of every slot that has a detection (assoc_plan.h): one workgroup
+// of 128 * K threads per stream present in the launch, plus one for the frames that belong to no stream when there are any.
+struct AssocArgs {
+  SmoothArgs s;          // slots [n,K,2,ACRMI_SLOT]; state [capacity][K][2][x_raw | x_filt | dx_filt][64]; init [capacity][K][2]
+  AssocSide* meta;       // [capacity][2]
+  int32_t* track_ids;    // [n,K,2]
+  int32_t* perm;         // [n,K,2] or null
+  int K, gate, max_miss, smooth, m;       // m: frames of the launch
+  uint32_t loose[SMOOTH_FRAMES_PER_LAUNCH / 32];      // bit f: frame f belongs to no stream (track_ids -1, perm identity)
+};
+hipError_t launch_associate(const AssocArgs& a, int n_streams, bool any_loose, hipStream_t s);
+// the n <= SMOOTH_FRAMES_PER_LAUNCH listed streams free every slot and restart their ids at 0
+hipError_t launch_assoc_reset(const SmoothIds& ids, int n, int K, AssocSide* meta, int* init, hipStream_t s);
 
 // Point heads: the six non-center head towers evaluated only at the pixels the decode reads (heads.hip).
 // Per tower (floats): entry W [9 taps][9 cin/4][64 cout][4] + b[64]; 4 x (conv W [9][16][64][4] + b[64]);

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, packer
+from . import _lib, ops as ops_mod, packer
 from .ops import HAND_COLORS_RGB
 
 
@@ -103,6 +103,61 @@ class StreamTable(object):
             self.close()
         except Exception:
             pass
+
+
+class TrackTable(object):
+    """The tracks of `capacity` video streams with max_hand slots per side on one GPU (acrmi_tracks):
+    what `Engine.associate(..., tracks=, table=)` / `Engine.forward(..., max_hand=K, tracks=, track_table=)` update.  gate: the
+    largest centre distance in map pixels at which a hand continues a track (0..128, 128 = any); max_miss: how many frames a
+    track may go unseen and still be continued (-1 = for ever).  8 and 5 are defaults of parameters, not measurements.  Like a
+    StreamTable it belongs to no Engine, and the library orders the updates of several contexts by the order of the calls."""
+
+    def __init__(self, device=0, capacity=64, max_hand=2, gate=8, max_miss=5):
+        self.L = _lib.lib()
+        self.device = torch.device('cuda', device if isinstance(device, int) else torch.device(device).index or 0)
+        self.capacity, self.max_hand, self.gate, self.max_miss = int(capacity), check_max_hand(max_hand), int(gate), int(max_miss)
+        self.handle = None
+        h = C.c_void_p()
+        _lib.check(self.L.acrmi_tracks_create(C.byref(h), self.device.index, self.capacity, self.max_hand, self.gate, self.max_miss))
+        self.handle = h
+
+    def reset(self, ids=None):
+        """The listed streams - every stream when ids is None - lose their tracks: every slot free, ids from 0 again.
+        Queued on the current stream, ordered with the association calls of every context."""
+        if self.handle is None:
+            raise ValueError('the TrackTable is closed')
+        arr, n = None, 0
+        if ids is not None:
+            a = np.atleast_1d(np.asarray(ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else ids))
+            if a.size == 0:
+                return
+            a = stream_ids(a, a.shape[0])
+            arr, n = a.ctypes.data_as(C.c_void_p), a.shape[0]
+        _lib.check(self.L.acrmi_tracks_reset(self.handle, arr, n, _stream(self.device)))
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            self.L.acrmi_tracks_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def track_args(tracks, track_table, streams, table, K, B):
+    """`tracks=` / `track_table=` of Engine.forward: both or neither, and not next to streams= / table=.  -> host int32 ids [B]
+    or None."""
+    if tracks is None and track_table is None:
+        return None
+    if tracks is None or track_table is None:
+        raise ValueError('tracks= and track_table= go together: the stream of each frame and the TrackTable that holds the tracks')
+    if streams is not None or table is not None:
+        raise ValueError('tracks= smooths every track with its own filter: not together with streams= / table=')
+    ops_mod.check_track_table(track_table, K)
+    return ops_mod.track_stream_ids(tracks, track_table, B)
 
 
 class Engine(object):
@@ -327,6 +382,11 @@ class Engine(object):
     def smooth_reset(self):
         _lib.check(self.L.acrmi_smooth_reset(self.ctx, _stream(self.device)), self.ctx)
 
+    def associate(self, slots, tracks, table, smooth=True):
+        """ops.associate_hands with this context's smoothing coefficient: slots [B,K,2,176] reordered in place into the
+        track order of `table` (a TrackTable of K slots), tracks = the stream of each frame -> (track_ids, perm) int32 [B,K,2]."""
+        return ops_mod.associate_hands(slots, tracks, table, smooth=smooth, ctx=self.ctx)
+
     # ---- multi-GPU (SURVEY.md 8e) ----------------------------------------------------------------
     def comm_init(self, n_ranks, rank, unique_id, allow_second_communicator=False):
         """acrmi_comm_init: RCCL communicator on this context's device (collective).
@@ -550,7 +610,8 @@ class Engine(object):
                                      _stream(dev)), self.ctx)
         return verts, joints, center, extra
 
-    def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None, max_hand=1):
+    def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None, max_hand=1,
+                tracks=None, track_table=None, smooth=True):
         """frames -> (slots [B,2,176], verts [B,2,778,3], joints [B,2,21,3][, verts_camed, pj2d, pj2d_org]).
         stream: raw hipStream_t (int) to queue the call on instead of torch's current stream; tensors this call
         allocates still come from the current stream's pool.
@@ -560,10 +621,14 @@ class Engine(object):
         section 17) - every output gains a dimension, slots [B,K,2,176], verts [B,K,2,778,3], ...: pair k = (left rank k,
         right rank k), `.flatten(0, 1)` is B * K rows of the usual shape.  The dense heads run whatever set_point_heads
         says; streams=, set_temporal and batch_semantics 'reference' are a ValueError (no identity across frames, and the
-        batch-wide rule knows one hand per side)."""
+        batch-wide rule knows one hand per side).
+        tracks= / track_table= (any max_hand): the stream of each frame and a TrackTable of max_hand
+        slots - the decoded hands are put into track order and (smooth) each track is smoothed with its own filter before MANO
+        (acrmi_forward_tracks); the output gains 'track_ids' int32 [B,K,2] and has the [B,K,...] shapes also for K = 1.  Not
+        together with streams= / table=."""
         max_hand = check_max_hand(max_hand)
-        if max_hand > 1:
-            return self._forward_multi(img, offsets, project, out, stream, streams, table, max_hand)
+        if max_hand > 1 or tracks is not None or track_table is not None:
+            return self._forward_multi(img, offsets, project, out, stream, streams, table, max_hand, tracks, track_table, smooth)
         img = self._check_img(img)
         B = img.shape[0]
         ids = stream_args(streams, table, B)
@@ -589,11 +654,12 @@ class Engine(object):
             _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), *args), self.ctx)
         return out
 
-    def _forward_multi(self, img, offsets, project, out, stream, streams, table, K):
-        if streams is not None or table is not None:
+    def _forward_multi(self, img, offsets, project, out, stream, streams, table, K, tracks=None, track_table=None, smooth=True):
+        if tracks is None and track_table is None and (streams is not None or table is not None):
             raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
         img = self._check_img(img)
         B = img.shape[0]
+        ids = track_args(tracks, track_table, streams, table, K, B)
         self.ensure_batch(B)
         dev = self.device
         if out is None:
@@ -611,10 +677,18 @@ class Engine(object):
             offsets = offsets.to(dev, torch.float32).contiguous()
             if tuple(offsets.shape) != (B, 10):
                 raise ValueError('offsets must be [B,10]: one row per frame')
-        _lib.check(self.L.acrmi_forward_multi(self.ctx, _ptr(img), B, K, _ptr(offsets), _ptr(out['slots']), _ptr(out['verts']),
-                                              _ptr(out['joints']), _ptr(out.get('verts_camed')), _ptr(out.get('pj2d')),
-                                              _ptr(out.get('pj2d_org')), _stream(dev) if stream is None else C.c_void_p(stream)),
-                   self.ctx)
+        tail = (_ptr(offsets), _ptr(out['slots']), _ptr(out['verts']), _ptr(out['joints']), _ptr(out.get('verts_camed')),
+                _ptr(out.get('pj2d')), _ptr(out.get('pj2d_org')))
+        raw = _stream(dev) if stream is None else C.c_void_p(stream)
+        if ids is None:
+            _lib.check(self.L.acrmi_forward_multi(self.ctx, _ptr(img), B, K, *tail, raw), self.ctx)
+            return out
+        if out.get('track_ids') is None:
+            out['track_ids'] = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
+        elif tuple(out['track_ids'].shape) != (B, K, 2) or out['track_ids'].dtype != torch.int32 or not out['track_ids'].is_contiguous():
+            raise ValueError("out['track_ids'] must be a contiguous int32 tensor [B,K,2]")
+        _lib.check(self.L.acrmi_forward_tracks(self.ctx, track_table.handle, ids.ctypes.data_as(C.c_void_p), int(bool(smooth)),
+                                               _ptr(img), B, K, *tail, _ptr(out['track_ids']), raw), self.ctx)
         return out
 
     def track_step(self, frames, boxes, box_frame=None, frame_hw=None, streams=None, table=None, pixel_format='bgr',
@@ -866,6 +940,7 @@ class EnginePool(object):
         self._busy = [None] * n
         self._inflight = []      # released tickets whose batch may still be running: their tensors stay referenced
         self.table = None        # stream_table(): the One-Euro state the contexts share
+        self.tracks = None       # track_table(): the tracks the contexts share
 
     def __len__(self):
         return len(self.engines)
@@ -879,6 +954,9 @@ class EnginePool(object):
             if self.table is not None:
                 self.table.close()
                 self.table = None
+            if self.tracks is not None:
+                self.tracks.close()
+                self.tracks = None
             self.streams = []
             L = _lib.lib()
             for st in self._raw:
@@ -935,10 +1013,24 @@ class EnginePool(object):
             raise ValueError('the pool holds a table of %d streams (asked for %d)' % (self.table.capacity, int(capacity)))
         return self.table
 
-    def submit(self, img, offsets=None, project=False, out=None, streams=None, max_hand=1):
+    def track_table(self, capacity, max_hand, gate=8, max_miss=5):
+        """The pool's TrackTable (created on the first call): ONE table for all contexts, as stream_table()."""
+        want = (int(capacity), int(max_hand), int(gate), int(max_miss))
+        if self.tracks is None:
+            self.tracks = TrackTable(self.device, *want)
+        elif (self.tracks.capacity, self.tracks.max_hand, self.tracks.gate, self.tracks.max_miss) != want:
+            raise ValueError('the pool holds a track table of (capacity, max_hand, gate, max_miss) = %s (asked for %s)' % (
+                (self.tracks.capacity, self.tracks.max_hand, self.tracks.gate, self.tracks.max_miss), want))
+        return self.tracks
+
+    def submit(self, img, offsets=None, project=False, out=None, streams=None, max_hand=1, tracks=None, smooth=True):
         """streams: the video stream of each frame (Engine.forward's `streams=`, on the pool's stream_table());
-        max_hand: Engine.forward's."""
+        max_hand: Engine.forward's; tracks / smooth: Engine.forward's `tracks=` on the pool's track_table()."""
         max_hand = check_max_hand(max_hand)
+        if tracks is not None:      # (checked before the turn moves on)
+            if self.tracks is None:
+                raise ValueError('tracks= needs the pool\'s table: call track_table(capacity, max_hand) first')
+            tracks = track_args(tracks, self.tracks, streams, None, max_hand, img.shape[0])
         if max_hand > 1 and streams is not None:
             raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % max_hand)
         if streams is not None and self.table is None:
@@ -962,13 +1054,14 @@ class EnginePool(object):
         # the batch)
         table = self.table if streams is not None else None
         res = self.engines[i].forward(img, offsets=offsets, project=project, out=out, stream=self._raw[i].value,
-                                      streams=streams, table=table, max_hand=max_hand)
+                                      streams=streams, table=table, max_hand=max_hand, tracks=tracks,
+                                      track_table=self.tracks if tracks is not None else None, smooth=smooth)
         done = torch.cuda.Event()
         done.record(st)
         # Everything the batch reads or writes stays referenced by the ticket until its event has completed: the call
         # runs on the pool's stream, so torch's caching allocator (which only knows the caller's stream) would hand a
         # dropped `img` / `offsets` block to the caller's next allocation while the kernels still read it.
-        ticket = {'slot': i, 'event': done, 'out': res, 'img': img, 'offsets': offsets, 'table': table}
+        ticket = {'slot': i, 'event': done, 'out': res, 'img': img, 'offsets': offsets, 'table': table, 'tracks': self.tracks}
         self._busy[i] = ticket
         return ticket
 

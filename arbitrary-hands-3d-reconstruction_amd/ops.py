@@ -684,6 +684,66 @@ def track_boxes(pj2d_org, slots, frame_hw, scale=1.5, min_size=64, out=None, str
     return out
 
 
+# ---- tracks: hand identity across frames with max_hand > 1 (csrc/assoc_plan.h, csrc/heads.hip) ----
+def check_track_table(table, K):
+    """`table=` of associate_hands / Engine.forward(tracks=): an open engine.TrackTable of K slots per side."""
+    if getattr(table, 'handle', None) is None or getattr(table, 'max_hand', None) is None:
+        raise ValueError('the track table must be an open TrackTable')
+    if int(table.max_hand) != int(K):
+        raise ValueError('the TrackTable holds %d slots per side, the slots %d hands' % (table.max_hand, K))
+    return table
+
+
+def track_stream_ids(tracks, table, B):
+    """`tracks=`: one stream id per frame (-1 = leave the frame alone) -> host int32 [B], checked against the table."""
+    from .engine import stream_ids
+    ids = stream_ids(tracks, B)
+    if ids.size and (int(ids.min()) < -1 or int(ids.max()) >= int(table.capacity)):
+        raise ValueError('tracks: an id outside -1..%d' % (int(table.capacity) - 1))
+    return ids
+
+
+def associate_hands(slots, tracks, table, smooth=True, ctx=None, stream=None):
+    """Which hand of each frame continues which track (acrmi_associate): slots [B,K,2,176] ([B,2,176]: K = 1) as
+    decode(max_hand=K) / decode_maps_multi leave them, reordered IN PLACE so that row k of a side is the hand of track slot k
+    of the frame's stream; tracks: the stream of each frame (-1 = leave the frame as it is), frames that share an id are one
+    sequence in batch order; table: an engine.TrackTable of K slots.  smooth: the rows that continue or start a track go
+    through that slot's own One-Euro filter (ctx: the context whose ACRMI_OPT_SMOOTH_COEFF applies; None = the default).
+    -> (track_ids, perm), int32 [B,K,2]: the id of the slot's track (-1: no hand of it in this frame) and the rank that moved
+    there.  Nothing here waits for the device."""
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.float32 or slots.dim() not in (3, 4) or \
+            tuple(slots.shape[-2:]) != (2, _lib.SLOT) or slots.shape[0] < 1 or not slots.is_contiguous():
+        raise ValueError('slots must be a contiguous float32 tensor [B,K,2,%d] or [B,2,%d], B >= 1' % (_lib.SLOT, _lib.SLOT))
+    B, K = slots.shape[0], (1 if slots.dim() == 3 else slots.shape[1])
+    if not 1 <= K <= _lib.MAX_HAND:
+        raise ValueError('slots hold %d hands per side: 1..%d' % (K, _lib.MAX_HAND))
+    check_track_table(table, K)
+    ids = track_stream_ids(tracks, table, B)
+    _need_cuda(slots)
+    dev = slots.device
+    track_ids = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
+    perm = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().acrmi_associate(ctx, table.handle, _p(slots), B, K, ids.ctypes.data_as(C.c_void_p), int(bool(smooth)),
+                                          _p(track_ids), _p(perm), _raw_stream(stream, dev)), ctx)
+    return track_ids, perm
+
+
+def assoc_step_host(rows, state, gate=8, max_miss=5):
+    """The association rule for one frame of one (stream, side) on the host (acrmi_assoc_step; no device): rows float32
+    [K,>=2] in rank order (flag and flat index in columns 0 and 1), state int32 [41] updated in place
+    -> (track_ids, perm, born), int32 [K]."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 2 or not isinstance(state, np.ndarray) or state.dtype != np.int32 or \
+            state.shape != (_lib.ASSOC_STATE,) or not state.flags['C_CONTIGUOUS']:
+        raise ValueError('rows must be [K,>=2] and state a contiguous int32 array [%d]' % _lib.ASSOC_STATE)
+    K = rows.shape[0]
+    out = np.zeros((3, max(K, 1)), np.int32)
+    _lib.check(_lib.lib().acrmi_assoc_step(K, int(gate), int(max_miss), rows.ctypes.data_as(C.c_void_p), rows.shape[1],
+                                           state.ctypes.data_as(C.c_void_p), out[0].ctypes.data_as(C.c_void_p),
+                                           out[1].ctypes.data_as(C.c_void_p), out[2].ctypes.data_as(C.c_void_p)))
+    return out[0, :K], out[1, :K], out[2, :K]
+
+
 def cam_trans(joints, pj2d, focal_length=600.0, img_size=512.0):
     """joints [n,21,3], pj2d [n,21,2] (device fp32) -> cam_trans [n,3]: the reference's closed-form least squares
     (acr/utils.py:430-472, unit confidences) on the device."""

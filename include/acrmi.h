@@ -567,6 +567,43 @@ int acrmi_forward_streams(acrmi_ctx* ctx, acrmi_streams* t, const int32_t* ids_h
                           const float* offsets_dev, float* slots_dev, float* verts_dev, float* joints_dev,
                           float* verts_camed_dev, float* pj2d_dev, float* pj2d_org_dev, void* stream);
 
+/* Tracks: with max_hand > 1 a hand's row is its rank by centre score, and ranks swap between frames.
+ * A track table keeps, per video stream and side, max_hand track slots (live, frames missed, id, last centre, a One-Euro state
+ * row in the layout of acrmi_streams) and says which hand of a frame continues which track: greedy nearest centre within
+ * `gate` map pixels (0..128, 128 = any distance), a track unseen for more than `max_miss` frames (-1 = never, else >= 0) ends,
+ * an unmatched hand starts a new track with the stream-and-side's next id (0, 1, ...) in the lowest free slot (evicting the
+ * longest-unseen track when none is free).  The rule in full: csrc/assoc_plan.h.  gate = 8 and max_miss = 5 are the package's
+ * defaults of these PARAMETERS, not measurements.  capacity >= 1 and capacity * max_hand <= 65536 (a hand's state is about
+ * 0.8 KB), max_hand 1..ACRMI_MAX_HAND, else ACRMI_EINVAL.  Created zeroed: every slot free.  Ordering between contexts: the
+ * table's event and host mutex, exactly as acrmi_streams. */
+typedef struct acrmi_tracks acrmi_tracks;
+int acrmi_tracks_create(acrmi_tracks** out, int device, int capacity, int max_hand, int gate, int max_miss);
+void acrmi_tracks_destroy(acrmi_tracks* t);
+/* ids_host == NULL: every stream; else the n listed streams (each in [0, capacity)): every slot free, the ids restart at 0. */
+int acrmi_tracks_reset(acrmi_tracks* t, const int32_t* ids_host, int n, void* stream);
+/* slots_dev [B,max_hand,2,ACRMI_SLOT] in place: per frame and side the rows are PERMUTED (whole rows; the two sides never look
+ * at each other) so that row k holds the hand of track slot k - the slots without a hand in this frame receive the remaining
+ * ranks in ascending order - and, with smooth != 0, every row that continues or starts a track is smoothed with that slot's own
+ * One-Euro state (the arithmetic and coefficients of acrmi_smooth_streams; ctx NULL: the default ACRMI_OPT_SMOOTH_COEFF, 4.0, on the table's device).
+ * ids_host [B]: the stream of each frame; frames that share an id are one sequence in batch order; -1 = the frame is left as
+ * it is (track_ids -1, perm the identity).  track_ids_dev int32 [B,max_hand,2]: the id of the slot's track, -1 where the slot
+ * has no hand in this frame; perm_dev int32 [B,max_hand,2] or NULL: the rank that moved there.  ACRMI_EINVAL before anything is
+ * launched for an id < -1 or >= capacity and for a max_hand that is not the table's. */
+int acrmi_associate(acrmi_ctx* ctx, acrmi_tracks* t, float* slots_dev, int B, int max_hand, const int32_t* ids_host, int smooth,
+                    int32_t* track_ids_dev, int32_t* perm_dev, void* stream);
+/* acrmi_forward_multi with acrmi_associate between decode and MANO: the meshes come out in track order.  ACRMI_OPT_TEMPORAL is
+ * not looked at (`smooth` says whether the tracks are smoothed); ACRMI_OPT_BATCH_PRIOR with max_hand > 1 is ACRMI_EINVAL. */
+int acrmi_forward_tracks(acrmi_ctx* ctx, acrmi_tracks* t, const int32_t* ids_host, int smooth, const uint8_t* img_dev, int B,
+                         int max_hand, const float* offsets_dev, float* slots_dev, float* verts_dev, float* joints_dev,
+                         float* verts_camed_dev, float* pj2d_dev, float* pj2d_org_dev, int32_t* track_ids_dev, void* stream);
+/* Host only, no device: the rule for one frame of one (stream, side).  rows_host: the max_hand rows of that side in rank order,
+ * row j at rows_host + j * row_stride floats (a frame's slots: rows_host = frame + side * ACRMI_SLOT, row_stride = 2 *
+ * ACRMI_SLOT); state int32 [ACRMI_ASSOC_STATE] in and out: next_id, then live, miss, id, cy, cx of 8 slots each (all zero =
+ * every slot free); track_ids, perm int32 [max_hand]; born int32 [max_hand] or NULL: 1 where the slot's track starts here. */
+#define ACRMI_ASSOC_STATE 41
+int acrmi_assoc_step(int max_hand, int gate, int max_miss, const float* rows_host, int row_stride, int32_t* state,
+                     int32_t* track_ids, int32_t* perm, int32_t* born);
+
 /* ---------------------------------------------------------------------------------------
  * Mesh overlay: acr/visualization.py:100-218 (Visualizer.visulize_result_live, show_items=['mesh'], settings ['put_org'])
  * + acr/renderer/renderer_pyrd.py / renderer_pt3d.py - the frame with the hand meshes drawn over it.  Nothing of those
