@@ -27,6 +27,26 @@ void release_weights(acrmi_ctx* c) {
   c->n_weights = 0;
 }
 
+// a context call that forwarded to a context-free one: the error it left becomes the context's
+static int from_global(acrmi_ctx* c, int r) {
+  if (r) c->err = g_err;
+  return r;
+}
+
+// What the calls that take a device NUMBER do first: there is a HIP device, `device` is one of them and can be selected.  It
+// stays selected while the object lives; then the caller's current device is restored.
+struct NewOnDevice {
+  int rc = ACRMI_OK;
+  std::optional<DeviceGuard> guard;
+  NewOnDevice(const char* who, int device) {
+    int n = 0;
+    const hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) rc = fail(nullptr, ACRMI_EHIP, "%s: no HIP device (%s)", who, hipGetErrorString(e));
+    else if (device < 0 || device >= n) rc = fail(nullptr, ACRMI_EINVAL, "%s: device %d of %d", who, device, n);
+    else if (guard.emplace(device).err != hipSuccess) rc = fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(guard->err));
+  }
+};
+
 extern "C" {
 
 int acrmi_version(void) { return ACRMI_VERSION; }
@@ -35,15 +55,8 @@ const char* acrmi_last_error(const acrmi_ctx* ctx) { return ctx ? ctx->err.c_str
 
 int acrmi_create(acrmi_ctx** out, int device) {
   if (!out) return fail(nullptr, ACRMI_EINVAL, "acrmi_create: out is NULL");
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return fail(nullptr, ACRMI_EHIP, "acrmi_create: no HIP device (%s)", hipGetErrorString(e));
-  if (device < 0 || device >= n) return fail(nullptr, ACRMI_EINVAL, "acrmi_create: device %d of %d", device, n);
-  {
-    DeviceGuard g(device);      // validates the device; the caller's current device is restored
-    if (g.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(g.err));
-  }
+  const NewOnDevice on("acrmi_create", device);
+  if (on.rc) return on.rc;
   acrmi_ctx* c = new acrmi_ctx();
   c->device = device;
   *out = c;
@@ -202,15 +215,10 @@ int acrmi_set_option(acrmi_ctx* c, int option, int value) {
     c->point_heads = value != 0;
     return ACRMI_OK;
   }
-  if (option == ACRMI_OPT_LANES) {
-    if (value < 0 || value > MAX_LANES) return fail(c, ACRMI_EINVAL, "acrmi_set_option: lanes %d outside 0..%d", value, MAX_LANES);
-    c->want_lanes = value;
-    if (c->have_program)
-      for (int v = 0; v < 4; ++v) build_schedule(c, v & 1, v & 2);
-    return ACRMI_OK;
-  }
-  if (option == ACRMI_OPT_LANE_PLAN) {
-    c->lane_plan = value != 0;
+  if (option == ACRMI_OPT_LANES || option == ACRMI_OPT_LANE_PLAN) {      // what the four schedules are built from
+    if (option == ACRMI_OPT_LANE_PLAN) c->lane_plan = value != 0;
+    else if (value < 0 || value > MAX_LANES) return fail(c, ACRMI_EINVAL, "acrmi_set_option: lanes %d outside 0..%d", value, MAX_LANES);
+    else c->want_lanes = value;
     if (c->have_program)
       for (int v = 0; v < 4; ++v) build_schedule(c, v & 1, v & 2);
     return ACRMI_OK;
@@ -250,46 +258,40 @@ int acrmi_set_option_f(acrmi_ctx* c, int option, float value) {
   return fail(c, ACRMI_EINVAL, "acrmi_set_option_f: unknown option %d", option);
 }
 
-// ---- temporal smoothing (acr/main.py:69-83) -------------------------------------------------------------
+// ---- the tables: what acrmi_streams and acrmi_tracks share (StateTable) ---------------------------------------------------
+// `t` (new; deleted here on failure) becomes a table of `capacity` streams on `device`: one zeroed allocation of `bytes`, of
+// which the first state_bytes are the filter rows and the rest - the init flags first - is what a reset of every stream clears.
 // shared: the table carries the event that orders the launches of different contexts and is zeroed before the call returns;
 // else (a context's own table) it is zeroed on `stream`, where the context's first smoothing launch follows it.
-static int streams_create(acrmi_streams** out, int device, int capacity, bool shared, hipStream_t stream) {
-  if (!out) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: out is NULL");
-  if (capacity < 1 || capacity > SMOOTH_MAX_STREAMS)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: capacity %d outside 1..%d", capacity, SMOOTH_MAX_STREAMS);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) return fail(nullptr, ACRMI_EHIP, "acrmi_streams_create: no HIP device (%s)", hipGetErrorString(e));
-  if (device < 0 || device >= n) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: device %d of %d", device, n);
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(g.err));
-  acrmi_streams* t = new acrmi_streams();
-  t->device = device;
-  t->capacity = capacity;
-  t->last.assign((size_t)capacity, -1);
-  const size_t state_bytes = (size_t)capacity * 2 * 3 * 64 * sizeof(float), bytes = state_bytes + (size_t)capacity * 2 * sizeof(int);
-  e = hipMalloc(&t->state, bytes);
-  if (e == hipSuccess && !shared) e = hipMemsetAsync(t->state, 0, bytes, stream);
-  if (e == hipSuccess && shared) {
-    // zeroed = every stream starts fresh; complete before the call returns: the streams that will use the table are not
-    // known here and need not be ordered behind the null stream.  Once per table.
-    e = hipMemset(t->state, 0, bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->order, hipEventDisableTiming);
-  }
-  if (e != hipSuccess) {
+static int table_create(const char* who, StateTable* t, int device, int capacity, size_t state_bytes, size_t bytes, bool shared,
+                        hipStream_t stream) {
+  const NewOnDevice on(who, device);
+  hipError_t e = hipSuccess;
+  if (!on.rc) {
+    t->device = device;
+    t->capacity = capacity;
+    t->last.assign((size_t)capacity, -1);
+    t->reset_bytes = bytes - state_bytes;
+    e = hipMalloc(&t->state, bytes);
+    if (e == hipSuccess && !shared) e = hipMemsetAsync(t->state, 0, bytes, stream);
+    if (e == hipSuccess && shared) {
+      // zeroed = every stream starts fresh, every slot free; complete before the call returns: the streams that will use the
+      // table are not known here and need not be ordered behind the null stream.  Once per table.
+      e = hipMemset(t->state, 0, bytes);
+      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&t->order, hipEventDisableTiming);
+    }
+    if (e == hipSuccess) {
+      t->init = reinterpret_cast<int*>(reinterpret_cast<char*>(t->state) + state_bytes);
+      return ACRMI_OK;
+    }
     if (t->state) (void)hipFree(t->state);
-    delete t;
-    return fail(nullptr, ACRMI_EHIP, "acrmi_streams_create: %d streams: %s", capacity, hipGetErrorString(e));
   }
-  t->init = reinterpret_cast<int*>(reinterpret_cast<char*>(t->state) + state_bytes);
-  *out = t;
-  return ACRMI_OK;
+  delete t;
+  return on.rc ? on.rc : fail(nullptr, ACRMI_EHIP, "%s: %d streams, %zu bytes: %s", who, capacity, bytes, hipGetErrorString(e));
 }
 
-int acrmi_streams_create(acrmi_streams** out, int device, int capacity) { return streams_create(out, device, capacity, true, nullptr); }
-
-void acrmi_streams_destroy(acrmi_streams* t) {
+static void table_destroy(StateTable* t) {
   if (!t) return;
   DeviceGuard guard_(t->device);
   if (t->order) (void)hipEventDestroy(t->order);
@@ -300,14 +302,12 @@ void acrmi_streams_destroy(acrmi_streams* t) {
 // One call's launches on a table: the table's lock is held, `s` waits for the table's ordering event before them and
 // done() records it behind them - also behind a call that failed midway, so that the next context still queues behind
 // whatever that call launched.
-extern "C++" {
-template <class Table>      // acrmi_streams or acrmi_tracks
 struct TableOrder {
-  Table* t;
+  StateTable* t;
   hipStream_t s;
   std::lock_guard<std::mutex> lock;
   hipError_t err;
-  TableOrder(Table* table, hipStream_t stream)
+  TableOrder(StateTable* table, hipStream_t stream)
       : t(table), s(stream), lock(table->mu), err(table->order ? hipStreamWaitEvent(stream, table->order, 0) : hipSuccess) {}
   hipError_t done(hipError_t e) {
     if (t->order && err == hipSuccess) {
@@ -317,28 +317,60 @@ struct TableOrder {
     return e;
   }
 };
-}      // extern "C++"
 
-int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids, int n, void* stream) {
-  if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_reset: bad arguments");
+// The listed streams - all of them when ids is null - start afresh: launch() clears what the table keeps for up to
+// SMOOTH_FRAMES_PER_LAUNCH of them.  A filter row behind a cleared init flag is overwritten by its next sample.
+typedef hipError_t (*ResetLaunch)(StateTable* t, const SmoothIds& ids, int n, hipStream_t s);
+static int table_reset(const char* who, StateTable* t, const int32_t* ids, int n, ResetLaunch launch, hipStream_t stream) {
+  if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "%s: bad arguments", who);
   if (ids) {
     const int bad = smooth_bad_id(ids, n, t->capacity, 0);
-    if (bad >= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_reset: ids[%d] = %d outside 0..%d", bad, ids[bad], t->capacity - 1);
+    if (bad >= 0) return fail(nullptr, ACRMI_EINVAL, "%s: ids[%d] = %d outside 0..%d", who, bad, ids[bad], t->capacity - 1);
   }
   DeviceGuard guard_(t->device);
   if (guard_.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice(%d): %s", t->device, hipGetErrorString(guard_.err));
-  // a stream whose init flags are clear passes its next sample through and overwrites the rest of its row with it
-  TableOrder ord(t, (hipStream_t)stream);
+  TableOrder ord(t, stream);
   hipError_t e = ord.err;
-  if (e == hipSuccess && !ids) e = hipMemsetAsync(t->init, 0, (size_t)t->capacity * 2 * sizeof(int), (hipStream_t)stream);
+  if (e == hipSuccess && !ids) e = hipMemsetAsync(t->init, 0, t->reset_bytes, stream);
   for (int i0 = 0; ids && e == hipSuccess && i0 < n; i0 += SMOOTH_FRAMES_PER_LAUNCH) {
     const int m = n - i0 < SMOOTH_FRAMES_PER_LAUNCH ? n - i0 : SMOOTH_FRAMES_PER_LAUNCH;
     SmoothIds k{};
     memcpy(k.id, ids + i0, (size_t)m * sizeof(int32_t));
-    e = launch_smooth_reset(k, m, t->init, (hipStream_t)stream);
+    e = launch(t, k, m, stream);
   }
   e = ord.done(e);
-  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_streams_reset: %s", hipGetErrorString(e));
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+// what the calls that take a table and the ids of their B frames check before anything is launched (c may be null)
+static int check_table(acrmi_ctx* c, const StateTable* t, const int32_t* ids, int B, const char* who) {
+  if (c && t->device != c->device) return fail(c, ACRMI_EINVAL, "%s: the table is on device %d, the context on %d", who, t->device, c->device);
+  const int bad = smooth_bad_id(ids, B, t->capacity, -1);
+  if (bad >= 0) return fail(c, ACRMI_EINVAL, "%s: ids[%d] = %d outside -1..%d", who, bad, ids[bad], t->capacity - 1);
+  return ACRMI_OK;
+}
+
+// ---- temporal smoothing (acr/main.py:69-83) -------------------------------------------------------------
+static int streams_create(acrmi_streams** out, int device, int capacity, bool shared, hipStream_t stream) {
+  if (!out) return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: out is NULL");
+  if (capacity < 1 || capacity > SMOOTH_MAX_STREAMS)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_streams_create: capacity %d outside 1..%d", capacity, SMOOTH_MAX_STREAMS);
+  acrmi_streams* t = new acrmi_streams();
+  const size_t state_bytes = (size_t)capacity * 2 * 3 * 64 * sizeof(float);
+  const int r = table_create("acrmi_streams_create", t, device, capacity, state_bytes, state_bytes + (size_t)capacity * 2 * sizeof(int),
+                             shared, stream);
+  if (!r) *out = t;
+  return r;
+}
+
+int acrmi_streams_create(acrmi_streams** out, int device, int capacity) { return streams_create(out, device, capacity, true, nullptr); }
+
+void acrmi_streams_destroy(acrmi_streams* t) { table_destroy(t); }
+
+int acrmi_streams_reset(acrmi_streams* t, const int32_t* ids, int n, void* stream) {
+  return table_reset("acrmi_streams_reset", t, ids, n,
+                     [](StateTable* t, const SmoothIds& k, int m, hipStream_t s) { return launch_smooth_reset(k, m, t->init, s); },
+                     (hipStream_t)stream);
 }
 
 // ids (may be null: every frame is stream 0) are valid for t.  Successive launches of SMOOTH_FRAMES_PER_LAUNCH frames on the
@@ -373,10 +405,7 @@ static int smooth_on(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, const 
 // what acrmi_smooth_streams and acrmi_forward_streams check before anything is launched
 static int check_streams(acrmi_ctx* c, const acrmi_streams* t, const int32_t* ids, int B, const char* who) {
   if (!t || !ids || B <= 0) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
-  if (t->device != c->device) return fail(c, ACRMI_EINVAL, "%s: the table is on device %d, the context on %d", who, t->device, c->device);
-  const int bad = smooth_bad_id(ids, B, t->capacity, -1);
-  if (bad >= 0) return fail(c, ACRMI_EINVAL, "%s: ids[%d] = %d outside -1..%d", who, bad, ids[bad], t->capacity - 1);
-  return ACRMI_OK;
+  return check_table(c, t, ids, B, who);
 }
 
 int acrmi_smooth_streams(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, const int32_t* ids, void* stream) {
@@ -389,14 +418,9 @@ int acrmi_smooth_streams(acrmi_ctx* c, acrmi_streams* t, float* slots, int B, co
 
 int acrmi_smooth_reset(acrmi_ctx* c, void* stream) {
   if (!c) return fail(c, ACRMI_EINVAL, "acrmi_smooth_reset: ctx is NULL");
-  if (!c->own_streams) {      // (a new table is zeroed, on `stream`)
-    const int r = streams_create(&c->own_streams, c->device, 1, false, (hipStream_t)stream);
-    if (r) c->err = g_err;
-    return r;
-  }
-  const int r = acrmi_streams_reset(c->own_streams, nullptr, 0, stream);
-  if (r) c->err = g_err;
-  return r;
+  if (!c->own_streams)      // (a new table is zeroed, on `stream`)
+    return from_global(c, streams_create(&c->own_streams, c->device, 1, false, (hipStream_t)stream));
+  return from_global(c, acrmi_streams_reset(c->own_streams, nullptr, 0, stream));
 }
 
 int acrmi_smooth(acrmi_ctx* c, float* slots, int B, void* stream) {
@@ -418,64 +442,28 @@ int acrmi_tracks_create(acrmi_tracks** out, int device, int capacity, int max_ha
   if (capacity < 1 || (long long)capacity * max_hand > ASSOC_MAX_TRACKS)
     return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: capacity %d x max_hand %d outside 1..%d hands per side", capacity,
                 max_hand, ASSOC_MAX_TRACKS);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) return fail(nullptr, ACRMI_EHIP, "acrmi_tracks_create: no HIP device (%s)", hipGetErrorString(e));
-  if (device < 0 || device >= n) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_create: device %d of %d", device, n);
-  DeviceGuard g(device);
-  if (g.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice: %s", hipGetErrorString(g.err));
   acrmi_tracks* t = new acrmi_tracks();
-  t->device = device;
-  t->capacity = capacity; t->max_hand = max_hand; t->gate = gate; t->max_miss = max_miss;
-  t->last.assign((size_t)capacity, -1);
+  t->max_hand = max_hand; t->gate = gate; t->max_miss = max_miss;
   const size_t hands = (size_t)capacity * max_hand * 2;
   const size_t state_bytes = hands * 3 * 64 * sizeof(float), init_bytes = hands * sizeof(int);
-  const size_t bytes = state_bytes + init_bytes + (size_t)capacity * 2 * sizeof(AssocSide);
-  e = hipMalloc(&t->state, bytes);
-  // zeroed = every slot free, every id counter at 0; complete before the call returns (as acrmi_streams_create)
-  if (e == hipSuccess) e = hipMemset(t->state, 0, bytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->order, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    if (t->state) (void)hipFree(t->state);
-    delete t;
-    return fail(nullptr, ACRMI_EHIP, "acrmi_tracks_create: %d streams of %d hands: %s", capacity, max_hand, hipGetErrorString(e));
-  }
-  t->init = reinterpret_cast<int*>(reinterpret_cast<char*>(t->state) + state_bytes);
+  // (zeroed = every slot free, every id counter at 0)
+  const int r = table_create("acrmi_tracks_create", t, device, capacity, state_bytes,
+                             state_bytes + init_bytes + (size_t)capacity * 2 * sizeof(AssocSide), true, nullptr);
+  if (r) return r;
   t->meta = reinterpret_cast<AssocSide*>(reinterpret_cast<char*>(t->init) + init_bytes);
   *out = t;
   return ACRMI_OK;
 }
 
-void acrmi_tracks_destroy(acrmi_tracks* t) {
-  if (!t) return;
-  DeviceGuard guard_(t->device);
-  if (t->order) (void)hipEventDestroy(t->order);
-  (void)hipFree(t->state);      // (waits for the launches that still use the table)
-  delete t;
-}
+void acrmi_tracks_destroy(acrmi_tracks* t) { table_destroy(t); }
 
 int acrmi_tracks_reset(acrmi_tracks* t, const int32_t* ids, int n, void* stream) {
-  if (!t || (ids && n < 0)) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_reset: bad arguments");
-  if (ids) {
-    const int bad = smooth_bad_id(ids, n, t->capacity, 0);
-    if (bad >= 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_tracks_reset: ids[%d] = %d outside 0..%d", bad, ids[bad], t->capacity - 1);
-  }
-  DeviceGuard guard_(t->device);
-  if (guard_.err != hipSuccess) return fail(nullptr, ACRMI_EHIP, "hipSetDevice(%d): %s", t->device, hipGetErrorString(guard_.err));
-  TableOrder ord(t, (hipStream_t)stream);
-  hipError_t e = ord.err;
-  // init flags and track slots lie next to each other; a filter row behind a cleared init flag is overwritten by its next sample
-  if (e == hipSuccess && !ids)
-    e = hipMemsetAsync(t->init, 0, (size_t)t->capacity * (t->max_hand * 2 * sizeof(int) + 2 * sizeof(AssocSide)), (hipStream_t)stream);
-  for (int i0 = 0; ids && e == hipSuccess && i0 < n; i0 += SMOOTH_FRAMES_PER_LAUNCH) {
-    const int m = n - i0 < SMOOTH_FRAMES_PER_LAUNCH ? n - i0 : SMOOTH_FRAMES_PER_LAUNCH;
-    SmoothIds k{};
-    memcpy(k.id, ids + i0, (size_t)m * sizeof(int32_t));
-    e = launch_assoc_reset(k, m, t->max_hand, t->meta, t->init, (hipStream_t)stream);
-  }
-  e = ord.done(e);
-  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_tracks_reset: %s", hipGetErrorString(e));
+  return table_reset("acrmi_tracks_reset", t, ids, n,
+                     [](StateTable* st, const SmoothIds& k, int m, hipStream_t s) {
+                       acrmi_tracks* t = static_cast<acrmi_tracks*>(st);
+                       return launch_assoc_reset(k, m, t->max_hand, t->meta, t->init, s);
+                     },
+                     (hipStream_t)stream);
 }
 
 // what acrmi_associate and acrmi_forward_tracks check before anything is launched
@@ -483,10 +471,7 @@ static int check_tracks(acrmi_ctx* c, const acrmi_tracks* t, const int32_t* ids,
   if (!t || !ids || B <= 0) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
   if (max_hand < 1 || max_hand > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "%s: max_hand %d outside 1..%d", who, max_hand, ACRMI_MAX_HAND);
   if (max_hand != t->max_hand) return fail(c, ACRMI_EINVAL, "%s: max_hand %d, the table holds %d slots per side", who, max_hand, t->max_hand);
-  if (c && t->device != c->device) return fail(c, ACRMI_EINVAL, "%s: the table is on device %d, the context on %d", who, t->device, c->device);
-  const int bad = smooth_bad_id(ids, B, t->capacity, -1);
-  if (bad >= 0) return fail(c, ACRMI_EINVAL, "%s: ids[%d] = %d outside -1..%d", who, bad, ids[bad], t->capacity - 1);
-  return ACRMI_OK;
+  return check_table(c, t, ids, B, who);
 }
 
 // arguments valid for t.  Successive launches of SMOOTH_FRAMES_PER_LAUNCH frames on the stream, in frame order.
@@ -576,44 +561,38 @@ int acrmi_buffer_dtype(acrmi_ctx* c, int buf) {
   return c->bufs[buf].dtype;
 }
 
+// The decode of the context's head buffers: the classic one, one hand per side, with the optional gate - or (top_k) the
+// max_hand best centres of each side.  Two different paths also at max_hand 1 (acrmi_ops.hip).
+static int decode_ctx(acrmi_ctx* c, const char* who, int B, const int32_t* prior_gate, bool top_k, int max_hand, float* slots,
+                      void* stream) {
+  if (!c || !slots) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (top_k && (max_hand < 1 || max_hand > ACRMI_MAX_HAND))
+    return fail(c, ACRMI_EINVAL, "%s: max_hand %d outside 1..%d", who, max_hand, ACRMI_MAX_HAND);
+  if (!c->have_program) return fail(c, ACRMI_ESTATE, "%s: no program", who);
+  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
+  ON_DEVICE(c);
+  const acrmi_head_layout& h = c->heads;
+  return from_global(c, decode_maps_impl(c->buf_ptr[h.center_buf[0]], c->buf_ptr[h.center_buf[1]], c->bufs[h.center_buf[0]].cs,
+                                         c->buf_ptr[h.params_buf[0]], c->buf_ptr[h.params_buf[1]], c->bufs[h.params_buf[0]].cs,
+                                         c->buf_ptr[h.prior_buf[0]], c->buf_ptr[h.prior_buf[1]], c->bufs[h.prior_buf[0]].cs, B,
+                                         c->conf_thresh, prior_gate, c->range_flag, slots, stream, top_k ? max_hand : 0));
+}
+
 int acrmi_decode(acrmi_ctx* c, int B, float* slots, void* stream) { return acrmi_decode_gated(c, B, nullptr, slots, stream); }
 
 int acrmi_decode_gated(acrmi_ctx* c, int B, const int32_t* prior_gate, float* slots, void* stream) {
-  if (!c || !slots) return fail(c, ACRMI_EINVAL, "acrmi_decode: bad arguments");
-  if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_decode: no program");
-  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
-  ON_DEVICE(c);
-  const acrmi_head_layout& h = c->heads;
-  int r = decode_maps_impl(c->buf_ptr[h.center_buf[0]], c->buf_ptr[h.center_buf[1]], c->bufs[h.center_buf[0]].cs,
-                           c->buf_ptr[h.params_buf[0]], c->buf_ptr[h.params_buf[1]], c->bufs[h.params_buf[0]].cs,
-                           c->buf_ptr[h.prior_buf[0]], c->buf_ptr[h.prior_buf[1]], c->bufs[h.prior_buf[0]].cs, B,
-                           c->conf_thresh, prior_gate, c->range_flag, slots, stream);
-  if (r) c->err = g_err;
-  return r;
+  return decode_ctx(c, "acrmi_decode", B, prior_gate, false, 0, slots, stream);
 }
 
 int acrmi_decode_multi(acrmi_ctx* c, int B, int max_hand, float* slots, void* stream) {
-  if (!c || !slots) return fail(c, ACRMI_EINVAL, "acrmi_decode_multi: bad arguments");
-  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
-    return fail(c, ACRMI_EINVAL, "acrmi_decode_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
-  if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_decode_multi: no program");
-  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
-  ON_DEVICE(c);
-  const acrmi_head_layout& h = c->heads;
-  int r = decode_maps_impl(c->buf_ptr[h.center_buf[0]], c->buf_ptr[h.center_buf[1]], c->bufs[h.center_buf[0]].cs,
-                           c->buf_ptr[h.params_buf[0]], c->buf_ptr[h.params_buf[1]], c->bufs[h.params_buf[0]].cs,
-                           c->buf_ptr[h.prior_buf[0]], c->buf_ptr[h.prior_buf[1]], c->bufs[h.prior_buf[0]].cs, B,
-                           c->conf_thresh, nullptr, c->range_flag, slots, stream, max_hand);
-  if (r) c->err = g_err;
-  return r;
+  return decode_ctx(c, "acrmi_decode_multi", B, nullptr, true, max_hand, slots, stream);
 }
 
 int acrmi_prior_gate(acrmi_ctx* c, const float* slots, int B, int32_t* gate, void* stream) {
   if (!slots || !gate || B <= 0) return fail(c, ACRMI_EINVAL, "acrmi_prior_gate: bad arguments");
   if (c) {
     ON_DEVICE(c);
-    HIPCHK(c, launch_prior_gate(slots, B, gate, (hipStream_t)stream));
-    return ACRMI_OK;
+    return from_global(c, acrmi_prior_gate(nullptr, slots, B, gate, stream));
   }
   HIPCHK(c, launch_prior_gate(slots, B, gate, (hipStream_t)stream));      // stand-alone (like acrmi_decode_maps): current device
   return ACRMI_OK;
@@ -636,48 +615,43 @@ int acrmi_check_range(acrmi_ctx* c, void* stream) {
                                "NaN); use precision 'bf16x3' or 'fp32' for this checkpoint");
 }
 
-int acrmi_mano(acrmi_ctx* c, const float* poses, int pose_stride, const float* betas, int beta_stride,
-               const int32_t* side, int H, int center_idx, float* verts, float* joints, float* center,
-               const float* cam, int cam_stride, const float* offsets, float* verts_camed, float* pj2d,
-               float* pj2d_org, void* stream) {
-  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_mano: ctx is NULL");
+// MANO of H rows the caller names one by one: what acrmi_mano and acrmi_mano_rotmat share.  m holds the poses and whatever
+// only one of the two knows.
+static int mano_rows(acrmi_ctx* c, const char* who, ManoArgs& m, const float* betas, int beta_stride, const int32_t* side, int H,
+                     int center_idx, float* verts, float* joints, float* center, void* stream) {
+  if (!c) return fail(c, ACRMI_EINVAL, "%s: ctx is NULL", who);
   if (H == 0) return ACRMI_OK;    // ManoLayer accepts N == 0 (acr/mano_wrapper.py:43 comment)
-  if (H < 0 || !poses || !betas || !verts || !joints || center_idx >= 21)
-    return fail(c, ACRMI_EINVAL, "acrmi_mano: bad arguments");
-  if (!c->have_mano[0] && !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_mano: MANO tables not loaded");
+  if (H < 0 || !m.poses || !betas || !verts || !joints || center_idx >= 21) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (!c->have_mano[0] && !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "%s: MANO tables not loaded", who);
   ON_DEVICE(c);
-  ManoArgs m{};
   // a context may hold one side only (a lone ManoLayer); rows must then all be of that side
   m.t[0] = c->have_mano[0] ? c->mano[0] : c->mano[1];
   m.t[1] = c->have_mano[1] ? c->mano[1] : c->mano[0];
-  m.poses = poses; m.pose_stride = pose_stride; m.betas = betas; m.beta_stride = beta_stride;
-  m.side = side; m.H = H; m.center_idx = center_idx;
-  m.verts = verts; m.joints = joints; m.center = center;
-  m.cam = cam; m.cam_stride = cam_stride; m.offsets = offsets; m.off_div = 1;
-  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
-  m.lbs_f16 = c->mano_f16;
-  HIPCHK(c, launch_mano(m, (hipStream_t)stream));
-  return ACRMI_OK;
-}
-
-int acrmi_mano_rotmat(acrmi_ctx* c, const float* rotmats, const float* betas, int beta_stride, const int32_t* side, int H,
-                      int center_idx, float* verts, float* joints, float* center, void* stream) {
-  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_mano_rotmat: ctx is NULL");
-  if (H == 0) return ACRMI_OK;
-  if (H < 0 || !rotmats || !betas || !verts || !joints || center_idx >= 21)
-    return fail(c, ACRMI_EINVAL, "acrmi_mano_rotmat: bad arguments");
-  if (!c->have_mano[0] && !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_mano_rotmat: MANO tables not loaded");
-  ON_DEVICE(c);
-  ManoArgs m{};
-  m.t[0] = c->have_mano[0] ? c->mano[0] : c->mano[1];
-  m.t[1] = c->have_mano[1] ? c->mano[1] : c->mano[0];
-  m.poses = rotmats; m.pose_stride = 144; m.pose_rotmat = 1; m.betas = betas; m.beta_stride = beta_stride;
+  m.betas = betas; m.beta_stride = beta_stride;
   m.side = side; m.H = H; m.center_idx = center_idx;
   m.verts = verts; m.joints = joints; m.center = center;
   m.off_div = 1;
   m.lbs_f16 = c->mano_f16;
   HIPCHK(c, launch_mano(m, (hipStream_t)stream));
   return ACRMI_OK;
+}
+
+int acrmi_mano(acrmi_ctx* c, const float* poses, int pose_stride, const float* betas, int beta_stride,
+               const int32_t* side, int H, int center_idx, float* verts, float* joints, float* center,
+               const float* cam, int cam_stride, const float* offsets, float* verts_camed, float* pj2d,
+               float* pj2d_org, void* stream) {
+  ManoArgs m{};
+  m.poses = poses; m.pose_stride = pose_stride;
+  m.cam = cam; m.cam_stride = cam_stride; m.offsets = offsets;
+  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
+  return mano_rows(c, "acrmi_mano", m, betas, beta_stride, side, H, center_idx, verts, joints, center, stream);
+}
+
+int acrmi_mano_rotmat(acrmi_ctx* c, const float* rotmats, const float* betas, int beta_stride, const int32_t* side, int H,
+                      int center_idx, float* verts, float* joints, float* center, void* stream) {
+  ManoArgs m{};
+  m.poses = rotmats; m.pose_stride = 144; m.pose_rotmat = 1;
+  return mano_rows(c, "acrmi_mano_rotmat", m, betas, beta_stride, side, H, center_idx, verts, joints, center, stream);
 }
 
 // The last op that writes the backbone map (heads.backbone_buf) and the channels it leaves there: an op whose out_buf is the
@@ -725,118 +699,111 @@ int acrmi_backbone_channels(acrmi_ctx* c) {
   return c0;
 }
 
-// MANO of the 2 * max_hand * B rows of slots [B,max_hand,2,ACRMI_SLOT] (side = row & 1), placeholders included
-static int mano_multi(acrmi_ctx* c, int B, int max_hand, const float* offsets, float* slots, float* verts, float* joints,
-                      float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream) {
+// ---- the fused forward calls ------------------------------------------------------------------------------------------------
+// MANO of the rows_per_frame * n_frames rows of slots [n_frames,rows_per_frame,ACRMI_SLOT] (side = row & 1), placeholders included
+static int mano_from_slots(acrmi_ctx* c, float* slots, int rows_per_frame, int n_frames, const float* offsets, float* verts,
+                           float* joints, float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream) {
   ManoArgs m{};
   m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
   m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
   m.betas = slots + ACRMI_SLOT_BETAS; m.beta_stride = ACRMI_SLOT;
-  m.side = nullptr; m.H = 2 * max_hand * B; m.center_idx = c->center_idx;      // rows [B,K,2]: side = r & 1
+  m.side = nullptr; m.H = rows_per_frame * n_frames; m.center_idx = c->center_idx;
   m.verts = verts; m.joints = joints; m.center = nullptr;
   const bool proj = verts_camed || pj2d || pj2d_org;
   m.cam = proj ? slots + ACRMI_SLOT_CAM : nullptr; m.cam_stride = ACRMI_SLOT;
-  m.offsets = offsets; m.off_div = 2 * max_hand;
+  m.offsets = offsets; m.off_div = rows_per_frame;
   m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
   m.lbs_f16 = c->mano_f16;
   HIPCHK(c, launch_mano(m, stream));
   return ACRMI_OK;
 }
 
-// decode + MANO of acrmi_forward on one stream
-static int forward_tail(acrmi_ctx* c, int B, const float* offsets, float* slots, float* verts, float* joints,
-                        float* verts_camed, float* pj2d, float* pj2d_org, hipStream_t stream, acrmi_streams* table = nullptr,
-                        const int32_t* ids = nullptr, acrmi_tracks* tracks = nullptr, int track_smooth = 0,
-                        int32_t* track_ids = nullptr) {
-  int r = acrmi_decode(c, B, slots, stream);
+// What distinguishes the four acrmi_forward* calls: the step between decode and MANO (acr/main.py:69-83), and whether the
+// caller names a hand count.
+struct ForwardKind {
+  // OPTION: what ACRMI_OPT_TEMPORAL says - nothing, or the frames as one stream on the context's own table;
+  // STREAMS: `streams` + ids; TRACKS: `tracks` + ids, smooth, track_ids (the track table takes the place of the smoothing)
+  enum { OPTION, STREAMS, TRACKS } temporal = OPTION;
+  bool multi = false;      // acrmi_forward_multi / _tracks: max_hand is the caller's, and the dense heads run whatever
+                           // ACRMI_OPT_POINT_HEADS says (the point heads evaluate the towers at one centre per side)
+  acrmi_streams* streams = nullptr;
+  acrmi_tracks* tracks = nullptr;
+  const int32_t* ids = nullptr;
+  int smooth = 0;
+  int32_t* track_ids = nullptr;
+};
+
+// program + decode + temporal step + MANO on one stream.  max_hand: 0 with the calls that have none; up to 1 the classic decode
+// with every option of acrmi_forward, above the top-K decode.
+static int fused_forward(acrmi_ctx* c, const char* who, const ForwardKind& k, int max_hand, const uint8_t* img, int B,
+                         const float* offsets, float* slots, float* verts, float* joints, float* verts_camed, float* pj2d,
+                         float* pj2d_org, void* stream) {
+  if (!c || !slots || !verts || !joints || (k.temporal == ForwardKind::TRACKS && !k.track_ids))
+    return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  int r = ACRMI_OK;
+  if (k.temporal == ForwardKind::STREAMS) r = check_streams(c, k.streams, k.ids, B, who);
+  else if (k.temporal == ForwardKind::TRACKS) r = check_tracks(c, k.tracks, k.ids, B, max_hand, who);
+  else if (k.multi && (max_hand < 1 || max_hand > ACRMI_MAX_HAND))
+    r = fail(c, ACRMI_EINVAL, "%s: max_hand %d outside 1..%d", who, max_hand, ACRMI_MAX_HAND);
   if (r) return r;
-  if (c->batch_prior && B > 1) {
-    // the reference's batch-wide prior rules (acr/result_parser.py:42-47, 102-145), all on the device: the first decode's flags
-    // and centers -> one decision per frame -> a second decode that applies it (the decode is ~40 us per 64 frames)
-    HIPCHK(c, launch_prior_gate(slots, B, c->gate_buf, stream));
-    if ((r = acrmi_decode_gated(c, B, c->gate_buf, slots, stream))) return r;
+  // the batch-wide prior rules and the smoothing filters know one hand of each side per frame (the reference cannot run
+  // either with more: acr/result_parser.py:134, acr/main.py:77)
+  if (max_hand > 1 && c->batch_prior) return fail(c, ACRMI_EINVAL, "%s: ACRMI_OPT_BATCH_PRIOR with max_hand %d > 1", who, max_hand);
+  if (max_hand > 1 && k.temporal == ForwardKind::OPTION && c->temporal)
+    return fail(c, ACRMI_EINVAL, "%s: ACRMI_OPT_TEMPORAL with max_hand %d > 1", who, max_hand);
+  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "%s: MANO tables not loaded", who);
+  ON_DEVICE(c);
+  if ((r = run_program(c, img, B, stream, k.multi ? false : c->point_heads))) return r;
+  hipStream_t s = (hipStream_t)stream;
+  if (max_hand > 1) {
+    if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
+  } else {
+    if ((r = acrmi_decode(c, B, slots, stream))) return r;
+    if (c->batch_prior && B > 1) {
+      // the reference's batch-wide prior rules (acr/result_parser.py:42-47, 102-145), all on the device: the first decode's flags
+      // and centers -> one decision per frame -> a second decode that applies it (the decode is ~40 us per 64 frames)
+      HIPCHK(c, launch_prior_gate(slots, B, c->gate_buf, s));
+      if ((r = acrmi_decode_gated(c, B, c->gate_buf, slots, stream))) return r;
+    }
   }
-  // acr/main.py:69-83, before MANO: per stream of the caller's table, or (ACRMI_OPT_TEMPORAL) the frames as one stream
-  if (tracks) {      // one slot per side (acrmi_forward_tracks with max_hand 1)
-    if ((r = associate_on(c, tracks, slots, B, ids, track_smooth, track_ids, nullptr, stream))) return r;
-  } else if (table) {
-    if ((r = smooth_on(c, table, slots, B, ids, stream))) return r;
-  } else if (c->temporal && (r = acrmi_smooth(c, slots, B, stream))) return r;
-  ManoArgs m{};
-  m.t[0] = c->mano[0]; m.t[1] = c->mano[1];
-  m.poses = slots + ACRMI_SLOT_POSES; m.pose_stride = ACRMI_SLOT;
-  m.betas = slots + ACRMI_SLOT_BETAS; m.beta_stride = ACRMI_SLOT;
-  m.side = nullptr; m.H = 2 * B; m.center_idx = c->center_idx;
-  m.verts = verts; m.joints = joints; m.center = nullptr;
-  const bool proj = verts_camed || pj2d || pj2d_org;
-  m.cam = proj ? slots + ACRMI_SLOT_CAM : nullptr; m.cam_stride = ACRMI_SLOT;
-  m.offsets = offsets; m.off_div = 2;
-  m.verts_camed = verts_camed; m.pj2d = pj2d; m.pj2d_org = pj2d_org;
-  m.lbs_f16 = c->mano_f16;
-  HIPCHK(c, launch_mano(m, stream));
-  return ACRMI_OK;
+  if (k.temporal == ForwardKind::TRACKS) r = associate_on(c, k.tracks, slots, B, k.ids, k.smooth, k.track_ids, nullptr, s);
+  else if (k.temporal == ForwardKind::STREAMS) r = smooth_on(c, k.streams, slots, B, k.ids, s);
+  else if (c->temporal) r = acrmi_smooth(c, slots, B, stream);
+  if (r) return r;
+  return mano_from_slots(c, slots, max_hand > 1 ? 2 * max_hand : 2, B, offsets, verts, joints, verts_camed, pj2d, pj2d_org, s);
 }
 
 int acrmi_forward(acrmi_ctx* c, const uint8_t* img, int B, const float* offsets, float* slots, float* verts,
                   float* joints, float* verts_camed, float* pj2d, float* pj2d_org, void* stream) {
-  if (!c || !slots || !verts || !joints) return fail(c, ACRMI_EINVAL, "acrmi_forward: bad arguments");
-  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward: MANO tables not loaded");
-  ON_DEVICE(c);
-  int r = run_program(c, img, B, stream, c->point_heads);
-  if (r) return r;
-  return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+  return fused_forward(c, "acrmi_forward", ForwardKind{}, 0, img, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org,
+                       stream);
 }
 
 int acrmi_forward_multi(acrmi_ctx* c, const uint8_t* img, int B, int max_hand, const float* offsets, float* slots, float* verts,
                         float* joints, float* verts_camed, float* pj2d, float* pj2d_org, void* stream) {
-  if (!c || !slots || !verts || !joints) return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: bad arguments");
-  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
-    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
-  // the batch-wide prior rules and the smoothing filters know one hand of each side per frame (the reference cannot run
-  // either with more: acr/result_parser.py:134, acr/main.py:77)
-  if (max_hand > 1 && c->batch_prior)
-    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: ACRMI_OPT_BATCH_PRIOR with max_hand %d > 1", max_hand);
-  if (max_hand > 1 && c->temporal)
-    return fail(c, ACRMI_EINVAL, "acrmi_forward_multi: ACRMI_OPT_TEMPORAL with max_hand %d > 1", max_hand);
-  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_multi: MANO tables not loaded");
-  ON_DEVICE(c);
-  // dense heads whatever ACRMI_OPT_POINT_HEADS says: the point heads evaluate the towers at one center per side
-  int r = run_program(c, img, B, stream, /*point=*/false);
-  if (r) return r;
-  if (max_hand == 1)      // every option of acrmi_forward keeps its meaning
-    return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
-  if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
-  return mano_multi(c, B, max_hand, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+  ForwardKind k;
+  k.multi = true;
+  return fused_forward(c, "acrmi_forward_multi", k, max_hand, img, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org,
+                       stream);
 }
 
 int acrmi_forward_tracks(acrmi_ctx* c, acrmi_tracks* t, const int32_t* ids, int smooth, const uint8_t* img, int B, int max_hand,
                          const float* offsets, float* slots, float* verts, float* joints, float* verts_camed, float* pj2d,
                          float* pj2d_org, int32_t* track_ids, void* stream) {
-  if (!c || !slots || !verts || !joints || !track_ids) return fail(c, ACRMI_EINVAL, "acrmi_forward_tracks: bad arguments");
-  int r = check_tracks(c, t, ids, B, max_hand, "acrmi_forward_tracks");
-  if (r) return r;
-  if (max_hand > 1 && c->batch_prior)
-    return fail(c, ACRMI_EINVAL, "acrmi_forward_tracks: ACRMI_OPT_BATCH_PRIOR with max_hand %d > 1", max_hand);
-  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_tracks: MANO tables not loaded");
-  ON_DEVICE(c);
-  if ((r = run_program(c, img, B, stream, /*point=*/false))) return r;      // dense heads, as acrmi_forward_multi
-  if (max_hand == 1)      // the decode of acrmi_forward with its options; the track table takes the place of the smoothing
-    return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream, nullptr, ids, t,
-                        smooth, track_ids);
-  if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;
-  if ((r = associate_on(c, t, slots, B, ids, smooth, track_ids, nullptr, (hipStream_t)stream))) return r;
-  return mano_multi(c, B, max_hand, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream);
+  ForwardKind k;
+  k.temporal = ForwardKind::TRACKS; k.multi = true;
+  k.tracks = t; k.ids = ids; k.smooth = smooth; k.track_ids = track_ids;
+  return fused_forward(c, "acrmi_forward_tracks", k, max_hand, img, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org,
+                       stream);
 }
 
 int acrmi_forward_streams(acrmi_ctx* c, acrmi_streams* t, const int32_t* ids, const uint8_t* img, int B, const float* offsets,
                           float* slots, float* verts, float* joints, float* verts_camed, float* pj2d, float* pj2d_org, void* stream) {
-  if (!c || !slots || !verts || !joints) return fail(c, ACRMI_EINVAL, "acrmi_forward_streams: bad arguments");
-  int r = check_streams(c, t, ids, B, "acrmi_forward_streams");
-  if (r) return r;
-  if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_forward_streams: MANO tables not loaded");
-  ON_DEVICE(c);
-  if ((r = run_program(c, img, B, stream, c->point_heads))) return r;
-  return forward_tail(c, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org, (hipStream_t)stream, t, ids);
+  ForwardKind k;
+  k.temporal = ForwardKind::STREAMS;
+  k.streams = t; k.ids = ids;
+  return fused_forward(c, "acrmi_forward_streams", k, 0, img, B, offsets, slots, verts, joints, verts_camed, pj2d, pj2d_org,
+                       stream);
 }
 
 // ---- mesh overlay (csrc/render.hip) --------------------------------------------------------------------------------
@@ -866,24 +833,51 @@ int acrmi_load_faces(acrmi_ctx* c, int side, const int32_t* faces_host, int n_fa
 }
 
 // The context's render scratch for B frames (or regions) of two hands: [mesh_frame | mesh_topo | rgb | view rows] and the
-// rasteriser's workspace behind them.  The head is sized for one view row per MESH, the larger of the two layouts.  Allocates
-// at the first call and when B grows: the one place the render calls allocate.
-static size_t render_head_bytes(int B, bool per_mesh) {
+// rasteriser's workspace behind them.  The head is sized for one view row per MESH, the larger of the two layouts.
+struct RenderScratch {
+  int32_t *mesh_frame, *mesh_topo;      // [2B] each
+  float *rgb, *view;                    // [2B,3]; [B,4] per frame or [2B,4] per mesh
+  char* ws;
+};
+static size_t render_head_bytes(int B) {
   const size_t M = 2 * (size_t)B;
-  return (M * 4 * 2 + M * 3 * 4 + (per_mesh ? M : (size_t)B) * 4 * 4 + 255) / 256 * 256;
+  return (M * 4 * 2 + M * 3 * 4 + M * 4 * 4 + 255) / 256 * 256;
 }
 
-static int render_ws_reserve(acrmi_ctx* c, int B) {
-  if (B <= c->render_ws_frames) return ACRMI_OK;
-  if (c->render_ws) {
-    HIPCHK(c, hipDeviceSynchronize());
-    (void)hipFree(c->render_ws);
-    c->render_ws = nullptr;
-    c->render_ws_frames = 0;
+// Allocates at the first call and when B grows: the one place the render calls allocate.
+static int render_scratch(acrmi_ctx* c, int B, RenderScratch* sc) {
+  if (B > c->render_ws_frames) {
+    if (c->render_ws) {
+      HIPCHK(c, hipDeviceSynchronize());
+      (void)hipFree(c->render_ws);
+      c->render_ws = nullptr;
+      c->render_ws_frames = 0;
+    }
+    HIPCHK(c, hipMalloc(&c->render_ws, render_head_bytes(B) + render_workspace_bytes(2 * B, c->n_faces[0])));
+    c->render_ws_frames = B;
   }
-  HIPCHK(c, hipMalloc(&c->render_ws, render_head_bytes(B, true) + render_workspace_bytes(2 * B, c->n_faces[0])));
-  c->render_ws_frames = B;
+  sc->mesh_frame = (int32_t*)c->render_ws;
+  sc->mesh_topo = sc->mesh_frame + 2 * B;
+  sc->rgb = (float*)(sc->mesh_topo + 2 * B);
+  sc->view = sc->rgb + 3 * 2 * B;
+  sc->ws = c->render_ws + render_head_bytes(B);
   return ACRMI_OK;
+}
+
+// the reference's colours by hand type (acr/visualization.py:76), as RGB
+static const float kHandColors[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};
+
+// the n_meshes hands the prep kernel described in sc, drawn into n_frames frames; one of view / mesh_view (or neither)
+static hipError_t render_launch(const acrmi_ctx* c, const RenderScratch& sc, const float* verts, const float* cam_trans,
+                                const float* view, const float* mesh_view, float focal, float visible_weight, const uint8_t* img_in,
+                                uint8_t* img_out, int32_t* ids_out, int n_meshes, int n_frames, int H, int W, hipStream_t stream) {
+  RenderArgs a{};
+  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
+  a.mesh_topo = sc.mesh_topo; a.mesh_frame = sc.mesh_frame; a.rgb = sc.rgb; a.view = view; a.mesh_view = mesh_view;
+  a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
+  a.ws = sc.ws;
+  a.n_meshes = n_meshes; a.n_verts = 778; a.n_faces = c->n_faces[0]; a.n_frames = n_frames; a.H = H; a.W = W;
+  return launch_render(a, stream);
 }
 
 int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
@@ -894,68 +888,77 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
     return fail(c, ACRMI_EINVAL, "acrmi_render: bad arguments");
   if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "acrmi_render: MANO faces not loaded (acrmi_load_faces)");
   ON_DEVICE(c);
-  const int M = 2 * B, F = c->n_faces[0];
-  const size_t head = (size_t)M * 4 * 2 + (size_t)M * 3 * 4 + (size_t)B * 4 * 4;      // mesh_frame, mesh_topo, rgb, view
-  const size_t head_al = (head + 255) / 256 * 256;
-  if (int r = render_ws_reserve(c, B)) return r;
-  int32_t* mesh_frame = (int32_t*)c->render_ws;
-  int32_t* mesh_topo = mesh_frame + M;
-  float* rgb = (float*)(mesh_topo + M);
-  float* view = rgb + 3 * M;
-  // the reference's colours by hand type (acr/visualization.py:76), as RGB
-  static const float kDefault[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};
-  hipError_t e = launch_render_prep(slots, offsets, B, ACRMI_SLOT, ACRMI_SLOT_FLAG, colors_host ? colors_host : kDefault,
-                                    mesh_frame, mesh_topo, rgb, view, (hipStream_t)stream);
+  RenderScratch sc;
+  if (int r = render_scratch(c, B, &sc)) return r;
+  hipError_t e = launch_render_prep(slots, offsets, B, ACRMI_SLOT, ACRMI_SLOT_FLAG, colors_host ? colors_host : kHandColors,
+                                    sc.mesh_frame, sc.mesh_topo, sc.rgb, sc.view, (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render prep: %s", hipGetErrorString(e));
-  RenderArgs a{};
-  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
-  a.mesh_topo = mesh_topo; a.mesh_frame = mesh_frame; a.rgb = rgb; a.view = offsets ? view : nullptr;
-  a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
-  a.ws = c->render_ws + head_al;
-  a.n_meshes = M; a.n_verts = 778; a.n_faces = F; a.n_frames = B; a.H = H; a.W = W;
-  e = launch_render(a, (hipStream_t)stream);
+  e = render_launch(c, sc, verts, cam_trans, offsets ? sc.view : nullptr, nullptr, focal, visible_weight, img_in, img_out, ids_out,
+                    2 * B, B, H, W, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render: %s", hipGetErrorString(e));
 }
 
 // ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------
+// what acrmi_overlay (n = n_frames = its batch) and acrmi_overlay_regions check first
+static int check_overlay(acrmi_ctx* c, const char* who, int what, const float* slots, const float* kps, int n, const uint8_t* img_in,
+                         const uint8_t* out, const uint8_t* out2, int n_frames, int H, int W) {
+  if (!c || !img_in || !out || n <= 0 || n_frames <= 0 || n_frames > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM ||
+      W > OVERLAY_MAX_DIM || (what != ACRMI_OVERLAY_SKELETON && what != ACRMI_OVERLAY_CENTERMAP))
+    return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (what == ACRMI_OVERLAY_SKELETON ? (!slots || !kps) : (!out2 || out2 == out || out2 == img_in))
+    return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "%s: no program has run", who);
+  return ACRMI_OK;
+}
+
+// the skeletons of n_hands hands, each drawn where its slot's flag says (hand h in frame h / 2) or into hand_frame[h]
+static hipError_t skeleton_launch(const float* kps, const float* slots, const int32_t* hand_frame, int normalized, int n_hands,
+                                  int n_frames, int H, int W, int bgr, const uint8_t* img_in, uint8_t* out, hipStream_t stream) {
+  SkeletonArgs a{};
+  a.kps = kps; a.hand_frame = hand_frame; a.normalized = normalized;
+  if (slots) { a.slots = slots; a.slot_stride = ACRMI_SLOT; a.flag_at = ACRMI_SLOT_FLAG; }
+  a.n_hands = n_hands; a.n_frames = n_frames; a.H = H; a.W = W; a.line_width = 3; a.circle_rad = 3;
+  a.img_in = img_in; a.img_out = out;
+  skeleton_default_colors(bgr != 0, a.colors);
+  return launch_skeleton(a, stream);
+}
+
+// What HeatmapArgs and RegionHeatmapArgs share: the maps are the head buffers the last program run left for n frames (NHWC,
+// channel 0, the buffer's channel stride between two cells); a 16-bit storage program's are converted to fp32 as the kernels
+// stage them in LDS.
+extern "C++" {
+template <class Args>
+static int heatmap_fill(acrmi_ctx* c, const char* who, Args& a, int n, const float* offsets, int bgr, const uint8_t* img_in,
+                        uint8_t* out, uint8_t* out2, int H, int W) {
+  if (n != c->last_batch)
+    return fail(c, ACRMI_ESTATE, "%s: the resident centre maps are those of a batch of %d, not %d", who, c->last_batch, n);
+  const acrmi_head_layout& hl = c->heads;
+  const acrmi_buffer_desc& d = c->bufs[hl.center_buf[0]];
+  a.maps[0] = c->buf_ptr[hl.center_buf[0]]; a.maps[1] = c->buf_ptr[hl.center_buf[1]];
+  a.pix_stride = d.cs; a.frame_stride = (long long)d.h * d.w * d.cs; a.dtype = d.dtype;
+  a.n = n; a.h = d.h; a.w = d.w; a.H = H; a.W = W; a.offsets = offsets; a.weight = 0.7f;
+  a.img_in = img_in; a.out[0] = out; a.out[1] = out2;
+  heatmap_default_lut(bgr != 0, a.lut);
+  return ACRMI_OK;
+}
+}      // extern "C++"
+
 int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d, int B, const float* offsets, int bgr,
                   const uint8_t* img_in, uint8_t* out, uint8_t* out2, int H, int W, void* stream) {
-  if (!c || !img_in || !out || B <= 0 || B > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM ||
-      (what != ACRMI_OVERLAY_SKELETON && what != ACRMI_OVERLAY_CENTERMAP))
-    return fail(c, ACRMI_EINVAL, "acrmi_overlay: bad arguments");
-  if (what == ACRMI_OVERLAY_SKELETON ? (!slots || !pj2d) : (!out2 || out2 == out || out2 == img_in))
-    return fail(c, ACRMI_EINVAL, "acrmi_overlay: bad arguments");
-  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "acrmi_overlay: no program has run");
+  if (int r = check_overlay(c, "acrmi_overlay", what, slots, pj2d, B, img_in, out, out2, B, H, W)) return r;
   ON_DEVICE(c);
   hipError_t e;
   if (what == ACRMI_OVERLAY_SKELETON) {
-    SkeletonArgs a{};
-    a.kps = pj2d; a.slots = slots; a.slot_stride = ACRMI_SLOT; a.flag_at = ACRMI_SLOT_FLAG; a.normalized = offsets ? 0 : 1;
-    a.n_hands = 2 * B; a.n_frames = B; a.H = H; a.W = W; a.line_width = 3; a.circle_rad = 3;
-    a.img_in = img_in; a.img_out = out;
-    skeleton_default_colors(bgr != 0, a.colors);
-    e = launch_skeleton(a, (hipStream_t)stream);
+    e = skeleton_launch(pj2d, slots, nullptr, offsets ? 0 : 1, 2 * B, B, H, W, bgr, img_in, out, (hipStream_t)stream);
   } else {
-    // the maps are the head buffers the last program run left (NHWC, channel 0, the buffer's channel stride between two
-    // cells); a 16-bit storage program's are converted to fp32 as heatmap_kernel stages them in LDS
-    if (B != c->last_batch)
-      return fail(c, ACRMI_ESTATE, "acrmi_overlay: the resident centre maps are those of a batch of %d, not %d", c->last_batch, B);
-    const acrmi_head_layout& hl = c->heads;
-    const acrmi_buffer_desc& d = c->bufs[hl.center_buf[0]];
     HeatmapArgs a{};
-    a.maps[0] = c->buf_ptr[hl.center_buf[0]]; a.maps[1] = c->buf_ptr[hl.center_buf[1]];
-    a.pix_stride = d.cs; a.frame_stride = (long long)d.h * d.w * d.cs; a.dtype = d.dtype;
-    a.n = B; a.h = d.h; a.w = d.w; a.H = H; a.W = W; a.offsets = offsets; a.weight = 0.7f;
-    a.img_in = img_in; a.out[0] = out; a.out[1] = out2;
-    heatmap_default_lut(bgr != 0, a.lut);
+    if (int r = heatmap_fill(c, "acrmi_overlay", a, B, offsets, bgr, img_in, out, out2, H, W)) return r;
     e = launch_heatmap(a, (hipStream_t)stream);
   }
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay: %s", hipGetErrorString(e));
 }
 
 // ---- views over regions (DESIGN.md "Views over regions") ------------------------------------------------------------------
-static const float kHandColors[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};      // acr/visualization.py:76, as RGB
-
 int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int n, const float* offsets,
                          const int32_t* region_frame, const float* colors_host, float focal, float visible_weight,
                          const uint8_t* img_in, uint8_t* img_out, int n_frames, int H, int W, int32_t* ids_out, void* stream) {
@@ -966,36 +969,22 @@ int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_tran
   if (!c->faces_topo[0] || !c->faces_topo[1])
     return fail(c, ACRMI_ESTATE, "acrmi_render_regions: MANO faces not loaded (acrmi_load_faces)");
   ON_DEVICE(c);
-  const int M = 2 * n, F = c->n_faces[0];
-  if (int r = render_ws_reserve(c, n)) return r;
-  int32_t* mesh_frame = (int32_t*)c->render_ws;
-  int32_t* mesh_topo = mesh_frame + M;
-  float* rgb = (float*)(mesh_topo + M);
-  float* mesh_view = rgb + 3 * M;
+  RenderScratch sc;
+  if (int r = render_scratch(c, n, &sc)) return r;
   hipError_t e = launch_render_region_prep(slots, offsets, region_frame, n, n_frames, H, W, ACRMI_SLOT, ACRMI_SLOT_FLAG,
-                                           colors_host ? colors_host : kHandColors, mesh_frame, mesh_topo, rgb, mesh_view,
+                                           colors_host ? colors_host : kHandColors, sc.mesh_frame, sc.mesh_topo, sc.rgb, sc.view,
                                            (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render region prep: %s", hipGetErrorString(e));
-  RenderArgs a{};
-  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
-  a.mesh_topo = mesh_topo; a.mesh_frame = mesh_frame; a.rgb = rgb; a.mesh_view = mesh_view;
-  a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
-  a.ws = c->render_ws + render_head_bytes(n, true);
-  a.n_meshes = M; a.n_verts = 778; a.n_faces = F; a.n_frames = n_frames; a.H = H; a.W = W;
-  e = launch_render(a, (hipStream_t)stream);
+  e = render_launch(c, sc, verts, cam_trans, nullptr, sc.view, focal, visible_weight, img_in, img_out, ids_out, 2 * n, n_frames, H, W,
+                    (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render regions: %s", hipGetErrorString(e));
 }
 
 int acrmi_overlay_regions(acrmi_ctx* c, int what, const float* slots, const float* pj2d_org, int n, const float* offsets,
                           const int32_t* region_frame, int bgr, const uint8_t* img_in, uint8_t* out, uint8_t* out2, int n_frames,
                           int H, int W, void* stream) {
-  if (!c || !offsets || !region_frame || !img_in || !out || n <= 0 || n > 0x3fffffff || n_frames <= 0 ||
-      n_frames > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM ||
-      (what != ACRMI_OVERLAY_SKELETON && what != ACRMI_OVERLAY_CENTERMAP))
-    return fail(c, ACRMI_EINVAL, "acrmi_overlay_regions: bad arguments");
-  if (what == ACRMI_OVERLAY_SKELETON ? (!slots || !pj2d_org) : (!out2 || out2 == out || out2 == img_in))
-    return fail(c, ACRMI_EINVAL, "acrmi_overlay_regions: bad arguments");
-  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "acrmi_overlay_regions: no program has run");
+  if (!offsets || !region_frame || n > 0x3fffffff) return fail(c, ACRMI_EINVAL, "acrmi_overlay_regions: bad arguments");
+  if (int r = check_overlay(c, "acrmi_overlay_regions", what, slots, pj2d_org, n, img_in, out, out2, n_frames, H, W)) return r;
   ON_DEVICE(c);
   hipError_t e;
   if (what == ACRMI_OVERLAY_SKELETON) {
@@ -1012,23 +1001,11 @@ int acrmi_overlay_regions(acrmi_ctx* c, int what, const float* slots, const floa
     e = launch_render_region_prep(slots, offsets, region_frame, n, n_frames, H, W, ACRMI_SLOT, ACRMI_SLOT_FLAG, nullptr,
                                   c->region_hand_frame, nullptr, nullptr, nullptr, (hipStream_t)stream);
     if (e != hipSuccess) return fail(c, ACRMI_EHIP, "overlay region prep: %s", hipGetErrorString(e));
-    SkeletonArgs a{};
-    a.kps = pj2d_org; a.hand_frame = c->region_hand_frame; a.n_hands = 2 * n; a.n_frames = n_frames; a.H = H; a.W = W;
-    a.line_width = 3; a.circle_rad = 3; a.img_in = img_in; a.img_out = out;
-    skeleton_default_colors(bgr != 0, a.colors);
-    e = launch_skeleton(a, (hipStream_t)stream);
+    e = skeleton_launch(pj2d_org, nullptr, c->region_hand_frame, 0, 2 * n, n_frames, H, W, bgr, img_in, out, (hipStream_t)stream);
   } else {
-    if (n != c->last_batch)
-      return fail(c, ACRMI_ESTATE, "acrmi_overlay_regions: the resident centre maps are those of a batch of %d, not %d",
-                  c->last_batch, n);
-    const acrmi_head_layout& hl = c->heads;
-    const acrmi_buffer_desc& d = c->bufs[hl.center_buf[0]];
     RegionHeatmapArgs a{};
-    a.maps[0] = c->buf_ptr[hl.center_buf[0]]; a.maps[1] = c->buf_ptr[hl.center_buf[1]];
-    a.pix_stride = d.cs; a.frame_stride = (long long)d.h * d.w * d.cs; a.dtype = d.dtype;
-    a.n = n; a.h = d.h; a.w = d.w; a.n_frames = n_frames; a.H = H; a.W = W; a.offsets = offsets; a.region_frame = region_frame;
-    a.weight = 0.7f; a.img_in = img_in; a.out[0] = out; a.out[1] = out2;
-    heatmap_default_lut(bgr != 0, a.lut);
+    if (int r = heatmap_fill(c, "acrmi_overlay_regions", a, n, offsets, bgr, img_in, out, out2, H, W)) return r;
+    a.n_frames = n_frames; a.region_frame = region_frame;
     e = launch_region_heatmap(a, (hipStream_t)stream);
   }
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay regions: %s", hipGetErrorString(e));

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -37,32 +38,30 @@ struct Schedule {
   std::vector<std::vector<int>> wait;
   std::vector<char> signal;
 };
-// One-Euro filter state of `capacity` video streams (acrmi_streams_create), owned outside any context: the contexts of a
-// pool share one, and it outlives a context that a checkpoint reload replaces.
-struct acrmi_streams {
+// Per-stream state on one device, owned outside any context: what acrmi_streams and acrmi_tracks share.
+struct StateTable {
   int device = 0;
-  int capacity = 0;
-  float* state = nullptr;       // [capacity][2 hands][x_raw | x_filt | dx_filt][64], then the init flags int [capacity][2]
-  int* init = nullptr;
+  int capacity = 0;             // video streams
+  float* state = nullptr;       // one allocation: the One-Euro rows [x_raw | x_filt | dx_filt][64] per hand, then `init`, then the rest
+  int* init = nullptr;          // one flag per hand
+  size_t reset_bytes = 0;       // from `init` to the end of the allocation: what a reset of every stream clears
   // Every launch that touches the table makes its stream wait for `order` and records it again, under `mu`: contexts on
   // different streams update the table in the order of their calls.  null: a context's own table (one stream at a time).
   hipEvent_t order = nullptr;
   std::mutex mu;
   std::vector<int32_t> last;    // smooth_plan's scratch, all -1 between calls
+  virtual ~StateTable() = default;      // (created and destroyed as the base: table_create / table_destroy in acrmi.hip)
 };
 
+// One-Euro filter state of `capacity` video streams (acrmi_streams_create): state [capacity][2 hands], init [capacity][2].  The
+// contexts of a pool share one, and it outlives a context that a checkpoint reload replaces.
+struct acrmi_streams : StateTable {};
+
 // The tracks of `capacity` video streams with max_hand slots per side (acrmi_tracks_create; assoc_plan.h): per slot a One-Euro
-// state row in acrmi_streams' layout, per (stream, side) an AssocSide.  Owned outside any context and ordered between
-// contexts like acrmi_streams.
-struct acrmi_tracks {
-  int device = 0;
-  int capacity = 0, max_hand = 0, gate = 0, max_miss = 0;
-  float* state = nullptr;       // [capacity][max_hand][2][x_raw | x_filt | dx_filt][64], then init, then meta (one allocation)
-  int* init = nullptr;          // [capacity][max_hand][2]
-  AssocSide* meta = nullptr;    // [capacity][2]
-  hipEvent_t order = nullptr;
-  std::mutex mu;
-  std::vector<int32_t> last;    // smooth_plan's scratch, all -1 between calls
+// state row in acrmi_streams' layout, per (stream, side) an AssocSide.  Ordered between contexts like acrmi_streams.
+struct acrmi_tracks : StateTable {      // state [capacity][max_hand][2], init [capacity][max_hand][2]
+  int max_hand = 0, gate = 0, max_miss = 0;
+  AssocSide* meta = nullptr;    // [capacity][2], behind init
 };
 
 struct acrmi_ctx {

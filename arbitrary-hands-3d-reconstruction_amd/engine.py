@@ -64,26 +64,26 @@ def stream_args(streams, table, B):
     return stream_ids(streams, B)
 
 
-class StreamTable(object):
-    """One-Euro filter state of `capacity` video streams on one GPU (acrmi_streams; acr/main.py:50-53 keeps one filter set
-    per video): what `Engine.smooth(..., streams=, table=)` / `Engine.forward(..., streams=, table=)` update.  It belongs to
-    no Engine: the contexts of an EnginePool share one (the library orders their updates by the order of the calls), and
-    it outlives an Engine that a checkpoint reload replaces.  Every stream starts fresh."""
+class _Table(object):
+    """What StreamTable and TrackTable share: a table of the library on one GPU that belongs to no Engine.  A subclass names
+    the library's three calls (`_calls`: create, reset, destroy) and what it is called (`_name`)."""
+    _calls = _name = None
 
-    def __init__(self, device=0, capacity=64):
+    def _open(self, device, capacity, *params):
         self.L = _lib.lib()
         self.device = torch.device('cuda', device if isinstance(device, int) else torch.device(device).index or 0)
         self.capacity = int(capacity)
         self.handle = None
         h = C.c_void_p()
-        _lib.check(self.L.acrmi_streams_create(C.byref(h), self.device.index, self.capacity))
+        _lib.check(getattr(self.L, self._calls[0])(C.byref(h), self.device.index, self.capacity, *params))
         self.handle = h
 
     def reset(self, ids=None):
-        """The listed streams - every stream when ids is None - start a new sequence: their next sample passes through.
-        Queued on the current stream, ordered with the smoothing calls of every context."""
+        """The listed streams - every stream when ids is None - start afresh.  A StreamTable: they start a new sequence, their
+        next sample passes through.  A TrackTable: they lose their tracks, every slot free, ids from 0 again.  Queued on the
+        current stream, ordered with the smoothing / association calls of every context."""
         if self.handle is None:
-            raise ValueError('the StreamTable is closed')
+            raise ValueError('the %s is closed' % self._name)
         arr, n = None, 0
         if ids is not None:
             a = np.atleast_1d(np.asarray(ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else ids))
@@ -91,12 +91,12 @@ class StreamTable(object):
                 return
             a = stream_ids(a, a.shape[0])
             arr, n = a.ctypes.data_as(C.c_void_p), a.shape[0]
-        _lib.check(self.L.acrmi_streams_reset(self.handle, arr, n, _stream(self.device)))
+        _lib.check(getattr(self.L, self._calls[1])(self.handle, arr, n, _stream(self.device)))
 
     def close(self):
         h, self.handle = self.handle, None
         if h:
-            self.L.acrmi_streams_destroy(h)
+            getattr(self.L, self._calls[2])(h)
 
     def __del__(self):
         try:
@@ -105,46 +105,28 @@ class StreamTable(object):
             pass
 
 
-class TrackTable(object):
+class StreamTable(_Table):
+    """One-Euro filter state of `capacity` video streams on one GPU (acrmi_streams; acr/main.py:50-53 keeps one filter set
+    per video): what `Engine.smooth(..., streams=, table=)` / `Engine.forward(..., streams=, table=)` update.  It belongs to
+    no Engine: the contexts of an EnginePool share one (the library orders their updates by the order of the calls), and
+    it outlives an Engine that a checkpoint reload replaces.  Every stream starts fresh."""
+    _calls, _name = ('acrmi_streams_create', 'acrmi_streams_reset', 'acrmi_streams_destroy'), 'StreamTable'
+
+    def __init__(self, device=0, capacity=64):
+        self._open(device, capacity)
+
+
+class TrackTable(_Table):
     """The tracks of `capacity` video streams with max_hand slots per side on one GPU (acrmi_tracks):
     what `Engine.associate(..., tracks=, table=)` / `Engine.forward(..., max_hand=K, tracks=, track_table=)` update.  gate: the
     largest centre distance in map pixels at which a hand continues a track (0..128, 128 = any); max_miss: how many frames a
     track may go unseen and still be continued (-1 = for ever).  8 and 5 are defaults of parameters, not measurements.  Like a
     StreamTable it belongs to no Engine, and the library orders the updates of several contexts by the order of the calls."""
+    _calls, _name = ('acrmi_tracks_create', 'acrmi_tracks_reset', 'acrmi_tracks_destroy'), 'TrackTable'
 
     def __init__(self, device=0, capacity=64, max_hand=2, gate=8, max_miss=5):
-        self.L = _lib.lib()
-        self.device = torch.device('cuda', device if isinstance(device, int) else torch.device(device).index or 0)
-        self.capacity, self.max_hand, self.gate, self.max_miss = int(capacity), check_max_hand(max_hand), int(gate), int(max_miss)
-        self.handle = None
-        h = C.c_void_p()
-        _lib.check(self.L.acrmi_tracks_create(C.byref(h), self.device.index, self.capacity, self.max_hand, self.gate, self.max_miss))
-        self.handle = h
-
-    def reset(self, ids=None):
-        """The listed streams - every stream when ids is None - lose their tracks: every slot free, ids from 0 again.
-        Queued on the current stream, ordered with the association calls of every context."""
-        if self.handle is None:
-            raise ValueError('the TrackTable is closed')
-        arr, n = None, 0
-        if ids is not None:
-            a = np.atleast_1d(np.asarray(ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else ids))
-            if a.size == 0:
-                return
-            a = stream_ids(a, a.shape[0])
-            arr, n = a.ctypes.data_as(C.c_void_p), a.shape[0]
-        _lib.check(self.L.acrmi_tracks_reset(self.handle, arr, n, _stream(self.device)))
-
-    def close(self):
-        h, self.handle = self.handle, None
-        if h:
-            self.L.acrmi_tracks_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.max_hand, self.gate, self.max_miss = check_max_hand(max_hand), int(gate), int(max_miss)
+        self._open(device, capacity, self.max_hand, self.gate, self.max_miss)
 
 
 def track_args(tracks, track_table, streams, table, K, B):
@@ -626,69 +608,52 @@ class Engine(object):
         slots - the decoded hands are put into track order and (smooth) each track is smoothed with its own filter before MANO
         (acrmi_forward_tracks); the output gains 'track_ids' int32 [B,K,2] and has the [B,K,...] shapes also for K = 1.  Not
         together with streams= / table=."""
-        max_hand = check_max_hand(max_hand)
-        if max_hand > 1 or tracks is not None or track_table is not None:
-            return self._forward_multi(img, offsets, project, out, stream, streams, table, max_hand, tracks, track_table, smooth)
-        img = self._check_img(img)
-        B = img.shape[0]
-        ids = stream_args(streams, table, B)
-        self.ensure_batch(B)
-        dev = self.device
-        if out is None:
-            out = {'slots': torch.empty(B, 2, _lib.SLOT, dtype=torch.float32, device=dev),
-                   'verts': torch.empty(B, 2, 778, 3, dtype=torch.float32, device=dev),
-                   'joints': torch.empty(B, 2, 21, 3, dtype=torch.float32, device=dev)}
-            if project:
-                out['verts_camed'] = torch.empty(B, 2, 778, 3, dtype=torch.float32, device=dev)
-                out['pj2d'] = torch.empty(B, 2, 21, 2, dtype=torch.float32, device=dev)
-                if offsets is not None:
-                    out['pj2d_org'] = torch.empty(B, 2, 21, 2, dtype=torch.float32, device=dev)
-        if offsets is not None:
-            offsets = offsets.to(dev, torch.float32).contiguous()
-        args = (_ptr(img), B, _ptr(offsets), _ptr(out['slots']), _ptr(out['verts']), _ptr(out['joints']),
-                _ptr(out.get('verts_camed')), _ptr(out.get('pj2d')), _ptr(out.get('pj2d_org')),
-                _stream(dev) if stream is None else C.c_void_p(stream))
-        if ids is None:
-            _lib.check(self.L.acrmi_forward(self.ctx, *args), self.ctx)
-        else:
-            _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), *args), self.ctx)
-        return out
-
-    def _forward_multi(self, img, offsets, project, out, stream, streams, table, K, tracks=None, track_table=None, smooth=True):
-        if tracks is None and track_table is None and (streams is not None or table is not None):
+        K = check_max_hand(max_hand)
+        multi = K > 1 or tracks is not None or track_table is not None      # the [B,K,...] shapes
+        if K > 1 and tracks is None and track_table is None and (streams is not None or table is not None):
             raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
         img = self._check_img(img)
         B = img.shape[0]
-        ids = track_args(tracks, track_table, streams, table, K, B)
+        ids = track_args(tracks, track_table, streams, table, K, B) if multi else stream_args(streams, table, B)
         self.ensure_batch(B)
         dev = self.device
-        if out is None:
-            out = {'slots': torch.empty(B, K, 2, _lib.SLOT, dtype=torch.float32, device=dev),
-                   'verts': torch.empty(B, K, 2, 778, 3, dtype=torch.float32, device=dev),
-                   'joints': torch.empty(B, K, 2, 21, 3, dtype=torch.float32, device=dev)}
-            if project:
-                out['verts_camed'] = torch.empty(B, K, 2, 778, 3, dtype=torch.float32, device=dev)
-                out['pj2d'] = torch.empty(B, K, 2, 21, 2, dtype=torch.float32, device=dev)
-                if offsets is not None:
-                    out['pj2d_org'] = torch.empty(B, K, 2, 21, 2, dtype=torch.float32, device=dev)
-        elif tuple(out['slots'].shape) != (B, K, 2, _lib.SLOT) or tuple(out['verts'].shape) != (B, K, 2, 778, 3):
-            raise ValueError('out does not hold %d frames of %d hand pairs' % (B, K))
+        out = self._outputs(out, (B, K, 2) if multi else (B, 2), project, offsets is not None)
         if offsets is not None:
             offsets = offsets.to(dev, torch.float32).contiguous()
-            if tuple(offsets.shape) != (B, 10):
+            if multi and tuple(offsets.shape) != (B, 10):
                 raise ValueError('offsets must be [B,10]: one row per frame')
         tail = (_ptr(offsets), _ptr(out['slots']), _ptr(out['verts']), _ptr(out['joints']), _ptr(out.get('verts_camed')),
                 _ptr(out.get('pj2d')), _ptr(out.get('pj2d_org')))
         raw = _stream(dev) if stream is None else C.c_void_p(stream)
-        if ids is None:
+        if not multi and ids is None:
+            _lib.check(self.L.acrmi_forward(self.ctx, _ptr(img), B, *tail, raw), self.ctx)
+        elif not multi:
+            _lib.check(self.L.acrmi_forward_streams(self.ctx, table.handle, ids.ctypes.data_as(C.c_void_p), _ptr(img), B, *tail, raw),
+                       self.ctx)
+        elif ids is None:
             _lib.check(self.L.acrmi_forward_multi(self.ctx, _ptr(img), B, K, *tail, raw), self.ctx)
+        else:
+            if out.get('track_ids') is None:
+                out['track_ids'] = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
+            elif tuple(out['track_ids'].shape) != (B, K, 2) or out['track_ids'].dtype != torch.int32 or not out['track_ids'].is_contiguous():
+                raise ValueError("out['track_ids'] must be a contiguous int32 tensor [B,K,2]")
+            _lib.check(self.L.acrmi_forward_tracks(self.ctx, track_table.handle, ids.ctypes.data_as(C.c_void_p), int(bool(smooth)),
+                                                   _ptr(img), B, K, *tail, _ptr(out['track_ids']), raw), self.ctx)
+        return out
+
+    def _outputs(self, out, lead, project, org):
+        """The result tensors of `forward` for the leading shape `lead` = (B, 2) or (B, K, 2): new ones (project: with
+        verts_camed and pj2d; org: and pj2d_org), or the caller's `out`, which must have that shape."""
+        if out is not None:
+            if tuple(out['slots'].shape) != lead + (_lib.SLOT,) or tuple(out['verts'].shape) != lead + (778, 3):
+                raise ValueError('out does not hold %d frames of %d hand pairs' % (lead[0], lead[1] if len(lead) == 3 else 1))
             return out
-        if out.get('track_ids') is None:
-            out['track_ids'] = torch.empty(B, K, 2, dtype=torch.int32, device=dev)
-        elif tuple(out['track_ids'].shape) != (B, K, 2) or out['track_ids'].dtype != torch.int32 or not out['track_ids'].is_contiguous():
-            raise ValueError("out['track_ids'] must be a contiguous int32 tensor [B,K,2]")
-        _lib.check(self.L.acrmi_forward_tracks(self.ctx, track_table.handle, ids.ctypes.data_as(C.c_void_p), int(bool(smooth)),
-                                               _ptr(img), B, K, *tail, _ptr(out['track_ids']), raw), self.ctx)
+        new = lambda *tail: torch.empty(lead + tail, dtype=torch.float32, device=self.device)
+        out = {'slots': new(_lib.SLOT), 'verts': new(778, 3), 'joints': new(21, 3)}
+        if project:
+            out['verts_camed'], out['pj2d'] = new(778, 3), new(21, 2)
+            if org:
+                out['pj2d_org'] = new(21, 2)
         return out
 
     def track_step(self, frames, boxes, box_frame=None, frame_hw=None, streams=None, table=None, pixel_format='bgr',
@@ -710,6 +675,98 @@ class Engine(object):
         out['image'], out['offsets'] = rgb, offsets      # what the network saw, and the rows render / overlay take
         return out, ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size), status
 
+    # ---- views: what render / overlay and their region forms share -----------------------------------------------------------
+    @staticmethod
+    def _check_frames(images, name, lead):
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError('%s must be uint8 [%s,H,W,3] on the device' % (name, lead))
+        return images.contiguous()
+
+    def _cam_trans(self, out, cam_trans, n, focal_length, st):
+        """cam_trans [n,2,3] of render: the caller's, out['cam_trans'], or computed from out['joints'] / out['pj2d']."""
+        if cam_trans is None:
+            cam_trans = out.get('cam_trans')
+        if cam_trans is None:
+            if out.get('pj2d') is None:
+                raise ValueError('cam_trans is needed (or out from forward(..., project=True))')
+            cam_trans = torch.empty(n, 2, 3, dtype=torch.float32, device=self.device)
+            _lib.check(self.L.acrmi_cam_trans(_ptr(out['joints']), _ptr(out['pj2d']), 2 * n, float(focal_length), 512.0,
+                                              _ptr(cam_trans), st))
+        return cam_trans.to(self.device, torch.float32).contiguous()
+
+    @staticmethod
+    def _colors(colors, bgr):
+        """colors [2,3] of render as a host array, None = the library's (the reference's, RGB)."""
+        if colors is None and not bgr:
+            return None
+        c = np.asarray(colors if colors is not None else [list(reversed(x)) for x in HAND_COLORS_RGB], np.float32)
+        if c.shape != (2, 3):
+            raise ValueError('colors must be [2,3] (left, right)')
+        return np.ascontiguousarray(c)
+
+    @staticmethod
+    def _dst(dst, src, shape, name):
+        if dst is None:
+            return torch.empty(shape, dtype=torch.uint8, device=src.device)
+        if dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != src.device:
+            raise ValueError('dst must be a contiguous uint8 tensor %s on the device of the %s' % (shape, name))
+        return dst
+
+    def _frame_offsets(self, offsets, B):
+        if offsets is not None:
+            offsets = offsets.to(self.device, torch.float32).contiguous()
+            if tuple(offsets.shape) != (B, 10):
+                raise ValueError('offsets must be [B,10]')
+        return offsets
+
+    def _render(self, out, src, n, name, offsets, region_frame, cam_trans, focal_length, visible_weight, colors, bgr, dst,
+                return_ids, stream):
+        """acrmi_render (region_frame None) / acrmi_render_regions of the n frames / regions of `out` over src."""
+        N, H, W, _ = src.shape
+        st = _stream(self.device) if stream is None else C.c_void_p(stream)
+        cam_trans = self._cam_trans(out, cam_trans, n, focal_length, st)
+        col = self._colors(colors, bgr)
+        dst = self._dst(dst, src, (N, H, W, 3), name)
+        ids = torch.empty(N, H, W, dtype=torch.int32, device=self.device) if return_ids else None
+        verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
+        head = (self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), n, _ptr(offsets))
+        tail = (None if col is None else col.ctypes.data_as(C.c_void_p), float(focal_length), float(visible_weight), _ptr(src),
+                _ptr(dst))
+        if region_frame is None:
+            _lib.check(self.L.acrmi_render(*head, *tail, H, W, _ptr(ids), st), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_render_regions(*head, _ptr(region_frame), *tail, N, H, W, _ptr(ids), st), self.ctx)
+        self._render_keep = (verts, slots, cam_trans, offsets, region_frame, src)      # referenced until the next call has been queued
+        return (dst, ids) if return_ids else dst
+
+    def _overlay(self, out, src, n, name, what, kps_key, offsets, region_frame, bgr, dst, stream):
+        """acrmi_overlay (region_frame None) / acrmi_overlay_regions of the n frames / regions of `out` over src."""
+        if what not in ('pj2d', 'centermap'):
+            raise ValueError("what: 'pj2d' or 'centermap'")
+        N, H, W, _ = src.shape
+        st = _stream(self.device) if stream is None else C.c_void_p(stream)
+        dst = self._dst(dst, src, (N, H, W, 3) if what == 'pj2d' else (2, N, H, W, 3), name)
+        slots = kps = None
+        if what == 'pj2d':
+            kps = out.get(kps_key)
+            if kps is None:
+                raise ValueError('out holds no %s (forward(..., project=True%s))' %
+                                 (kps_key, ', offsets=offsets' if kps_key == 'pj2d_org' else ''))
+            if tuple(kps.shape) != (n, 2, 21, 2) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
+                raise ValueError('out does not hold the results of %d %s' % (n, 'frames' if region_frame is None else 'regions'))
+            kps, slots = kps.contiguous(), out['slots'].contiguous()
+            mode, outs = _lib.OVERLAY_SKELETON, (_ptr(dst), None)
+        else:
+            mode, outs = _lib.OVERLAY_CENTERMAP, (_ptr(dst[0]), _ptr(dst[1]))
+        if region_frame is None:
+            _lib.check(self.L.acrmi_overlay(self.ctx, mode, _ptr(slots), _ptr(kps), n, _ptr(offsets), int(bool(bgr)), _ptr(src), *outs,
+                                            H, W, st), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_overlay_regions(self.ctx, mode, _ptr(slots), _ptr(kps), n, _ptr(offsets), _ptr(region_frame),
+                                                    int(bool(bgr)), _ptr(src), *outs, N, H, W, st), self.ctx)
+        self._overlay_keep = (slots, kps, offsets, region_frame, src)      # referenced until the next call has been queued
+        return dst
+
     def render(self, out, images, offsets=None, cam_trans=None, focal_length=1265., visible_weight=0.9, colors=None,
                bgr=False, dst=None, return_ids=False, stream=None):
         """The hands of `out` (what `forward(..., project=True)` returned: slots, verts, joints, pj2d) drawn over `images`
@@ -720,45 +777,12 @@ class Engine(object):
         colors [2,3] left / right in the images' channel order (default: the reference's, RGB or - bgr=True - BGR).
         dst: uint8 tensor like images to draw into (may be `images` itself: in place).  Returns the frames, or (frames,
         ids int32 [B,H,W] = (2 * frame + hand) * F + face, -1 where no hand is) with return_ids.  stream: as `forward`."""
-        dev = self.device
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
-            raise ValueError('images must be uint8 [B,H,W,3] on the device')
-        B, H, W, _ = images.shape
+        src = self._check_frames(images, 'images', 'B')
+        B = src.shape[0]
         if tuple(out['verts'].shape) != (B, 2, 778, 3) or tuple(out['slots'].shape) != (B, 2, _lib.SLOT):
             raise ValueError('out does not hold the results of %d frames' % B)
-        st = _stream(dev) if stream is None else C.c_void_p(stream)
-        if cam_trans is None:
-            if out.get('cam_trans') is not None:
-                cam_trans = out['cam_trans']
-            else:
-                if out.get('pj2d') is None:
-                    raise ValueError('cam_trans is needed (or out from forward(..., project=True))')
-                cam_trans = torch.empty(B, 2, 3, dtype=torch.float32, device=dev)
-                _lib.check(self.L.acrmi_cam_trans(_ptr(out['joints']), _ptr(out['pj2d']), 2 * B, float(focal_length), 512.0,
-                                                  _ptr(cam_trans), st))
-        cam_trans = cam_trans.to(dev, torch.float32).contiguous()
-        if offsets is not None:
-            offsets = offsets.to(dev, torch.float32).contiguous()
-            if tuple(offsets.shape) != (B, 10):
-                raise ValueError('offsets must be [B,10]')
-        col = None
-        if colors is not None or bgr:
-            c = np.asarray(colors if colors is not None else [list(reversed(x)) for x in HAND_COLORS_RGB], np.float32)
-            if c.shape != (2, 3):
-                raise ValueError('colors must be [2,3] (left, right)')
-            col = np.ascontiguousarray(c)
-        src = images.contiguous()
-        if dst is None:
-            dst = torch.empty_like(src)
-        elif dst.dtype != torch.uint8 or tuple(dst.shape) != (B, H, W, 3) or not dst.is_contiguous() or dst.device != src.device:
-            raise ValueError('dst must be a contiguous uint8 tensor shaped like images, on their device')
-        ids = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_ids else None
-        verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
-        _lib.check(self.L.acrmi_render(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, _ptr(offsets),
-                                       None if col is None else col.ctypes.data_as(C.c_void_p), float(focal_length),
-                                       float(visible_weight), _ptr(src), _ptr(dst), H, W, _ptr(ids), st), self.ctx)
-        self._render_keep = (verts, slots, cam_trans, offsets, src)      # referenced until the next call has been queued
-        return (dst, ids) if return_ids else dst
+        return self._render(out, src, B, 'images', self._frame_offsets(offsets, B), None, cam_trans, focal_length, visible_weight,
+                            colors, bgr, dst, return_ids, stream)
 
     def overlay(self, out, images, what, offsets=None, bgr=False, dst=None, stream=None):
         """The reference's other two views of a result over `images` (acrmi_overlay; acr/visualization.py:228-300, rules in
@@ -769,48 +793,17 @@ class Engine(object):
         maps of the LAST program run of this context (it must be the forward that produced `out`) in false colour at
         weight 0.7 -> uint8 [2,B,H,W,3] (left, right).  bgr: the images' channel order.  dst: tensor to draw into, shaped
         like the result ('pj2d': may be `images` itself).  stream: as `forward`."""
-        dev = self.device
-        if what not in ('pj2d', 'centermap'):
-            raise ValueError("what: 'pj2d' or 'centermap'")
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
-            raise ValueError('images must be uint8 [B,H,W,3] on the device')
-        B, H, W, _ = images.shape
-        st = _stream(dev) if stream is None else C.c_void_p(stream)
-        if offsets is not None:
-            offsets = offsets.to(dev, torch.float32).contiguous()
-            if tuple(offsets.shape) != (B, 10):
-                raise ValueError('offsets must be [B,10]')
-        src = images.contiguous()
-        shape = (B, H, W, 3) if what == 'pj2d' else (2, B, H, W, 3)
-        if dst is None:
-            dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
-        elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != src.device:
-            raise ValueError('dst must be a contiguous uint8 tensor %s on the images\' device' % (shape,))
-        slots = kps = None
-        if what == 'pj2d':
-            kps = out.get('pj2d') if offsets is None else out.get('pj2d_org')
-            if kps is None:
-                raise ValueError('out holds no %s (forward(..., project=True%s))' %
-                                 (('pj2d', '') if offsets is None else ('pj2d_org', ', offsets=offsets')))
-            if tuple(kps.shape) != (B, 2, 21, 2) or tuple(out['slots'].shape) != (B, 2, _lib.SLOT):
-                raise ValueError('out does not hold the results of %d frames' % B)
-            kps, slots = kps.contiguous(), out['slots'].contiguous()
-            _lib.check(self.L.acrmi_overlay(self.ctx, _lib.OVERLAY_SKELETON, _ptr(slots), _ptr(kps), B, _ptr(offsets),
-                                            int(bool(bgr)), _ptr(src), _ptr(dst), None, H, W, st), self.ctx)
-        else:
-            _lib.check(self.L.acrmi_overlay(self.ctx, _lib.OVERLAY_CENTERMAP, None, None, B, _ptr(offsets), int(bool(bgr)),
-                                            _ptr(src), _ptr(dst[0]), _ptr(dst[1]), H, W, st), self.ctx)
-        self._overlay_keep = (slots, kps, offsets, src)      # referenced until the next call has been queued
-        return dst
+        src = self._check_frames(images, 'images', 'B')
+        B = src.shape[0]
+        return self._overlay(out, src, B, 'images', what, 'pj2d' if offsets is None else 'pj2d_org', self._frame_offsets(offsets, B),
+                             None, bgr, dst, stream)
 
     def _regions(self, images, offsets, region_frame, n):
         """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->
         (src, offsets, region_frame) on the device."""
-        from . import ops
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
-            raise ValueError('frames must be uint8 [N,H,W,3] on the device')
-        _, o, rf = ops.check_regions(offsets, region_frame, n)
-        return images.contiguous(), o.to(self.device, torch.float32).contiguous(), rf.to(self.device, torch.int32).contiguous()
+        src = self._check_frames(images, 'frames', 'N')
+        _, o, rf = ops_mod.check_regions(offsets, region_frame, n)
+        return src, o.to(self.device, torch.float32).contiguous(), rf.to(self.device, torch.int32).contiguous()
 
     def render_regions(self, out, frames, offsets, region_frame, cam_trans=None, focal_length=1265., visible_weight=0.9,
                        colors=None, bgr=False, dst=None, return_ids=False, stream=None):
@@ -820,41 +813,12 @@ class Engine(object):
         offsets [n,10] and region_frame [n] may be device tensors (out['offsets'] of track_step is one): the kernels read
         them, nothing here waits for the device.  A region whose window has no pixel, whose scale is not > 0 or whose
         frame index is outside [0, N) draws nothing.  The other arguments as `render`; ids = (2 * region + hand) * F + face."""
-        dev = self.device
         n = out['slots'].shape[0]
         if tuple(out['verts'].shape) != (n, 2, 778, 3) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
             raise ValueError('out does not hold the results of %d regions' % n)
         src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
-        N, H, W, _ = src.shape
-        st = _stream(dev) if stream is None else C.c_void_p(stream)
-        if cam_trans is None:
-            if out.get('cam_trans') is not None:
-                cam_trans = out['cam_trans']
-            else:
-                if out.get('pj2d') is None:
-                    raise ValueError('cam_trans is needed (or out from forward(..., project=True))')
-                cam_trans = torch.empty(n, 2, 3, dtype=torch.float32, device=dev)
-                _lib.check(self.L.acrmi_cam_trans(_ptr(out['joints']), _ptr(out['pj2d']), 2 * n, float(focal_length), 512.0,
-                                                  _ptr(cam_trans), st))
-        cam_trans = cam_trans.to(dev, torch.float32).contiguous()
-        col = None
-        if colors is not None or bgr:
-            c = np.asarray(colors if colors is not None else [list(reversed(x)) for x in HAND_COLORS_RGB], np.float32)
-            if c.shape != (2, 3):
-                raise ValueError('colors must be [2,3] (left, right)')
-            col = np.ascontiguousarray(c)
-        if dst is None:
-            dst = torch.empty_like(src)
-        elif dst.dtype != torch.uint8 or tuple(dst.shape) != (N, H, W, 3) or not dst.is_contiguous() or dst.device != src.device:
-            raise ValueError('dst must be a contiguous uint8 tensor shaped like frames, on their device')
-        ids = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_ids else None
-        verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
-        _lib.check(self.L.acrmi_render_regions(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), n, _ptr(offsets),
-                                               _ptr(region_frame), None if col is None else col.ctypes.data_as(C.c_void_p),
-                                               float(focal_length), float(visible_weight), _ptr(src), _ptr(dst), N, H, W,
-                                               _ptr(ids), st), self.ctx)
-        self._render_keep = (verts, slots, cam_trans, offsets, region_frame, src)      # referenced until the next call has been queued
-        return (dst, ids) if return_ids else dst
+        return self._render(out, src, n, 'frames', offsets, region_frame, cam_trans, focal_length, visible_weight, colors, bgr, dst,
+                            return_ids, stream)
 
     def overlay_regions(self, out, frames, what, offsets, region_frame, bgr=False, dst=None, stream=None):
         """`overlay` for the results of a forward on n REGIONS (acrmi_overlay_regions; DESIGN.md "Views over regions").
@@ -862,35 +826,10 @@ class Engine(object):
         -> uint8 [N,H,W,3].  what = 'centermap': the centre maps of the LAST program run of this context (the forward on
         these n regions), region i tinting the pixels of its window; where windows overlap the larger colour index wins ->
         uint8 [2,N,H,W,3].  offsets, region_frame: as `render_regions`; the other arguments as `overlay`."""
-        dev = self.device
-        if what not in ('pj2d', 'centermap'):
-            raise ValueError("what: 'pj2d' or 'centermap'")
         n = out['slots'].shape[0]
         src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
-        N, H, W, _ = src.shape
-        st = _stream(dev) if stream is None else C.c_void_p(stream)
-        shape = (N, H, W, 3) if what == 'pj2d' else (2, N, H, W, 3)
-        if dst is None:
-            dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
-        elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != src.device:
-            raise ValueError('dst must be a contiguous uint8 tensor %s on the frames\' device' % (shape,))
-        slots = kps = None
-        if what == 'pj2d':
-            kps = out.get('pj2d_org')
-            if kps is None:
-                raise ValueError('out holds no pj2d_org (forward(..., project=True, offsets=offsets))')
-            if tuple(kps.shape) != (n, 2, 21, 2) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
-                raise ValueError('out does not hold the results of %d regions' % n)
-            kps, slots = kps.contiguous(), out['slots'].contiguous()
-            _lib.check(self.L.acrmi_overlay_regions(self.ctx, _lib.OVERLAY_SKELETON, _ptr(slots), _ptr(kps), n, _ptr(offsets),
-                                                    _ptr(region_frame), int(bool(bgr)), _ptr(src), _ptr(dst), None, N, H, W,
-                                                    st), self.ctx)
-        else:
-            _lib.check(self.L.acrmi_overlay_regions(self.ctx, _lib.OVERLAY_CENTERMAP, None, None, n, _ptr(offsets),
-                                                    _ptr(region_frame), int(bool(bgr)), _ptr(src), _ptr(dst[0]), _ptr(dst[1]),
-                                                    N, H, W, st), self.ctx)
-        self._overlay_keep = (slots, kps, offsets, region_frame, src)      # referenced until the next call has been queued
-        return dst
+        return self._overlay(out, src, n, 'frames', what, 'pj2d_org', offsets, region_frame, bgr, dst, stream)
+
 
     def profile_ops(self, img):
         img = self._check_img(img)
@@ -1065,72 +1004,68 @@ class EnginePool(object):
         self._busy[i] = ticket
         return ticket
 
+    def _on_ticket(self, ticket, name, prepare, call, keep=None, caller_waits=False):
+        """One more call on the ticket's batch, on the ticket's stream behind its forward and behind what the caller's
+        current stream holds now.  prepare(engine) -> the tensors the call takes: the host-side conversions, which run on
+        the caller's stream and so must be queued before `ready` is recorded; call(engine, raw stream, tensors) -> the
+        result; keep: the Engine attribute that names what else the call touched.  collect() then also orders the caller's
+        stream behind this call; caller_waits: it is made to wait for it now, on the device."""
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('%s() belongs between submit() and collect() of its ticket' % name)
+        eng = self.engines[i]
+        tensors = prepare(eng)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        self.streams[i].wait_event(ready)
+        res = call(eng, self._raw[i].value, tensors)
+        done = torch.cuda.Event()
+        done.record(self.streams[i])
+        if caller_waits:
+            torch.cuda.current_stream(self.device).wait_event(done)
+        # as in submit: everything the call touches stays referenced by the ticket until its event has completed - appended,
+        # so that a second call on the ticket does not drop what the kernels of the first may still be reading
+        ticket['event'] = done
+        ticket.setdefault('kept', []).append((res, tensors, getattr(eng, keep) if keep else None))
+        return res
+
+    def _view(self, ticket, name, keep, prepare, **kw):
+        """Engine.<name> of the ticket's batch over the frames prepare() returns (as keyword arguments)."""
+        return self._on_ticket(ticket, name, prepare, keep=keep,
+                               call=lambda eng, raw, frames: getattr(eng, name)(ticket['out'], stream=raw, **frames, **kw))
+
+    def _frames(self, images, offsets):
+        def prepare(eng):
+            return {'images': images.contiguous(),
+                    'offsets': None if offsets is None else offsets.to(self.device, torch.float32).contiguous()}
+        return prepare
+
+    @staticmethod
+    def _region_frames(ticket, frames, offsets, region_frame):
+        def prepare(eng):
+            f, o, rf = eng._regions(frames, offsets, region_frame, ticket['out']['slots'].shape[0])
+            return {'frames': f, 'offsets': o, 'region_frame': rf}
+        return prepare
+
     def render(self, ticket, images, offsets=None, **kw):
         """Engine.render of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
         project=True) and collect().  `images` (and offsets) as the caller's current stream left them.  collect() then
         also orders the caller's stream behind the drawing.  Returns what Engine.render returns."""
-        i = ticket['slot']
-        if self._busy[i] is not ticket:
-            raise RuntimeError('render() belongs between submit() and collect() of its ticket')
-        images = images.contiguous()
-        if offsets is not None:
-            offsets = offsets.to(self.device, torch.float32).contiguous()
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(self.device))
-        self.streams[i].wait_event(ready)
-        res = self.engines[i].render(ticket['out'], images, offsets=offsets, stream=self._raw[i].value, **kw)
-        done = torch.cuda.Event()
-        done.record(self.streams[i])
-        # as in submit: everything the drawing touches stays referenced by the ticket until its event has completed
-        ticket['event'] = done
-        ticket['render'] = (res, images, offsets, self.engines[i]._render_keep)
-        return res
+        return self._view(ticket, 'render', '_render_keep', self._frames(images, offsets), **kw)
 
     def overlay(self, ticket, images, what, offsets=None, **kw):
         """Engine.overlay of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
         project=True) and collect(), like render().  Returns what Engine.overlay returns."""
-        i = ticket['slot']
-        if self._busy[i] is not ticket:
-            raise RuntimeError('overlay() belongs between submit() and collect() of its ticket')
-        images = images.contiguous()
-        if offsets is not None:
-            offsets = offsets.to(self.device, torch.float32).contiguous()
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(self.device))
-        self.streams[i].wait_event(ready)
-        res = self.engines[i].overlay(ticket['out'], images, what, offsets=offsets, stream=self._raw[i].value, **kw)
-        done = torch.cuda.Event()
-        done.record(self.streams[i])
-        ticket['event'] = done
-        ticket.setdefault('overlay', []).append((res, images, offsets, self.engines[i]._overlay_keep))
-        return res
-
-    def _on_ticket(self, ticket, name, key, keep, frames, offsets, region_frame, args, kw):
-        """render_regions / overlay_regions of the ticket's batch on the ticket's stream, behind its forward."""
-        i = ticket['slot']
-        if self._busy[i] is not ticket:
-            raise RuntimeError('%s() belongs between submit() and collect() of its ticket' % name)
-        # (host-side conversions run on the caller's stream: they must be queued before `ready` is recorded)
-        frames, offsets, region_frame = self.engines[i]._regions(frames, offsets, region_frame, ticket['out']['slots'].shape[0])
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(self.device))
-        self.streams[i].wait_event(ready)
-        res = getattr(self.engines[i], name)(ticket['out'], frames, *args, offsets, region_frame, stream=self._raw[i].value, **kw)
-        done = torch.cuda.Event()
-        done.record(self.streams[i])
-        # as in submit: everything the drawing touches stays referenced by the ticket until its event has completed
-        ticket['event'] = done
-        ticket.setdefault(key, []).append((res, frames, offsets, region_frame, getattr(self.engines[i], keep)))
-        return res
+        return self._view(ticket, 'overlay', '_overlay_keep', self._frames(images, offsets), what=what, **kw)
 
     def render_regions(self, ticket, frames, offsets, region_frame, **kw):
         """Engine.render_regions of the ticket's batch (a forward on regions) on the ticket's stream, like render()."""
-        return self._on_ticket(ticket, 'render_regions', 'render_regions', '_render_keep', frames, offsets, region_frame, (), kw)
+        return self._view(ticket, 'render_regions', '_render_keep', self._region_frames(ticket, frames, offsets, region_frame), **kw)
 
     def overlay_regions(self, ticket, frames, what, offsets, region_frame, **kw):
         """Engine.overlay_regions of the ticket's batch on the ticket's stream, like overlay()."""
-        return self._on_ticket(ticket, 'overlay_regions', 'overlay_regions', '_overlay_keep', frames, offsets, region_frame,
-                               (what,), kw)
+        return self._view(ticket, 'overlay_regions', '_overlay_keep', self._region_frames(ticket, frames, offsets, region_frame),
+                          what=what, **kw)
 
     def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
         """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
@@ -1138,28 +1073,19 @@ class EnginePool(object):
         caller's current stream is made to wait for them ON THE DEVICE, so they can go straight into
         ops.preprocess_rois_device and the submit() of the next batch while this ticket is still outstanding; the host waits
         for nothing."""
-        from . import ops
-        i = ticket['slot']
-        if self._busy[i] is not ticket:
-            raise RuntimeError('track_boxes() belongs between submit() and collect() of its ticket')
-        res = ticket['out']
-        if res.get('pj2d_org') is None:
-            raise ValueError('the ticket holds no pj2d_org (submit(..., offsets=offsets, project=True))')
-        n = res['slots'].shape[0]
-        hw = ops.frame_hw_device(frame_hw, n, self.device)      # (on the caller's stream, before `ready` is recorded)
-        if out is None:
-            out = torch.empty(n, 4, dtype=torch.int32, device=self.device)
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(self.device))
-        self.streams[i].wait_event(ready)
-        boxes = ops.track_boxes(res['pj2d_org'], res['slots'], hw, scale=scale, min_size=min_size, out=out, stream=self._raw[i].value)
-        done = torch.cuda.Event()
-        done.record(self.streams[i])
-        torch.cuda.current_stream(self.device).wait_event(done)
-        # as in submit: everything the kernel touches stays referenced by the ticket until its event has completed
-        ticket['event'] = done
-        ticket.setdefault('track', []).append((boxes, hw))
-        return boxes
+        def prepare(eng):
+            res = ticket['out']
+            if res.get('pj2d_org') is None:
+                raise ValueError('the ticket holds no pj2d_org (submit(..., offsets=offsets, project=True))')
+            n = res['slots'].shape[0]
+            boxes = out if out is not None else torch.empty(n, 4, dtype=torch.int32, device=self.device)
+            return ops_mod.frame_hw_device(frame_hw, n, self.device), boxes
+
+        def call(eng, raw, hw_boxes):
+            return ops_mod.track_boxes(ticket['out']['pj2d_org'], ticket['out']['slots'], hw_boxes[0], scale=scale,
+                                       min_size=min_size, out=hw_boxes[1], stream=raw)
+
+        return self._on_ticket(ticket, 'track_boxes', prepare, call, caller_waits=True)
 
     def _reap(self):
         self._inflight = [t for t in self._inflight if not t['event'].query()]

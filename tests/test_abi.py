@@ -75,3 +75,37 @@ def test_null_arguments_are_rejected_without_a_gpu():
     bad[0].H, bad[0].W = 4, 4                                         # a frame without a pointer
     assert lib.acrmi_preprocess_frames(bad, 1, ctypes.c_void_p(16), None, None) == L.E_INVAL
     assert lib.acrmi_decode_maps(None, None, 4, None, None, 112, None, None, 108, 1, 0.35, None, None) == L.E_INVAL
+
+
+def test_table_and_fused_calls_check_their_arguments_before_the_device():
+    """What is wrong with the arguments alone is ACRMI_EINVAL also on a machine without a GPU (where the device prelude of
+    the table constructors answers ACRMI_EHIP): the argument checks come first."""
+    L = pkg('_lib')
+    lib = L.lib()
+    h = ctypes.c_void_p()
+    assert lib.acrmi_streams_create(None, 0, 4) == L.E_INVAL
+    assert lib.acrmi_streams_create(ctypes.byref(h), 0, 0) == L.E_INVAL and not h.value
+    for max_hand in (0, L.MAX_HAND + 1):
+        assert lib.acrmi_tracks_create(ctypes.byref(h), 0, 4, max_hand, 8, 5) == L.E_INVAL and not h.value
+        assert b'max_hand %d' % max_hand in lib.acrmi_last_error(None)
+    assert lib.acrmi_tracks_create(ctypes.byref(h), 0, 0, 2, 8, 5) == L.E_INVAL and not h.value
+    assert lib.acrmi_tracks_create(None, 0, 4, 2, 8, 5) == L.E_INVAL
+    assert lib.acrmi_streams_reset(None, None, 0, None) == L.E_INVAL
+    assert b'acrmi_streams_reset' in lib.acrmi_last_error(None)
+    assert lib.acrmi_tracks_reset(None, None, 0, None) == L.E_INVAL
+    assert b'acrmi_tracks_reset' in lib.acrmi_last_error(None)
+    p = ctypes.c_void_p(16)      # never read: the context is looked at first
+    ids = (ctypes.c_int32 * 2)(0, 1)
+    calls = {
+        'acrmi_forward': (None, None, 2, None, None, None, None, None, None, None, None),
+        'acrmi_forward_multi': (None, None, 2, 2, None, None, None, None, None, None, None, None),
+        'acrmi_forward_streams': (None, p, ids, None, 2, None, None, None, None, None, None, None, None),
+        'acrmi_forward_tracks': (None, p, ids, 1, None, 2, 2, None, None, None, None, None, None, None, None, None),
+        'acrmi_render': (None, None, None, None, 2, None, None, 1265.0, 0.9, None, None, 8, 8, None, None),
+        'acrmi_render_regions': (None, None, None, None, 2, None, None, None, 1265.0, 0.9, None, None, 1, 8, 8, None, None),
+        'acrmi_overlay': (None, L.OVERLAY_SKELETON, None, None, 2, None, 0, None, None, None, 8, 8, None),
+        'acrmi_overlay_regions': (None, L.OVERLAY_CENTERMAP, None, None, 2, None, None, 0, None, None, None, 1, 8, 8, None),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(*args) == L.E_INVAL, name
+        assert lib.acrmi_last_error(None).startswith(name.encode() + b':'), name

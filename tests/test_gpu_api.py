@@ -865,3 +865,141 @@ def test_raw_1080p_batch_end_to_end(synth_sd, mano_tables):
             assert int(hb['hand_type']) == int(hs['hand_type'])
             assert np.abs(hb['verts'].astype(np.float32) - hs['verts'].astype(np.float32)).max() < 5e-3
             assert np.abs(hb['pj2d_org'].astype(np.float32) - hs['pj2d_org'].astype(np.float32)).max() < 4.0   # px of 1920
+
+
+def test_fused_entry_points_refuse_and_agree_as_documented(synth_sd, mano_tables, frames2):
+    """The four acrmi_forward* and the four view entry points share one host path: (1) every documented refusal keeps its
+    code and a message that names the function called and the offending value; (2) acrmi_forward_multi and
+    acrmi_forward_tracks at max_hand 1 go through the classic decode - bit-equal to acrmi_forward and, on fresh tables, to
+    acrmi_forward_streams; (3) a ticket of an EnginePool keeps what EVERY render() on it touched."""
+    import ctypes as C
+    L, E = pkg('_lib'), pkg('engine')
+    lib = L.lib()
+    img = torch.from_numpy(frames2).cuda()
+    B = 2
+    bare = E.Engine(0)      # a program, no MANO tables, no faces, nothing run
+    bare.load_state_dict(synth_sd, max_batch=B)
+    eng = E.Engine(0)
+    eng.load_state_dict(synth_sd, max_batch=B)
+    eng.load_mano(mano_tables)
+    table, tracks1, tracks2 = E.StreamTable(0, 4), E.TrackTable(0, 4, max_hand=1), E.TrackTable(0, 4, max_hand=2)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    ids_ok, ids_bad = (C.c_int32 * B)(0, 1), (C.c_int32 * B)(0, 4)
+
+    def outputs(K=None):
+        lead = (B, 2) if K is None else (B, K, 2)
+        return {'slots': torch.zeros(*lead, L.SLOT, device='cuda'), 'verts': torch.zeros(*lead, 778, 3, device='cuda'),
+                'joints': torch.zeros(*lead, 21, 3, device='cuda'), 'track_ids': torch.zeros(*lead, dtype=torch.int32, device='cuda')}
+
+    def forward(name, e, o, K=1, table=None, ids=ids_ok, slots=True):
+        tail = (None, p(o['slots']) if slots else None, p(o['verts']), p(o['joints']), None, None, None)
+        if name == 'acrmi_forward':
+            return lib.acrmi_forward(e.ctx, p(img), B, *tail, st)
+        if name == 'acrmi_forward_multi':
+            return lib.acrmi_forward_multi(e.ctx, p(img), B, K, *tail, st)
+        if name == 'acrmi_forward_streams':
+            return lib.acrmi_forward_streams(e.ctx, table.handle, ids, p(img), B, *tail, st)
+        return lib.acrmi_forward_tracks(e.ctx, table.handle, ids, 1, p(img), B, K, *tail, p(o['track_ids']), st)
+
+    def refused(rc, e, code, name, fragment):
+        msg = lib.acrmi_last_error(e.ctx).decode()
+        assert rc == code and msg.startswith(name + ':') and fragment in msg, (name, rc, msg)
+
+    # ---- (1) the forward calls -----------------------------------------------------------------------------------------------
+    tables = {'acrmi_forward': None, 'acrmi_forward_multi': None, 'acrmi_forward_streams': table, 'acrmi_forward_tracks': tracks1}
+    o1, o2 = outputs(1), outputs(2)
+    for name, t in tables.items():
+        refused(forward(name, eng, o1, table=t, slots=False), eng, L.E_INVAL, name, 'bad arguments')
+        refused(forward(name, bare, o1, table=t), bare, L.E_STATE, name, 'MANO tables not loaded')
+    for K in (0, L.MAX_HAND + 1):
+        refused(forward('acrmi_forward_multi', eng, o2, K=K), eng, L.E_INVAL, 'acrmi_forward_multi', 'max_hand %d outside 1..%d' % (K, L.MAX_HAND))
+        refused(forward('acrmi_forward_tracks', eng, o2, K=K, table=tracks2), eng, L.E_INVAL, 'acrmi_forward_tracks',
+                'max_hand %d outside 1..%d' % (K, L.MAX_HAND))
+    eng.set_batch_semantics('reference')
+    refused(forward('acrmi_forward_multi', eng, o2, K=2), eng, L.E_INVAL, 'acrmi_forward_multi', 'ACRMI_OPT_BATCH_PRIOR with max_hand 2')
+    refused(forward('acrmi_forward_tracks', eng, o2, K=2, table=tracks2), eng, L.E_INVAL, 'acrmi_forward_tracks',
+            'ACRMI_OPT_BATCH_PRIOR with max_hand 2')
+    eng.set_batch_semantics('frame')
+    eng.set_temporal(True)
+    refused(forward('acrmi_forward_multi', eng, o2, K=2), eng, L.E_INVAL, 'acrmi_forward_multi', 'ACRMI_OPT_TEMPORAL with max_hand 2')
+    eng.set_temporal(False)
+    refused(forward('acrmi_forward_tracks', eng, o1, K=1, table=tracks2), eng, L.E_INVAL, 'acrmi_forward_tracks',
+            'max_hand 1, the table holds 2 slots')
+    refused(forward('acrmi_forward_tracks', eng, o2, K=2, table=tracks1), eng, L.E_INVAL, 'acrmi_forward_tracks',
+            'max_hand 2, the table holds 1 slots')
+    refused(forward('acrmi_forward_streams', eng, o1, table=table, ids=ids_bad), eng, L.E_INVAL, 'acrmi_forward_streams', 'ids[1] = 4 outside -1..3')
+    refused(forward('acrmi_forward_tracks', eng, o1, table=tracks1, ids=ids_bad), eng, L.E_INVAL, 'acrmi_forward_tracks', 'ids[1] = 4 outside -1..3')
+    torch.cuda.synchronize()
+    assert not any(bool(v.any()) for o in (o1, o2) for v in o.values())      # a refused call has launched nothing
+
+    # ---- (1) the views ---------------------------------------------------------------------------------------------------------
+    H = W = 512
+    dst, dst2 = torch.zeros_like(img), torch.zeros_like(img)
+    offs = torch.tensor([[512., 512., 0, 0, 0, 0, 0, 0, 0, 0]] * B, device='cuda')
+    rf = torch.arange(B, dtype=torch.int32, device='cuda')
+    f4 = torch.zeros(B, 2, 778, 3, device='cuda')      # verts / cam_trans / slots / key points of refused calls: never read
+
+    def view(name, e, n=B, what=L.OVERLAY_CENTERMAP, out=True):
+        d = p(dst) if out else None
+        if name == 'acrmi_render':
+            return lib.acrmi_render(e.ctx, p(f4), p(f4), p(f4), n, None, None, 1265.0, 0.9, p(img), d, H, W, None, st)
+        if name == 'acrmi_render_regions':
+            return lib.acrmi_render_regions(e.ctx, p(f4), p(f4), p(f4), n, p(offs), p(rf), None, 1265.0, 0.9, p(img), d, B, H, W, None, st)
+        if name == 'acrmi_overlay':
+            return lib.acrmi_overlay(e.ctx, what, p(f4), p(f4), n, None, 0, p(img), d, p(dst2), H, W, st)
+        return lib.acrmi_overlay_regions(e.ctx, what, p(f4), p(f4), n, p(offs), p(rf), 0, p(img), d, p(dst2), B, H, W, st)
+
+    for name in ('acrmi_render', 'acrmi_render_regions', 'acrmi_overlay', 'acrmi_overlay_regions'):
+        refused(view(name, eng, out=False), eng, L.E_INVAL, name, 'bad arguments')
+    for name in ('acrmi_render', 'acrmi_render_regions'):
+        refused(view(name, bare), bare, L.E_STATE, name, 'faces not loaded')
+    for name in ('acrmi_overlay', 'acrmi_overlay_regions'):      # `eng` has a program, and every forward on it was refused
+        for what in (L.OVERLAY_SKELETON, L.OVERLAY_CENTERMAP):
+            refused(view(name, eng, what=what), eng, L.E_STATE, name, 'no program has run')
+    bare.close()
+
+    # ---- (2) max_hand 1 is the classic path ------------------------------------------------------------------------------------
+    got = {}
+    for name, t in tables.items():
+        got[name] = outputs(1)
+        assert forward(name, eng, got[name], K=1, table=t) == 0, lib.acrmi_last_error(eng.ctx)
+    torch.cuda.synchronize()
+    assert bool((got['acrmi_forward']['slots'][..., L.SLOT_FLAG] > 0.5).any())
+    for a, b in (('acrmi_forward', 'acrmi_forward_multi'), ('acrmi_forward_streams', 'acrmi_forward_tracks')):
+        for k in ('slots', 'verts', 'joints'):
+            assert torch.equal(got[a][k], got[b][k]), (a, b, k)
+    # the centre maps resident now are those of a batch of 2
+    for name in ('acrmi_overlay', 'acrmi_overlay_regions'):
+        refused(view(name, eng, n=1), eng, L.E_STATE, name, 'batch of 2, not 1')
+    for t in (table, tracks1, tracks2):
+        t.close()
+    eng.close()
+
+    # ---- (3) two render() calls on one ticket ----------------------------------------------------------------------------------
+    pool = E.EnginePool(0, n=1)
+    pool.load_state_dict(synth_sd, max_batch=B)
+    pool.load_mano(mano_tables)
+    ticket = pool.submit(img, project=True)
+    imgs = [img.clone(), img.clone()]
+    drawn = [pool.render(ticket, im) for im in imgs]
+
+    def kept(x, found):
+        if isinstance(x, torch.Tensor):
+            found.append(x)
+        elif isinstance(x, dict):
+            kept(list(x.values()), found)
+        elif isinstance(x, (list, tuple)):
+            for y in x:
+                kept(y, found)
+        return found
+
+    held = kept(ticket, [])
+    for k in range(2):      # ... the first call's tensors too: its kernels may still be reading them
+        assert any(t is imgs[k] for t in held) and any(t is drawn[k] for t in held), k
+    # (the camera translations Engine.render computed for each call: temporaries nobody else references)
+    assert len({t.data_ptr() for t in held if tuple(t.shape) == (B, 2, 3)}) == 2
+    pool.collect(ticket)
+    torch.cuda.synchronize()
+    assert torch.equal(drawn[0], drawn[1])
+    pool.close()
