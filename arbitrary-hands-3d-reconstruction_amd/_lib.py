@@ -15,6 +15,7 @@ CONV_DUAL = 32         # acrmi_op.flags of a CONV: ACRMI_CONV_DUAL (second outpu
 OPT_POINT_HEADS, OPT_LANES, OPT_CENTER_IDX, OPT_TEMPORAL, OPT_CONF_THRESH, OPT_SMOOTH_COEFF, OPT_MANO_FP16 = 1, 2, 3, 4, 5, 6, 7
 OPT_LANE_PLAN = 8
 OPT_BATCH_PRIOR = 9
+OPT_POINT_HEADS_MULTI = 10
 VERSION = 303
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 SLOT = 176
@@ -86,7 +87,7 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_nv12_compose', 'acrmi_rasterize_views', 'acrmi_draw_region_heatmaps', 'acrmi_render_regions',
            'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi',
            'acrmi_tracks_create', 'acrmi_tracks_destroy', 'acrmi_tracks_reset', 'acrmi_associate', 'acrmi_forward_tracks',
-           'acrmi_assoc_step']
+           'acrmi_assoc_step', 'acrmi_point_heads_multi']
 
 _lib = None
 
@@ -179,6 +180,7 @@ def lib():
     L.acrmi_cam_trans.argtypes = [f32p, f32p, i32, C.c_float, C.c_float, f32p, vp]
     L.acrmi_set_option.argtypes = [vp, i32, i32]
     L.acrmi_point_heads.argtypes = [vp, i32, vp]
+    L.acrmi_point_heads_multi.argtypes = [vp, i32, i32, vp]
     L.acrmi_set_option_f.argtypes = [vp, i32, C.c_float]
     L.acrmi_smooth.argtypes = [vp, f32p, i32, vp]
     L.acrmi_smooth_reset.argtypes = [vp, vp]

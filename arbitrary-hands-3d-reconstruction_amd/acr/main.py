@@ -259,7 +259,7 @@ class ACR(object):
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
-                      track_gate=None, track_max_miss=None):
+                      track_gate=None, track_max_miss=None, multi_point_heads=False):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -281,8 +281,10 @@ class ACR(object):
         it) that this object owns across load_state_dict; reset_streams() starts streams anew.
         max_hand (None = args().hands_per_side; 1..8): up to that many hands of EACH side per frame (Engine.forward's
         max_hand).  results[path] then lists the flagged left hands in rank order, then the flagged right
-        hands in rank order.  With max_hand > 1 the dense heads run even with point_heads=True (the point heads know one
-        centre per side); batch_semantics='reference', streams= and temporal optimisation are a ValueError; 'mesh' and 'pj2d'
+        hands in rank order.  With max_hand > 1 the dense heads run even with point_heads=True, unless multi_point_heads=True:
+        then the towers run only at the max_hand best centres of each side (Engine.set_point_heads_multi; same results within
+        fp32 round-off; a program without the point heads stays dense; DESIGN.md section 17 says at which max_hand it pays);
+        batch_semantics='reference', streams= and temporal optimisation are a ValueError; 'mesh' and 'pj2d'
         are drawn as the views of max_hand regions per frame (Engine.render_regions / overlay_regions with the frame's own
         offsets row), 'centermap' and 'org_img' as always.
         tracks (any max_hand): the video stream (camera) of each frame, ints in [0, max_streams), -1 =
@@ -297,9 +299,9 @@ class ACR(object):
         K = int(self.hands_per_side if max_hand is None else max_hand)
         if K != 1 or tracks is not None:
             return self._forward_batch_multi(rgb_u8_frames, paths, offsets, batch_semantics, render, render_bgr, show_items,
-                                             streams, K, tracks, max_streams, track_gate, track_max_miss)
+                                             streams, K, tracks, max_streams, track_gate, track_max_miss, multi_point_heads)
         results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
-                                                        max_streams)
+                                                        max_streams, multi_point_heads)
         render_offsets = offsets
         if render is None:
             return results
@@ -315,8 +317,11 @@ class ACR(object):
                 views[name] = self._overlay_batch(eng, out, render, name, render_offsets, render_bgr)
         return results, views
 
-    def _forward_batch_results(self, rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams, max_streams):
-        """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned)."""
+    def _forward_batch_results(self, rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams, max_streams,
+                               multi_point_heads=False):
+        """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).
+        multi_point_heads: checked, and without effect on one hand of each side (point_heads is the switch here)."""
+        _check_multi_point_heads(multi_point_heads)
         B = rgb_u8_frames.shape[0]
         ids, table = (None, None) if streams is None else self._streams_for(streams, max_streams, B)
         eng = self.model.engine(B)
@@ -342,12 +347,13 @@ class ACR(object):
         return results_from_out(out, paths), eng, out
 
     def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K, tracks=None,
-                             max_streams=None, gate=None, max_miss=None):
+                             max_streams=None, gate=None, max_miss=None, multi_point_heads=False):
         """forward_batch with max_hand = K > 1 or with tracks=: Engine.forward(max_hand=K), the packaging, and the views of K
         regions per frame."""
         from .. import ops
         from ..engine import check_max_hand
         K = check_max_hand(K)
+        _check_multi_point_heads(multi_point_heads)
         if tracks is not None and streams is not None:
             raise ValueError('tracks= smooths every track with its own filter: not together with streams=')
         if streams is not None:
@@ -365,13 +371,18 @@ class ACR(object):
         eng.set_point_heads(False)
         eng.set_temporal(False)
         eng.set_batch_semantics('frame')
-        if tracks is None:
-            out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
-        else:
-            # (smooth_coeff travels with the call, as in _forward_batch_results; ACRMI_OPT_TEMPORAL itself stays off)
-            eng.set_temporal(False, smooth_coeff=self._args.smooth_coeff)
-            out = eng.forward(frames, offsets=offsets, project=True, max_hand=K, tracks=tracks,
-                              track_table=self._tracks_for(K, max_streams, gate, max_miss), smooth=bool(self.temporal_optimization))
+        eng.set_point_heads_multi(multi_point_heads and K > 1)
+        try:
+            if tracks is None:
+                out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
+            else:
+                # (smooth_coeff travels with the call, as in _forward_batch_results; ACRMI_OPT_TEMPORAL itself stays off)
+                eng.set_temporal(False, smooth_coeff=self._args.smooth_coeff)
+                out = eng.forward(frames, offsets=offsets, project=True, max_hand=K, tracks=tracks,
+                                  track_table=self._tracks_for(K, max_streams, gate, max_miss),
+                                  smooth=bool(self.temporal_optimization))
+        finally:
+            eng.set_point_heads_multi(False)
         eng.check_range()
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(B, K, 2, 3)
@@ -427,6 +438,11 @@ class ACR(object):
             for j, i in enumerate(idx):
                 drawn[i] = got[j]
         return drawn
+
+
+def _check_multi_point_heads(value):
+    if not isinstance(value, bool):
+        raise ValueError('multi_point_heads must be True or False, not %r' % (value,))
 
 
 def results_from_out(out, paths):
@@ -513,7 +529,7 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
-                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None):
+                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -539,8 +555,10 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     ops.bgr_to_nv12, and `matrix` is a name, a pair or a row of ten integers; H and W must be even.
     max_hand: as forward_batch (None = args().hands_per_side).  With boxes= more than one hand of a side per REGION is a
     ValueError: the box is there because the caller has found the person.
-    tracks / track_gate / track_max_miss: as forward_batch; with boxes= a ValueError (ops.track_boxes follows a region)."""
+    tracks / track_gate / track_max_miss: as forward_batch; with boxes= a ValueError (ops.track_boxes follows a region).
+    multi_point_heads: as forward_batch (without effect with boxes=: a region has one hand of each side)."""
     from .utils import img_preprocess_gpu
+    _check_multi_point_heads(multi_point_heads)
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
@@ -569,7 +587,8 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
             canvas = ops.nv12_to_bgr(bgr_frames_dev, matrix) if pixel_format == 'nv12' else bgr_frames_dev
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
-                                 max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss)
+                                 max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
+                                 multi_point_heads=multi_point_heads)
     if to_nv12 is None:
         return got
     results, views = got

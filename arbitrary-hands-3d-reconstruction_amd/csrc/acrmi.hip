@@ -204,15 +204,34 @@ int acrmi_point_heads(acrmi_ctx* c, int B, void* stream) {
   return ACRMI_OK;
 }
 
+static bool has_point_heads_ops(const acrmi_ctx* c) {
+  bool any = false;
+  for (const acrmi_op& op : c->ops) any |= op.kind == ACRMI_OP_POINTHEADS;
+  return any;
+}
+
+int acrmi_point_heads_multi(acrmi_ctx* c, int B, int max_hand, void* stream) {
+  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_point_heads_multi: ctx is NULL");
+  if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_point_heads_multi: no program");
+  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "acrmi_point_heads_multi: batch %d outside 1..%d", B, c->max_batch);
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND)
+    return fail(c, ACRMI_EINVAL, "acrmi_point_heads_multi: max_hand %d outside 1..%d", max_hand, ACRMI_MAX_HAND);
+  if (!has_point_heads_ops(c)) return fail(c, ACRMI_EINVAL, "acrmi_point_heads_multi: the program has no point-heads ops");
+  ON_DEVICE(c);
+  for (const acrmi_op& op : c->ops)
+    if (op.kind == ACRMI_OP_POINTHEADS) {
+      // (run_op's point_hands = 1 is the classic pick with its gate; here max_hand = 1 is the K = 1 case of the plan)
+      HIPCHK(c, launch_point_heads_multi(point_args(c, op, B), max_hand, (hipStream_t)stream));
+    }
+  return ACRMI_OK;
+}
+
 int acrmi_set_option(acrmi_ctx* c, int option, int value) {
   if (!c) return fail(c, ACRMI_EINVAL, "acrmi_set_option: ctx is NULL");
-  if (option == ACRMI_OPT_POINT_HEADS) {
-    if (value && c->have_program) {
-      bool any = false;
-      for (const acrmi_op& op : c->ops) any |= op.kind == ACRMI_OP_POINTHEADS;
-      if (!any) return fail(c, ACRMI_EINVAL, "acrmi_set_option: the program has no point-heads ops");
-    }
-    c->point_heads = value != 0;
+  if (option == ACRMI_OPT_POINT_HEADS || option == ACRMI_OPT_POINT_HEADS_MULTI) {
+    if (value && c->have_program && !has_point_heads_ops(c))
+      return fail(c, ACRMI_EINVAL, "acrmi_set_option: the program has no point-heads ops");
+    (option == ACRMI_OPT_POINT_HEADS ? c->point_heads : c->point_heads_multi) = value != 0;
     return ACRMI_OK;
   }
   if (option == ACRMI_OPT_LANES || option == ACRMI_OPT_LANE_PLAN) {      // what the four schedules are built from
@@ -724,8 +743,8 @@ struct ForwardKind {
   // OPTION: what ACRMI_OPT_TEMPORAL says - nothing, or the frames as one stream on the context's own table;
   // STREAMS: `streams` + ids; TRACKS: `tracks` + ids, smooth, track_ids (the track table takes the place of the smoothing)
   enum { OPTION, STREAMS, TRACKS } temporal = OPTION;
-  bool multi = false;      // acrmi_forward_multi / _tracks: max_hand is the caller's, and the dense heads run whatever
-                           // ACRMI_OPT_POINT_HEADS says (the point heads evaluate the towers at one centre per side)
+  bool multi = false;      // acrmi_forward_multi / _tracks: max_hand is the caller's, and ACRMI_OPT_POINT_HEADS_MULTI, not
+                           // ACRMI_OPT_POINT_HEADS, says whether the point variant of the program runs
   acrmi_streams* streams = nullptr;
   acrmi_tracks* tracks = nullptr;
   const int32_t* ids = nullptr;
@@ -753,7 +772,9 @@ static int fused_forward(acrmi_ctx* c, const char* who, const ForwardKind& k, in
     return fail(c, ACRMI_EINVAL, "%s: ACRMI_OPT_TEMPORAL with max_hand %d > 1", who, max_hand);
   if (!c->have_mano[0] || !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "%s: MANO tables not loaded", who);
   ON_DEVICE(c);
-  if ((r = run_program(c, img, B, stream, k.multi ? false : c->point_heads))) return r;
+  // the calls with a hand count: the dense heads unless ACRMI_OPT_POINT_HEADS_MULTI asks for the towers at the top max_hand centres
+  const bool point = k.multi ? c->point_heads_multi : c->point_heads;
+  if ((r = run_program(c, img, B, stream, point, 0, k.multi ? max_hand : 1))) return r;
   hipStream_t s = (hipStream_t)stream;
   if (max_hand > 1) {
     if ((r = acrmi_decode_multi(c, B, max_hand, slots, stream))) return r;

@@ -78,12 +78,13 @@ struct acrmi_ctx {
   int max_batch = 0;
   float* att_ws = nullptr;      // attention-pool workspace
   size_t att_ws_floats = 0;
-  int* picks = nullptr;         // point heads: decoded centers per frame [max_batch,4]
+  int* picks = nullptr;         // point heads: decoded centers per frame [max_batch,4], or one PointPlan per frame (point_plan.h)
   int* gate_buf = nullptr;      // ACRMI_OPT_BATCH_PRIOR: the batch-wide prior decision per frame [max_batch] (acrmi_prior_gate)
   bool batch_prior = false;     // ACRMI_OPT_BATCH_PRIOR: acrmi_forward applies the reference's batch-wide prior rules at B > 1
   unsigned* range_flag = nullptr;   // 'fp16x3' programs (algo 6): set by conv_x3 / conv_x3p when an activation left the f16 range
                                     // (acrmi_check_range reads and clears it; acrmi_decode poisons the slots while it is set)
   bool point_heads = false;     // ACRMI_OPT_POINT_HEADS
+  bool point_heads_multi = false;   // ACRMI_OPT_POINT_HEADS_MULTI
   Schedule sched[2][2];         // [point][0: small batches / 1: large batches]
   // ACRMI_OPT_LANES: independent chains of the program on parallel HIP streams (lane 0 = the caller's stream)
   int want_lanes = 0;           // 0 = by batch size (AUTO_LANES_*)
@@ -159,10 +160,12 @@ int fail(acrmi_ctx* c, int code, const char* fmt, ...);
 void free_program(acrmi_ctx* c);                       // acrmi_program.hip
 void release_weights(acrmi_ctx* c);                    // acrmi.hip: drops this context's hold on its weight blob
 void comm_destroy(acrmi_ctx* c);                       // acrmi_comm.hip
-int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane = 0);
+PointArgs point_args(const acrmi_ctx* c, const acrmi_op& op, int B);      // acrmi_program.hip: a validated ACRMI_OP_POINTHEADS op
+// point_hands: the centres of each side at which a point-heads op evaluates its towers (1: the classic pick)
+int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane = 0, int point_hands = 1);
 bool op_active(const acrmi_op& op, bool point);
 void build_schedule(acrmi_ctx* c, bool point, bool large);
-int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op = 0);
+int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op = 0, int point_hands = 1);
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params, const float* r_params,
                      int params_cs, const float* l_prior, const float* r_prior, int prior_cs, int B, float conf_thresh,
                      const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream,

@@ -57,7 +57,26 @@ static ConvArgs conv_geometry(const acrmi_op& op, const acrmi_buffer_desc* bufs,
   return a;
 }
 
-int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane) {
+PointArgs point_args(const acrmi_ctx* c, const acrmi_op& op, int B) {
+  auto ptr = [&](int id) -> float* { return c->buf_ptr[id]; };
+  auto desc = [&](int id) -> const acrmi_buffer_desc& { return c->bufs[id]; };
+  const acrmi_head_layout& h = c->heads;
+  const int side = op.flags & 1;
+  PointArgs p{};
+  p.x34 = ptr(op.in_buf); p.x_cs = desc(op.in_buf).cs;
+  p.center[0] = ptr(h.center_buf[0]); p.center[1] = ptr(h.center_buf[1]); p.center_cs = desc(h.center_buf[0]).cs;
+  p.w = c->weights + op.w_off;
+  p.mix_w = c->weights + op.w_off2;
+  p.bias = ptr(op.aux_buf); p.bias_stride = desc(op.aux_buf).cs;
+  p.p109 = ptr(op.res_buf); p.p109_cs = desc(op.res_buf).cs;
+  p.prior = ptr(h.prior_buf[side]); p.prior_cs = desc(h.prior_buf[side]).cs;
+  p.final_ = ptr(op.out_buf); p.final_cs = desc(op.out_buf).cs;
+  p.picks = c->picks; p.side = side; p.B = B; p.thresh = c->conf_thresh;
+  p.prior_when_both = c->batch_prior ? 1 : 0;
+  return p;
+}
+
+int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane, int point_hands) {
   auto ptr = [&](int id) -> float* { return id >= 0 ? c->buf_ptr[id] : nullptr; };
   auto desc = [&](int id) -> const acrmi_buffer_desc& { return c->bufs[id]; };
   // buffer `id` advanced by `coff` ELEMENTS of its storage type (the pointers stay typed float*: they are opaque here)
@@ -180,20 +199,9 @@ int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStrea
       return ACRMI_OK;
     }
     case ACRMI_OP_POINTHEADS: {
-      const acrmi_head_layout& h = c->heads;
-      const int side = op.flags & 1;
-      PointArgs p{};
-      p.x34 = ptr(op.in_buf); p.x_cs = desc(op.in_buf).cs;
-      p.center[0] = ptr(h.center_buf[0]); p.center[1] = ptr(h.center_buf[1]); p.center_cs = desc(h.center_buf[0]).cs;
-      p.w = c->weights + op.w_off;
-      p.mix_w = c->weights + op.w_off2;
-      p.bias = ptr(op.aux_buf); p.bias_stride = desc(op.aux_buf).cs;
-      p.p109 = ptr(op.res_buf); p.p109_cs = desc(op.res_buf).cs;
-      p.prior = ptr(h.prior_buf[side]); p.prior_cs = desc(h.prior_buf[side]).cs;
-      p.final_ = ptr(op.out_buf); p.final_cs = desc(op.out_buf).cs;
-      p.picks = c->picks; p.side = side; p.B = B; p.thresh = c->conf_thresh;
-      p.prior_when_both = c->batch_prior ? 1 : 0;
-      HIPCHK(c, launch_point_heads(p, s));
+      const PointArgs p = point_args(c, op, B);
+      if (point_hands > 1) HIPCHK(c, launch_point_heads_multi(p, point_hands, s));
+      else HIPCHK(c, launch_point_heads(p, s));
       return ACRMI_OK;
     }
     default:
@@ -575,7 +583,7 @@ int acrmi_set_program(acrmi_ctx* c, const acrmi_buffer_desc* bufs, int n_bufs, c
     }
   c->att_ws_floats = attpool_ws_floats(max_batch, 320);
   HIPCHK(c, hipMalloc(&c->att_ws, c->att_ws_floats * sizeof(float)));
-  HIPCHK(c, hipMalloc(&c->picks, (size_t)max_batch * 4 * sizeof(int)));
+  HIPCHK(c, hipMalloc(&c->picks, (size_t)max_batch * POINT_PLAN_INTS * sizeof(int)));
   HIPCHK(c, hipMalloc(&c->gate_buf, (size_t)max_batch * sizeof(int)));
   for (int i = 0; i < n_ops; ++i)
     if (ops[i].kind == ACRMI_OP_CONV && (ops[i].flags & 7) == 6 && !c->range_flag) {
@@ -609,7 +617,7 @@ static unsigned lane_event_flags() {
   return f;
 }
 
-static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_t user, bool point) {
+static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_t user, bool point, int point_hands) {
   const Schedule& S = c->sched[point ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0];
   for (int l = 1; l < S.n_lanes; ++l) {
     if (!c->lanes[l]) HIPCHK(c, hipStreamCreateWithFlags(&c->lanes[l], hipStreamNonBlocking));
@@ -632,7 +640,7 @@ static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_
       return v;
     }();
     if (!(ablate & 1)) for (int d : S.wait[j]) HIPCHK(c, hipStreamWaitEvent(s, c->op_ev[d], 0));
-    r = run_op(c, c->ops[j], img, B, s, S.lane[j]);
+    r = run_op(c, c->ops[j], img, B, s, S.lane[j], point_hands);
     if (r) break;
     if (S.signal[j] && !(ablate & 2)) {
       if (!c->op_ev[j]) HIPCHK(c, hipEventCreateWithFlags(&c->op_ev[j], lane_event_flags()));
@@ -648,7 +656,7 @@ static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_
 
 // first_op > 0 (acrmi_heads): only ops [first_op, n) run - in program order on the caller's stream (the lanes' events of the
 // skipped ops would be stale) - and `img` is not read
-int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op) {
+int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op, int point_hands) {
   if (!c || (!img && first_op <= 0)) return fail(c, ACRMI_EINVAL, "acrmi_backbone_heads: bad arguments");
   if (!c->have_program) return fail(c, ACRMI_ESTATE, "acrmi_backbone_heads: no program");
   if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
@@ -656,13 +664,13 @@ int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool poin
   c->last_batch = B;
   static const bool dbg_sync = getenv("ACRMI_DEBUG_SYNC") != nullptr;   // attribute a fault/hang to an op
   if (c->sched[point ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0].n_lanes > 1 && !dbg_sync && first_op <= 0)
-    return run_program_lanes(c, img, B, (hipStream_t)stream, point);
+    return run_program_lanes(c, img, B, (hipStream_t)stream, point, point_hands);
   int i = 0;
   for (const acrmi_op& op : c->ops) {
     ++i;
     if (!op_active(op, point) || i - 1 < first_op) continue;
     if (dbg_sync) fprintf(stderr, "[acrmi] op %d kind %d B %d\n", i - 1, (int)op.kind, B), fflush(stderr);
-    int r = run_op(c, op, img, B, (hipStream_t)stream);
+    int r = run_op(c, op, img, B, (hipStream_t)stream, 0, point_hands);
     if (r) return r;
     if (dbg_sync) HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
   }

@@ -424,8 +424,10 @@ struct MultiPick {
   float topv[2][4];                    // the four waves' candidates of a round, two rounds in flight
   int topi[2][4];
 };
-__device__ inline void pick_centers_multi(const float* const* center, int center_cs, int b, float thresh, int K,
-                                          PickScratch& sc, MultiPick& pk) {
+// (forced inline: with two kernels calling it the compiler otherwise keeps it a function, and both callers then pay a call's
+// register budget - 215 VGPRs and a scratch slot instead of 96 and none)
+__device__ __forceinline__ void pick_centers_multi(const float* const* center, int center_cs, int b, float thresh, int K,
+                                                   PickScratch& sc, MultiPick& pk) {
   const int tid = threadIdx.x;
   load_center_maps(center, center_cs, b, sc);
   __syncthreads();
@@ -915,13 +917,11 @@ __device__ __forceinline__ void tp_conv64(const float* in, float* out, const flo
   __syncthreads();
 }
 
-__global__ __launch_bounds__(TP_WAVES * 64) void tower_point_kernel(const PointArgs a) {
-  extern __shared__ float tp_lds[];
-  const int b = blockIdx.x / 3, t = blockIdx.x % 3, tid = threadIdx.x;
+// Tower t (0 params, 1 cam, 2 prior) of side a.side at pixel `flat` of frame b -> that pixel of the dense p109 / prior map.  One
+// workgroup of TP_WAVES waves, all of its threads; tp_lds: TP_LDS_FLOATS floats.
+__device__ __forceinline__ void tower_point(const PointArgs& a, const int b, const int t, const int flat, float* tp_lds) {
+  const int tid = threadIdx.x;
   const int co = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int* pk = a.picks + b * 4;
-  if (t == 2 && !pk[2]) return;                  // the prior is only read when the gate is open
-  const int flat = t == 2 ? pk[1 - a.side] : pk[a.side];
   const int cy = flat >> 6, cx = flat & 63;
   float* xin = tp_lds;                           // [19*19][36], dead after the entry conv
   float* t0 = tp_lds + TP_XIN;                   // [9*9][64]   tower input (block 0 residual)
@@ -1005,10 +1005,35 @@ __global__ __launch_bounds__(TP_WAVES * 64) void tower_point_kernel(const PointA
   }
 }
 
-__global__ __launch_bounds__(128) void point_mix_kernel(const PointArgs a) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int flat = a.picks[b * 4 + a.side];
-  __shared__ float p[112];
+__global__ __launch_bounds__(TP_WAVES * 64) void tower_point_kernel(const PointArgs a) {
+  extern __shared__ float tp_lds[];
+  const int b = blockIdx.x / 3, t = blockIdx.x % 3;
+  const int* pk = a.picks + b * 4;
+  if (t == 2 && !pk[2]) return;                  // the prior is only read when the gate is open
+  tower_point(a, b, t, t == 2 ? pk[1 - a.side] : pk[a.side], tp_lds);
+}
+
+// The towers of side a.side at the pixels of the frame's PointPlan, on a grid that B and K alone size: workgroup (b, e) takes
+// entry e of point_plan_entry's 3 K and returns at once when the entry lies beyond its list - nothing on the host reads the
+// counts.  One point per workgroup, tower_point's arithmetic: K = 1 gives the bits of tower_point_kernel.  Measured on one
+// MI355X at batch 64 with every rank detected (3 K points per side and frame; tools/multi_hand_bench.py): both sides' pick +
+// towers + mix take 0.23 / 0.39 / 0.56 / 1.04 ms at K = 1 / 2 / 4 / 8, and forward(max_hand=K) is 1.9 / 1.7 / 1.0 ms of 33
+// faster than with the dense heads at K = 2 / 4 / 8: no crossover up to ACRMI_MAX_HAND.  At batch 1 the point variant is
+// 0.14 - 0.22 ms of 2.7 slower at every K (so is the one-centre variant).  Two points of one tower per workgroup (half the
+// weight reads from L2, 145 KB of LDS, one workgroup per CU instead of two) was not built: the towers are 1 ms of the step at most.
+__global__ __launch_bounds__(TP_WAVES * 64) void tower_point_multi_kernel(const PointArgs a, const int K) {
+  extern __shared__ float tp_lds[];
+  const int b = blockIdx.x / (3 * K), e = blockIdx.x % (3 * K);
+  const PointPlan& plan = reinterpret_cast<const PointPlan*>(a.picks)[b];
+  int t = 0;
+  const int flat = point_plan_entry(plan, a.side, K, e, &t);
+  if ((unsigned)flat >= 4096u) return;           // (uniform) beyond the list
+  tower_point(a, b, t, flat, tp_lds);
+}
+
+// cam scale + mix conv + pare bias of side a.side at pixel `flat` of frame b; p: 112 floats of LDS.  128 threads, all of them.
+__device__ __forceinline__ void point_mix(const PointArgs& a, const int b, const int flat, float* p) {
+  const int tid = threadIdx.x;
   if (tid < 109) {
     float v = a.p109[((size_t)b * 4096 + flat) * a.p109_cs + tid];
     p[tid] = tid == 0 ? powf(1.1f, v) : v;         // cam scale (acr/model.py:95-96)
@@ -1021,10 +1046,42 @@ __global__ __launch_bounds__(128) void point_mix_kernel(const PointArgs a) {
   }
 }
 
+__global__ __launch_bounds__(128) void point_mix_kernel(const PointArgs a) {
+  __shared__ float p[112];
+  point_mix(a, blockIdx.x, a.picks[blockIdx.x * 4 + a.side], p);
+}
+
+// own pixel i of frame b, workgroup b * K + i; beyond the list: nothing
+__global__ __launch_bounds__(128) void point_mix_multi_kernel(const PointArgs a, const int K) {
+  __shared__ float p[112];
+  const int b = blockIdx.x / K, i = blockIdx.x % K;
+  const PointPlan& plan = reinterpret_cast<const PointPlan*>(a.picks)[b];
+  if (i >= plan.n_own[a.side]) return;
+  const int flat = plan.own[a.side][i];
+  if ((unsigned)flat >= 4096u) return;
+  point_mix(a, b, flat, p);
+}
+
+// The K picks of both sides of a frame and their PointPlan -> the frame's row of the picks workspace, written whole: the ops of
+// the two sides both run this and write the same ints.
+__global__ __launch_bounds__(256) void center_pick_multi_kernel(const PointArgs a, const int K) {
+  __shared__ PickScratch sc;
+  __shared__ MultiPick pk;
+  __shared__ PointPlan plan;
+  pick_centers_multi(a.center, a.center_cs, blockIdx.x, a.thresh, K, sc, pk);
+  if (threadIdx.x < 2) point_plan_side(pk.flat[threadIdx.x], pk.partner[threadIdx.x], K, threadIdx.x, &plan);
+  __syncthreads();
+  if (threadIdx.x < POINT_PLAN_INTS)
+    a.picks[blockIdx.x * POINT_PLAN_INTS + threadIdx.x] = reinterpret_cast<const int32_t*>(&plan)[threadIdx.x];
+}
+
+constexpr int TP_LDS_BYTES = TP_LDS_FLOATS * (int)sizeof(float);
+static_assert(TP_XIN >= (49 + 25 + 9 + 1 + TP_WAVES) * 64, "window buffers alias the dead x34 window");
+static_assert(POINT_MAX_HAND == ACRMI_MAX_HAND && POINT_PLAN_INTS >= 4, "the picks workspace, POINT_PLAN_INTS per frame, holds either layout");
+
 hipError_t launch_point_heads(const PointArgs& a, hipStream_t s) {
   static unsigned char attr_set[MAX_DEVICES] = {};
-  constexpr int LDS_BYTES = TP_LDS_FLOATS * (int)sizeof(float);
-  static_assert(TP_XIN >= (49 + 25 + 9 + 1 + TP_WAVES) * 64, "window buffers alias the dead x34 window");
+  constexpr int LDS_BYTES = TP_LDS_BYTES;
   std::lock_guard<std::recursive_mutex> lock(launch_mutex());
   if (first_use_on_device(attr_set)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_point_kernel),
@@ -1034,6 +1091,21 @@ hipError_t launch_point_heads(const PointArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(center_pick_kernel, dim3(a.B), dim3(256), 0, s, a);
   hipLaunchKernelGGL(tower_point_kernel, dim3(a.B * 3), dim3(TP_WAVES * 64), LDS_BYTES, s, a);
   hipLaunchKernelGGL(point_mix_kernel, dim3(a.B), dim3(128), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_point_heads_multi(const PointArgs& a, int max_hand, hipStream_t s) {
+  static unsigned char attr_set[MAX_DEVICES] = {};
+  if (max_hand < 1 || max_hand > ACRMI_MAX_HAND || a.B < 1) return hipErrorInvalidValue;
+  std::lock_guard<std::recursive_mutex> lock(launch_mutex());
+  if (first_use_on_device(attr_set)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tower_point_multi_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_BYTES);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(center_pick_multi_kernel, dim3(a.B), dim3(256), 0, s, a, max_hand);
+  hipLaunchKernelGGL(tower_point_multi_kernel, dim3(a.B * 3 * max_hand), dim3(TP_WAVES * 64), TP_LDS_BYTES, s, a, max_hand);
+  hipLaunchKernelGGL(point_mix_multi_kernel, dim3(a.B * max_hand), dim3(128), 0, s, a, max_hand);
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include "nv12_out_plan.h"
 #include "smooth_plan.h"
 #include "assoc_plan.h"
+#include "point_plan.h"
 
 namespace acrmi {
 
@@ -378,7 +379,8 @@ struct PointArgs {
   float* p109; int p109_cs;                // [B,64,64,cs] cam(3) | params(106) before the mix
   float* prior; int prior_cs;              // [B,64,64,cs] 106-ch prior map
   float* final_; int final_cs;             // [B,64,64,cs] 109-ch params map after the mix
-  int* picks;                              // [B,4] workspace: flat_l, flat_r, prior gate
+  int* picks;                              // workspace of max_batch * POINT_PLAN_INTS ints: [B,4] flat_l, flat_r, prior gate
+                                           // (launch_point_heads) or [B] PointPlan (launch_point_heads_multi)
   int side, B;
   float thresh;                            // centermap_conf_thresh
   int prior_when_both;                     // ACRMI_OPT_BATCH_PRIOR: evaluate the prior point whenever the frame has BOTH hands - the
@@ -386,6 +388,9 @@ struct PointArgs {
                                            // more than 32 px apart; the gated decode then decides whether the value is added
 };
 hipError_t launch_point_heads(const PointArgs& a, hipStream_t s);
+// the same towers at the max_hand (1..ACRMI_MAX_HAND) best centres of each side: the pixels of point_plan.h, which are the ones
+// decode_multi_kernel reads.  prior_when_both is not read (the batch-wide prior rule knows one hand per side).
+hipError_t launch_point_heads_multi(const PointArgs& a, int max_hand, hipStream_t s);
 
 struct ManoTables {   // device pointers
   const float* v_template;   // [778*3]

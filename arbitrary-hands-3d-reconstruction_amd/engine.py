@@ -154,6 +154,7 @@ class Engine(object):
         self.program = None
         self.have_mano = False
         self.point_heads = False
+        self.point_heads_multi = False
         self.lanes = 0
         self.lane_plan = False
         self.conf_thresh = 0.35
@@ -241,6 +242,21 @@ class Engine(object):
         on = bool(on) and self.has_point_heads
         _lib.check(self.L.acrmi_set_option(self.ctx, _lib.OPT_POINT_HEADS, int(on)), self.ctx)
         self.point_heads = on
+        return on
+
+    def set_point_heads_multi(self, on):
+        """ACRMI_OPT_POINT_HEADS_MULTI: `forward(max_hand=K)`, with or without `tracks=`, evaluates the params/cam/prior head
+        towers and the mix conv only at the pixels the top-K decode reads - the distinct K best centres of each side and the
+        distinct partners (csrc/point_plan.h), at most 3 K tower points per side and frame - instead of running the dense heads.
+        Same flags, centres and scores, the rest up to fp32 round-off; `forward` without max_hand does not look at it, and
+        set_point_heads is not looked at with max_hand.
+        Measured on one MI355X (every rank with a detection): at batch 64 `forward` is 1.9 / 1.7 / 1.0 ms
+        of 33 faster than with the dense heads at K = 2 / 4 / 8 - no crossover up to K = 8; at batch 1 it is 0.14 - 0.22 ms of
+        2.7 slower at every K, as set_point_heads is there: an option for large batches.
+        Returns what is in effect: a program without the point-heads ops stays on its dense heads (same results)."""
+        on = bool(on) and self.has_point_heads
+        _lib.check(self.L.acrmi_set_option(self.ctx, _lib.OPT_POINT_HEADS_MULTI, int(on)), self.ctx)
+        self.point_heads_multi = on
         return on
 
     def set_lanes(self, n):
@@ -394,9 +410,14 @@ class Engine(object):
         _lib.check(self.L.acrmi_allgather(self.ctx, None, _ptr(send), _ptr(recv), send.numel(), st), self.ctx)
         return recv
 
-    def run_point_heads(self, B):
-        """Re-evaluates the point heads on the resident buffers for the current center maps (acrmi_point_heads)."""
-        _lib.check(self.L.acrmi_point_heads(self.ctx, B, _stream(self.device)), self.ctx)
+    def run_point_heads(self, B, max_hand=1):
+        """Re-evaluates the point heads on the resident buffers for the current center maps (acrmi_point_heads); max_hand > 1:
+        at the pixels `decode(B, max_hand=max_hand)` reads (acrmi_point_heads_multi)."""
+        max_hand = check_max_hand(max_hand)
+        if max_hand > 1:
+            _lib.check(self.L.acrmi_point_heads_multi(self.ctx, B, max_hand, _stream(self.device)), self.ctx)
+        else:
+            _lib.check(self.L.acrmi_point_heads(self.ctx, B, _stream(self.device)), self.ctx)
 
     def ensure_batch(self, B):
         if self.program is None:
@@ -602,7 +623,7 @@ class Engine(object):
         max_hand = K > 1 (up to _lib.MAX_HAND): up to K hands of each side per frame (acrmi_forward_multi; DESIGN.md
         section 17) - every output gains a dimension, slots [B,K,2,176], verts [B,K,2,778,3], ...: pair k = (left rank k,
         right rank k), `.flatten(0, 1)` is B * K rows of the usual shape.  The dense heads run whatever set_point_heads
-        says; streams=, set_temporal and batch_semantics 'reference' are a ValueError (no identity across frames, and the
+        says, unless set_point_heads_multi(True) asked for the towers at the K best centres of each side; streams=, set_temporal and batch_semantics 'reference' are a ValueError (no identity across frames, and the
         batch-wide rule knows one hand per side).
         tracks= / track_table= (any max_hand): the stream of each frame and a TrackTable of max_hand
         slots - the decoded hands are put into track order and (smooth) each track is smoothed with its own filter before MANO

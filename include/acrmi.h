@@ -280,7 +280,8 @@ int acrmi_forward(acrmi_ctx* ctx, const uint8_t* img_dev, int B, const float* of
                   float* pj2d_org_dev, void* stream);
 
 /* acrmi_forward for up to max_hand (1..ACRMI_MAX_HAND) hands of each side per frame: the program with its DENSE heads
- * (whatever ACRMI_OPT_POINT_HEADS says: the point heads know one center per side), acrmi_decode_multi, one MANO launch over
+ * (whatever ACRMI_OPT_POINT_HEADS says) or, with ACRMI_OPT_POINT_HEADS_MULTI, with the head towers at the top max_hand
+ * centers of each side only, acrmi_decode_multi, one MANO launch over
  * the 2 * max_hand * B rows (placeholders included) -> slots [B,max_hand,2,ACRMI_SLOT], verts [B,max_hand,2,778,3], joints
  * [B,max_hand,2,21,3], the projections alike; offsets_dev [B,10] = one row per FRAME.  max_hand = 1 is acrmi_forward with
  * dense heads.  ACRMI_EINVAL, before anything is launched, for max_hand outside 1..ACRMI_MAX_HAND and for max_hand > 1 with
@@ -523,6 +524,17 @@ int acrmi_parebias(const float* pooled_dev, int C, int part0, const float* lc_w_
  * rules at B > 1 (acr/result_parser.py:42-47, 102-145: see acrmi_prior_gate) - decode, acrmi_prior_gate, gated decode, all on
  * the stream, no host round trip.  What ResultParser(batch_semantics='reference') / forward_batch(batch_semantics=...) set. */
 #define ACRMI_OPT_BATCH_PRIOR 9
+/* ACRMI_OPT_POINT_HEADS_MULTI (0/1, default 0): acrmi_forward_multi and acrmi_forward_tracks run the point variant of the
+ * program, with the params/cam/prior towers and the mix conv at the pixels acrmi_decode_multi reads for max_hand - the distinct
+ * top-max_hand centers of each side and the distinct partners (csrc/point_plan.h): at most 3 * max_hand tower points per side
+ * and frame, found on the device, no host read.  Same slots / vertices within fp32 round-off (centers, flags and scores exactly);
+ * the dense params / prior maps are then not produced.  0 = the dense heads, whatever ACRMI_OPT_POINT_HEADS says.  acrmi_forward
+ * and acrmi_forward_streams do not look at it.  Setting it on a program without point-heads ops is ACRMI_EINVAL, as for
+ * ACRMI_OPT_POINT_HEADS.  Measured on one MI355X (every rank with a detection, the most points there can
+ * be): at batch 64 the call is 1.9 / 1.7 / 1.0 ms of 33 faster than with the dense heads at max_hand 2 / 4 / 8 - no crossover up
+ * to ACRMI_MAX_HAND; at batch 1 it is 0.14 - 0.22 ms of 2.7 SLOWER at every max_hand, as ACRMI_OPT_POINT_HEADS is there: an
+ * option for large batches. */
+#define ACRMI_OPT_POINT_HEADS_MULTI 10
 int acrmi_set_option(acrmi_ctx* ctx, int option, int value);
 /* ACRMI_OPT_CONF_THRESH (default 0.35): center score threshold, strict > (args().centermap_conf_thresh,
  * acr/result_parser.py:198-205,241).  ACRMI_OPT_SMOOTH_COEFF (default 4.0): One-Euro mincutoff of the pose filters
@@ -764,6 +776,11 @@ int acrmi_allgather(acrmi_ctx* ctx, void* nccl_comm, const float* send_dev, floa
  * params/cam/prior towers + mix (acr/model.py:71-99,160-164) at the centers of the CURRENT center maps, written
  * into the pixels of the params/prior maps acrmi_decode samples. */
 int acrmi_point_heads(acrmi_ctx* ctx, int B, void* stream);
+/* acrmi_point_heads for the max_hand (1..ACRMI_MAX_HAND) best centers of each side: the towers and the mix at the pixels
+ * acrmi_decode_multi(ctx, B, max_hand, ...) reads (csrc/point_plan.h), nothing else is written.  max_hand = 1 writes the bits
+ * acrmi_point_heads writes without ACRMI_OPT_BATCH_PRIOR (which this call does not look at).  ACRMI_EINVAL / ACRMI_ESTATE before any device call: NULL ctx, no program, B or max_hand out of
+ * range, a program without point-heads ops. */
+int acrmi_point_heads_multi(acrmi_ctx* ctx, int B, int max_hand, void* stream);
 
 /* Profiling aid for bench.py: time every op of the program with hipEvents on `stream`
  * (one untimed warm-up pass first; ops outside the active head mode report 0).  ms_out[n_ops]; returns n_ops or <0.

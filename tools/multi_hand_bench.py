@@ -4,8 +4,13 @@
 
   decode alone   HIP events around one call as the caller sees it, median of `repeats`, on the resident head maps of a batch of
                  64: Engine.decode (acrmi_decode) and Engine.decode(max_hand=K) for K = 1, 2, 4, 8.
-  fused call     Engine.forward with the point heads off and on, and Engine.forward(max_hand=K) for K = 1, 2, 4 (dense heads),
-                 at batch 64 and at batch 1; the variants alternate `rounds` times.
+  fused call     Engine.forward with the point heads off and on, Engine.forward(max_hand=K) for K = 1, 2, 4, 8 with the dense
+                 heads and, for K = 2, 4, 8, with the point heads at the K best centres (set_point_heads_multi), at batch 64 and
+                 at batch 1; the variants alternate `rounds` times.  The K > 1 variants run with a threshold under every
+                 value of the maps: every rank has a detection, so the point heads evaluate as many points as they ever do
+                 (`tower_points_per_frame` says how many; the dense heads do not depend on the threshold).
+  point heads    acrmi_point_heads and acrmi_point_heads_multi (K = 1, 2, 4, 8) alone on the resident maps of the batch of 64,
+                 under the same threshold.
   MANO           Engine.mano on the 2 * K * B rows the fused call hands it (placeholders included), for the same K and batches.
 The run ends itself after `--timeout` seconds."""
 import argparse
@@ -21,6 +26,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PKG = 'arbitrary-hands-3d-reconstruction_amd'
+
+
+ALL_RANKS = -3.0e38      # a threshold every value of an NMS'd centre map passes
 
 
 def timed(fn, warmup, repeats):
@@ -75,13 +83,30 @@ def main():
             for K in (2, 4, 8):
                 alone['max_hand_%d' % K] = timed(lambda: eng.decode(B, max_hand=K), a.warmup, a.repeats)
             line['decode_alone_batch_%d' % B] = alone
+            eng.set_conf_thresh(ALL_RANKS)
+            heads = {'acrmi_point_heads': timed(lambda: eng.run_point_heads(B), a.warmup, a.repeats)}
+            for K in (1, 2, 4, 8):
+                call = lambda: L.check(eng.L.acrmi_point_heads_multi(eng.ctx, B, K, stream), eng.ctx)
+                heads['max_hand_%d' % K] = timed(call, a.warmup, a.repeats)
+            slots = eng.decode(B, max_hand=8)
+            flat, flag = slots[..., L.SLOT_FLATIND], slots[..., L.SLOT_FLAG]
+            assert bool((flag > 0.5).all())
+            line['tower_points_per_frame'] = {'max_hand_%d' % K: round(sum(
+                2 * len(set(flat[b, :K, h].tolist())) + len(set(flat[b, :K, 1 - h].tolist())) for b in range(B) for h in (0, 1)) / B, 2)
+                for K in (2, 4, 8)}      # an upper bound: every hand has a partner within 32 px
+            eng.set_conf_thresh(0.35)
+            line['point_heads_alone_batch_%d' % B] = heads
 
         def forward(point, K):
-            eng.set_point_heads(point)
+            eng.set_point_heads(point and K == 1)
+            eng.set_point_heads_multi(point and K > 1)
+            eng.set_conf_thresh(ALL_RANKS if K > 1 else 0.35)
             try:
                 return timed(lambda: eng.forward(frames, max_hand=K), a.warmup, a.repeats)['median_ms']
             finally:
                 eng.set_point_heads(False)
+                eng.set_point_heads_multi(False)
+                eng.set_conf_thresh(0.35)
 
         def forward_multi_1():      # acrmi_forward_multi with max_hand = 1 (Engine.forward(max_hand=1) is acrmi_forward)
             out = eng.forward(frames)
@@ -91,13 +116,15 @@ def main():
                                                              stream), eng.ctx)
             return timed(call, a.warmup, a.repeats)['median_ms']
 
-        runs = {'forward_dense': [], 'forward_point_heads': [], 'max_hand_1': [], 'max_hand_2': [], 'max_hand_4': []}
+        runs = {'forward_dense': [], 'forward_point_heads': [], 'max_hand_1': [], 'max_hand_2': [], 'max_hand_4': [],
+                'max_hand_8': [], 'max_hand_2_point_heads': [], 'max_hand_4_point_heads': [], 'max_hand_8_point_heads': []}
         for _ in range(a.rounds):      # the variants alternate, so that a drift of the machine meets all of them
             runs['forward_dense'].append(forward(False, 1))
             runs['forward_point_heads'].append(forward(True, 1))
             runs['max_hand_1'].append(forward_multi_1())
-            runs['max_hand_2'].append(forward(False, 2))
-            runs['max_hand_4'].append(forward(False, 4))
+            for K in (2, 4, 8):
+                runs['max_hand_%d' % K].append(forward(False, K))
+                runs['max_hand_%d_point_heads' % K].append(forward(True, K))
         fused['batch_%d_ms' % B] = runs
         rows = {}
         for K in (1, 2, 4):
