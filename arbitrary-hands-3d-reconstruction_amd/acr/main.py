@@ -259,7 +259,7 @@ class ACR(object):
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
-                      track_gate=None, track_max_miss=None, multi_point_heads=False):
+                      track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -292,16 +292,27 @@ class ACR(object):
         the engine.TrackTable, created by the first such call: max_streams streams, track_gate map pixels, track_max_miss
         frames; reset_tracks() / close_tracks()), every hand dict gains 'track_id', and results[path] lists the flagged lefts
         then the flagged rights in SLOT order, so a hand keeps its place while its rank changes.  With -t every track is smoothed
-        with its own One-Euro filter.  Not together with streams=."""
+        with its own One-Euro filter.  Not together with streams=.
+        contact=True: Engine.contact runs behind the fused call, and every hand dict gains four keys
+        (only then): 'contact_dist' - metres from the hand's nearest vertex to the nearest hand of the OTHER side in the same
+        row (inf when there is none); 'contact_with' - the index of that hand in results[path] (-1: none; with max_hand > 1
+        the partner is the pair with the smallest distance, the lower rank on a tie); 'contact_verts' - the hand's own vertex
+        indices within ops.CONTACT_DIST of that hand's nearest vertex; 'penetration' - metres, the depth estimate of the
+        hand's vertices inside the partner.  A nearest-vertex heuristic on two independently placed meshes, not a measurement.
+        Pairs are formed inside a row only: hands of different frames - and, with boxes=, of different regions, each of
+        which has its own camera - are never paired."""
+        if not isinstance(contact, bool):
+            raise ValueError('contact must be True or False, not %r' % (contact,))
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
         K = int(self.hands_per_side if max_hand is None else max_hand)
         if K != 1 or tracks is not None:
             return self._forward_batch_multi(rgb_u8_frames, paths, offsets, batch_semantics, render, render_bgr, show_items,
-                                             streams, K, tracks, max_streams, track_gate, track_max_miss, multi_point_heads)
+                                             streams, K, tracks, max_streams, track_gate, track_max_miss, multi_point_heads,
+                                             contact)
         results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
-                                                        max_streams, multi_point_heads)
+                                                        max_streams, multi_point_heads, contact)
         render_offsets = offsets
         if render is None:
             return results
@@ -318,7 +329,7 @@ class ACR(object):
         return results, views
 
     def _forward_batch_results(self, rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams, max_streams,
-                               multi_point_heads=False):
+                               multi_point_heads=False, contact=False):
         """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).
         multi_point_heads: checked, and without effect on one hand of each side (point_heads is the switch here)."""
         _check_multi_point_heads(multi_point_heads)
@@ -344,10 +355,12 @@ class ACR(object):
         from .. import ops
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(B, 2, 3)
+        if contact:
+            _add_contact(eng, out, 1)
         return results_from_out(out, paths), eng, out
 
     def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K, tracks=None,
-                             max_streams=None, gate=None, max_miss=None, multi_point_heads=False):
+                             max_streams=None, gate=None, max_miss=None, multi_point_heads=False, contact=False):
         """forward_batch with max_hand = K > 1 or with tracks=: Engine.forward(max_hand=K), the packaging, and the views of K
         regions per frame."""
         from .. import ops
@@ -386,6 +399,8 @@ class ACR(object):
         eng.check_range()
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(B, K, 2, 3)
+        if contact:
+            _add_contact(eng, out, K)
         results = results_from_out(out, paths)
         if render is None:
             return results
@@ -445,6 +460,32 @@ def _check_multi_point_heads(value):
         raise ValueError('multi_point_heads must be True or False, not %r' % (value,))
 
 
+def _add_contact(eng, out, K):
+    """out['contact'] = Engine.contact of `out` at the package's default parameters, with the parameters beside it."""
+    from .. import ops
+    out['contact'] = dict(eng.contact(out, max_hand=K, cam_trans=out['cam_trans']), contact_dist=ops.CONTACT_DIST,
+                          max_depth=ops.CONTACT_MAX_DEPTH)
+
+
+def _contact_keys(con, b, k, h, K, index_of):
+    """The four contact keys of hand (row b, rank k, side h): its partner is the flagged hand of the other side in the row whose
+    pair has the smallest min_d2, the lower rank on a tie.  con: out['contact'] as host arrays; index_of: (rank, side) -> the
+    index in the row's list."""
+    best, rank, pair = np.float32(np.inf), -1, -1
+    for q in range(K):
+        p = (b * K + k) * K + q if h == 0 else (b * K + q) * K + k
+        if con['min_d2'][p] < best:
+            best, rank, pair = con['min_d2'][p], q, p
+    if pair < 0:
+        return {'contact_dist': np.float32(np.inf), 'contact_with': np.int32(-1), 'contact_verts': np.zeros(0, np.int32),
+                'penetration': np.float32(0)}
+    r = np.float32(con['contact_dist'])
+    touching = (con['nn'][pair, h] >= 0) & (con['d2'][pair, h] <= r * r)
+    return {'contact_dist': np.sqrt(best, dtype=np.float32), 'contact_with': np.int32(index_of.get((rank, 1 - h), -1)),
+            'contact_verts': np.nonzero(touching)[0].astype(np.int32),
+            'penetration': np.sqrt(con['depth2'][pair, h], dtype=np.float32)}
+
+
 def results_from_out(out, paths):
     """What the fused call returned -> {path: [hand dicts]} ({} for a frame without a flagged hand).  out: 'slots' [B,2,176] or
     [B,K,2,176] and 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans' shaped alike (tensors or arrays: nothing here needs
@@ -463,9 +504,13 @@ def results_from_out(out, paths):
         ids = (ids.detach().cpu().numpy() if hasattr(ids, 'detach') else np.asarray(ids)).reshape(slots.shape[:3])
     if len(paths) != B:
         raise ValueError('one path per frame: %d paths, %d frames' % (len(paths), B))
+    con = out.get('contact')      # with contact=True: every hand dict gains the four contact keys
+    if con is not None:
+        con = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in con.items()}
     results = {}
     for b, path in enumerate(paths):
         hands = []
+        where = []
         for h in (0, 1):
             for k in range(slots.shape[1]):
                 if slots[b, k, h, S.SLOT_FLAG] > 0.5:
@@ -481,6 +526,11 @@ def results_from_out(out, paths):
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
                     if ids is not None:
                         hands[-1]['track_id'] = np.int32(ids[b, k, h])
+                    where.append((k, h))
+        if con is not None:
+            index_of = {kh: n for n, kh in enumerate(where)}
+            for hand, (k, h) in zip(hands, where):
+                hand.update(_contact_keys(con, b, k, h, slots.shape[1], index_of))
         results[path] = hands if hands else {}
     return results
 
@@ -529,7 +579,7 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
-                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False):
+                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -556,9 +606,13 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     max_hand: as forward_batch (None = args().hands_per_side).  With boxes= more than one hand of a side per REGION is a
     ValueError: the box is there because the caller has found the person.
     tracks / track_gate / track_max_miss: as forward_batch; with boxes= a ValueError (ops.track_boxes follows a region).
-    multi_point_heads: as forward_batch (without effect with boxes=: a region has one hand of each side)."""
+    multi_point_heads: as forward_batch (without effect with boxes=: a region has one hand of each side).
+    contact: as forward_batch.  With boxes= the two hands of a REGION are paired: every region has its own camera, so hands of
+    different regions are never paired, also when the regions lie in one frame."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
+    if not isinstance(contact, bool):
+        raise ValueError('contact must be True or False, not %r' % (contact,))
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
@@ -576,7 +630,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         raise ValueError('region_views=True draws the views of regions: it needs boxes=')
     if boxes is not None:
         got = _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
-                               pixel_format, matrix, region_views)
+                               pixel_format, matrix, region_views, contact)
     else:
         if box_frame is not None:
             raise ValueError('box_frame says which frame each box is of: it needs boxes=')
@@ -588,7 +642,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
                                  max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                 multi_point_heads=multi_point_heads)
+                                 multi_point_heads=multi_point_heads, contact=contact)
     if to_nv12 is None:
         return got
     results, views = got
@@ -669,7 +723,7 @@ def _region_views(self, eng, out, canvas, offsets, box_frame, items):
 
 
 def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix,
-                     region_views=False):
+                     region_views=False, contact=False):
     """forward_raw_batch with boxes."""
     from .. import _lib as S
     from .. import ops
@@ -684,7 +738,8 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     n = meta['image'].shape[0]
     if len(paths) != n:
         raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
-    results, eng, out = self._forward_batch_results(meta['image'], paths, meta['offsets'], True, None, streams, max_streams)
+    results, eng, out = self._forward_batch_results(meta['image'], paths, meta['offsets'], True, None, streams, max_streams,
+                                                    contact=contact)
     if not render:
         return results
     canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames

@@ -1,6 +1,7 @@
 // libacrmi.so: context life cycle, options and the fused entry points of the C ABI declared in include/acrmi.h
 // (program replay: acrmi_program.hip; stand-alone operators: acrmi_ops.hip; RCCL: acrmi_comm.hip).
 #include "acrmi_ctx.h"
+#include "contact_plan.h"
 
 std::string g_err;
 
@@ -76,6 +77,7 @@ void acrmi_destroy(acrmi_ctx* c) {
   release_weights(c);
   acrmi_streams_destroy(c->own_streams);
   if (c->render_ws) (void)hipFree(c->render_ws);
+  if (c->contact_ws) (void)hipFree(c->contact_ws);
   if (c->region_hand_frame) (void)hipFree(c->region_hand_frame);
   for (int32_t* p : c->faces_topo)
     if (p) (void)hipFree(p);
@@ -117,6 +119,14 @@ int acrmi_share_weights(acrmi_ctx* c, acrmi_ctx* donor) {
   return ACRMI_OK;
 }
 
+// The orientation of a side's topology (csrc/contact_plan.h) from its template vertices, once both are loaded; +1 before.
+static void update_contact_sign(acrmi_ctx* c, int side) {
+  c->contact_sign[side] = 1;
+  if (c->v_template_host[side].size() == 778 * 3 && !c->faces_host[side].empty())
+    c->contact_sign[side] = contact_orientation_sign(c->v_template_host[side].data(), c->faces_host[side].data(),
+                                                     (int)(c->faces_host[side].size() / 3));
+}
+
 int acrmi_load_mano(acrmi_ctx* c, int side, const float* v_template, const float* shapedirs, const float* posedirs,
                     const float* J_regressor, const float* weights, const float* hands_mean) {
   if (!c || side < 0 || side > 1 || !v_template || !shapedirs || !posedirs || !J_regressor || !weights || !hands_mean)
@@ -144,6 +154,8 @@ int acrmi_load_mano(acrmi_ctx* c, int side, const float* v_template, const float
     *dst = d;
     return ACRMI_OK;
   };
+  c->v_template_host[side].assign(v_template, v_template + NV3);
+  update_contact_sign(c, side);
   ManoTables& t = c->mano[side];
   int r;
   if ((r = up(v_template, NV3, &t.v_template))) return r;
@@ -850,6 +862,8 @@ int acrmi_load_faces(acrmi_ctx* c, int side, const int32_t* faces_host, int n_fa
   }
   c->faces_topo[side] = d;
   c->n_faces[side] = n_faces;
+  c->faces_host[side].assign(faces_host, faces_host + 3 * (size_t)n_faces);      // (validated by build_mesh_topology above)
+  update_contact_sign(c, side);
   return ACRMI_OK;
 }
 
@@ -917,6 +931,52 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
   e = render_launch(c, sc, verts, cam_trans, offsets ? sc.view : nullptr, nullptr, focal, visible_weight, img_in, img_out, ids_out,
                     2 * B, B, H, W, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render: %s", hipGetErrorString(e));
+}
+
+// ---- contact between the hands of a row (csrc/contact.hip) ---------------------------------------------------------------
+// The context's contact scratch for n = B * K hand pairs: [pairs n*K*2 | mesh_topo 2n | sign 2n] int32 (sized for K =
+// ACRMI_MAX_HAND) and the P / N records of the 2n meshes behind them.  Allocates at the first call and when n grows.
+static size_t contact_head_bytes(long long n) {
+  return ((size_t)n * (2 * CONTACT_MAX_HAND + 4) * sizeof(int32_t) + 255) / 256 * 256;
+}
+
+int acrmi_contact(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, int K, const int32_t* sign_host,
+                  float contact_dist, float max_depth, int32_t* nn, float* d2, float* s_out, float* sum_f, int32_t* sum_i,
+                  void* stream) {
+  if (!c || !verts || !cam_trans || !slots || !nn || !d2 || !s_out || !sum_f || !sum_i || B <= 0)
+    return fail(c, ACRMI_EINVAL, "acrmi_contact: bad arguments");
+  if (K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "acrmi_contact: max_hand %d outside 1..%d", K, ACRMI_MAX_HAND);
+  if (!contact_params_ok(contact_dist, max_depth))
+    return fail(c, ACRMI_EINVAL, "acrmi_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
+  const long long n = (long long)B * K, n_pairs = n * K;
+  if (2 * n > 0x7fffffffll || n_pairs > 0x7fffffffll || !contact_plan((int)(2 * n), 778, (int)n_pairs).ok)
+    return fail(c, ACRMI_EINVAL, "acrmi_contact: %d frames of %d x %d pairs are beyond 2^31 - 1 elements", B, K, K);
+  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "acrmi_contact: MANO faces not loaded (acrmi_load_faces)");
+  ON_DEVICE(c);
+  if (n > c->contact_ws_hands) {
+    if (c->contact_ws) {
+      HIPCHK(c, hipDeviceSynchronize());
+      (void)hipFree(c->contact_ws);
+      c->contact_ws = nullptr;
+      c->contact_ws_hands = 0;
+    }
+    HIPCHK(c, hipMalloc(&c->contact_ws, contact_head_bytes(n) + contact_workspace_bytes((int)(2 * n), 778)));
+    c->contact_ws_hands = n;
+  }
+  int32_t* pairs = (int32_t*)c->contact_ws;
+  int32_t* mesh_topo = pairs + 2 * n_pairs;
+  int32_t* sign = mesh_topo + 2 * n;
+  const int sl = sign_host ? sign_host[0] : c->contact_sign[0], sr = sign_host ? sign_host[1] : c->contact_sign[1];
+  hipError_t e = launch_contact_prep(slots, B, K, sl < 0 ? -1 : 1, sr < 0 ? -1 : 1, pairs, mesh_topo, sign, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "acrmi_contact: prep: %s", hipGetErrorString(e));
+  ContactArgs a{};
+  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1]; a.mesh_topo = mesh_topo;
+  a.sign = sign; a.pairs = pairs; a.contact_dist = contact_dist; a.max_depth = max_depth;
+  a.nn = nn; a.d2 = d2; a.side = s_out; a.sum_f = sum_f; a.sum_i = sum_i;
+  a.ws = (float4*)(c->contact_ws + contact_head_bytes(c->contact_ws_hands));
+  a.n_meshes = (int)(2 * n); a.n_verts = 778; a.n_faces = c->n_faces[0]; a.n_pairs = (int)n_pairs;
+  e = launch_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "acrmi_contact: %s", hipGetErrorString(e));
 }
 
 // ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------

@@ -119,6 +119,14 @@ struct acrmi_ctx {
   int render_ws_frames = 0;
   int32_t* region_hand_frame = nullptr;   // acrmi_overlay_regions: the frame of each hand, derived on the device
   int region_hand_cap = 0;                // regions it holds
+  // contact between the hands (acrmi_contact; csrc/contact_plan.h): host copies of what the orientation sign of a side's
+  // topology is derived from (the side's template vertices and its faces; +1 until both are there), and the call's scratch
+  // (pairs, per-mesh topology index and sign, the P / N records), grown on demand
+  std::vector<float> v_template_host[2];
+  std::vector<int32_t> faces_host[2];
+  int contact_sign[2] = {1, 1};
+  char* contact_ws = nullptr;
+  long long contact_ws_hands = 0;      // B * K it holds
   int last_batch = 0;          // batch of the last program run: whose centre maps the head buffers hold (acrmi_overlay)
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;

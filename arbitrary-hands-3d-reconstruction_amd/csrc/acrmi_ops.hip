@@ -1,5 +1,6 @@
 // libacrmi.so: the stand-alone operators of the C ABI (unit tests / callers with their own tensors; no context).
 #include "acrmi_ctx.h"
+#include "contact_plan.h"
 #include "conv_frame.h"   // conv_shape
 #include "roi_plan.h"
 #include "track_plan.h"
@@ -696,6 +697,37 @@ int acrmi_rasterize_views(const float* verts_dev, const float* trans_dev, int n_
   return rasterize("acrmi_rasterize_views", true, verts_dev, trans_dev, n_meshes, n_verts, n_faces, topo_dev, topo2_dev,
                    mesh_topo_dev, mesh_frame_dev, rgb_dev, view_dev, focal, visible_weight, img_in_dev, img_out_dev, n_frames, H, W,
                    ids_out_dev, ws_dev, stream);
+}
+
+// ---- contact and interpenetration between meshes (csrc/contact.hip, csrc/contact_plan.h) ----
+size_t acrmi_contact_workspace(int n_meshes, int n_verts) { return contact_workspace_bytes(n_meshes, n_verts); }
+
+int acrmi_mesh_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                       const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev, const int32_t* sign_dev,
+                       const int32_t* pairs_dev, int n_pairs, float contact_dist, float max_depth, int32_t* nn_dev, float* d2_dev,
+                       float* s_dev, float* sum_f_dev, int32_t* sum_i_dev, void* ws_dev, void* stream) {
+  if (n_meshes <= 0 || n_verts <= 0 || n_faces <= 0 || n_pairs < 0)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: bad sizes (%d meshes, %d vertices, %d faces, %d pairs)", n_meshes, n_verts,
+                n_faces, n_pairs);
+  if (n_verts > CONTACT_MAX_VERTS)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: %d vertices, at most %d (the other mesh is held in LDS)", n_verts,
+                CONTACT_MAX_VERTS);
+  if (!contact_params_ok(contact_dist, max_depth))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
+  if (n_pairs == 0) return ACRMI_OK;
+  if (!verts_dev || !topo_dev || !pairs_dev || !nn_dev || !d2_dev || !s_dev || !sum_f_dev || !sum_i_dev || !ws_dev)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: a null pointer");
+  if (((uintptr_t)ws_dev & 15) != 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: the workspace is not 16-byte aligned");
+  if (!contact_plan(n_meshes, n_verts, n_pairs).ok)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: %d pairs of %d vertices (or %d meshes) are beyond 2^31 - 1 elements", n_pairs,
+                n_verts, n_meshes);
+  ContactArgs a{};
+  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
+  a.sign = sign_dev; a.pairs = pairs_dev; a.contact_dist = contact_dist; a.max_depth = max_depth;
+  a.nn = nn_dev; a.d2 = d2_dev; a.side = s_dev; a.sum_f = sum_f_dev; a.sum_i = sum_i_dev; a.ws = (float4*)ws_dev;
+  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_pairs = n_pairs;
+  hipError_t e = launch_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_mesh_contact: %s", hipGetErrorString(e));
 }
 
 // ---- key-point skeleton and heat-map views (csrc/overlay.hip) ----

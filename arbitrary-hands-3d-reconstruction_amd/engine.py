@@ -167,6 +167,8 @@ class Engine(object):
         self._mano_tables = {}
         self.have_faces = False
         self._faces = {}
+        self._contact_sign = [1, 1]            # derived at load_faces / load_mano time (the context derives the same)
+        self._contact_sign_set = None          # set_contact_sign's override
 
     def close(self):
         # (the handle is dropped first and without touching module globals: during interpreter shutdown `C` may already
@@ -443,6 +445,7 @@ class Engine(object):
         self.set_temporal(other.temporal, smooth_coeff=other.smooth_coeff)
         self.set_mano_fp16(other.mano_fp16)
         self.set_batch_semantics(getattr(other, 'batch_semantics', 'frame'))
+        self._contact_sign_set = getattr(other, '_contact_sign_set', None)
 
     def load_mano_side(self, name, t):
         """One side's tables (mano/manolayer.py:61-102 buffers) -> HBM, blend-shape tables transposed."""
@@ -459,6 +462,7 @@ class Engine(object):
         self._mano_tables[name] = {k: a for k, a in zip(('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights',
                                                           'hands_mean'), arrs)}
         self.have_mano = len(self._mano_tables) == 2
+        self._derive_contact_sign(name)
         if t.get('faces') is not None:      # tables without faces load as before; `render` then raises the ACRMI_ESTATE error
             self.load_faces(name, t['faces'])
 
@@ -474,6 +478,31 @@ class Engine(object):
             self._mano_tables[name]['faces'] = f
         self._faces[name] = f
         self.have_faces = len(self._faces) == 2
+        self._derive_contact_sign(name)
+
+    def _derive_contact_sign(self, name):
+        """The orientation of a side's faces on its template vertices (ops.mesh_orientation), +1 while either is missing -
+        what acrmi_load_faces / acrmi_load_mano derive for the context."""
+        t, f = self._mano_tables.get(name), self._faces.get(name)
+        side = {'left': 0, 'right': 1}[name]
+        self._contact_sign[side] = 1
+        if t is not None and f is not None:
+            self._contact_sign[side] = ops_mod.mesh_orientation(np.asarray(t['v_template'], np.float32).reshape(778, 3), f)
+
+    @property
+    def contact_sign(self):
+        """(left, right): the sign `contact` multiplies each side's vertex normals with."""
+        return tuple(self._contact_sign_set or self._contact_sign)
+
+    def set_contact_sign(self, left, right):
+        """Overrides the per-side orientation signs of `contact` (+1: the faces are wound outwards); None, None: back to the
+        derived ones."""
+        if left is None and right is None:
+            self._contact_sign_set = None
+            return
+        if left not in (1, -1) or right not in (1, -1):
+            raise ValueError('contact signs are +1 or -1')
+        self._contact_sign_set = [int(left), int(right)]
 
     # ---- hot path ------------------------------------------------------------------------------
     def _check_img(self, img):
@@ -819,6 +848,40 @@ class Engine(object):
         return self._overlay(out, src, B, 'images', what, 'pj2d' if offsets is None else 'pj2d_org', self._frame_offsets(offsets, B),
                              None, bgr, dst, stream)
 
+    def contact(self, out, max_hand=1, cam_trans=None, contact_dist=None, max_depth=None, focal_length=1265., stream=None):
+        """Contact and interpenetration between the left and the right hands of every row of `out` (what `forward(...,
+        project=True[, max_hand=K])` returned) on the GPU (acrmi_contact): the nearest-vertex half-space
+        heuristic - not a point-to-triangle distance, not a true inside test - on the two meshes placed by their cam_trans,
+        so it is only as good as those two independent fits.  Pairs are formed inside a row only: with regions (boxes=) every
+        region has its own camera, and hands of different regions are never paired.
+        max_hand = K: the K the forward ran with; pair (b*K + i)*K + j is (left rank i, right rank j) of row b, skipped when
+        either hand's flag is not set (read on the device: nothing here waits for it).  cam_trans [B,(K,)2,3]: as `render`
+        obtains it - the caller's, out['cam_trans'], or computed from out['joints'] / out['pj2d'].  contact_dist / max_depth:
+        metres, defaults ops.CONTACT_DIST / ops.CONTACT_MAX_DEPTH (parameters, not measurements).  The orientation signs:
+        `contact_sign` / set_contact_sign.  Returns what ops.mesh_contact returns, for the B*K*K pairs; direction 0 = the left
+        hand's vertices.  stream: as `forward`."""
+        K = check_max_hand(max_hand)
+        slots = out['slots']
+        B = slots.shape[0]
+        lead = tuple(slots.shape[:-1])
+        if lead not in ((B, K, 2),) + (((B, 2),) if K == 1 else ()) or tuple(out['verts'].shape) != lead + (778, 3):
+            raise ValueError('out does not hold %d rows of %d hand pairs' % (B, K))
+        contact_dist, max_depth = ops_mod.check_contact_params(ops_mod.CONTACT_DIST if contact_dist is None else contact_dist,
+                                                               ops_mod.CONTACT_MAX_DEPTH if max_depth is None else max_depth)
+        st = _stream(self.device) if stream is None else C.c_void_p(stream)
+        flat = out if len(lead) == 2 else {k: out[k].flatten(0, 1) for k in ('joints', 'pj2d', 'cam_trans') if out.get(k) is not None}
+        if cam_trans is not None:
+            cam_trans = cam_trans.reshape(B * K, 2, 3)
+        cam_trans = self._cam_trans(flat, cam_trans, B * K, focal_length, st)
+        verts, slots = out['verts'].contiguous(), slots.contiguous()
+        raw = ops_mod.contact_outputs(B * K * K, 778, self.device)
+        sign = None if self._contact_sign_set is None else (C.c_int32 * 2)(*self._contact_sign_set)
+        _lib.check(self.L.acrmi_contact(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, sign, contact_dist, max_depth,
+                                        _ptr(raw['nn']), _ptr(raw['d2']), _ptr(raw['side']), _ptr(raw['sum_f']), _ptr(raw['sum_i']),
+                                        st), self.ctx)
+        self._contact_keep = (verts, slots, cam_trans)      # referenced until the next call has been queued
+        return ops_mod.contact_result(raw)
+
     def _regions(self, images, offsets, region_frame, n):
         """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->
         (src, offsets, region_frame) on the device."""
@@ -1087,6 +1150,21 @@ class EnginePool(object):
         """Engine.overlay_regions of the ticket's batch on the ticket's stream, like overlay()."""
         return self._view(ticket, 'overlay_regions', '_overlay_keep', self._region_frames(ticket, frames, offsets, region_frame),
                           what=what, **kw)
+
+    def contact(self, ticket, **kw):
+        """Engine.contact of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True) and collect(), like render().  max_hand is the ticket's.  Returns what Engine.contact returns; collect()
+        then also orders the caller's stream behind it."""
+        out = ticket['out']
+        K = out['slots'].shape[1] if out['slots'].dim() == 4 else 1
+
+        def prepare(eng):
+            ct = kw.get('cam_trans')
+            return {} if ct is None else {'cam_trans': ct.to(self.device, torch.float32).contiguous()}
+
+        rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
+        return self._on_ticket(ticket, 'contact', prepare, keep='_contact_keep',
+                               call=lambda eng, raw, t: eng.contact(out, max_hand=K, stream=raw, **t, **rest))
 
     def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
         """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

@@ -977,6 +977,108 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
     return (out, ids) if return_ids else out
 
 
+# ---- contact and interpenetration between meshes (csrc/contact.hip; DESIGN.md section 19) --------------------------------
+CONTACT_DIST, CONTACT_MAX_DEPTH = 0.005, 0.02      # metres; defaults of PARAMETERS, not measurements
+
+
+def mesh_orientation(verts, faces):
+    """+1 / -1: the sign of the signed volume sum v0 . (v1 x v2) of a closed mesh (verts [V,3], faces [F,3]) in float64; +1
+    when it is exactly 0.  +1 means the face normals (v1 - v0) x (v2 - v0) point outwards - the `sign` mesh_contact takes.
+    Pure host: works without a GPU."""
+    v = verts.detach().cpu().numpy() if hasattr(verts, 'detach') else np.asarray(verts)
+    f = faces.detach().cpu().numpy() if hasattr(faces, 'detach') else np.asarray(faces)
+    v = v.astype(np.float64)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('verts must be [V,3] and faces [F,3]')
+    f = f.astype(np.int64)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError('a face names a vertex outside [0, %d)' % v.shape[0])
+    vol = float((v[f[:, 0]] * np.cross(v[f[:, 1]], v[f[:, 2]])).sum())
+    return -1 if vol < 0 else 1
+
+
+def check_contact_params(contact_dist, max_depth):
+    contact_dist, max_depth = float(contact_dist), float(max_depth)
+    if not (0 <= contact_dist < float('inf')) or not (max_depth >= 0):
+        raise ValueError('contact_dist must be finite and >= 0, max_depth >= 0 (inf allowed)')
+    return contact_dist, max_depth
+
+
+def contact_outputs(n_pairs, V, dev):
+    """The raw output tensors of acrmi_mesh_contact / acrmi_contact for n_pairs pairs of V vertices."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    return {'nn': new((n_pairs, 2, V), torch.int32), 'd2': new((n_pairs, 2, V), torch.float32),
+            'side': new((n_pairs, 2, V), torch.float32), 'sum_f': new((n_pairs, 4), torch.float32),
+            'sum_i': new((n_pairs, 6), torch.int32)}
+
+
+def contact_result(raw):
+    """The raw outputs -> the dict mesh_contact returns (views of the summaries, no copy, no host visit)."""
+    return {'nn': raw['nn'], 'd2': raw['d2'], 'side': raw['side'], 'min_d2': raw['sum_f'][:, 0], 'closest': raw['sum_i'][:, 0:2],
+            'n_contact': raw['sum_i'][:, 2:4], 'n_inside': raw['sum_i'][:, 4:6], 'depth2': raw['sum_f'][:, 1:3]}
+
+
+def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, contact_dist=CONTACT_DIST,
+                 max_depth=CONTACT_MAX_DEPTH):
+    """Contact and interpenetration between pairs of meshes on the GPU (acrmi_mesh_contact): the nearest-vertex half-space
+    heuristic of DESIGN.md section 19 - not a point-to-triangle distance, not a true inside test; meaningful for closed
+    meshes.  verts [M,V,3] device fp32 (metres), trans [M,3] added to them (cam_trans) or None.  faces: as render_meshes -
+    [F,3] integers or a mesh_topology blob, or a pair of either chosen per mesh by topo_index [M] (0 / 1).  sign [M] (+1 / -1,
+    mesh_orientation of each mesh's topology) or None = all +1.  pairs [n,2] mesh indices (a, b): a host list / array is
+    checked here (an index >= M is a ValueError; < 0 = skip the pair), a device tensor is not read - the kernel treats every
+    index outside [0, M) as a skipped pair.  contact_dist / max_depth in metres (max_depth may be inf).
+    Returns device tensors, nothing is copied to the host: 'nn' int32, 'd2', 'side' fp32 [n,2,V] (direction 0: the vertices of
+    a against b; 1: those of b against a; nearest vertex, its squared distance, the side value - inside where negative);
+    'min_d2' [n] with 'closest' [n,2] = (i, j); 'n_contact', 'n_inside' int32 [n,2]; 'depth2' [n,2] = the largest d2 among the
+    inside vertices (its square root: the penetration depth estimate).  A skipped pair: nn -1, d2 inf, side 0, zero counts,
+    closest (-1, -1)."""
+    _need_cuda(verts)
+    if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
+        raise ValueError('verts must be [M,V,3]')
+    contact_dist, max_depth = check_contact_params(contact_dist, max_depth)
+    dev = verts.device
+    M, V, _ = verts.shape
+    if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+        pr = pairs.to(dev, torch.int32).contiguous()
+    else:
+        host = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs)
+        if host.size and not np.issubdtype(host.dtype, np.integer):
+            raise ValueError('pairs must be integers')
+        host = host.reshape(-1, 2) if host.size else np.zeros((0, 2), np.int32)
+        if host.size and host.max() >= M:
+            raise ValueError('a pair names mesh %d, there are %d meshes' % (int(host.max()), M))
+        pr = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev)
+    if pr.dim() != 2 or pr.shape[1] != 2:
+        raise ValueError('pairs must be [n,2]')
+    n = pr.shape[0]
+    pair = isinstance(faces, (tuple, list)) and len(faces) == 2 and not np.isscalar(faces[0]) and np.ndim(faces[0]) >= 1
+    topos = [_topology_on(t, V, dev) for t in (faces if pair else [faces])]
+    head = [t[:2].tolist() for t in topos]      # (one small D2H copy per topology; [F, V])
+    F = head[0][0]
+    if any(h != [F, V] for h in head):
+        raise ValueError('topology is for (faces, verts) = %s, verts have %d vertices' % (head, V))
+    v = verts.to(dev, torch.float32).contiguous()
+    t = None if trans is None else trans.to(dev, torch.float32).contiguous().view(M, 3)
+    ti = None
+    if topo_index is not None:
+        ti = torch.as_tensor(topo_index).to(dev, torch.int32).contiguous()
+        if ti.numel() != M or not pair:
+            raise ValueError('topo_index needs a pair of topologies and one int per mesh')
+    sg = None
+    if sign is not None:
+        sg = torch.as_tensor(sign).to(dev, torch.int32).contiguous()
+        if sg.numel() != M:
+            raise ValueError('sign must hold one int per mesh')
+    raw = contact_outputs(n, V, dev)
+    L = _lib.lib()
+    ws = torch.empty(int(L.acrmi_contact_workspace(M, V)) + 16, dtype=torch.uint8, device=dev)
+    ws_p = (ws.data_ptr() + 15) // 16 * 16
+    _lib.check(L.acrmi_mesh_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(sg), _p(pr), n,
+                                    contact_dist, max_depth, _p(raw['nn']), _p(raw['d2']), _p(raw['side']), _p(raw['sum_f']),
+                                    _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
+    return contact_result(raw)
+
+
 # ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------
 # mano/skeleton.txt (first 21 rows) of the reference: five fingers of four joints, tip to base, then the wrist (no parent)
 SKELETON_PARENTS = (1, 2, 3, 20, 5, 6, 7, 20, 9, 10, 11, 20, 13, 14, 15, 20, 17, 18, 19, 20, -1)

@@ -661,6 +661,58 @@ int acrmi_render(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_
                  const uint8_t* img_in_dev, uint8_t* img_out_dev, int H, int W, int32_t* ids_out_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Contact and interpenetration between two meshes (csrc/contact_plan.h, csrc/contact.hip): are the
+ * two hands touching, where, and do the reconstructions run through each other.  The reference has no such measure.  It is
+ * the usual nearest-VERTEX half-space heuristic - not a point-to-triangle distance and not a true inside test - and is
+ * meaningful for closed meshes.  All fp32, every operation rounded on its own:
+ *  position  P_m[i] = verts[m,i] + trans[m] per component; without trans the vertex as given.
+ *  normal    N_m[i] = sign[m] * the sum, over the faces incident to vertex i in the order of the vertex -> faces table of
+ *            acrmi_mesh_topology (by face, then by corner), of (v1 - v0) x (v2 - v0) taken on verts as given (before trans),
+ *            each component (a*b) - (c*d), accumulated from 0.  NOT normalised: only its sign is used, there is no square
+ *            root and no division.  sign[m] = +1 / -1 makes the rule hold for a topology wound inwards.  A vertex no face
+ *            references has N = 0.
+ *  nearest   for the ordered pair (a, b) and every vertex i of a: d = P_a[i] - P_b[j], d2(i,j) = (dx*dx + dy*dy) + dz*dz;
+ *            nn[i] = the j with the smallest d2, the lowest j on a tie.  A NaN d2 never wins, nor does +inf (an overflowed
+ *            square); if no j qualifies nn = -1, d2 = +inf, s = 0.
+ *  side      s[i] = (dx*Nx + dy*Ny) + dz*Nz with the d and N_b of j = nn[i].  Vertex i is IN CONTACT when d2[i] <= r*r (r =
+ *            contact_dist, the product in fp32) and INSIDE when s[i] < 0 and d2[i] <= m*m (m = max_depth, +inf allowed).
+ *  both directions of a pair are computed: direction 0 = the vertices of a against b, direction 1 = those of b against a.
+ *  summary   sum_f = (the smallest d2 of direction 0, the largest d2 among the inside vertices of direction 0, of direction 1
+ *            - 0 when there are none; its square root is the penetration depth estimate -, 0);  sum_i = (i, j of that
+ *            smallest d2 - the lowest i on a tie, (-1, -1) when there is none -, contact vertices of direction 0, 1, inside
+ *            vertices of direction 0, 1).
+ *  skipped   a pair with a mesh index < 0 (or >= n_meshes) is skipped: nn = -1, d2 = +inf, s = 0, zero counts, (-1, -1).
+ * The defaults of the Python layer, contact_dist = 0.005 m and max_depth = 0.02 m, are parameters, not measurements.  The
+ * relative placement of two hands is only as good as their two independent cam_trans fits.  No atomics on global memory:
+ * deterministic; a pair computed alone equals the same pair computed in a batch.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of device workspace acrmi_mesh_contact needs for n_meshes meshes of n_verts vertices (0 for non-positive sizes). */
+size_t acrmi_contact_workspace(int n_meshes, int n_verts);
+/* verts_dev [n_meshes,n_verts,3] fp32, trans_dev [n_meshes,3] or NULL; topo_dev / topo2_dev / mesh_topo_dev as acrmi_rasterize
+ * takes them; sign_dev [n_meshes] int32 (< 0: -1, else +1) or NULL = all +1; pairs_dev [n_pairs,2] int32 mesh indices (a
+ * mesh may sit in several pairs, or be paired with itself); outputs nn_dev int32, d2_dev, s_dev fp32, each
+ * [n_pairs,2,n_verts], sum_f_dev [n_pairs,4], sum_i_dev [n_pairs,6]; ws_dev: acrmi_contact_workspace() bytes, 16-byte aligned,
+ * not shared by launches that may overlap.  n_verts <= 4000; contact_dist finite and >= 0, max_depth >= 0; n_pairs * 2 *
+ * n_verts and n_meshes * n_verts at most 2^31 - 1.  NULL pointers and sizes are checked before any GPU call (ACRMI_EINVAL);
+ * n_pairs == 0 is success and touches nothing.  The topology blobs are trusted (acrmi_mesh_topology validates them); the
+ * pair indices are read on the device and need not be valid. */
+int acrmi_mesh_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                       const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev, const int32_t* sign_dev,
+                       const int32_t* pairs_dev, int n_pairs, float contact_dist, float max_depth, int32_t* nn_dev, float* d2_dev,
+                       float* s_dev, float* sum_f_dev, int32_t* sum_i_dev, void* ws_dev, void* stream);
+/* The outputs of the forward calls in: verts_dev [B,K,2,778,3], cam_trans_dev [B,K,2,3], slots_dev [B,K,2,ACRMI_SLOT] (the row
+ * layout of acrmi_forward_multi; K = 1: what acrmi_forward writes), K = 1..ACRMI_MAX_HAND.  The pairs of row b are (left rank
+ * i, right rank j) with pair index (b*K + i)*K + j, direction 0 = the left hand's vertices; a pair with either ACRMI_SLOT_FLAG
+ * not > 0.5 is skipped - the flags are read on the device, there is no host visit.  Pairs are formed inside a row only.
+ * sign_host [2] (left, right) or NULL = the signs the context derived when the faces were loaded: the orientation of the
+ * side's faces on its template vertices (sign of sum v0 . (v1 x v2) in double, +1 when 0 or before acrmi_load_mano).
+ * Outputs as acrmi_mesh_contact with n_pairs = B*K*K, n_verts = 778.  The context's scratch is allocated at the first call
+ * (and when B*K grows); otherwise asynchronous on `stream`.  ACRMI_ESTATE before both sides' faces are loaded. */
+int acrmi_contact(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int B, int K,
+                  const int32_t* sign_host, float contact_dist, float max_depth, int32_t* nn_dev, float* d2_dev, float* s_dev,
+                  float* sum_f_dev, int32_t* sum_i_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Key-point skeleton and centre heat-map views: acr/visualization.py:228-300 (Visualizer.visulize_result_live with
  * show_items 'pj2d' / 'centermap', vis_keypoints, make_heatmaps), drawn on the device.  Nothing of PIL or cv2 is used; the
  * rules are (DESIGN.md "Key-point and heat-map views"):

@@ -1,0 +1,146 @@
+"""Time of the contact / interpenetration measure between the hands of a row (Engine.contact) next to
+two comparisons, on one GPU, one JSON line.
+
+    python tools/contact_bench.py [--repeats 30] [--warmup 5] [--timeout 600] [--out FILE]
+
+The 64 bench frames (512 x 512) go through Engine.forward once per K = max_hand in (1, 2, 4); every slot is then flagged and
+the hands of a row are placed a few centimetres from each other 0.8 m in front of the camera, so that all K * K pairs of every
+row are computed: the most work there can be.  Timed in one process with HIP events around the calls on one stream - a
+warm-up, then the median over `repeats`:
+  contact   Engine.contact on those outputs (cam_trans handed in): prep + setup + pair + reduce kernels
+  torch     the same quantities written in torch ops on the same tensors: vertex normals by index_add over the faces, the
+            [pairs,778,778] squared distances, arg-min, side value, counts and maxima, both directions - what a caller would
+            write today, without the host visit it would end in
+  forward   Engine.forward(project=True[, max_hand=K]) of those frames: the step that feeds it.  This pull request does not
+            touch the forward path, so this is also the parent commit's forward, taken in the same process.
+The torch form is a yardstick for the cost, not for the bits: its summation order is torch's.  The run ends itself after
+`--timeout` seconds."""
+import argparse
+import importlib
+import json
+import os
+import signal
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = 'arbitrary-hands-3d-reconstruction_amd'
+
+
+def pkg(sub):
+    return importlib.import_module(PKG + '.' + sub)
+
+
+def timed(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {'median_ms': round(statistics.median(ms), 4), 'min_ms': round(min(ms), 4), 'max_ms': round(max(ms), 4)}
+
+
+def torch_normals(v, faces, sign):
+    """v [n,778,3], faces [F,3] long on the device -> the signed un-normalised vertex normals [n,778,3]."""
+    p0, p1, p2 = (v[:, faces[:, k]] for k in range(3))
+    fn = torch.cross(p1 - p0, p2 - p0, dim=-1)
+    n = torch.zeros_like(v)
+    for k in range(3):
+        n.index_add_(1, faces[:, k], fn)
+    return n * sign
+
+
+def torch_direction(Pa, Pb, Nb):
+    d = [Pa[:, :, None, c] - Pb[:, None, :, c] for c in range(3)]
+    d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+    best, nn = d2.min(2)
+    q = torch.gather(Pb, 1, nn[..., None].expand(-1, -1, 3))
+    nb = torch.gather(Nb, 1, nn[..., None].expand(-1, -1, 3))
+    e = Pa - q
+    return nn, best, (e * nb).sum(-1)
+
+
+def torch_contact(verts, trans, faces, signs, K, r, m):
+    """verts [B,K,2,778,3], trans [B,K,2,3] -> the quantities of Engine.contact for the B*K*K pairs, every pair computed."""
+    B = verts.shape[0]
+    P = verts + trans[..., None, :]
+    N = [torch_normals(verts[:, :, h].reshape(B * K, 778, 3), faces[h], signs[h]).view(B, K, 778, 3) for h in (0, 1)]
+    i = torch.arange(K, device=verts.device).repeat_interleave(K)
+    j = torch.arange(K, device=verts.device).repeat(K)
+    Pl, Pr = P[:, i, 0].reshape(-1, 778, 3), P[:, j, 1].reshape(-1, 778, 3)
+    Nl, Nr = N[0][:, i].reshape(-1, 778, 3), N[1][:, j].reshape(-1, 778, 3)
+    out = []
+    for Pa, Pb, Nb in ((Pl, Pr, Nr), (Pr, Pl, Nl)):
+        nn, d2, s = torch_direction(Pa, Pb, Nb)
+        inside = (s < 0) & (d2 <= m * m)
+        out.append((nn, d2, s, (d2 <= r * r).sum(1), inside.sum(1), torch.where(inside, d2, torch.zeros_like(d2)).amax(1)))
+    best, bi = out[0][1].min(1)
+    return out, best, bi, torch.gather(out[0][0], 1, bi[:, None])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--repeats', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--timeout', type=int, default=600, help='seconds after which the run ends itself')
+    ap.add_argument('--out', default=None, help='also write the JSON line to this file')
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('contact_bench needs a GPU: there is no CPU path to time')
+    signal.alarm(a.timeout)
+    synth, L, ops = pkg('synth'), pkg('_lib'), pkg('ops')
+    eng = pkg('engine').Engine(0)
+    eng.load_state_dict(synth.make_state_dict(seed=0), max_batch=64)
+    tables = synth.make_mano_tables(seed=1)
+    tables['left']['shapedirs'] = tables['left']['shapedirs'].copy()
+    tables['left']['shapedirs'][:, 0, :] *= -1
+    eng.load_mano(tables)
+    B = 64
+    frames = torch.from_numpy(synth.make_frames(B, seed=0, structured=False)).cuda()
+    faces = [torch.from_numpy(np.asarray(tables[s]['faces'], np.int64)).cuda() for s in ('left', 'right')]
+    r, m = ops.CONTACT_DIST, ops.CONTACT_MAX_DEPTH
+    line = {'tool': 'contact_bench', 'device': torch.cuda.get_device_name(0), 'repeats': a.repeats, 'warmup': a.warmup,
+            'timing': 'HIP events, median', 'frames': B, 'contact_dist': r, 'max_depth': m}
+    rng = np.random.default_rng(0)
+    for K in (1, 2, 4):
+        kw = dict(project=True) if K == 1 else dict(project=True, max_hand=K)
+        fwd = timed(lambda: eng.forward(frames, **kw), a.warmup, a.repeats)
+        out = eng.forward(frames, **kw)
+        lead = (B, K, 2)
+        out = {k: v.view(lead + tuple(v.shape[len(v.shape) - (1 if k == 'slots' else 2):])) for k, v in out.items()}
+        out['slots'][..., L.SLOT_FLAG] = 1.0
+        ct = torch.from_numpy((np.array((0, 0, 0.8)) + rng.uniform(-0.03, 0.03, lead + (3,))).astype(np.float32)).cuda()
+        con = timed(lambda: eng.contact(out, max_hand=K, cam_trans=ct), a.warmup, a.repeats)
+        res = eng.contact(out, max_hand=K, cam_trans=ct)
+        signs = eng.contact_sign
+        tor = timed(lambda: torch_contact(out['verts'], ct, faces, signs, K, r, m), a.warmup, a.repeats)
+        ref, best, bi, bj = torch_contact(out['verts'], ct, faces, signs, K, r, m)
+        # the two forms describe the same thing (the torch one rounds in its own order: nn may differ on near ties)
+        agree = float((ref[0][0] == res['nn'][:, 0]).float().mean())
+        line['max_hand_%d' % K] = {
+            'pairs': B * K * K, 'contact': con, 'torch': tor, 'forward': fwd,
+            'torch_over_contact': round(tor['median_ms'] / con['median_ms'], 2),
+            'share_of_forward': round(con['median_ms'] / fwd['median_ms'], 4),
+            'nn_agreement_with_torch': round(agree, 6),
+            'contact_verts_per_pair': round(float(res['n_contact'].float().sum(1).mean()), 1),
+            'inside_verts_per_pair': round(float(res['n_inside'].float().sum(1).mean()), 1)}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+    eng.close()
+
+
+if __name__ == '__main__':
+    main()
