@@ -307,152 +307,161 @@ class ACR(object):
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
         K = int(self.hands_per_side if max_hand is None else max_hand)
-        if K != 1 or tracks is not None:
-            return self._forward_batch_multi(rgb_u8_frames, paths, offsets, batch_semantics, render, render_bgr, show_items,
-                                             streams, K, tracks, max_streams, track_gate, track_max_miss, multi_point_heads,
-                                             contact)
-        results, eng, out = self._forward_batch_results(rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams,
-                                                        max_streams, multi_point_heads, contact)
-        render_offsets = offsets
+        results, eng, out = self._fused_call(rgb_u8_frames, paths, offsets=offsets, point_heads=point_heads,
+                                             batch_semantics=batch_semantics, streams=streams, max_streams=max_streams, K=K,
+                                             tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
+                                             multi_point_heads=multi_point_heads, contact=contact)
         if render is None:
             return results
-        if show_items is None:
-            return results, self._render_batch(eng, out, render, render_offsets, render_bgr)
-        views = {}
-        for name in show_items:
+        if K != 1 or tracks is not None:      # the [B,K,...] shapes: K pairs per frame
+            return results, _multi_views(self, eng, out, render, offsets, render_bgr, show_items)
+
+        def draw(name):
             if name == 'mesh':
-                views[name] = self._render_batch(eng, out, render, render_offsets, render_bgr)
-            elif name == 'org_img':
-                views[name] = render
-            else:
-                views[name] = self._overlay_batch(eng, out, render, name, render_offsets, render_bgr)
-        return results, views
+                return self._render_batch(eng, out, render, offsets, render_bgr)
+            return self._overlay_batch(eng, out, render, name, offsets, render_bgr)
 
-    def _forward_batch_results(self, rgb_u8_frames, paths, offsets, point_heads, batch_semantics, streams, max_streams,
-                               multi_point_heads=False, contact=False):
-        """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).
-        multi_point_heads: checked, and without effect on one hand of each side (point_heads is the switch here)."""
-        _check_multi_point_heads(multi_point_heads)
-        B = rgb_u8_frames.shape[0]
-        ids, table = (None, None) if streams is None else self._streams_for(streams, max_streams, B)
-        eng = self.model.engine(B)
-        semantics = batch_semantics or self.model._result_parser.batch_semantics
-        if offsets is None:
-            offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
-        eng.set_point_heads(point_heads)
-        # frames of the batch = one video stream, in order (smooth_coeff travels with the call: a reloaded checkpoint
-        # builds a new context); with `streams` the table holds the state and the frames are not one stream
-        eng.set_temporal(bool(self.temporal_optimization) and ids is None, smooth_coeff=self._args.smooth_coeff)
-        eng.set_batch_semantics(semantics)
-        try:
-            out = eng.forward(rgb_u8_frames, offsets=offsets, project=True, streams=ids, table=table)
-        finally:
-            eng.set_point_heads(False)
-            eng.set_temporal(False)
-            eng.set_batch_semantics('frame')
-        eng.check_range()      # 'fp16x3' only: an activation outside the f16 range is an error, not an empty result
-        # cam_trans for every slot (acr/utils.py:399-412): the device least-squares kernel on [B*2] hands
-        from .. import ops
-        out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
-                                         focal_length=self.focal_length).view(B, 2, 3)
-        if contact:
-            _add_contact(eng, out, 1)
-        return results_from_out(out, paths), eng, out
+        return results, _views(show_items, render, draw)
 
-    def _forward_batch_multi(self, frames, paths, offsets, batch_semantics, render, render_bgr, items, streams, K, tracks=None,
-                             max_streams=None, gate=None, max_miss=None, multi_point_heads=False, contact=False):
-        """forward_batch with max_hand = K > 1 or with tracks=: Engine.forward(max_hand=K), the packaging, and the views of K
-        regions per frame."""
+    def _fused_call(self, frames, paths, *, offsets=None, point_heads=True, batch_semantics=None, streams=None, max_streams=None,
+                    K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
+        """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).  K = 1 without
+        tracks: one hand of each side, `point_heads` is the switch and multi_point_heads is checked and without effect.
+        K > 1 or tracks=: Engine.forward(max_hand=K) on the dense heads, or with multi_point_heads (K > 1) at the K best centres.
+        Everything that can be refused is refused before anything runs; the engine's options are back at their defaults
+        afterwards, also after an exception."""
         from .. import ops
         from ..engine import check_max_hand
         K = check_max_hand(K)
         _check_multi_point_heads(multi_point_heads)
-        if tracks is not None and streams is not None:
-            raise ValueError('tracks= smooths every track with its own filter: not together with streams=')
-        if streams is not None:
-            raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
-        if self.temporal_optimization and tracks is None:
-            raise ValueError('temporal optimisation follows one hand of each side: not with max_hand=%d' % K)
-        if (batch_semantics or self.model._result_parser.batch_semantics) != 'frame':
-            raise ValueError("batch_semantics='reference' is the reference's rule for one hand of each side (it cannot run "
-                             'more: acr/result_parser.py:134): not with max_hand=%d' % K)
+        multi = K != 1 or tracks is not None
+        if multi:
+            if tracks is not None and streams is not None:
+                raise ValueError('tracks= smooths every track with its own filter: not together with streams=')
+            if streams is not None:
+                raise ValueError('streams= follows one hand of each side through a video: not with max_hand=%d' % K)
+            if self.temporal_optimization and tracks is None:
+                raise ValueError('temporal optimisation follows one hand of each side: not with max_hand=%d' % K)
+            if (batch_semantics or self.model._result_parser.batch_semantics) != 'frame':
+                raise ValueError("batch_semantics='reference' is the reference's rule for one hand of each side (it cannot run "
+                                 'more: acr/result_parser.py:134): not with max_hand=%d' % K)
         B = frames.shape[0]
+        ids, table = (None, None) if streams is None else self._streams_for(streams, max_streams, B)
         eng = self.model.engine(B)
-        render_offsets = offsets
         if offsets is None:
-            offsets = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
-        eng.set_point_heads(False)
-        eng.set_temporal(False)
-        eng.set_batch_semantics('frame')
-        eng.set_point_heads_multi(multi_point_heads and K > 1)
+            offsets = _whole_frame_offsets(B)
+        # coeff: smooth_coeff travels with a call that may smooth (a reloaded checkpoint builds a new context)
+        if not multi:
+            # frames of the batch = one video stream, in order; with `streams` the table holds the state and the frames are
+            # not one stream
+            heads, temporal, coeff = point_heads, bool(self.temporal_optimization) and ids is None, self._args.smooth_coeff
+            semantics, heads_multi = batch_semantics or self.model._result_parser.batch_semantics, False
+            kw = dict(streams=ids, table=table)
+        else:
+            heads, temporal, coeff, semantics, heads_multi = False, False, None, 'frame', multi_point_heads and K > 1
+            kw = dict(max_hand=K)
+            if tracks is not None:      # every track is smoothed by its own filter: ACRMI_OPT_TEMPORAL itself stays off
+                coeff = self._args.smooth_coeff
+                kw.update(tracks=tracks, track_table=self._tracks_for(K, max_streams, track_gate, track_max_miss),
+                          smooth=bool(self.temporal_optimization))
         try:
-            if tracks is None:
-                out = eng.forward(frames, offsets=offsets, project=True, max_hand=K)
-            else:
-                # (smooth_coeff travels with the call, as in _forward_batch_results; ACRMI_OPT_TEMPORAL itself stays off)
-                eng.set_temporal(False, smooth_coeff=self._args.smooth_coeff)
-                out = eng.forward(frames, offsets=offsets, project=True, max_hand=K, tracks=tracks,
-                                  track_table=self._tracks_for(K, max_streams, gate, max_miss),
-                                  smooth=bool(self.temporal_optimization))
+            eng.set_point_heads(heads)
+            eng.set_temporal(temporal, smooth_coeff=coeff)
+            eng.set_batch_semantics(semantics)
+            eng.set_point_heads_multi(heads_multi)
+            out = eng.forward(frames, offsets=offsets, project=True, **kw)
         finally:
+            eng.set_point_heads(False)
+            eng.set_temporal(False)
+            eng.set_batch_semantics('frame')
             eng.set_point_heads_multi(False)
-        eng.check_range()
+        eng.check_range()      # 'fp16x3' only: an activation outside the f16 range is an error, not an empty result
+        # cam_trans for every slot (acr/utils.py:399-412): the device least-squares kernel on all hands
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
-                                         focal_length=self.focal_length).view(B, K, 2, 3)
+                                         focal_length=self.focal_length).view(*out['slots'].shape[:-1], 3)
         if contact:
             _add_contact(eng, out, K)
-        results = results_from_out(out, paths)
-        if render is None:
-            return results
-        views = _multi_views(self, eng, out, render, offsets if render_offsets is not None else None, render_bgr, items)
-        return results, views
+        return results_from_out(out, paths), eng, out
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
-        kw = dict(focal_length=float(self.focal_length), bgr=bgr)
-        if not isinstance(frames, (list, tuple)):
-            return eng.render(out, frames, offsets=offsets, **kw)
-        if len(frames) != out['slots'].shape[0]:
-            raise ValueError('one frame to draw into per input frame')
-        groups = {}
-        for i, f in enumerate(frames):
-            groups.setdefault(tuple(f.shape), []).append(i)
-        rendered = [None] * len(frames)
-        for idx in groups.values():
-            sel = torch.tensor(idx, device=out['slots'].device)
-            sub = {k: out[k].index_select(0, sel) for k in ('slots', 'verts', 'cam_trans')}
-            got = eng.render(sub, torch.stack([frames[i] for i in idx]),
-                             offsets=None if offsets is None else torch.as_tensor(offsets)[idx], **kw)
-            for j, i in enumerate(idx):
-                rendered[i] = got[j]
-        return rendered
+        """The meshes over a tensor of frames (Engine.render) or a list of frames of different sizes."""
+        def draw(imgs, idx, place):
+            sub, off = _frames_of(out, offsets, idx, ('slots', 'verts', 'cam_trans'))
+            return eng.render(sub, imgs, offsets=off, focal_length=float(self.focal_length), bgr=bgr)
+
+        return _per_size(frames, draw, count=out['slots'].shape[0])
 
     def _overlay_batch(self, eng, out, frames, what, offsets, bgr):
-        """'pj2d' / 'centermap' over a tensor of frames (Engine.overlay) or a list of frames of different sizes (one call
-        per size, output order = input order)."""
+        """'pj2d' / 'centermap' over a tensor of frames (Engine.overlay) or a list of frames of different sizes."""
         from .. import ops
-        if not isinstance(frames, (list, tuple)):
-            return eng.overlay(out, frames, what, offsets=offsets, bgr=bgr)
         B = out['slots'].shape[0]
-        if len(frames) != B:
-            raise ValueError('one frame to draw into per input frame')
-        groups = {}
-        for i, f in enumerate(frames):
-            groups.setdefault(tuple(f.shape), []).append(i)
-        drawn = [None] * len(frames)
-        maps = eng.center_maps(B) if what == 'centermap' else None
-        for idx in groups.values():
-            sel = torch.tensor(idx, device=out['slots'].device)
-            imgs = torch.stack([frames[i] for i in idx])
-            off = None if offsets is None else torch.as_tensor(offsets)[idx]
-            if what == 'pj2d':
-                sub = {k: out[k].index_select(0, sel) for k in ('slots', 'pj2d', 'pj2d_org') if out.get(k) is not None}
-                got = eng.overlay(sub, imgs, what, offsets=off, bgr=bgr)
-            else:      # the context's maps are those of the whole batch: a subset goes through the stand-alone operator
-                got = ops.draw_heatmaps(maps.index_select(0, sel), imgs, view=None if off is None else ops.view_from_offsets(off),
-                                        bgr=bgr).transpose(0, 1)
-            for j, i in enumerate(idx):
-                drawn[i] = got[j]
-        return drawn
+        whole = {}      # 'maps': the centre maps of the whole batch, fetched by the first group that needs them
+
+        def draw(imgs, idx, place):
+            if idx is None or what == 'pj2d':
+                sub, off = _frames_of(out, offsets, idx, ('slots', 'pj2d', 'pj2d_org'))
+                return eng.overlay(sub, imgs, what, offsets=off, bgr=bgr)
+            # the context's maps are those of the whole batch: a subset goes through the stand-alone operator
+            if not whole:
+                whole['maps'] = eng.center_maps(B)
+            sub, off = _frames_of(whole, offsets, idx, ('maps',))
+            return ops.draw_heatmaps(sub['maps'], imgs, view=None if off is None else ops.view_from_offsets(off), bgr=bgr)
+
+        return _per_size(frames, draw, count=B, pair=what == 'centermap')
+
+
+def _whole_frame_offsets(B):
+    """The offsets rows of B frames that are the 512 x 512 network input itself."""
+    return torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
+
+
+def _per_size(frames, draw, count=None, pair=False):
+    """draw(imgs [n,H,W,3], idx, place) over `frames`.  A tensor [N,H,W,3]: one call with idx = place = None, its result as it
+    is.  A list of frames [H_i,W_i,3] of different sizes (`count` of them, where the caller expects a number): one call per
+    size in the order the sizes appear, with idx = the positions in `frames` of the stacked imgs and place [len(frames)] =
+    frame of the list -> frame of imgs, -1 = another group's; -> a list in input order.  pair: draw returns [2,n,H,W,3] (left,
+    right - 'centermap') instead of [n,H,W,3], and the list holds [2,H_i,W_i,3]."""
+    if not isinstance(frames, (list, tuple)):
+        return draw(frames, None, None)
+    if count is not None and len(frames) != count:
+        raise ValueError('one frame to draw into per input frame')
+    groups = {}
+    for i, f in enumerate(frames):
+        groups.setdefault(tuple(f.shape), []).append(i)
+    drawn = [None] * len(frames)
+    for idx in groups.values():
+        place = torch.full((len(frames),), -1, dtype=torch.long)
+        place[idx] = torch.arange(len(idx))
+        got = draw(torch.stack([frames[i] for i in idx]), idx, place)
+        for j, i in enumerate(idx):
+            drawn[i] = got[:, j] if pair else got[j]
+    return drawn
+
+
+def _frames_of(out, offsets, idx, keys):
+    """(the tensors `keys` of `out`, offsets) of the frames idx of a _per_size group (None: `out` and offsets as they are)."""
+    if idx is None:
+        return out, offsets
+    sel = torch.tensor(idx, device=out[keys[0]].device)
+    return ({k: out[k].index_select(0, sel) for k in keys if out.get(k) is not None},
+            None if offsets is None else torch.as_tensor(offsets)[idx])
+
+
+def _local_frames(frame_of, place):
+    """frame_of [M] (the frame of each hand or region, -1 = none) in the frames of a _per_size group -> int32; -1 stays -1 and
+    the frames of other groups become -1."""
+    if place is not None:
+        frame_of = torch.where(frame_of >= 0, place[frame_of.clamp(min=0)], torch.full_like(frame_of, -1))
+    return frame_of.to(torch.int32)
+
+
+def _views(items, frames, draw):
+    """The views `items` over `frames`: None -> draw('mesh') alone, not in a dict; else {name: draw(name)}, with 'org_img' the
+    frames as given."""
+    def one(name):
+        return frames if name == 'org_img' else draw(name)
+
+    return one('mesh') if items is None else {name: one(name) for name in items}
 
 
 def _check_multi_point_heads(value):
@@ -541,40 +550,11 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
     B, K = out['slots'].shape[:2]
     if len(frames) != B:
         raise ValueError('one frame to draw into per input frame')
-    whole = torch.tensor([[512., 512, 0, 0, 0, 0, 0, 0, 0, 0]]).repeat(B, 1)
-    rows = (whole if offsets is None else torch.as_tensor(offsets).to(torch.float32)).repeat_interleave(K, 0)
+    rows = (_whole_frame_offsets(B) if offsets is None else torch.as_tensor(offsets).to(torch.float32)).repeat_interleave(K, 0)
     flat = {k: out[k].flatten(0, 1) for k in ('slots', 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans') if out.get(k) is not None}
-    frame_of = torch.arange(B).repeat_interleave(K)
-
-    def draw(name, imgs, region_frame):
-        if name == 'mesh':
-            return eng.render_regions(flat, imgs, rows, region_frame, focal_length=float(self.focal_length), bgr=bgr)
-        if name == 'pj2d':
-            return eng.overlay_regions(flat, imgs, name, rows, region_frame, bgr=bgr)
-        raise AssertionError(name)
-
-    def one(name):
-        if name == 'org_img':
-            return frames
-        if name == 'centermap':
-            return self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, name, offsets, bgr)
-        if not isinstance(frames, (list, tuple)):
-            return draw(name, frames, frame_of.to(torch.int32))
-        groups = {}
-        for i, f in enumerate(frames):
-            groups.setdefault(tuple(f.shape), []).append(i)
-        drawn = [None] * len(frames)
-        for idx in groups.values():
-            place = torch.full((len(frames),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
-            place[idx] = torch.arange(len(idx))
-            got = draw(name, torch.stack([frames[i] for i in idx]), place[frame_of].to(torch.int32))
-            for j, i in enumerate(idx):
-                drawn[i] = got[j]
-        return drawn
-
-    if items is None:
-        return one('mesh')
-    return {name: one(name) for name in items}
+    # the centre maps are the frame's, not a pair's: drawn per frame, with pair 0's slots standing for the frame
+    return _region_views(self, eng, flat, frames, rows, torch.arange(B).repeat_interleave(K), items, bgr=bgr,
+                         centermap=lambda: self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, 'centermap', offsets, bgr))
 
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
@@ -617,15 +597,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
         raise ValueError('boxes= with max_hand > 1 is not implemented: a region is one person (DESIGN.md section 17)')
-    if show_items is not None and not render:
-        raise ValueError('show_items needs render=True')
-    if render_format not in ('bgr', 'nv12'):
-        raise ValueError("render_format: %r is not 'bgr' or 'nv12'" % (render_format,))
-    to_nv12 = None
-    if render_format == 'nv12':
-        if not render:
-            raise ValueError("render_format='nv12' needs render=True")
-        to_nv12, matrix = _nv12_views(bgr_frames_dev, pixel_format, matrix)
+    to_nv12, matrix = _check_render_args(bgr_frames_dev, show_items, render, render_format, pixel_format, matrix)
     if region_views and boxes is None:
         raise ValueError('region_views=True draws the views of regions: it needs boxes=')
     if boxes is not None:
@@ -645,10 +617,28 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
                                  multi_point_heads=multi_point_heads, contact=contact)
     if to_nv12 is None:
         return got
-    results, views = got
+    return got[0], _views_to_nv12(to_nv12, got[1])
+
+
+def _check_render_args(frames, items, render, render_format, pixel_format, matrix):
+    """The render arguments of forward_raw_batch / track_raw_batch, refused before anything runs -> (None, matrix), or with
+    render_format='nv12' what _nv12_views returns."""
+    if items is not None and not render:
+        raise ValueError('show_items needs render=True')
+    if render_format not in ('bgr', 'nv12'):
+        raise ValueError("render_format: %r is not 'bgr' or 'nv12'" % (render_format,))
+    if render_format != 'nv12':
+        return None, matrix
+    if not render:
+        raise ValueError("render_format='nv12' needs render=True")
+    return _nv12_views(frames, pixel_format, matrix)
+
+
+def _views_to_nv12(to_nv12, views):
+    """`to_nv12` of _nv12_views over a view of the meshes alone or over a dict of views."""
     if not isinstance(views, dict):
-        return results, to_nv12('mesh', views)
-    return results, {name: to_nv12(name, view) for name, view in views.items()}
+        return to_nv12('mesh', views)
+    return {name: to_nv12(name, view) for name, view in views.items()}
 
 
 def _nv12_views(frames, pixel_format, matrix):
@@ -687,39 +677,27 @@ def _nv12_views(frames, pixel_format, matrix):
     return view, row6
 
 
-def _region_views(self, eng, out, canvas, offsets, box_frame, items):
-    """The views `items` (None: the meshes alone, not in a dict) of the n regions of `out` over their BGR frames `canvas` - a
+def _region_views(self, eng, out, canvas, offsets, box_frame, items, bgr=True, centermap=None):
+    """The views `items` (None: the meshes alone, not in a dict) of the n regions of `out` over their frames `canvas` - a
     tensor [N,H,W,3], or a list of frames of different sizes, drawn per size and returned in input order; 'centermap' is
-    [2,N,H,W,3], respectively a list of [2,H_i,W_i,3].  offsets: the regions' rows, on the host or on the device."""
+    [2,N,H,W,3], respectively a list of [2,H_i,W_i,3].  offsets: the regions' rows, on the host or on the device.  bgr: the
+    frames' channel order.  centermap: a function that draws that view instead of Engine.overlay_regions."""
     n = out['slots'].shape[0]
     frame_of = torch.arange(n) if box_frame is None else torch.as_tensor(np.asarray(box_frame)).long()
-    kw = dict(bgr=True)
-
-    def draw(name, imgs, region_frame):
-        if name == 'mesh':
-            return eng.render_regions(out, imgs, offsets, region_frame, focal_length=float(self.focal_length), **kw)
-        return eng.overlay_regions(out, imgs, name, offsets, region_frame, **kw)
 
     def one(name):
-        if name == 'org_img':
-            return canvas
-        if not isinstance(canvas, (list, tuple)):
-            return draw(name, canvas, frame_of.to(torch.int32))
-        groups = {}
-        for i, f in enumerate(canvas):
-            groups.setdefault(tuple(f.shape), []).append(i)
-        drawn = [None] * len(canvas)
-        for idx in groups.values():
-            place = torch.full((len(canvas),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
-            place[idx] = torch.arange(len(idx))
-            got = draw(name, torch.stack([canvas[i] for i in idx]), place[frame_of].to(torch.int32))
-            for j, i in enumerate(idx):
-                drawn[i] = got[:, j] if name == 'centermap' else got[j]
-        return drawn
+        if name == 'centermap' and centermap is not None:
+            return centermap()
 
-    if items is None:
-        return one('mesh')
-    return {name: one(name) for name in items}
+        def draw(imgs, idx, place):
+            region_frame = _local_frames(frame_of, place)
+            if name == 'mesh':
+                return eng.render_regions(out, imgs, offsets, region_frame, focal_length=float(self.focal_length), bgr=bgr)
+            return eng.overlay_regions(out, imgs, name, offsets, region_frame, bgr=bgr)
+
+        return _per_size(canvas, draw, pair=name == 'centermap')
+
+    return _views(items, canvas, one)
 
 
 def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix,
@@ -738,8 +716,8 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     n = meta['image'].shape[0]
     if len(paths) != n:
         raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
-    results, eng, out = self._forward_batch_results(meta['image'], paths, meta['offsets'], True, None, streams, max_streams,
-                                                    contact=contact)
+    results, eng, out = self._fused_call(meta['image'], paths, offsets=meta['offsets'], point_heads=True, streams=streams,
+                                         max_streams=max_streams, contact=contact)
     if not render:
         return results
     canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames
@@ -750,30 +728,15 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     flagged = (out['slots'][:, :, S.SLOT_FLAG] > 0.5).cpu()
     hand_frame = torch.where(flagged, frame_of[:, None].expand(n, 2), torch.full((n, 2), -1)).reshape(-1)
     kps = out['pj2d_org'].reshape(-1, 21, 2).float().contiguous()
-    views = {}
-    for name in items:
-        views[name] = canvas if name == 'org_img' else _draw_over_frames(kps, canvas, hand_frame)
-    return results, views
+    return results, _views(items, canvas, lambda name: _draw_over_frames(kps, canvas, hand_frame))
 
 
 def _draw_over_frames(kps, canvas, hand_frame):
     """ops.draw_skeletons of hands [M,21,2] over a tensor of frames, or over a list of frames of different sizes (one call per
     size, output order = input order); hand_frame [M] = the frame of each hand, -1 = not drawn."""
     from .. import ops
-    if not isinstance(canvas, (list, tuple)):
-        return ops.draw_skeletons(kps, canvas, hand_frame=hand_frame.to(torch.int32), bgr=True)
-    groups = {}
-    for i, f in enumerate(canvas):
-        groups.setdefault(tuple(f.shape), []).append(i)
-    drawn = [None] * len(canvas)
-    for idx in groups.values():
-        place = torch.full((len(canvas),), -1, dtype=torch.long)      # frame of the call -> frame of this group, -1 = another group's
-        place[idx] = torch.arange(len(idx))
-        local = torch.where(hand_frame >= 0, place[hand_frame.clamp(min=0)], torch.full_like(hand_frame, -1))
-        got = ops.draw_skeletons(kps, torch.stack([canvas[i] for i in idx]), hand_frame=local.to(torch.int32), bgr=True)
-        for j, i in enumerate(idx):
-            drawn[i] = got[j]
-    return drawn
+    return _per_size(canvas, lambda imgs, idx, place: ops.draw_skeletons(kps, imgs, hand_frame=_local_frames(hand_frame, place),
+                                                                          bgr=True))
 
 
 def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=None, max_streams=None, pixel_format='bgr',
@@ -790,15 +753,7 @@ def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=No
     and returned in input order.  render_format='nv12': as forward_raw_batch."""
     from .. import ops
     items = check_show_items(show_items)
-    if items is not None and not render:
-        raise ValueError('show_items needs render=True')
-    if render_format not in ('bgr', 'nv12'):
-        raise ValueError("render_format: %r is not 'bgr' or 'nv12'" % (render_format,))
-    to_nv12 = None
-    if render_format == 'nv12':
-        if not render:
-            raise ValueError("render_format='nv12' needs render=True")
-        to_nv12, matrix = _nv12_views(frames, pixel_format, matrix)
+    to_nv12, matrix = _check_render_args(frames, items, render, render_format, pixel_format, matrix)
     scale, min_size = ops.check_track_args(scale, min_size)
     frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)
     if boxes is None:
@@ -809,15 +764,13 @@ def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=No
     n = rgb.shape[0]
     if len(paths) != n:
         raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
-    results, eng, out = self._forward_batch_results(rgb, paths, offsets, True, None, streams, max_streams)
+    results, eng, out = self._fused_call(rgb, paths, offsets=offsets, point_heads=True, streams=streams, max_streams=max_streams)
     next_boxes = ops.track_boxes(out['pj2d_org'], out['slots'], frame_hw, scale=scale, min_size=min_size)
     if not render:
         return results, next_boxes
     canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames
     views = _region_views(self, eng, out, canvas, offsets, box_frame, items)
-    if to_nv12 is not None:
-        views = to_nv12('mesh', views) if items is None else {name: to_nv12(name, view) for name, view in views.items()}
-    return results, next_boxes, views
+    return results, next_boxes, views if to_nv12 is None else _views_to_nv12(to_nv12, views)
 
 
 ACR.forward_raw_batch = _forward_raw_batch

@@ -376,3 +376,29 @@ def test_acr_forward_reads_hands_per_side_from_the_config(mano_tables):
     assert not np.array_equal(r['mesh_rendering_orgimgs'][0], frame) and r['mesh_rendering_orgimgs'][0].shape == frame.shape
     one = acr.forward_raw_batch(dev, ['p'], max_hand=1)
     assert len(one['p']) <= 2
+
+
+def test_views_over_a_list_of_frames_with_two_hands_per_side_are_those_of_each_frame_alone(mano_tables):
+    """forward_raw_batch(max_hand=2, render=True, show_items=...) on a LIST of frames of two sizes (A, B, A: one draw call per
+    size, the regions of the other size's frames switched off): every view of frame i equals, byte for byte, the view the same
+    call gives for frame i alone as a one-frame tensor - a frame's results do not depend on the batch it is in."""
+    cfg = pkg('config')
+    acr = pkg('acr.main').ACR(args_set=cfg.parse_args(['--configs_yml', '/nonexistent.yml', '--renderer', 'hip']),
+                              state_dict=pkg('synth').make_state_dict(seed=10), mano_tables=mano_tables, max_batch=3)
+    g = np.random.default_rng(5)
+    sizes = [(96, 128), (64, 112), (96, 128)]
+    frames = [torch.from_numpy(g.integers(0, 256, (h, w, 3)).astype(np.uint8)).cuda() for h, w in sizes]
+    paths, items = ['a', 'b', 'c'], ('mesh', 'pj2d', 'centermap', 'org_img')
+    res, views = acr.forward_raw_batch(frames, paths, max_hand=2, render=True, show_items=items)
+    assert sorted(views) == sorted(items) and all(isinstance(views[name], list) and len(views[name]) == 3 for name in items)
+    for i, (frame, path) in enumerate(zip(frames, paths)):
+        alone_res, alone = acr.forward_raw_batch(frame[None], [path], max_hand=2, render=True, show_items=items)
+        torch.cuda.synchronize()
+        assert len(res[path]) > 2 and len(alone_res[path]) == len(res[path]), 'the synthetic checkpoint flags every rank'
+        for name in items:
+            got, want = views[name][i], alone[name][:, 0] if name == 'centermap' else alone[name][0]
+            assert tuple(got.shape) == ((2,) if name == 'centermap' else ()) + tuple(frame.shape), (name, i)
+            assert torch.equal(got, want), (name, i)
+        assert torch.equal(views['org_img'][i], frame)
+        for name, view in (('mesh', views['mesh'][i]), ('pj2d', views['pj2d'][i]), ('centermap', views['centermap'][i][0])):
+            assert not torch.equal(view, frame), (name, i)      # something was drawn

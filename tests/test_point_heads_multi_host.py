@@ -212,15 +212,15 @@ def test_python_layer_has_the_option_and_refuses_a_non_bool():
     E, main = pkg('engine'), pkg('acr.main')
     assert hasattr(E.Engine, 'set_point_heads_multi')
     assert inspect.signature(E.Engine.run_point_heads).parameters['max_hand'].default == 1
-    for fn in (main.ACR.forward_batch, main.ACR.forward_raw_batch, main.ACR._forward_batch_results, main.ACR._forward_batch_multi):
+    for fn in (main.ACR.forward_batch, main.ACR.forward_raw_batch, main.ACR._fused_call):
         assert inspect.signature(fn).parameters['multi_point_heads'].default is False, fn
     frames = np.zeros((1, 512, 512, 3), np.uint8)
     for bad in (1, 0, None, 'yes', np.bool_(True)):
         # refused before the frames, the model or the engine are looked at
         with pytest.raises(ValueError, match='multi_point_heads must be True or False'):
-            main.ACR._forward_batch_results(None, frames, ['a'], None, True, None, None, None, multi_point_heads=bad)
+            main.ACR._fused_call(None, frames, ['a'], point_heads=True, K=1, multi_point_heads=bad)
         with pytest.raises(ValueError, match='multi_point_heads must be True or False'):
-            main.ACR._forward_batch_multi(None, frames, ['a'], None, None, None, False, None, None, 2, multi_point_heads=bad)
+            main.ACR._fused_call(None, frames, ['a'], K=2, multi_point_heads=bad)
         with pytest.raises(ValueError, match='multi_point_heads must be True or False'):
             main._forward_raw_batch(None, None, ['a'], multi_point_heads=bad)
     assert 'hands_per_side' in pkg('config').DEFAULTS and not any('point' in k for k in pkg('config').DEFAULTS)      # no new config key
