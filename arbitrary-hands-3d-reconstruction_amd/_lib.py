@@ -69,6 +69,12 @@ class HeadLayout(C.Structure):
                 ('segm_buf', C.c_int32), ('backbone_buf', C.c_int32)]
 
 
+class ConvProblem(C.Structure):      # acrmi_conv_problem
+    _fields_ = [('in_', C.c_void_p), ('w_packed', C.c_void_p), ('bias', C.c_void_p), ('res', C.c_void_p), ('out', C.c_void_p)] + \
+               [(k, C.c_int32) for k in ('B', 'H', 'W', 'in_cs', 'in_coff', 'cin', 'bias_frame_stride', 'res_cs', 'res_coff', 'out_cs',
+                                         'out_coff', 'cout', 'ksize', 'stride', 'relu', 'groups', 'algo', 'reserved')]
+
+
 EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy', 'acrmi_load_weights',
            'acrmi_set_program', 'acrmi_load_mano', 'acrmi_backbone_heads', 'acrmi_buffer_ptr', 'acrmi_decode',
            'acrmi_decode_maps', 'acrmi_mano', 'acrmi_forward', 'acrmi_conv2d', 'acrmi_u8norm', 'acrmi_bilinear2x',
@@ -87,7 +93,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_nv12_compose', 'acrmi_rasterize_views', 'acrmi_draw_region_heatmaps', 'acrmi_render_regions',
            'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi',
            'acrmi_tracks_create', 'acrmi_tracks_destroy', 'acrmi_tracks_reset', 'acrmi_associate', 'acrmi_forward_tracks',
-           'acrmi_assoc_step', 'acrmi_point_heads_multi', 'acrmi_contact_workspace', 'acrmi_mesh_contact', 'acrmi_contact']
+           'acrmi_assoc_step', 'acrmi_point_heads_multi', 'acrmi_contact_workspace', 'acrmi_mesh_contact', 'acrmi_contact',
+           'acrmi_conv2d_group', 'acrmi_program_groups']
 
 _lib = None
 
@@ -176,6 +183,8 @@ def lib():
     L.acrmi_attpool_ws_floats.restype = C.c_size_t
     L.acrmi_profile_ops.argtypes = [vp, u8p, i32, vp, i32, vp]
     L.acrmi_tune.argtypes = [i32, i32]
+    L.acrmi_conv2d_group.argtypes = [C.POINTER(ConvProblem), i32, vp]
+    L.acrmi_program_groups.argtypes = [vp, i32]
     L.acrmi_preprocess.argtypes = [u8p, i32, i32, i32, u8p, vp, vp]
     L.acrmi_cam_trans.argtypes = [f32p, f32p, i32, C.c_float, C.c_float, f32p, vp]
     L.acrmi_set_option.argtypes = [vp, i32, i32]

@@ -544,6 +544,13 @@ int acrmi_associate(acrmi_ctx* c, acrmi_tracks* t, float* slots, int B, int max_
   return associate_on(c, t, slots, B, ids, smooth, track_ids, perm, (hipStream_t)stream);
 }
 
+int acrmi_program_groups(acrmi_ctx* c, int B) {
+  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_program_groups: bad arguments");
+  if (!c->have_program) return fail(c, ACRMI_ESTATE, "no program");
+  if (B <= 0 || B > c->max_batch) return fail(c, ACRMI_EINVAL, "batch %d outside 1..%d", B, c->max_batch);
+  return c->sched[c->point_heads ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0].n_groups;
+}
+
 int acrmi_profile_ops(acrmi_ctx* c, const uint8_t* img, int B, float* ms_out, int n_ms, void* stream) {
   if (!c || !img || !ms_out) return fail(c, ACRMI_EINVAL, "acrmi_profile_ops: bad arguments");
   if (!c->have_program) return fail(c, ACRMI_ESTATE, "no program");
@@ -1118,6 +1125,7 @@ int acrmi_tune(int key, int value) {
   if (key == 0) { conv_force_cfg(value); return ACRMI_OK; }
   if (key == 3) { conv_set_phase_delay(value); return ACRMI_OK; }
   if (key == 4) { conv_set_xcd_swizzle(value); return ACRMI_OK; }   // XCD-banded item order on/off (default on)
+  if (key == 5) { program_set_grouping(value != 0); return ACRMI_OK; }   // grouped launches in the programs set from now on
   static long long* dbg = nullptr;
   if (key == 1) {   // enable (value != 0) / disable the conv kernel's cycle stamps (workgroup 0, wave 0)
     if (value && !dbg) { if (hipMalloc(&dbg, 128 * sizeof(long long)) != hipSuccess) return ACRMI_EHIP; }

@@ -37,6 +37,10 @@ struct Schedule {
   std::vector<int> lane;
   std::vector<std::vector<int>> wait;
   std::vector<char> signal;
+  // grouped launches (csrc/group_plan.h): per op the op whose launch runs it (itself: it launches), followers directly behind
+  // their leader in `order` and on its lane
+  std::vector<int> leader;
+  int n_groups = 0;
 };
 // Per-stream state on one device, owned outside any context: what acrmi_streams and acrmi_tracks share.
 struct StateTable {
@@ -76,6 +80,7 @@ struct acrmi_ctx {
   acrmi_head_layout heads{};
   bool have_program = false;
   int max_batch = 0;
+  bool grouping = false;        // grouped launches in this program's schedules (the process-wide switch when the program was set)
   float* att_ws = nullptr;      // attention-pool workspace
   size_t att_ws_floats = 0;
   int* picks = nullptr;         // point heads: decoded centers per frame [max_batch,4], or one PointPlan per frame (point_plan.h)
@@ -173,6 +178,7 @@ PointArgs point_args(const acrmi_ctx* c, const acrmi_op& op, int B);      // acr
 int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane = 0, int point_hands = 1);
 bool op_active(const acrmi_op& op, bool point);
 void build_schedule(acrmi_ctx* c, bool point, bool large);
+void program_set_grouping(bool on);                    // acrmi_tune key 5: grouped launches in the programs set from now on
 int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool point, int first_op = 0, int point_hands = 1);
 int decode_maps_impl(const float* l_center, const float* r_center, int center_cs, const float* l_params, const float* r_params,
                      int params_cs, const float* l_prior, const float* r_prior, int prior_cs, int B, float conf_thresh,

@@ -55,8 +55,8 @@ int acrmi_decode_maps_multi(const float* l_center, const float* r_center, int ce
 // ---- stand-alone operators -------------------------------------------------------------------------
 }  // extern "C"
 
-// the tail of the three convolution entry points: channel ranges, derived fields, the shape rules (csrc/conv_rules.h), the launch
-static int conv_check_and_launch(const char* who, ConvArgs& a, void* stream) {
+// the tail of the convolution entry points: channel ranges, derived fields, the shape rules (csrc/conv_rules.h); then the launch
+static int conv_check(const char* who, ConvArgs& a) {
   if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2))
     return fail(nullptr, ACRMI_EINVAL, "%s: only 3x3 and 1x1 at stride 1 / 2 are implemented (got k%d s%d)", who, a.ks, a.stride);
   const int og = a.splitk ? 1 : a.groups;      // the slices of a split-K conv share the output channels
@@ -65,6 +65,10 @@ static int conv_check_and_launch(const char* who, ConvArgs& a, void* stream) {
     return fail(nullptr, ACRMI_EINVAL, "%s: channel slice outside its tensor's channel stride", who);
   conv_derive(a);
   if (const char* why = conv_algo_reject(a.algo, conv_shape(a))) return fail(nullptr, ACRMI_EINVAL, "%s: %s", who, why);
+  return ACRMI_OK;
+}
+static int conv_check_and_launch(const char* who, ConvArgs& a, void* stream) {
+  if (int r = conv_check(who, a)) return r;
   hipError_t e = launch_conv(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "conv launch: %s", hipGetErrorString(e));
 }
@@ -91,6 +95,34 @@ int acrmi_conv2d(const float* in, int B, int H, int W, int in_cs, int in_coff, i
   a.algo = algo;
   a.res_bcast = bias_map ? 1 : 0;
   return conv_check_and_launch("acrmi_conv2d", a, stream);
+}
+
+int acrmi_conv2d_group(const acrmi_conv_problem* p, int n, void* stream) {
+  if (!p || n < 1 || n > 2) return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_group: 1 or 2 problems");
+  if (n == 1)
+    return acrmi_conv2d(p->in, p->B, p->H, p->W, p->in_cs, p->in_coff, p->cin, p->w_packed, p->bias, p->bias_frame_stride, p->res, p->res_cs,
+                        p->res_coff, p->out, p->out_cs, p->out_coff, p->cout, p->ksize, p->stride, p->relu, p->groups, p->algo, stream);
+  ConvArgs a[2];
+  for (int i = 0; i < n; ++i) {
+    const acrmi_conv_problem& q = p[i];
+    if (!q.in || !q.w_packed || !q.bias || !q.out || q.B <= 0 || q.H <= 0 || q.W <= 0 || q.cin <= 0 || q.cout <= 0 || q.groups <= 0 ||
+        q.algo < 0 || (q.algo & ACRMI_CONV_BIAS_MAP))
+      return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_group: bad arguments (problem %d)", i);
+    a[i] = ConvArgs{};
+    a[i].in = q.in; a[i].w = q.w_packed; a[i].bias = q.bias; a[i].res = q.res; a[i].out = q.out;
+    a[i].B = q.B; a[i].H = q.H; a[i].W = q.W;
+    a[i].in_cs = q.in_cs; a[i].in_coff = q.in_coff; a[i].Cin = q.cin;
+    a[i].out_cs = q.out_cs; a[i].out_coff = q.out_coff; a[i].Cout = q.cout;
+    a[i].res_cs = q.res_cs; a[i].res_coff = q.res_coff;
+    a[i].ks = q.ksize; a[i].stride = q.stride; a[i].relu = q.relu; a[i].groups = q.groups;
+    a[i].bias_fstride = q.bias_frame_stride;
+    a[i].algo = q.algo;
+    if (int r = conv_check("acrmi_conv2d_group", a[i])) return r;
+  }
+  if (!conv_can_group(a[0], a[1]))
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_conv2d_group: the two problems do not run on one kernel instantiation with a group form");
+  hipError_t e = launch_conv_group(a, n, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "conv group launch: %s", hipGetErrorString(e));
 }
 
 size_t acrmi_conv2d_splitk_workspace(int B, int H, int W, int cout, int splits) {

@@ -1,6 +1,7 @@
 // libacrmi.so: the op program - validation (acrmi_set_program), dependency schedule and lanes, replay.
 #include "acrmi_ctx.h"
 #include "conv_frame.h"   // conv_shape
+#include "group_plan.h"
 
 void free_program(acrmi_ctx* c) {
   for (hipEvent_t e : c->op_ev)
@@ -76,6 +77,32 @@ PointArgs point_args(const acrmi_ctx* c, const acrmi_op& op, int B) {
   return p;
 }
 
+// a validated ACRMI_OP_CONV op as launch_conv takes it, on the lane it runs on
+static ConvArgs conv_args(const acrmi_ctx* c, const acrmi_op& op, int B, int lane) {
+  auto ptr = [&](int id) -> float* { return id >= 0 ? c->buf_ptr[id] : nullptr; };
+  ConvArgs a = conv_geometry(op, c->bufs.data(), B);
+  a.in = ptr(op.in_buf);
+  a.w = c->weights + op.w_off;
+  a.bias = op.bias_per_frame ? ptr(op.aux_buf) : c->weights + op.b_off;
+  a.res = a.res_bcast ? c->weights + op.w_off2 : ptr(op.res_buf);
+  a.out = ptr(op.out_buf);
+  if (a.splitk) {     // workspace of the lane this op runs on
+    a.split_ws = c->split_ws[lane]; a.split_cnt = c->split_cnt[lane];
+  }
+  for (int t = 0; t < op.nterms && t < 3; ++t) a.xt[t] = ptr(op.term_buf[t]);
+  if (op.flags & ACRMI_CONV_DUAL) a.out2 = ptr(op.aux_buf);      // the full-resolution HR fuse sum (conv_wino3's store waves)
+  a.range_flag = a.algo == 6 ? c->range_flag : nullptr;      // f16 operand halves: |x| must stay inside the f16 range
+  return a;
+}
+
+// Grouped launches (csrc/group_plan.h): on unless ACRMI_GROUP=0 is in the environment when the library loads (A/B runs);
+// acrmi_tune key 5 switches it for the programs set afterwards (a program keeps what it was set with).
+static bool g_grouping = [] {
+  const char* e = getenv("ACRMI_GROUP");
+  return !(e && atoi(e) == 0);
+}();
+void program_set_grouping(bool on) { g_grouping = on; }
+
 int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStream_t s, int lane, int point_hands) {
   auto ptr = [&](int id) -> float* { return id >= 0 ? c->buf_ptr[id] : nullptr; };
   auto desc = [&](int id) -> const acrmi_buffer_desc& { return c->bufs[id]; };
@@ -110,19 +137,7 @@ int run_op(acrmi_ctx* c, const acrmi_op& op, const uint8_t* img, int B, hipStrea
       return ACRMI_OK;
     }
     case ACRMI_OP_CONV: {
-      ConvArgs a = conv_geometry(op, c->bufs.data(), B);
-      a.in = ptr(op.in_buf);
-      a.w = c->weights + op.w_off;
-      a.bias = op.bias_per_frame ? ptr(op.aux_buf) : c->weights + op.b_off;
-      a.res = a.res_bcast ? c->weights + op.w_off2 : ptr(op.res_buf);
-      a.out = ptr(op.out_buf);
-      if (a.splitk) {     // workspace of the lane this op runs on
-        a.split_ws = c->split_ws[lane]; a.split_cnt = c->split_cnt[lane];
-      }
-      for (int t = 0; t < op.nterms && t < 3; ++t) a.xt[t] = ptr(op.term_buf[t]);
-      if (op.flags & ACRMI_CONV_DUAL) a.out2 = ptr(op.aux_buf);      // the full-resolution HR fuse sum (conv_wino3's store waves)
-      a.range_flag = a.algo == 6 ? c->range_flag : nullptr;      // f16 operand halves: |x| must stay inside the f16 range
-      HIPCHK(c, launch_conv(a, s));
+      HIPCHK(c, launch_conv(conv_args(c, op, B, lane), s));
       return ACRMI_OK;
     }
     case ACRMI_OP_FUSESUM: {
@@ -251,20 +266,15 @@ void build_schedule(acrmi_ctx* c, bool point, bool large) {
   S = Schedule();
   S.deps.assign(n, std::vector<int>());
   S.leaf.assign(n, 1);
-  std::vector<int> last_writer(nb, -1), R, W;
-  std::vector<std::vector<int>> readers(nb);
+  std::vector<std::vector<int>> reads(n), writes(n);
   for (int j = 0; j < n; ++j) {
     if (!op_active(c->ops[j], point)) continue;
     S.order.push_back(j);
-    op_rw(c, c->ops[j], R, W);
-    std::vector<int>& deps = S.deps[j];
-    auto dep = [&](int i) { if (i >= 0 && i != j && std::find(deps.begin(), deps.end(), i) == deps.end()) deps.push_back(i); };
-    for (int b : R) dep(last_writer[b]);
-    for (int b : W) { dep(last_writer[b]); for (int i : readers[b]) dep(i); }
-    for (int b : R) readers[b].push_back(j);
-    for (int b : W) { last_writer[b] = j; readers[b].clear(); }
-    for (int d : deps) S.leaf[d] = 0;
+    op_rw(c, c->ops[j], reads[j], writes[j]);
   }
+  S.deps = hazard_deps(S.order, reads, writes, n, nb);
+  for (int j : S.order)
+    for (int d : S.deps[j]) S.leaf[d] = 0;
   const int want = c->want_lanes > 0 ? c->want_lanes : (large ? AUTO_LANES_LARGE : AUTO_LANES_SMALL);
   const int max_lanes = std::max(1, std::min(want, MAX_LANES));
   S.lane.assign(n, 0);
@@ -303,11 +313,29 @@ void build_schedule(acrmi_ctx* c, bool point, bool large) {
     }
     std::stable_sort(S.order.begin(), S.order.end(), [&](int x, int y) { return ru[x] > ru[y]; });
   }
+  // Grouped launches (group_plan.h): programs of large-batch contexts only (max_batch >= 16, the gate of the other large-batch
+  // lowerings) - at small batches a launch leaves CUs idle and the ops sit on the dependency chain, where a group would only
+  // delay its first op's consumers to the end of both.  The routing is asked with the arguments run_program will launch.
+  S.leader.assign(n, 0);
+  for (int j = 0; j < n; ++j) S.leader[j] = j;
+  S.n_groups = 0;
+  if (c->grouping && c->max_batch >= 16) {
+    std::vector<ConvArgs> ca(n);
+    std::vector<char> is_conv(n, 0);
+    for (int j : S.order)
+      if (c->ops[j].kind == ACRMI_OP_CONV) { ca[j] = conv_args(c, c->ops[j], c->max_batch, 0); is_conv[j] = 1; }
+    S.leader = plan_groups(S.order, S.deps, n, [&](int x, int y) { return is_conv[x] && is_conv[y] && conv_can_group(ca[x], ca[y]); },
+                           CONV_GROUP_MAX);
+    for (int j : S.order) S.n_groups += S.leader[j] != j;      // (groups of two: one follower each)
+  }
   std::vector<int> pos(n, -1);               // position in the enqueue order (a lane runs its ops in this order)
   for (int k = 0; k < (int)S.order.size(); ++k) pos[S.order[k]] = k;
   for (int j : S.order) {
     int lane = -1;
-    if (planned) {
+    if (S.leader[j] != j) {      // a follower runs inside its leader's launch
+      lane = S.lane[S.leader[j]];
+      if (planned) fin[j] = fin[S.leader[j]] = lane_free[lane] = lane_free[lane] + std::max(ms[j] - EVENT_MS, 0.002f);
+    } else if (planned) {
       float best = 0.f;
       bool best_prod = false;
       for (int l = 0; l < max_lanes; ++l) {
@@ -354,9 +382,10 @@ void build_schedule(acrmi_ctx* c, bool point, bool large) {
     }
     int waits = 0;
     for (int j : S.order) waits += (int)S.wait[j].size();
-    fprintf(stderr, "[acrmi] schedule(%s, %s batches, %s): %zu ops, %d edges, critical path %d ops; %d lanes, %d cross-lane waits\n",
+    fprintf(stderr, "[acrmi] schedule(%s, %s batches, %s): %zu ops, %d edges, critical path %d ops; %d lanes, %d cross-lane waits, "
+                    "%d grouped launches\n",
             point ? "point" : "dense", large ? "large" : "small", planned ? "planned from measured op times" : "structural",
-            S.order.size(), edges, maxd, S.n_lanes, waits);
+            S.order.size(), edges, maxd, S.n_lanes, waits, S.n_groups);
   }
 }
 
@@ -560,6 +589,7 @@ int acrmi_set_program(acrmi_ctx* c, const acrmi_buffer_desc* bufs, int n_bufs, c
   c->ops.assign(ops, ops + n_ops);
   c->heads = *heads;
   c->max_batch = max_batch;
+  c->grouping = g_grouping;
   c->buf_ptr.assign(n_bufs, nullptr);
   for (int i = 0; i < n_bufs; ++i) {
     const auto& d = bufs[i];
@@ -623,12 +653,17 @@ static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_
     if (!c->lanes[l]) HIPCHK(c, hipStreamCreateWithFlags(&c->lanes[l], hipStreamNonBlocking));
     if (!c->join_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->join_ev[l], lane_event_flags()));
   }
-  if (!c->fork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, lane_event_flags()));
   auto st = [&](int l) { return l == 0 ? user : c->lanes[l]; };
-  HIPCHK(c, hipEventRecord(c->fork_ev, user));
+  if (S.n_lanes > 1) {      // (one lane: a schedule that is here for its grouped launches - the caller's stream, no events)
+    if (!c->fork_ev) HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, lane_event_flags()));
+    HIPCHK(c, hipEventRecord(c->fork_ev, user));
+  }
   for (int l = 1; l < S.n_lanes; ++l) HIPCHK(c, hipStreamWaitEvent(c->lanes[l], c->fork_ev, 0));
   int r = ACRMI_OK;
-  for (int j : S.order) {
+  const int n_order = (int)S.order.size();
+  for (int k = 0; k < n_order; ++k) {
+    const int j = S.order[k];
+    if (S.leader[j] != j) continue;      // ran inside its leader's launch
     hipStream_t s = st(S.lane[j]);
     // timing ablation (WRONG results: data races between lanes): 1 = no waits, 2 = no waits and no records.  Loud, so that a
     // leaked environment variable cannot silently corrupt a real run.
@@ -639,12 +674,40 @@ static int run_program_lanes(acrmi_ctx* c, const uint8_t* img, int B, hipStream_
                              "(timing experiment only)\n", v);
       return v;
     }();
-    if (!(ablate & 1)) for (int d : S.wait[j]) HIPCHK(c, hipStreamWaitEvent(s, c->op_ev[d], 0));
-    r = run_op(c, c->ops[j], img, B, s, S.lane[j], point_hands);
-    if (r) break;
-    if (S.signal[j] && !(ablate & 2)) {
-      if (!c->op_ev[j]) HIPCHK(c, hipEventCreateWithFlags(&c->op_ev[j], lane_event_flags()));
-      HIPCHK(c, hipEventRecord(c->op_ev[j], s));
+    // the launch's ops: j and the followers behind it in the order (the group waits for what any of them waits for, and
+    // its end is the end of each)
+    int members[CONV_GROUP_MAX] = {j}, nm = 1;
+    while (nm < CONV_GROUP_MAX && k + nm < n_order && S.leader[S.order[k + nm]] == j && S.order[k + nm] != j) { members[nm] = S.order[k + nm]; ++nm; }
+    if (!(ablate & 1))
+      for (int m = 0; m < nm; ++m)
+        for (int d : S.wait[members[m]]) HIPCHK(c, hipStreamWaitEvent(s, c->op_ev[d], 0));
+    if (nm > 1) {
+      ConvArgs ga[CONV_GROUP_MAX];
+      bool same = true;
+      for (int m = 0; m < nm; ++m) {
+        ga[m] = conv_args(c, c->ops[members[m]], B, S.lane[j]);
+        same = same && conv_can_group(ga[0], ga[m]);
+      }
+      hipError_t e = hipSuccess;
+      if (same) {
+        e = launch_conv_group(ga, nm, s);
+      } else {      // (a tuning cfg forced since the program was set routes them apart: their own launches)
+        for (int m = 0; m < nm && e == hipSuccess; ++m) e = launch_conv(ga[m], s);
+      }
+      if (e != hipSuccess) {      // (on to the join, like an op that fails)
+        r = fail(c, ACRMI_EHIP, "grouped conv launch: %s", hipGetErrorString(e));
+        break;
+      }
+    } else {
+      r = run_op(c, c->ops[j], img, B, s, S.lane[j], point_hands);
+      if (r) break;
+    }
+    for (int m = 0; m < nm; ++m) {
+      const int jm = members[m];
+      if (S.signal[jm] && !(ablate & 2)) {
+        if (!c->op_ev[jm]) HIPCHK(c, hipEventCreateWithFlags(&c->op_ev[jm], lane_event_flags()));
+        HIPCHK(c, hipEventRecord(c->op_ev[jm], s));
+      }
     }
   }
   for (int l = 1; l < S.n_lanes; ++l) {       // join also on the error path: nothing may outlive the call unordered
@@ -663,7 +726,10 @@ int run_program(acrmi_ctx* c, const uint8_t* img, int B, void* stream, bool poin
   ON_DEVICE(c);
   c->last_batch = B;
   static const bool dbg_sync = getenv("ACRMI_DEBUG_SYNC") != nullptr;   // attribute a fault/hang to an op
-  if (c->sched[point ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0].n_lanes > 1 && !dbg_sync && first_op <= 0)
+  // (the schedule's order: several lanes, or one with grouped launches.  Ops replayed one by one - ACRMI_DEBUG_SYNC, acrmi_heads,
+  //  acrmi_profile_ops - are never grouped)
+  const Schedule& S = c->sched[point ? 1 : 0][B > AUTO_SMALL_BATCH ? 1 : 0];
+  if ((S.n_lanes > 1 || S.n_groups > 0) && !dbg_sync && first_op <= 0)
     return run_program_lanes(c, img, B, (hipStream_t)stream, point, point_hands);
   int i = 0;
   for (const acrmi_op& op : c->ops) {

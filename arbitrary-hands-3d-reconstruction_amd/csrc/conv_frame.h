@@ -60,6 +60,15 @@ inline ConvShape conv_shape(const ConvArgs& a) {
                    a.out2_cs, a.out2_coff, a.res != nullptr, a.bias_fstride, a.nxt, a.out2 != nullptr, a.splitk, a.res_bcast, a.in_sub, a.dtype, a.out_f32};
 }
 
+// A grouped launch (launch_conv_kernel's second form): the problems of ONE kernel instantiation whose items a single persistent
+// launch walks back to back - problem 0's [0, wk[0].total), then problem 1's, dealt to the workgroups like one problem's.  By
+// value in the kernel arguments: what a kernel reads from it is wave-uniform, fetched by scalar loads where it is needed.
+constexpr int CONV_GROUP_MAX = 2;
+struct ConvGroup {
+  ConvArgs a[CONV_GROUP_MAX];
+  ConvWork wk[CONV_GROUP_MAX];
+};
+
 // One kernel instantiation as its launcher names it: the host handle, the instantiation's own "dynamic LDS attribute set"
 // flags (one per device) and what ACRMI_DEBUG prints.  CONV_KERNEL(conv_x_kernel<...>) creates the flags where the
 // instantiation is named: every expansion has its own, and inside a template launcher every instantiation of it.
@@ -68,11 +77,20 @@ struct ConvKernel {
   unsigned char* first_use;   // [MAX_DEVICES]
   const char* name;           // the kernel expression as written ...
   const char* where;          // ... and the launcher that names it (a template launcher: with its arguments' values)
+  // opt-in: the same instantiation walking a ConvGroup (null: the kernel takes one problem per launch)
+  void (*group_fn)(const ConvGroup) = nullptr;
+  unsigned char* group_first_use = nullptr;
 };
 #define CONV_KERNEL(...)                                                    \
   ({                                                                        \
     static unsigned char first_use_[MAX_DEVICES] = {};                      \
     ConvKernel{__VA_ARGS__, first_use_, #__VA_ARGS__, __PRETTY_FUNCTION__}; \
+  })
+// ... and of a kernel with a group form: CONV_KERNEL_GROUPED((conv_x_kernel<...>), (conv_x_group_kernel<...>))
+#define CONV_KERNEL_GROUPED(one, grp)                                                            \
+  ({                                                                                             \
+    static unsigned char first_use_[MAX_DEVICES] = {}, group_first_use_[MAX_DEVICES] = {};       \
+    ConvKernel{one, first_use_, #one, __PRETTY_FUNCTION__, grp, group_first_use_};               \
   })
 
 // The host path of every persistent conv kernel (defined in conv_mfma.hip; the caller holds launch_mutex(), as launch_conv
@@ -81,6 +99,14 @@ struct ConvKernel {
 // items).  nb_inner: ConvWork::nb_inner.
 hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, int tiles_x, int tiles_y, int nblk,
                               const ConvArgs& a, hipStream_t s, int nb_inner = 1);
+// The grouped form: n <= CONV_GROUP_MAX problems of one instantiation, each with its own arguments and item space, in one launch
+// of k.group_fn (one persistent workgroup per CU over the concatenated items).  A group of one IS the launch above; a kernel
+// without a group form refuses more (hipErrorInvalidValue).  The problems must be independent: no workgroup waits for another.
+struct ConvProblem {
+  ConvArgs a;
+  int tiles_x, tiles_y, nblk;
+};
+hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, const ConvProblem* p, int n, hipStream_t s);
 
 // Workgroup b of a launch lands on XCD b % 8 (observed dispatch order on gfx950; used for speed only, never for
 // correctness).  A persistent workgroup walks items vb, vb + grid, vb + 2*grid, ...; with vb = b the 256 items in

@@ -484,29 +484,57 @@ int conv_forced_cfg() { return g_force_cfg; }
 int conv_num_cus() { return g_num_cus_dev[current_device()]; }
 hipError_t conv_ensure_device_info() { return ensure_device_info(); }
 
-hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, int tiles_x, int tiles_y, int nblk,
-                              const ConvArgs& a, hipStream_t s, int nb_inner) {
-  if (first_use_on_device(k.first_use)) {
-    const void* fn = reinterpret_cast<const void*>(k.fn);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (getenv("ACRMI_DEBUG")) {
-      hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, fn);
-      fprintf(stderr, "[acrmi] %s in %s: threads %d lds %zu regs %d scratch %zu\n", k.name, k.where, threads, lds, fa.numRegs,
-              (size_t)fa.localSizeBytes);
-    }
+// first use of a kernel handle on the current device: its dynamic LDS size (and, under ACRMI_DEBUG, what it was compiled to)
+static hipError_t conv_first_use(const void* fn, unsigned char* flags, const ConvKernel& k, const char* form, int threads, size_t lds) {
+  if (!first_use_on_device(flags)) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  if (getenv("ACRMI_DEBUG")) {
+    hipFuncAttributes fa;
+    (void)hipFuncGetAttributes(&fa, fn);
+    fprintf(stderr, "[acrmi] %s%s in %s: threads %d lds %zu regs %d scratch %zu\n", k.name, form, k.where, threads, lds, fa.numRegs,
+            (size_t)fa.localSizeBytes);
   }
-  ConvWork wk;
+  return hipSuccess;
+}
+// the item space of one problem (false: too many items for the multiply-shift divisions)
+static bool conv_work(ConvWork& wk, int tiles_x, int tiles_y, int nblk, int nb_inner, const ConvArgs& a) {
   wk.tiles_x = tiles_x;
   wk.tiles_per_frame = tiles_x * tiles_y;
   wk.n_tiles_total = wk.tiles_per_frame * a.B;
   wk.nblk = nblk;
   wk.nb_inner = nb_inner;
   wk.total = wk.n_tiles_total * wk.nblk * a.groups;
-  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return hipErrorInvalidValue;
+  if ((unsigned long long)wk.total * (unsigned long long)wk.n_tiles_total >= (1ull << 40)) return false;
   set_magics(wk);
+  return true;
+}
+
+hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, int tiles_x, int tiles_y, int nblk,
+                              const ConvArgs& a, hipStream_t s, int nb_inner) {
+  hipError_t e = conv_first_use(reinterpret_cast<const void*>(k.fn), k.first_use, k, "", threads, lds);
+  if (e != hipSuccess) return e;
+  ConvWork wk;
+  if (!conv_work(wk, tiles_x, tiles_y, nblk, nb_inner, a)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k.fn, dim3((unsigned)pick_grid(wk.total)), dim3(threads), lds, s, a, wk);
+  return hipGetLastError();
+}
+
+hipError_t launch_conv_kernel(const ConvKernel& k, int threads, size_t lds, const ConvProblem* p, int n, hipStream_t s) {
+  if (!p || n < 1 || n > CONV_GROUP_MAX) return hipErrorInvalidValue;
+  if (n == 1) return launch_conv_kernel(k, threads, lds, p[0].tiles_x, p[0].tiles_y, p[0].nblk, p[0].a, s);
+  if (!k.group_fn) return hipErrorInvalidValue;      // a missing group form is an error, never two quiet launches
+  hipError_t e = conv_first_use(reinterpret_cast<const void*>(k.group_fn), k.group_first_use, k, " (group form)", threads, lds);
+  if (e != hipSuccess) return e;
+  ConvGroup g;
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    g.a[i] = p[i].a;
+    if (!conv_work(g.wk[i], p[i].tiles_x, p[i].tiles_y, p[i].nblk, 1, p[i].a) || g.wk[i].total <= 0) return hipErrorInvalidValue;
+    total += g.wk[i].total;
+  }
+  if (total >= (1l << 30)) return hipErrorInvalidValue;      // (item indices stay ints)
+  hipLaunchKernelGGL(k.group_fn, dim3((unsigned)pick_grid(total)), dim3(threads), lds, s, g);
   return hipGetLastError();
 }
 
@@ -531,11 +559,8 @@ static hipError_t launch_wino(const ConvArgs& a, hipStream_t s) {
 #include "conv_x3s2.inc"
 #include "conv_p1.inc"
 
-// Tile selection.  N32: one 32-cout tile per wave (Cout <= 32); N64: two.
-// Small frames (<=16x16 outputs) take the 8x16 pixel tile so a batch still fills 256 CUs.
-hipError_t launch_conv(ConvArgs a, hipStream_t s) {
-  if (conv_algo_reject(a.algo, conv_shape(a))) return hipErrorInvalidValue;      // no kernel for this algo and shape (conv_rules.h)
-  std::lock_guard<std::recursive_mutex> launch_lock(g_init_mutex);
+// what every launch adds to its arguments: the tuning state, the zeros the LDS-DMA loaders read, the device's CU count
+static hipError_t conv_prepare(ConvArgs& a) {
   a.dbg = g_dbg;
   a.phase_delay = g_phase_delay;
   static const char* swz_env = experiment_env("ACRMI_XCD_SWIZZLE");      // A/B runs: 0 = round-robin item order
@@ -558,8 +583,46 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s) {
     }
     a.zeros = zeros[dev];
   }
+  return ensure_device_info();   // the CU count steers the item shape at small batches
+}
+
+// The instantiation with a group form that launch_conv below routes `a` to: its identity (two convolutions may share a launch
+// when theirs are equal), or null.  Follows launch_conv's own order of questions.
+static const void* conv_group_instance(const ConvArgs& a, int* tw_out) {
+  if (a.dtype != ACRMI_DT_F32 || a.algo != 4 || conv_algo_reject(a.algo, conv_shape(a)) || wino24c_ok(a)) return nullptr;
+  const int tw = wino24b_ok(a);
+  Wino24bPick p;
+  if (!tw || !wino24b_pick(a, tw, p) || !p.k.group_fn) return nullptr;
+  if (tw_out) *tw_out = tw;
+  return reinterpret_cast<const void*>(p.k.fn);
+}
+bool conv_can_group(const ConvArgs& a, const ConvArgs& b) {
+  const void* ka = conv_group_instance(a, nullptr);
+  return ka && ka == conv_group_instance(b, nullptr);
+}
+
+hipError_t launch_conv_group(const ConvArgs* a, int n, hipStream_t s) {
+  if (!a || n < 1 || n > CONV_GROUP_MAX) return hipErrorInvalidValue;
+  if (n == 1) return launch_conv(a[0], s);
+  std::lock_guard<std::recursive_mutex> launch_lock(g_init_mutex);
+  ConvArgs p[CONV_GROUP_MAX];
+  int tw[CONV_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    p[i] = a[i];
+    hipError_t e = conv_prepare(p[i]);
+    if (e != hipSuccess) return e;
+    if (!conv_group_instance(p[i], &tw[i]) || !conv_can_group(p[0], p[i])) return hipErrorInvalidValue;
+  }
+  return launch_wino24b_group(p, tw, n, s);
+}
+
+// Tile selection.  N32: one 32-cout tile per wave (Cout <= 32); N64: two.
+// Small frames (<=16x16 outputs) take the 8x16 pixel tile so a batch still fills 256 CUs.
+hipError_t launch_conv(ConvArgs a, hipStream_t s) {
+  if (conv_algo_reject(a.algo, conv_shape(a))) return hipErrorInvalidValue;      // no kernel for this algo and shape (conv_rules.h)
+  std::lock_guard<std::recursive_mutex> launch_lock(g_init_mutex);
   {
-    hipError_t de = ensure_device_info();   // the CU count steers the item shape at small batches
+    hipError_t de = conv_prepare(a);
     if (de != hipSuccess) return de;
   }
   if (a.dtype != ACRMI_DT_F32) return launch_conv_h16(a, s);   // f16 / bf16 storage: conv_h16.hip

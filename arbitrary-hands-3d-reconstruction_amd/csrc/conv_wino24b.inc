@@ -52,8 +52,23 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, float* ds
 #ifndef ACRMI_W24_ABLATE
 #define ACRMI_W24_ABLATE 0
 #endif
-template <int NT, int TW, bool ONE = false>
-__global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, const ConvWork wk) {
+//
+// GROUP (conv_wino24b_group_kernel): one launch walks the items of TWO independent problems of this instantiation, problem 0's
+// [0, total0) then problem 1's [total0, total0 + total1), dealt to the workgroups like one problem's.  Everything the body reads
+// from a problem is wave-uniform and belongs to one of three cursors, each with the index of its problem:
+//   ix_d  the DMA cursor (input map; enters the next problem up to two chunks ahead of the MFMAs: dma_begin_scalar),
+//   ix_c  the weights and the chunk count (switches in the epilogue of problem 0's last item, in front of the next item's
+//         first fragments),
+//   ix_e  the epilogue (output, residual, bias; switches behind that item's last store).
+// A switch is scalar loads and moves, plus once per launch the per-lane offsets that hold a map width (doff, lane_out,
+// lane_res); the steps between two switches are those of the ungrouped kernel, and so is every sum.  The workgroups never
+// wait for each other: the two problems are independent by construction (csrc/group_plan.h).
+// Registers of the <2, 32> group form: 256 VGPRs + 201 AGPRs, no scratch (ungrouped: 240 + 192) - nine values are parked in
+// AGPRs; measured per chunk and per epilogue it runs at the ungrouped kernel's pace (profiles/group_launch_ab.txt, stamps).
+template <int NT, int TW, bool ONE, bool GROUP>
+__device__ __forceinline__ void wino24b_body(const ConvArgs* ga, const ConvWork* gw) {
+  const ConvArgs& a = ga[0];      // the launch-wide fields (tuning state) and, ungrouped, the problem
+  const ConvWork& wk = gw[0];
 
   constexpr int CK = 32, TH = TW == 32 ? 8 : 16, PH = TH + 2, PWP = TW + 2;
   constexpr int W24_ABLATE = ACRMI_W24_ABLATE;
@@ -70,10 +85,31 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nchunks = a.Cin / CK;                  // >= 1
   const int vb = virtual_block(a);
-  const int my_items = wk.total > vb ? (wk.total - 1 - vb) / (int)gridDim.x + 1 : 0;
-  const int ktotal = my_items * nchunks;
+  // GROUP: the cursors' problems (0 / 1).  A cursor reads its problem's fields from the kernel arguments where it needs them
+  // - once per item, next to scalar work that is there anyway - and not from registers held across the steps: the frame has
+  // no scalar register to spare, and a copy of both problems would live in VGPR lanes (v_readlane in every step).  What the
+  // STEPS read (cin8_c, cin_d, tap_b, step_b, the descriptors) is kept in variables that a switch renews.
+  // A workgroup whose first item lies in problem 1 starts there.
+  const int total0 = wk.total;
+  int ix_d = (GROUP && vb >= total0) ? 1 : 0, ix_c = ix_d, ix_e = ix_d;
+  auto AD = [&]() -> const ConvArgs& { return ga[GROUP ? ix_d : 0]; };
+  auto AC = [&]() -> const ConvArgs& { return ga[GROUP ? ix_c : 0]; };
+  auto AE = [&]() -> const ConvArgs& { return ga[GROUP ? ix_e : 0]; };
+  auto WD = [&]() -> const ConvWork& { return gw[GROUP ? ix_d : 0]; };
+  auto WC = [&]() -> const ConvWork& { return gw[GROUP ? ix_c : 0]; };
+  auto WE = [&]() -> const ConvWork& { return gw[GROUP ? ix_e : 0]; };
+  auto base = [&](int ix) -> int { return (GROUP && ix) ? total0 : 0; };      // first item of the cursor's problem
+  bool doff_stale = false;                         // the DMA cursor changed problem: dma_begin_vector renews doff
+  int nchunks = AC().Cin / CK;                       // >= 1 (GROUP: of the problem the MFMAs are in)
+  int cin8_c = AC().cin8, cin_d = AD().Cin;
+  const int total = GROUP ? total0 + gw[GROUP ? 1 : 0].total : total0;
+  const int my_items = total > vb ? (total - 1 - vb) / (int)gridDim.x + 1 : 0;
+  int ktotal = my_items * nchunks;
+  if constexpr (GROUP) {
+    const int items0 = total0 > vb ? (total0 - 1 - vb) / (int)gridDim.x + 1 : 0;
+    ktotal = items0 * (ga[0].Cin / CK) + (my_items - items0) * (ga[1].Cin / CK);
+  }
   const int py = wave;
   const int li = lane & 31, lh = lane >> 5;
   const int ra = py == 0 ? 0 : (py == 2 ? 2 : 1);
@@ -87,26 +123,26 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
   const int oy = wave >> 1, oh = wave & 1;
   const int p8 = lane >> 3, q8 = lane & 7;
   // (reader slot 8 gq + p8 = block row (8 gq + p8) / BCOLS, block column p8 % BCOLS)
-  const int lane_pix = (2 * (p8 / BCOLS) + oy) * a.Wo + 4 * (p8 % BCOLS) + 2 * oh;
-  const int lane_out = lane_pix * a.out_cs + 4 * q8, lane_res = lane_pix * a.res_cs + 4 * q8;
-  const int gs_out = (16 / BCOLS) * a.Wo * a.out_cs, gs_res = (16 / BCOLS) * a.Wo * a.res_cs;   // gq + 1 = 8 slots on = 2 / 4 pixel rows
+  int lane_pix = (2 * (p8 / BCOLS) + oy) * AE().Wo + 4 * (p8 % BCOLS) + 2 * oh;
+  int lane_out = lane_pix * AE().out_cs + 4 * q8, lane_res = lane_pix * AE().res_cs + 4 * q8;
+  int gs_out = (16 / BCOLS) * AE().Wo * AE().out_cs, gs_res = (16 / BCOLS) * AE().Wo * AE().res_cs;   // gq + 1 = 8 slots on = 2 / 4 pixel rows
   const float ysign = oy ? -1.f : 1.f;
-  const bool has_res = a.res != nullptr;
-  const float floor_ = a.relu ? 0.f : -__builtin_inff();
+  bool has_res = AE().res != nullptr;
+  float floor_ = AE().relu ? 0.f : -__builtin_inff();
   f32x16 acc[6][NT];
 
   // ---- weights: as conv_wino24_kernel, NT n-tiles per position
-  const int tap_b = a.cin8 * a.n_tiles * 1024, step_b = a.n_tiles * 1024;
-  const __amdgpu_buffer_rsrc_t wrsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.groups * 24 * tap_b, 0x00020000);
+  int tap_b = cin8_c * AC().n_tiles * 1024, step_b = AC().n_tiles * 1024;
+  __amdgpu_buffer_rsrc_t wrsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AC().w), 0, AC().groups * 24 * tap_b, 0x00020000);
   const unsigned wlane = lane * 16;
   auto wbase = [&](int w_item) -> int {
-    const ItemPos ip = item_pos(wk, w_item);
+    const ItemPos ip = item_pos(WC(), w_item - base(ix_c));
     return (ip.g * 24 + py * 6) * tap_b + ip.rest * NT * 1024;
   };
   f32x4 d[2][6], v[6], bq[6][NT];
   auto load_frag = [&](int p, int base, int step) {
-    const int so = base + p * tap_b + (step < a.cin8 ? step : a.cin8 - 1) * step_b;
+    const int so = base + p * tap_b + (step < cin8_c ? step : cin8_c - 1) * step_b;
 #pragma unroll
     for (int n = 0; n < NT; ++n)
       bq[p][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, so + n * 1024, 0));
@@ -175,14 +211,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
     const int grp = rem / GQ, q = rem - grp * GQ;
     const int pix = grp * 4 + (q >> 3);
     const bool live = row < PH && q < 32 && pix < PWP;
-    doff[i] = ((row * a.W + pix) * a.in_cs + 4 * (q & 7)) * 4;
+    doff[i] = ((row * AD().W + pix) * AD().in_cs + 4 * (q & 7)) * 4;
     const unsigned hb = (row == 0 ? 1u : 0u) | (row == PH - 1 ? 2u : 0u) | (pix == 0 ? 4u : 0u) | (pix == PWP - 1 ? 8u : 0u) |
                         (live ? 0u : 16u);
     dhb[i >> 2] |= hb << (8 * (i & 3));
     eff[i] = (int)0x80000000;
   }
-  const int tiles_y = wk.tiles_per_frame / wk.tiles_x;
-  __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, 0, 0x00020000);
+  int tiles_y = WD().tiles_per_frame / WD().tiles_x;
+  __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AD().in), 0, 0, 0x00020000);
   int wd = vb, cd0 = 0, kd = 0;     // DMA cursor: item, first channel and index of the next chunk to request
   // The cursor enters an item (cd0 == 0, uniform): descriptor at its patch origin, halo lanes.  In two halves since round 6:
   // the SCALAR half (item position by multiply-shift division, the 64-bit origin, the descriptor: ~100 dependent scalar
@@ -196,17 +232,37 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
   auto dma_begin_scalar = [&]() {
     if (cd0 == 0) {
       const bool valid = kd < ktotal;
-      const ItemPos ip = item_pos(wk, valid ? wd : vb);
+      if constexpr (GROUP) {
+        if (valid && ix_d == 0 && wd >= total0) {   // the cursor's first item of problem 1
+          ix_d = 1;
+          tiles_y = WD().tiles_per_frame / WD().tiles_x;
+          cin_d = AD().Cin;
+          doff_stale = true;
+        }
+      }
+      const ItemPos ip = item_pos(WD(), (valid ? wd : vb) - base(ix_d));
       dma_edge = (ip.ty == 0 ? 1u : 0u) | (ip.ty == tiles_y - 1 ? 2u : 0u) | (ip.tx == 0 ? 4u : 0u) |
-                 (ip.tx == wk.tiles_x - 1 ? 8u : 0u) | 16u;
-      const long long org = (((long long)ip.b * a.H + (ip.ty * TH - 1)) * a.W + (ip.tx * TW - 1)) * (long long)a.in_cs +
-                            a.in_coff + ip.g * a.Cin;
+                 (ip.tx == WD().tiles_x - 1 ? 8u : 0u) | 16u;
+      const long long org = (((long long)ip.b * AD().H + (ip.ty * TH - 1)) * AD().W + (ip.tx * TW - 1)) * (long long)AD().in_cs +
+                            AD().in_coff + ip.g * AD().Cin;
       // past the last item: zero records, every lane out of range (the pieces then write zeros into a buffer nobody reads)
-      drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in + org), 0, valid ? 0x7ffffff0 : 0, 0x00020000);
+      drsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AD().in + org), 0, valid ? 0x7ffffff0 : 0, 0x00020000);
     }
   };
   auto dma_begin_vector = [&]() {
     if (cd0 == 0) {
+      if constexpr (GROUP) {
+        if (doff_stale) {      // (uniform; once per launch) the lanes' source offsets on problem 1's map
+          doff_stale = false;
+#pragma unroll
+          for (int i = 0; i < NI; ++i) {
+            const int f = jj[i] * 64 + lane;
+            const int row = f / RS, rem = f - row * RS;
+            const int grp = rem / GQ, q = rem - grp * GQ;
+            doff[i] = ((row * AD().W + grp * 4 + (q >> 3)) * AD().in_cs + 4 * (q & 7)) * 4;
+          }
+        }
+      }
 #pragma unroll
       for (int i = 0; i < NI; ++i)
         eff[i] = ((dhb[i >> 2] >> (8 * (i & 3))) & dma_edge) ? (int)0x80000000 : doff[i];
@@ -221,7 +277,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
   };
   auto dma_end = [&]() {
     cd0 += CK;
-    if (cd0 >= a.Cin) { cd0 = 0; wd += (int)gridDim.x; }
+    if (cd0 >= cin_d) { cd0 = 0; wd += (int)gridDim.x; }
     ++kd;
   };
 
@@ -258,7 +314,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
     const float* patch_n = lds + ((k + 1) & 1) * BUF;
     const int nw = LAST ? w + (int)gridDim.x : w;
     const bool more = k + 1 < ktotal;
-    const int wsn = (LAST && more) ? wbase(nw) : wsc;
+    // the next item's weights (GROUP: named in the epilogue, behind the switch of ac - the steps below still read this item's)
+    int wsn = (!GROUP && LAST && more) ? wbase(nw) : wsc;
     int rest = 0;
     float* out_tile = nullptr;
     f32x4 rv[NT][4], bv[NT];
@@ -267,17 +324,17 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
     // inside the LAST chunk's second step, interleaved with its MFMAs - at the top of the chunk its ~500 cycles of dependent
     // scalar arithmetic ran with the matrix pipe idle (profiles/r06_wino24b_ablation_epilogue.txt: 696 vs 200 cycles)
     auto prep_last = [&]() {
-      const ItemPos ip = item_pos(wk, w);
+      const ItemPos ip = item_pos(WE(), w - base(ix_e));
       const int g = ip.g, b = ip.b;
       rest = ip.rest;
-      const float* bias = a.bias + (size_t)g * a.n_tiles * 32 + (size_t)b * a.bias_fstride;
-      const int tile_pix = ip.ty * TH * a.Wo + ip.tx * TW;
-      out_tile = a.out + (size_t)b * a.Ho * a.Wo * a.out_cs + a.out_coff + g * a.Cout + (size_t)tile_pix * a.out_cs;
-      const size_t res_off = (res_frame_off(a, b) + (size_t)tile_pix * a.res_cs) + a.res_coff + g * a.Cout;
-      const size_t res_left = has_res ? (res_total(a) - res_off) * 4 : 0;
-      rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(has_res ? a.res + res_off : a.in), 0,
+      const float* bias = AE().bias + (size_t)g * AE().n_tiles * 32 + (size_t)b * AE().bias_fstride;
+      const int tile_pix = ip.ty * TH * AE().Wo + ip.tx * TW;
+      out_tile = AE().out + (size_t)b * AE().Ho * AE().Wo * AE().out_cs + AE().out_coff + g * AE().Cout + (size_t)tile_pix * AE().out_cs;
+      const size_t res_off = (res_frame_off(AE(), b) + (size_t)tile_pix * AE().res_cs) + AE().res_coff + g * AE().Cout;
+      const size_t res_left = has_res ? (res_total(AE()) - res_off) * 4 : 0;
+      rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(has_res ? AE().res + res_off : AE().in), 0,
                                                 (int)(unsigned)(res_left > 0xffffffffu ? 0xffffffffu : res_left), 0x00020000);
-      brsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias_row_left(a, g), 0x00020000);
+      brsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias_row_left(AE(), g), 0x00020000);
     };
     // residual of one round (column offset oc pixels) and the bias: unconditional raw buffer loads (zero records: 0)
     auto request_res = [&](int oc) {
@@ -286,7 +343,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq)
           rv[n][gq] = __builtin_bit_cast(
-              f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (lane_res + oc * a.res_cs) * 4,
+              f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (lane_res + oc * AE().res_cs) * 4,
                                                            ((rest * NT + n) * 32 + gq * gs_res) * 4, RES_CACHE_WINO));
     };
     auto request_bias = [&]() {
@@ -357,6 +414,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
     else step(std::false_type(), std::true_type(), std::false_type(), H0(), patch_n, 0, wsc, s0 + 4);
     __builtin_amdgcn_sched_barrier(0);
     if (stamp && ns_ < 60) a.dbg[ns_++] = clock64();
+    bool to1 = false;      // GROUP: this item is the workgroup's last of problem 0 and one of problem 1 follows
+    if constexpr (GROUP && LAST) to1 = more && ix_c == 0 && nw >= total0;
 
     // ---- item epilogue: x-fold with A4^T in registers (even output columns from the sums, odd ones from the
     // differences), y-fold across the waves through LDS in two rounds
@@ -443,7 +502,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
               asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(o4[e]), "v"(floor_));
               o4[e] = r;
             }
-            char* ub = reinterpret_cast<char*>(out_tile + (rest * NT + n) * 32 + gq * gs_out + oc * a.out_cs);   // uniform
+            char* ub = reinterpret_cast<char*>(out_tile + (rest * NT + n) * 32 + gq * gs_out + oc * AE().out_cs);   // uniform
             if (!(W24_ABLATE & 16)) __builtin_nontemporal_store(o4, reinterpret_cast<f32x4*>(ub + (unsigned)(lane_out * 4)));
             else asm volatile("" :: "v"(o4));
           }
@@ -489,11 +548,34 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
           park8(1, n, h, pk_add8(pk_fma8(p8p, d34, d12), half(acc[5][n], h)));     // o3 = (d12 + 8 d34) + m5
         }
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (GROUP) {
+        if (to1) {      // the weights' cursor enters problem 1 (scalar)
+          ix_c = 1;
+          nchunks = AC().Cin / CK;
+          cin8_c = AC().cin8;
+          tap_b = cin8_c * AC().n_tiles * 1024;
+          step_b = AC().n_tiles * 1024;
+          wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AC().w), 0, AC().groups * 24 * tap_b, 0x00020000);
+        }
+        if (more) wsn = wbase(nw);
+      }
 #pragma unroll
       for (int p = 0; p < 6; ++p) load_frag(p, wsn, 0);   // the next item's first step: round B's fold covers their latency
       __syncthreads();                        // round B is parked
       fold_store(1);
       if (stamp && ns_ < 60) a.dbg[ns_++] = clock64();
+      if constexpr (GROUP) {
+        if (to1) {      // ... and the epilogue's: once per launch, the store and residual offsets of the lanes on problem 1's map
+          ix_e = 1;
+          lane_pix = (2 * (p8 / BCOLS) + oy) * AE().Wo + 4 * (p8 % BCOLS) + 2 * oh;
+          lane_out = lane_pix * AE().out_cs + 4 * q8;
+          lane_res = lane_pix * AE().res_cs + 4 * q8;
+          gs_out = (16 / BCOLS) * AE().Wo * AE().out_cs;
+          gs_res = (16 / BCOLS) * AE().Wo * AE().res_cs;
+          has_res = AE().res != nullptr;
+          floor_ = AE().relu ? 0.f : -__builtin_inff();
+        }
+      }
     }
     wsc = wsn;
     c0 = LAST ? 0 : c0 + CK;
@@ -512,6 +594,16 @@ __global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, 
   if (stamp) a.dbg[63] = ns_;
 }
 
+template <int NT, int TW, bool ONE = false>
+__global__ __launch_bounds__(256, 1) void conv_wino24b_kernel(const ConvArgs a, const ConvWork wk) {
+  wino24b_body<NT, TW, ONE, false>(&a, &wk);
+}
+// two problems of the <NT, TW, false> instantiation in one launch (launch_conv_group)
+template <int NT, int TW>
+__global__ __launch_bounds__(256, 1) void conv_wino24b_group_kernel(const ConvGroup g) {
+  wino24b_body<NT, TW, false, true>(g.a, g.wk);
+}
+
 // item width of conv_wino24b_kernel for the shapes it takes (conv_rules.h takes_wino24b), else 0: everything else stays on
 // conv_wino24_kernel; ACRMI_WINO24B=0 / cfg 840 keep the old frame
 static int wino24b_ok(const ConvArgs& a) {
@@ -526,17 +618,46 @@ static constexpr size_t wino24b_lds(int NT, int TW) {      // two patches (row s
 static_assert(wino24b_lds(2, 32) <= 160 * 1024 && wino24b_lds(2, 16) <= 160 * 1024, "patches + exchange area must fit the 160 KiB LDS");
 // (plain functions, not a template over NT / TW: referenced only from a function template, hipcc left the host-side handles
 //  of the kernel instantiations undefined)
-static hipError_t launch_wino24b_impl(const ConvArgs& a, hipStream_t s, int NT, int TW, const ConvKernel& k) {
-  // (the packed weights pad Cout to whole 64-cout blocks: a.n_tiles may count a tile of zeros)
-  return launch_conv_kernel(k, 256, wino24b_lds(NT, TW), a.Wo / TW, a.Ho / wino24b_th(TW), (a.Cout / 32) / NT, a, s);
-}
-static hipError_t launch_wino24b(const ConvArgs& a, int tw, hipStream_t s) {
+// the instantiation that takes `a` (tw = wino24b_ok(a)), with its n-tiles per wave and item width; false: none
+struct Wino24bPick {
+  ConvKernel k;
+  int NT, TW;
+};
+static bool wino24b_pick(const ConvArgs& a, int tw, Wino24bPick& p) {
   const bool one = a.Cin == 32;
   if (a.Cout % 64 == 0) {
-    if (tw == 16) return one ? hipErrorInvalidValue : launch_wino24b_impl(a, s, 2, 16, CONV_KERNEL(conv_wino24b_kernel<2, 16>));
-    return one ? launch_wino24b_impl(a, s, 2, 32, CONV_KERNEL(conv_wino24b_kernel<2, 32, true>))
-               : launch_wino24b_impl(a, s, 2, 32, CONV_KERNEL(conv_wino24b_kernel<2, 32>));
+    if (tw == 16) {
+      if (one) return false;
+      p = Wino24bPick{CONV_KERNEL(conv_wino24b_kernel<2, 16>), 2, 16};
+    } else if (one) {
+      p = Wino24bPick{CONV_KERNEL(conv_wino24b_kernel<2, 32, true>), 2, 32};
+    } else {      // HRNet branches 1 and 2 at large batches: the instantiation with a group form
+      p = Wino24bPick{CONV_KERNEL_GROUPED((conv_wino24b_kernel<2, 32>), (conv_wino24b_group_kernel<2, 32>)), 2, 32};
+    }
+    return true;
   }
-  return one ? launch_wino24b_impl(a, s, 1, 32, CONV_KERNEL(conv_wino24b_kernel<1, 32, true>))
-             : launch_wino24b_impl(a, s, 1, 32, CONV_KERNEL(conv_wino24b_kernel<1, 32>));
+  p = one ? Wino24bPick{CONV_KERNEL(conv_wino24b_kernel<1, 32, true>), 1, 32} : Wino24bPick{CONV_KERNEL(conv_wino24b_kernel<1, 32>), 1, 32};
+  return true;
+}
+static ConvProblem wino24b_problem(const ConvArgs& a, const Wino24bPick& p) {
+  // (the packed weights pad Cout to whole 64-cout blocks: a.n_tiles may count a tile of zeros)
+  return ConvProblem{a, a.Wo / p.TW, a.Ho / wino24b_th(p.TW), (a.Cout / 32) / p.NT};
+}
+static hipError_t launch_wino24b(const ConvArgs& a, int tw, hipStream_t s) {
+  Wino24bPick p;
+  if (!wino24b_pick(a, tw, p)) return hipErrorInvalidValue;
+  const ConvProblem pr = wino24b_problem(a, p);
+  return launch_conv_kernel(p.k, 256, wino24b_lds(p.NT, p.TW), &pr, 1, s);
+}
+// n problems that wino24b_pick sends to ONE instantiation with a group form, as one launch
+static hipError_t launch_wino24b_group(const ConvArgs* a, const int* tw, int n, hipStream_t s) {
+  Wino24bPick p0;
+  ConvProblem pr[CONV_GROUP_MAX];
+  if (n < 1 || n > CONV_GROUP_MAX || !wino24b_pick(a[0], tw[0], p0)) return hipErrorInvalidValue;
+  for (int i = 0; i < n; ++i) {
+    Wino24bPick p;
+    if (!wino24b_pick(a[i], tw[i], p) || p.k.fn != p0.k.fn) return hipErrorInvalidValue;
+    pr[i] = wino24b_problem(a[i], p);
+  }
+  return launch_conv_kernel(p0.k, 256, wino24b_lds(p0.NT, p0.TW), pr, n, s);
 }

@@ -102,6 +102,12 @@ std::recursive_mutex& launch_mutex();
 // returns hipSuccess or the launch error; cout tiles etc. derived inside
 hipError_t launch_conv(ConvArgs a, hipStream_t s);
 hipError_t launch_conv_h16(ConvArgs a, hipStream_t s);   // called by launch_conv when a.dtype != ACRMI_DT_F32
+// Two INDEPENDENT convolutions that launch_conv routes to one kernel instantiation with a group form (conv_frame.h ConvGroup;
+// today conv_wino24b_kernel<2, 32>) as ONE launch: the second's work items follow the first's inside the persistent
+// workgroups, so its start-up and one launch boundary are not paid.  Each output is bit-identical to its own launch's.
+// conv_can_group asks the routing; launch_conv_group with n = 1 is launch_conv, with a pair that cannot share a launch an error.
+bool conv_can_group(const ConvArgs& a, const ConvArgs& b);
+hipError_t launch_conv_group(const ConvArgs* a, int n, hipStream_t s);
 const char* conv_kernel_name(const ConvArgs& a);
 void conv_force_cfg(int cfg);
 void conv_set_debug(long long* dbg);

@@ -93,6 +93,39 @@ def conv2d(x, weight, bias=None, stride=1, relu=False, residual=None, groups=1, 
     return out
 
 
+def conv2d_group(problems):
+    """Up to two INDEPENDENT 3x3 stride-1 convolutions on the F(2x4,3x3) kernel as ONE launch (acrmi_conv2d_group): the
+    second problem's work items follow the first's inside the persistent workgroups.  problems: dicts with x (NHWC fp32
+    [B,H,W,cs] on the device) and weight ([Cout, Cin, 3, 3]), optionally bias, relu, residual ([B,H,W,rcs]) and frame_bias
+    ([B, >= Cout rounded up to 64]).  Returns the outputs; each is bit-identical to conv2d(..., algo='winograd24').  Two
+    problems that do not run on one kernel instantiation with a group form raise (there is no pair of launches instead)."""
+    arr = (_lib.ConvProblem * len(problems))()
+    outs, keep = [], []
+    for q, pr in zip(arr, problems):
+        x, residual, frame_bias = pr['x'], pr.get('residual'), pr.get('frame_bias')
+        _need_cuda(x, residual, frame_bias)
+        w = pr['weight']
+        w = w.detach().cpu().numpy() if hasattr(w, 'detach') else np.asarray(w)
+        cout, cin, k, _ = w.shape
+        if k != 3:
+            raise ValueError('conv2d_group takes 3x3 stride-1 convolutions')
+        b = pr.get('bias')
+        b = np.zeros(cout, np.float32) if b is None else (b.detach().cpu().numpy() if hasattr(b, 'detach') else np.asarray(b))
+        wp, bp = pack_conv(winograd24_weights(w.astype(np.float64)), b)
+        wp, bp = torch.from_numpy(wp).to(x.device), torch.from_numpy(bp).to(x.device)
+        B, H, W, cs = x.shape
+        out = torch.zeros(B, H, W, (cout + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+        bias_t, fstride = (bp, 0) if frame_bias is None else (frame_bias.contiguous(), frame_bias.shape[-1])
+        keep += [wp, bp, bias_t]
+        q.in_, q.w_packed, q.bias, q.res, q.out = [t.data_ptr() if t is not None else None for t in (x, wp, bias_t, residual, out)]
+        q.B, q.H, q.W, q.in_cs, q.in_coff, q.cin = B, H, W, cs, 0, cin
+        q.bias_frame_stride, q.res_cs, q.res_coff = fstride, (residual.shape[-1] if residual is not None else 0), 0
+        q.out_cs, q.out_coff, q.cout, q.ksize, q.stride, q.relu, q.groups, q.algo = out.shape[-1], 0, cout, 3, 1, int(bool(pr.get('relu'))), 1, 4
+        outs.append(out)
+    _lib.check(_lib.lib().acrmi_conv2d_group(arr, len(problems), _s(problems[0]['x'])))
+    return outs
+
+
 def conv2d_splitk(x, weight, bias=None, splits=2, relu=False, residual=None, in_coff=0, out=None, out_coff=0, out_cs=None,
                   workspace=None):
     """3x3 stride-1 convolution as Winograd F(2x2,3x3) with the input channels split into `splits` slices that run as

@@ -311,6 +311,21 @@ int acrmi_conv2d(const float* in, int B, int H, int W, int in_cs, int in_coff, i
                  const float* bias, int bias_frame_stride, const float* res, int res_cs, int res_coff,
                  float* out, int out_cs, int out_coff, int cout, int ksize, int stride, int relu, int groups,
                  int algo, void* stream);
+/* Up to two INDEPENDENT fp32 convolutions as ONE launch: problem 1's work items follow problem 0's inside the persistent
+ * workgroups, so the second start-up and one launch boundary are not paid.  The fields are acrmi_conv2d's arguments.  n = 1 is
+ * acrmi_conv2d; n = 2 needs two problems that the library routes to one kernel instantiation with a group form (today: algo 4,
+ * 3x3 stride 1, Cin >= 64 and % 32 == 0, Cout % 64 == 0, maps of whole 8x32-pixel tiles), else ACRMI_EINVAL - never two quiet
+ * launches.  No output may be read or written by the other problem.  Each output is bit-identical to acrmi_conv2d's. */
+typedef struct acrmi_conv_problem {
+  const float* in;
+  const float* w_packed;
+  const float* bias;
+  const float* res;
+  float* out;
+  int32_t B, H, W, in_cs, in_coff, cin, bias_frame_stride, res_cs, res_coff, out_cs, out_coff, cout, ksize, stride, relu,
+      groups, algo, reserved;
+} acrmi_conv_problem;
+int acrmi_conv2d_group(const acrmi_conv_problem* problems, int n, void* stream);
 /* The convolution of a 16-bit program (acr/model.py:33-37, the autocast branch): in / res / out point at f16 (dtype =
  * ACRMI_DT_F16) or bf16 (ACRMI_DT_BF16) NHWC tensors, strides / offsets / channel counts in elements (strides multiples
  * of 8), w_packed = packer.pack_conv_h16(w, b, dtype) (BN-folded filters rounded once to the storage type, A fragments
@@ -839,6 +854,10 @@ int acrmi_point_heads_multi(acrmi_ctx* ctx, int B, int max_hand, void* stream);
  * At a small batch (<= 32 frames) the times are also kept in the context (per head mode) as the input of
  * ACRMI_OPT_LANE_PLAN; they change how later calls are scheduled only after that option has been switched on. */
 int acrmi_profile_ops(acrmi_ctx* ctx, const uint8_t* img_dev, int B, float* ms_out, int n_ms, void* stream);
+/* Diagnostic: the grouped launches (acrmi_conv2d_group's launch, formed by the executor between independent convolutions of one
+ * kernel instantiation; csrc/group_plan.h) in the schedule a call at batch B replays; < 0 on error.  Programs of contexts with
+ * max_batch >= 16 only, and none with ACRMI_GROUP=0 in the environment / after acrmi_tune(5, 0). */
+int acrmi_program_groups(acrmi_ctx* ctx, int B);
 
 /* A non-blocking HIP stream on `device` / its release - for hosts without a stream API of their own (the Python
  * package runs the contexts of an EnginePool on these instead of torch's pooled streams). */
@@ -850,7 +869,8 @@ int acrmi_stream_destroy(void* stream);
  * the launchers in csrc/conv_mfma.hip, conv_wino2.inc, conv_wino3.inc, conv_ws2.inc - e.g. 806 large-batch item shapes
  * at any batch, 837 the 16x32 wave tile of conv_wino3b_kernel, 839 no store waves); key 1: cycle stamps of
  * workgroup 0 on/off; key 2: print them; key 3: loader-wave switches (8 idle loader - wrong results, 9 priority 0);
- * key 4: XCD-banded item order on/off. */
+ * key 4: XCD-banded item order on/off; key 5: grouped launches on/off in the programs set from now on (default on; the
+ * environment variable ACRMI_GROUP=0, read when the library loads, starts with off). */
 int acrmi_tune(int key, int value);
 
 #ifdef __cplusplus

@@ -3,6 +3,9 @@
 
     python tools/conv_bench.py [--cfg N] [--batch 64] [--filter 3x3]
 Prints one line per shape: avg ms over `--iters` launches and algorithmic TFLOP/s.
+    python tools/conv_bench.py --group [--stamps]
+times HRNet's branch-1 and branch-2 3x3 convs (64->64 @64, 128->128 @32) each alone, as two launches back to back, and as ONE
+grouped launch (ops.conv2d_group; csrc/conv_frame.h ConvGroup).
 """
 import argparse
 import ctypes as C
@@ -49,6 +52,52 @@ SHAPES = [
 ]
 
 
+def group_mode(args, L, lib):
+    """A alone, B alone, A then B (two launches) and the group A + B (one launch), `--iters` times each in a loop on one stream;
+    --stamps: the cycle stamps of workgroup 0 for B alone and for the group (its first item lies in A)."""
+    packer = importlib.import_module(PKG + '.packer')
+    B = args.batch
+    p = lambda t: t.data_ptr() if t is not None else None
+    arr = (L.ConvProblem * 2)()
+    keep = []
+    for q, (cin, cout, H, W) in zip(arr, ((64, 64, 64, 64), (128, 128, 32, 32))):
+        x = torch.randn(B, H, W, cin, device='cuda')
+        res = torch.randn(B, H, W, cout, device='cuda')
+        out = torch.empty(B, H, W, cout, device='cuda')
+        w = (np.random.randn(cout, cin, 3, 3) / np.sqrt(cin * 9)).astype(np.float32)
+        wp, bp = (torch.from_numpy(t).cuda() for t in packer.pack_conv(packer.winograd24_weights(w), np.zeros(cout, np.float32)))
+        keep += [x, res, out, wp, bp]
+        q.in_, q.w_packed, q.bias, q.res, q.out = p(x), p(wp), p(bp), p(res), p(out)
+        q.B, q.H, q.W, q.in_cs, q.in_coff, q.cin = B, H, W, cin, 0, cin
+        q.bias_frame_stride, q.res_cs, q.res_coff = 0, cout, 0
+        q.out_cs, q.out_coff, q.cout, q.ksize, q.stride, q.relu, q.groups, q.algo = cout, 0, cout, 3, 1, 1, 1, 4
+
+    def launch(first, n):
+        rc = lib.acrmi_conv2d_group(C.byref(arr[first]), n, None)
+        assert rc == 0, lib.acrmi_last_error(None)
+    forms = (('A  64->64 @64 alone', lambda: launch(0, 1)), ('B  128->128 @32 alone', lambda: launch(1, 1)),
+             ('A, B: two launches', lambda: (launch(0, 1), launch(1, 1))), ('A + B: one grouped launch', lambda: launch(0, 2)))
+    for rep in range(args.reps):
+        for name, fn in forms:
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            print('%-28s %8.4f ms' % (name, e0.elapsed_time(e1) / args.iters), flush=True)
+    if args.stamps:
+        for name, fn in forms[1:2] + forms[3:]:
+            print(name)
+            lib.acrmi_tune(1, 1)
+            fn()
+            lib.acrmi_tune(2, 0)
+            lib.acrmi_tune(1, 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', type=int, default=-1)
@@ -64,12 +113,16 @@ def main():
     ap.add_argument('--h16', default='', help="'fp16' | 'bf16': the 16-bit direct kernels (conv_h16.hip) on 16-bit tensors")
     ap.add_argument('--phase', type=int, default=0, help='loader-wave tuning switch: 8 = idle loader (timing ablation, wrong results), 9 = loader at priority 0')
     ap.add_argument('--stamps', action='store_true', help='print clock64 deltas of workgroup 0 (ws kernel)')
+    ap.add_argument('--group', action='store_true', help='branch-1 / branch-2 3x3 convs alone, back to back and as one grouped launch')
+    ap.add_argument('--reps', type=int, default=3, help='--group: rounds of the four timings')
     args = ap.parse_args()
     L = importlib.import_module(PKG + '._lib')
     packer = importlib.import_module(PKG + '.packer')
     lib = L.lib()
     lib.acrmi_tune(0, args.cfg)
     lib.acrmi_tune(3, args.phase)
+    if args.group:
+        return group_mode(args, L, lib)
     B = args.batch
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     for name, cin, cout, H, W, k, stride, groups, use_res in SHAPES:
