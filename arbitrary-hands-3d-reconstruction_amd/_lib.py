@@ -94,7 +94,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_overlay_regions', 'acrmi_decode_multi', 'acrmi_decode_maps_multi', 'acrmi_forward_multi',
            'acrmi_tracks_create', 'acrmi_tracks_destroy', 'acrmi_tracks_reset', 'acrmi_associate', 'acrmi_forward_tracks',
            'acrmi_assoc_step', 'acrmi_point_heads_multi', 'acrmi_contact_workspace', 'acrmi_mesh_contact', 'acrmi_contact',
-           'acrmi_conv2d_group', 'acrmi_program_groups']
+           'acrmi_conv2d_group', 'acrmi_program_groups', 'acrmi_surface_contact_workspace', 'acrmi_mesh_surface_contact',
+           'acrmi_surface_contact']
 
 _lib = None
 
@@ -237,10 +238,16 @@ def lib():
     L.acrmi_mesh_contact.argtypes = [f32p, f32p, i32, i32, i32, vp, vp, vp, vp, vp, i32, C.c_float, C.c_float, vp, f32p, f32p,
                                      f32p, vp, vp, vp]
     L.acrmi_contact.argtypes = [vp, f32p, f32p, f32p, i32, i32, vp, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp, vp]
+    L.acrmi_surface_contact_workspace.argtypes = [i32, i32, i32]
+    L.acrmi_surface_contact_workspace.restype = C.c_size_t
+    L.acrmi_mesh_surface_contact.argtypes = [f32p, f32p, i32, i32, i32, vp, vp, vp, vp, i32, C.c_float, C.c_float, vp, f32p, f32p,
+                                             vp, f32p, vp, vp, vp]
+    L.acrmi_surface_contact.argtypes = [vp, f32p, f32p, f32p, i32, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, f32p, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
-                        'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy', 'acrmi_contact_workspace'):
+                        'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy', 'acrmi_contact_workspace',
+                        'acrmi_surface_contact_workspace'):
             fn.restype = C.c_int
     _lib = L
     return L

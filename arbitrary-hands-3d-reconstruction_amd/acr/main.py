@@ -300,9 +300,12 @@ class ACR(object):
         indices within ops.CONTACT_DIST of that hand's nearest vertex; 'penetration' - metres, the depth estimate of the
         hand's vertices inside the partner.  A nearest-vertex heuristic on two independently placed meshes, not a measurement.
         Pairs are formed inside a row only: hands of different frames - and, with boxes=, of different regions, each of
-        which has its own camera - are never paired."""
-        if not isinstance(contact, bool):
-            raise ValueError('contact must be True or False, not %r' % (contact,))
+        which has its own camera - are never paired.
+        contact='surface' (DESIGN.md section 20): the same four keys from the surface measure (Engine.contact(mode='surface')):
+        'contact_dist' - metres between the two SURFACES, the square root of the smaller min_d2 of the pair's two directions;
+        'contact_verts' - the hand's own vertices within ops.CONTACT_DIST of the partner's surface; 'penetration' - metres,
+        the largest distance to the partner's surface among the hand's own vertices inside it (ray crossings)."""
+        _check_contact(contact)
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
@@ -380,7 +383,7 @@ class ACR(object):
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(*out['slots'].shape[:-1], 3)
         if contact:
-            _add_contact(eng, out, K)
+            _add_contact(eng, out, K, 'surface' if contact == 'surface' else 'vertex')
         return results_from_out(out, paths), eng, out
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
@@ -469,27 +472,36 @@ def _check_multi_point_heads(value):
         raise ValueError('multi_point_heads must be True or False, not %r' % (value,))
 
 
-def _add_contact(eng, out, K):
+def _check_contact(value):
+    if not isinstance(value, bool) and not (isinstance(value, str) and value == 'surface'):
+        raise ValueError("contact must be True, False or 'surface', not %r" % (value,))
+
+
+def _add_contact(eng, out, K, mode='vertex'):
     """out['contact'] = Engine.contact of `out` at the package's default parameters, with the parameters beside it."""
     from .. import ops
-    out['contact'] = dict(eng.contact(out, max_hand=K, cam_trans=out['cam_trans']), contact_dist=ops.CONTACT_DIST,
+    kw = {} if mode == 'vertex' else {'mode': mode}
+    out['contact'] = dict(eng.contact(out, max_hand=K, cam_trans=out['cam_trans'], **kw), contact_dist=ops.CONTACT_DIST,
                           max_depth=ops.CONTACT_MAX_DEPTH)
 
 
 def _contact_keys(con, b, k, h, K, index_of):
     """The four contact keys of hand (row b, rank k, side h): its partner is the flagged hand of the other side in the row whose
     pair has the smallest min_d2, the lower rank on a tie.  con: out['contact'] as host arrays; index_of: (rank, side) -> the
-    index in the row's list."""
+    index in the row's list.  The surface measure (con has 'face', min_d2 is [n,2]): a pair's distance is the smaller min_d2 of
+    its two directions; the hand's own direction is h."""
+    surface = 'face' in con
     best, rank, pair = np.float32(np.inf), -1, -1
     for q in range(K):
         p = (b * K + k) * K + q if h == 0 else (b * K + q) * K + k
-        if con['min_d2'][p] < best:
-            best, rank, pair = con['min_d2'][p], q, p
+        d = con['min_d2'][p].min() if surface else con['min_d2'][p]
+        if d < best:
+            best, rank, pair = d, q, p
     if pair < 0:
         return {'contact_dist': np.float32(np.inf), 'contact_with': np.int32(-1), 'contact_verts': np.zeros(0, np.int32),
                 'penetration': np.float32(0)}
     r = np.float32(con['contact_dist'])
-    touching = (con['nn'][pair, h] >= 0) & (con['d2'][pair, h] <= r * r)
+    touching = (con['face' if surface else 'nn'][pair, h] >= 0) & (con['d2'][pair, h] <= r * r)
     return {'contact_dist': np.sqrt(best, dtype=np.float32), 'contact_with': np.int32(index_of.get((rank, 1 - h), -1)),
             'contact_verts': np.nonzero(touching)[0].astype(np.int32),
             'penetration': np.sqrt(con['depth2'][pair, h], dtype=np.float32)}
@@ -591,8 +603,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     different regions are never paired, also when the regions lie in one frame."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
-    if not isinstance(contact, bool):
-        raise ValueError('contact must be True or False, not %r' % (contact,))
+    _check_contact(contact)
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:

@@ -2,6 +2,7 @@
 // (program replay: acrmi_program.hip; stand-alone operators: acrmi_ops.hip; RCCL: acrmi_comm.hip).
 #include "acrmi_ctx.h"
 #include "contact_plan.h"
+#include "surface_contact_plan.h"
 
 std::string g_err;
 
@@ -78,6 +79,7 @@ void acrmi_destroy(acrmi_ctx* c) {
   acrmi_streams_destroy(c->own_streams);
   if (c->render_ws) (void)hipFree(c->render_ws);
   if (c->contact_ws) (void)hipFree(c->contact_ws);
+  if (c->surface_ws) (void)hipFree(c->surface_ws);
   if (c->region_hand_frame) (void)hipFree(c->region_hand_frame);
   for (int32_t* p : c->faces_topo)
     if (p) (void)hipFree(p);
@@ -984,6 +986,52 @@ int acrmi_contact(acrmi_ctx* c, const float* verts, const float* cam_trans, cons
   a.n_meshes = (int)(2 * n); a.n_verts = 778; a.n_faces = c->n_faces[0]; a.n_pairs = (int)n_pairs;
   e = launch_contact(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "acrmi_contact: %s", hipGetErrorString(e));
+}
+
+// The surface measure of the same pairs (csrc/surface_contact.hip): the prep kernel of acrmi_contact forms them from the slot
+// flags; the scratch is the context's own ([pairs | mesh_topo | sign] as above, then the P and face records of the 2n meshes).
+int acrmi_surface_contact(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, int K,
+                          float contact_dist, float max_depth, int32_t* face, float* d2, float* point, int32_t* cross, float* sum_f,
+                          int32_t* sum_i, void* stream) {
+  if (!c || !verts || !cam_trans || !slots || !face || !d2 || !point || !cross || !sum_f || !sum_i || B <= 0)
+    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: bad arguments");
+  if (K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: max_hand %d outside 1..%d", K, ACRMI_MAX_HAND);
+  if (!contact_params_ok(contact_dist, max_depth))
+    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
+  if (!c->faces_topo[0] || !c->faces_topo[1])
+    return fail(c, ACRMI_ESTATE, "acrmi_surface_contact: MANO faces not loaded (acrmi_load_faces)");
+  const int F = c->n_faces[0];
+  if (c->n_faces[1] != F || F > SURFACE_MAX_FACES)
+    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: the two sides have %d and %d faces (equal counts, at most %d)", F,
+                c->n_faces[1], SURFACE_MAX_FACES);
+  const long long n = (long long)B * K, n_pairs = n * K;
+  if (2 * n > 0x7fffffffll || n_pairs > 0x7fffffffll || !surface_plan((int)(2 * n), 778, F, (int)n_pairs).ok)
+    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: %d frames of %d x %d pairs are beyond 2^31 - 1 elements", B, K, K);
+  ON_DEVICE(c);
+  if (n > c->surface_ws_hands || F != c->surface_ws_faces) {
+    if (c->surface_ws) {
+      HIPCHK(c, hipDeviceSynchronize());
+      (void)hipFree(c->surface_ws);
+      c->surface_ws = nullptr;
+      c->surface_ws_hands = 0;
+    }
+    HIPCHK(c, hipMalloc(&c->surface_ws, contact_head_bytes(n) + surface_workspace_bytes((int)(2 * n), 778, F)));
+    c->surface_ws_hands = n;
+    c->surface_ws_faces = F;
+  }
+  int32_t* pairs = (int32_t*)c->surface_ws;
+  int32_t* mesh_topo = pairs + 2 * n_pairs;
+  int32_t* sign = mesh_topo + 2 * n;
+  hipError_t e = launch_contact_prep(slots, B, K, 1, 1, pairs, mesh_topo, sign, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "acrmi_surface_contact: prep: %s", hipGetErrorString(e));
+  SurfaceContactArgs a{};
+  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1]; a.mesh_topo = mesh_topo;
+  a.pairs = pairs; a.contact_dist = contact_dist; a.max_depth = max_depth;
+  a.face = face; a.d2 = d2; a.point = point; a.cross = cross; a.sum_f = sum_f; a.sum_i = sum_i;
+  a.ws = (float4*)(c->surface_ws + contact_head_bytes(c->surface_ws_hands));
+  a.n_meshes = (int)(2 * n); a.n_verts = 778; a.n_faces = F; a.n_pairs = (int)n_pairs;
+  e = launch_surface_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "acrmi_surface_contact: %s", hipGetErrorString(e));
 }
 
 // ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------

@@ -132,6 +132,9 @@ struct acrmi_ctx {
   int contact_sign[2] = {1, 1};
   char* contact_ws = nullptr;
   long long contact_ws_hands = 0;      // B * K it holds
+  char* surface_ws = nullptr;          // acrmi_surface_contact's scratch (csrc/surface_contact_plan.h), grown on demand
+  long long surface_ws_hands = 0;      // B * K it holds
+  int surface_ws_faces = 0;            // ... of meshes with this many faces
   int last_batch = 0;          // batch of the last program run: whose centre maps the head buffers hold (acrmi_overlay)
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;

@@ -1,6 +1,7 @@
 // libacrmi.so: the stand-alone operators of the C ABI (unit tests / callers with their own tensors; no context).
 #include "acrmi_ctx.h"
 #include "contact_plan.h"
+#include "surface_contact_plan.h"
 #include "conv_frame.h"   // conv_shape
 #include "roi_plan.h"
 #include "track_plan.h"
@@ -760,6 +761,42 @@ int acrmi_mesh_contact(const float* verts_dev, const float* trans_dev, int n_mes
   a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_pairs = n_pairs;
   hipError_t e = launch_contact(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_mesh_contact: %s", hipGetErrorString(e));
+}
+
+// ---- the surface contact measure between meshes (csrc/surface_contact.hip, csrc/surface_contact_plan.h) ----
+size_t acrmi_surface_contact_workspace(int n_meshes, int n_verts, int n_faces) {
+  return surface_workspace_bytes(n_meshes, n_verts, n_faces);
+}
+
+int acrmi_mesh_surface_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                               const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                               const int32_t* pairs_dev, int n_pairs, float contact_dist, float max_depth, int32_t* face_dev,
+                               float* d2_dev, float* point_dev, int32_t* cross_dev, float* sum_f_dev, int32_t* sum_i_dev,
+                               void* ws_dev, void* stream) {
+  const char* who = "acrmi_mesh_surface_contact";
+  if (n_meshes <= 0 || n_verts <= 0 || n_faces <= 0 || n_pairs < 0)
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d meshes, %d vertices, %d faces, %d pairs)", who, n_meshes, n_verts, n_faces,
+                n_pairs);
+  if (n_verts > CONTACT_MAX_VERTS || n_faces > SURFACE_MAX_FACES)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d vertices and %d faces, at most %d and %d", who, n_verts, n_faces, CONTACT_MAX_VERTS,
+                SURFACE_MAX_FACES);
+  if (!contact_params_ok(contact_dist, max_depth))
+    return fail(nullptr, ACRMI_EINVAL, "%s: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)", who);
+  if (n_pairs == 0) return ACRMI_OK;
+  if (!verts_dev || !topo_dev || !pairs_dev || !face_dev || !d2_dev || !point_dev || !cross_dev || !sum_f_dev || !sum_i_dev || !ws_dev)
+    return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)ws_dev & 15) != 0) return fail(nullptr, ACRMI_EINVAL, "%s: the workspace is not 16-byte aligned", who);
+  if (!surface_plan(n_meshes, n_verts, n_faces, n_pairs).ok)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d pairs of %d vertices (or %d meshes of %d faces) are beyond 2^31 - 1 elements", who,
+                n_pairs, n_verts, n_meshes, n_faces);
+  SurfaceContactArgs a{};
+  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
+  a.pairs = pairs_dev; a.contact_dist = contact_dist; a.max_depth = max_depth;
+  a.face = face_dev; a.d2 = d2_dev; a.point = point_dev; a.cross = cross_dev; a.sum_f = sum_f_dev; a.sum_i = sum_i_dev;
+  a.ws = (float4*)ws_dev;
+  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_pairs = n_pairs;
+  hipError_t e = launch_surface_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 
 // ---- key-point skeleton and heat-map views (csrc/overlay.hip) ----

@@ -488,6 +488,24 @@ hipError_t launch_contact(const ContactArgs& a, hipStream_t s);
 hipError_t launch_contact_prep(const float* slots, int B, int K, int sign_left, int sign_right, int32_t* pairs, int32_t* mesh_topo,
                                int32_t* sign, hipStream_t s);
 
+// The surface contact measure between meshes (csrc/surface_contact.hip, csrc/surface_contact_plan.h).
+struct SurfaceContactArgs {
+  const float* verts;            // [M, n_verts, 3]
+  const float* trans;            // [M, 3] or null
+  const int32_t* topo[2];        // mesh topology blobs on the device; [1] may be null
+  const int32_t* mesh_topo;      // [M] 0 / 1 = which blob, or null (all 0)
+  const int32_t* pairs;          // [n_pairs, 2] mesh indices; outside [0, M): the pair is skipped
+  float contact_dist, max_depth;
+  int32_t *face, *cross;         // [n_pairs, 2, n_verts]
+  float* d2;                     // [n_pairs, 2, n_verts]
+  float* point;                  // [n_pairs, 2, n_verts, 3]
+  float* sum_f;                  // [n_pairs, SURFACE_SUM_F]
+  int32_t* sum_i;                // [n_pairs, SURFACE_SUM_I]
+  float4* ws;                    // surface_workspace_bytes(M, n_verts, n_faces), 16-byte aligned
+  int n_meshes, n_verts, n_faces, n_pairs;
+};
+hipError_t launch_surface_contact(const SurfaceContactArgs& a, hipStream_t s);
+
 // Key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views").
 struct SkeletonArgs {
   const float* kps;              // [n_hands, 21, 2] MANO joint order; pixels of the image, or (normalized) [-1, 1] of the 512 canvas

@@ -848,7 +848,8 @@ class Engine(object):
         return self._overlay(out, src, B, 'images', what, 'pj2d' if offsets is None else 'pj2d_org', self._frame_offsets(offsets, B),
                              None, bgr, dst, stream)
 
-    def contact(self, out, max_hand=1, cam_trans=None, contact_dist=None, max_depth=None, focal_length=1265., stream=None):
+    def contact(self, out, max_hand=1, cam_trans=None, contact_dist=None, max_depth=None, focal_length=1265., stream=None,
+                mode='vertex'):
         """Contact and interpenetration between the left and the right hands of every row of `out` (what `forward(...,
         project=True[, max_hand=K])` returned) on the GPU (acrmi_contact): the nearest-vertex half-space
         heuristic - not a point-to-triangle distance, not a true inside test - on the two meshes placed by their cam_trans,
@@ -859,7 +860,12 @@ class Engine(object):
         obtains it - the caller's, out['cam_trans'], or computed from out['joints'] / out['pj2d'].  contact_dist / max_depth:
         metres, defaults ops.CONTACT_DIST / ops.CONTACT_MAX_DEPTH (parameters, not measurements).  The orientation signs:
         `contact_sign` / set_contact_sign.  Returns what ops.mesh_contact returns, for the B*K*K pairs; direction 0 = the left
-        hand's vertices.  stream: as `forward`."""
+        hand's vertices.  stream: as `forward`.
+        mode='surface' (acrmi_surface_contact): the same pairs by the surface measure - the distance
+        from every vertex to the other hand's surface, the point on it, and containment by ray crossings - and what
+        ops.mesh_surface_contact returns.  It has no orientation sign.  Any other mode is a ValueError."""
+        if mode not in ('vertex', 'surface'):
+            raise ValueError("mode must be 'vertex' or 'surface', not %r" % (mode,))
         K = check_max_hand(max_hand)
         slots = out['slots']
         B = slots.shape[0]
@@ -874,6 +880,13 @@ class Engine(object):
             cam_trans = cam_trans.reshape(B * K, 2, 3)
         cam_trans = self._cam_trans(flat, cam_trans, B * K, focal_length, st)
         verts, slots = out['verts'].contiguous(), slots.contiguous()
+        if mode == 'surface':
+            raw = ops_mod.surface_contact_outputs(B * K * K, 778, self.device)
+            _lib.check(self.L.acrmi_surface_contact(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, contact_dist,
+                                                    max_depth, _ptr(raw['face']), _ptr(raw['d2']), _ptr(raw['point']),
+                                                    _ptr(raw['cross']), _ptr(raw['sum_f']), _ptr(raw['sum_i']), st), self.ctx)
+            self._contact_keep = (verts, slots, cam_trans)
+            return ops_mod.surface_contact_result(raw)
         raw = ops_mod.contact_outputs(B * K * K, 778, self.device)
         sign = None if self._contact_sign_set is None else (C.c_int32 * 2)(*self._contact_sign_set)
         _lib.check(self.L.acrmi_contact(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, sign, contact_dist, max_depth,

@@ -1069,6 +1069,28 @@ def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, co
     if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
         raise ValueError('verts must be [M,V,3]')
     contact_dist, max_depth = check_contact_params(contact_dist, max_depth)
+    v, t, topos, ti, pr = _contact_inputs(verts, faces, pairs, trans, topo_index)
+    dev = v.device
+    M, V, _ = v.shape
+    n, F = pr.shape[0], int(topos[2])
+    sg = None
+    if sign is not None:
+        sg = torch.as_tensor(sign).to(dev, torch.int32).contiguous()
+        if sg.numel() != M:
+            raise ValueError('sign must hold one int per mesh')
+    raw = contact_outputs(n, V, dev)
+    L = _lib.lib()
+    ws = torch.empty(int(L.acrmi_contact_workspace(M, V)) + 16, dtype=torch.uint8, device=dev)
+    ws_p = (ws.data_ptr() + 15) // 16 * 16
+    _lib.check(L.acrmi_mesh_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]), _p(ti), _p(sg), _p(pr), n,
+                                    contact_dist, max_depth, _p(raw['nn']), _p(raw['d2']), _p(raw['side']), _p(raw['sum_f']),
+                                    _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
+    return contact_result(raw)
+
+
+def _contact_inputs(verts, faces, pairs, trans, topo_index):
+    """The host checks mesh_contact and mesh_surface_contact share -> (verts, trans or None, (topology, second topology or
+    None, F), topo_index or None, pairs [n,2] int32), all on the device of verts."""
     dev = verts.device
     M, V, _ = verts.shape
     if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
@@ -1083,7 +1105,6 @@ def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, co
         pr = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev)
     if pr.dim() != 2 or pr.shape[1] != 2:
         raise ValueError('pairs must be [n,2]')
-    n = pr.shape[0]
     pair = isinstance(faces, (tuple, list)) and len(faces) == 2 and not np.isscalar(faces[0]) and np.ndim(faces[0]) >= 1
     topos = [_topology_on(t, V, dev) for t in (faces if pair else [faces])]
     head = [t[:2].tolist() for t in topos]      # (one small D2H copy per topology; [F, V])
@@ -1097,19 +1118,53 @@ def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, co
         ti = torch.as_tensor(topo_index).to(dev, torch.int32).contiguous()
         if ti.numel() != M or not pair:
             raise ValueError('topo_index needs a pair of topologies and one int per mesh')
-    sg = None
-    if sign is not None:
-        sg = torch.as_tensor(sign).to(dev, torch.int32).contiguous()
-        if sg.numel() != M:
-            raise ValueError('sign must hold one int per mesh')
-    raw = contact_outputs(n, V, dev)
+    return v, t, (topos[0], topos[1] if pair else None, F), ti, pr
+
+
+SURFACE_FACE_TILE, SURFACE_MAX_FACES = 256, 8000      # = csrc/surface_contact_plan.h
+
+
+def surface_contact_outputs(n_pairs, V, dev):
+    """The raw output tensors of acrmi_mesh_surface_contact / acrmi_surface_contact for n_pairs pairs of V vertices."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    return {'face': new((n_pairs, 2, V), torch.int32), 'd2': new((n_pairs, 2, V), torch.float32),
+            'point': new((n_pairs, 2, V, 3), torch.float32), 'cross': new((n_pairs, 2, V), torch.int32),
+            'sum_f': new((n_pairs, 4), torch.float32), 'sum_i': new((n_pairs, 8), torch.int32)}
+
+
+def surface_contact_result(raw):
+    """The raw outputs -> the dict mesh_surface_contact returns (views of the summaries, no copy, no host visit)."""
+    return {'face': raw['face'], 'd2': raw['d2'], 'point': raw['point'], 'cross': raw['cross'], 'min_d2': raw['sum_f'][:, 0:2],
+            'closest': raw['sum_i'][:, 0:4].unflatten(1, (2, 2)), 'n_contact': raw['sum_i'][:, 4:6],
+            'n_inside': raw['sum_i'][:, 6:8], 'depth2': raw['sum_f'][:, 2:4]}
+
+
+def mesh_surface_contact(verts, faces, pairs, trans=None, topo_index=None, contact_dist=CONTACT_DIST, max_depth=CONTACT_MAX_DEPTH):
+    """The surface contact measure between pairs of meshes on the GPU (acrmi_mesh_surface_contact): the
+    distance from every vertex to the other mesh's SURFACE (closest point of every triangle) and containment by the parity of
+    the crossings of the +Z ray, exact on a closed mesh.  Every vertex meets every face: it costs more than mesh_contact.
+    verts, faces, pairs, trans, topo_index, contact_dist, max_depth: as mesh_contact, with the same host checks; there is no
+    sign - the rule does not depend on the winding.  At most 4000 vertices and 8000 faces.
+    Returns device tensors, nothing is copied to the host, direction 0 = the vertices of a against b, 1 = those of b against
+    a: 'face' int32 [n,2,V] (the nearest face, -1: none), 'd2' [n,2,V] (squared distance to it), 'point' [n,2,V,3] (the point
+    on it), 'cross' int32 [n,2,V] (crossings; odd = inside); 'min_d2' [n,2] with 'closest' [n,2,2] = (i, face) per direction;
+    'n_contact', 'n_inside' int32 [n,2]; 'depth2' [n,2] = the largest d2 among the inside vertices.  A skipped pair: face -1,
+    d2 inf, point 0, cross 0, zero counts, closest (-1, -1)."""
+    _need_cuda(verts)
+    if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
+        raise ValueError('verts must be [M,V,3]')
+    contact_dist, max_depth = check_contact_params(contact_dist, max_depth)
+    v, t, topos, ti, pr = _contact_inputs(verts, faces, pairs, trans, topo_index)
+    M, V, _ = v.shape
+    n, F = pr.shape[0], int(topos[2])
+    raw = surface_contact_outputs(n, V, v.device)
     L = _lib.lib()
-    ws = torch.empty(int(L.acrmi_contact_workspace(M, V)) + 16, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(L.acrmi_surface_contact_workspace(M, V, F)) + 16, dtype=torch.uint8, device=v.device)
     ws_p = (ws.data_ptr() + 15) // 16 * 16
-    _lib.check(L.acrmi_mesh_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(sg), _p(pr), n,
-                                    contact_dist, max_depth, _p(raw['nn']), _p(raw['d2']), _p(raw['side']), _p(raw['sum_f']),
-                                    _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
-    return contact_result(raw)
+    _lib.check(L.acrmi_mesh_surface_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]), _p(ti), _p(pr), n, contact_dist,
+                                            max_depth, _p(raw['face']), _p(raw['d2']), _p(raw['point']), _p(raw['cross']),
+                                            _p(raw['sum_f']), _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
+    return surface_contact_result(raw)
 
 
 # ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------

@@ -728,6 +728,60 @@ int acrmi_contact(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans
                   float* sum_f_dev, int32_t* sum_i_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The SURFACE contact measure between two meshes (csrc/surface_contact_plan.h,
+ * csrc/surface_contact.hip): the distance from every vertex to the other mesh's surface with the point on it, and
+ * containment by counting ray crossings in a way that is exact on a closed mesh.  The measure above stays the default; this
+ * one costs every vertex against every face.  All fp32, every operation rounded on its own, `/` correctly rounded:
+ *  dot(a,b) = (ax*bx + ay*by) + az*bz; a cross component is (a*b) - (c*d); P_m[i] = verts[m,i] + trans[m] as above.
+ *  For the ordered pair (a, b), vertex p = P_a[i] and face f of b with corners A, B, C = P_b[f0], P_b[f1], P_b[f2]:
+ *  closest   point of the triangle (Ericson, Real-Time Collision Detection 5.1.5); every comparison is false on NaN, the first
+ *            true branch wins.  ab = B-A, ac = C-A, ap = p-A, d1 = dot(ab,ap), d2 = dot(ac,ap); bp = p-B, d3 = dot(ab,bp),
+ *            d4 = dot(ac,bp); cp = p-C, d5 = dot(ab,cp), d6 = dot(ac,cp); vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6,
+ *            va = d3*d6 - d5*d4; e43 = d4-d3, e56 = d5-d6.
+ *            1. d1<=0 && d2<=0: q = A.   2. d3>=0 && d4<=d3: q = B.   3. vc<=0 && d1>=0 && d3<=0: q = A + (d1/(d1-d3))*ab.
+ *            4. d6>=0 && d5<=d6: q = C.   5. vb<=0 && d2>=0 && d6<=0: q = A + (d2/(d2-d6))*ac.
+ *            6. va<=0 && e43>=0 && e56>=0: q = B + (e43/(e43+e56))*(C-B).
+ *            7. otherwise: den = 1/((va+vb)+vc), q = (A + ab*(vb*den)) + ac*(vc*den).
+ *            e = p-q, D2(i,f) = dot(e,e).  face[i] = the f with the smallest D2 below +inf, the lowest f on a tie; NaN and
+ *            +inf never win, degenerate faces need no special case; d2[i] is that value and point[i] that face's q.  When no
+ *            face qualifies: face = -1, d2 = +inf, point = 0.
+ *  crossings of the ray from p towards +Z.  For each face edge u -> v (mesh vertex indices; f0->f1, f1->f2, f2->f0): lo, hi =
+ *            the positions of min(u,v), max(u,v); E = (hi.x-lo.x)*(p.y-lo.y) - (hi.y-lo.y)*(p.x-lo.x); sc = (E >= 0) ? +1 : -1;
+ *            the edge's sign is sc when u < v, -sc when u > v, 0 when u == v.  The face covers p when its three signs are
+ *            equal and not zero.  The ray meets the face's plane in front of p when o = dot(ap, n), n = ab x ac, and n.z have
+ *            strictly opposite signs (neither zero, NaN fails).  cross[i] = the number of faces that do both; vertex i is
+ *            inside when cross[i] is odd.  The two faces that share an edge compute its value identically: exact on a closed
+ *            mesh, meaningless on an open one.
+ *  flags     per direction (surface distance is not symmetric).  IN CONTACT: face >= 0 and d2 <= r*r.  INSIDE: face >= 0,
+ *            cross odd and d2 <= m*m.
+ *  summary   sum_f = (min d2 of direction 0, of direction 1, depth2 of direction 0, of direction 1: the largest d2 among the
+ *            inside vertices, 0 when there are none); sum_i = (closest (i, face) of direction 0, of direction 1 - the lowest
+ *            i on a tie, (-1, -1) when there is none -, contact vertices of direction 0, 1, inside vertices of direction 0, 1).
+ *  skipped   a pair with a mesh index < 0 (or >= n_meshes): face = -1, d2 = +inf, point = 0, cross = 0, zero counts, (-1, -1).
+ * No cull, no atomics on global memory: deterministic; a pair computed alone equals the same pair computed in a batch.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of device workspace acrmi_mesh_surface_contact needs (0 for non-positive sizes). */
+size_t acrmi_surface_contact_workspace(int n_meshes, int n_verts, int n_faces);
+/* Arguments as acrmi_mesh_contact takes them (there is no sign: the crossing rule does not depend on the winding).  Outputs
+ * face_dev, cross_dev int32 and d2_dev fp32 [n_pairs,2,n_verts], point_dev fp32 [n_pairs,2,n_verts,3], sum_f_dev [n_pairs,4],
+ * sum_i_dev [n_pairs,8]; ws_dev: acrmi_surface_contact_workspace() bytes, 16-byte aligned, not shared by launches that may
+ * overlap.  n_verts <= 4000, n_faces <= 8000; contact_dist finite and >= 0, max_depth >= 0; n_pairs * 6 * n_verts, n_meshes *
+ * n_verts and n_meshes * n_faces * 3 at most 2^31 - 1: beyond any of these ACRMI_EINVAL, nothing is clamped.  NULL pointers
+ * and sizes are checked before any GPU call; n_pairs == 0 is success and touches nothing.  The topology blobs are trusted;
+ * the pair indices are read on the device and need not be valid. */
+int acrmi_mesh_surface_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                               const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                               const int32_t* pairs_dev, int n_pairs, float contact_dist, float max_depth, int32_t* face_dev,
+                               float* d2_dev, float* point_dev, int32_t* cross_dev, float* sum_f_dev, int32_t* sum_i_dev,
+                               void* ws_dev, void* stream);
+/* The surface measure of the pairs acrmi_contact forms (same inputs, same pair order, the context's face tables, which must
+ * have equally many faces on both sides); outputs as acrmi_mesh_surface_contact with n_pairs = B*K*K, n_verts = 778.  Its
+ * scratch is the context's own, allocated at the first call (and when B*K grows); otherwise asynchronous on `stream`. */
+int acrmi_surface_contact(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int B,
+                          int K, float contact_dist, float max_depth, int32_t* face_dev, float* d2_dev, float* point_dev,
+                          int32_t* cross_dev, float* sum_f_dev, int32_t* sum_i_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Key-point skeleton and centre heat-map views: acr/visualization.py:228-300 (Visualizer.visulize_result_live with
  * show_items 'pj2d' / 'centermap', vis_keypoints, make_heatmaps), drawn on the device.  Nothing of PIL or cv2 is used; the
  * rules are (DESIGN.md "Key-point and heat-map views"):
