@@ -1,8 +1,10 @@
 // libacrmi.so: context life cycle, options and the fused entry points of the C ABI declared in include/acrmi.h
 // (program replay: acrmi_program.hip; stand-alone operators: acrmi_ops.hip; RCCL: acrmi_comm.hip).
 #include "acrmi_ctx.h"
-#include "contact_plan.h"
-#include "surface_contact_plan.h"
+#include "surface_contact_plan.h"      // and contact_plan.h
+
+#include <initializer_list>
+#include <type_traits>
 
 std::string g_err;
 
@@ -49,6 +51,65 @@ struct NewOnDevice {
   }
 };
 
+// ---- what the two contact entry points share (below: "contact between the hands of a row") ----
+// A measure's scratch in the context for n = B * K hand pairs: [pairs n*K*2 | mesh_topo 2n | sign 2n] int32 (sized for K =
+// ACRMI_MAX_HAND) and the measure's records of the 2n meshes behind them.
+static size_t contact_head_bytes(long long n) {
+  return ((size_t)n * (2 * CONTACT_MAX_HAND + 4) * sizeof(int32_t) + 255) / 256 * 256;
+}
+
+// What acrmi_contact and acrmi_surface_contact do around their kernels: the checks (own: the measure's own outputs, already in
+// `a`), the measure's scratch (allocated at the first call, again when n grows - or the face count changes, which only the
+// surface records depend on), its carve-up, the prep kernel, which forms the pairs from the slot flags (sign_host: the two
+// orientation signs), the frame of the launch, and the launch on the context's device.
+template <class Args>
+static int contact_call(acrmi_ctx* c, const char* who, acrmi_ctx::ContactScratch acrmi_ctx::*scratch,
+                        hipError_t (*launch)(const Args&, hipStream_t), Args a, std::initializer_list<const void*> own,
+                        const float* verts, const float* cam_trans, const float* slots, int B, int K, const int32_t* sign_host,
+                        float contact_dist, float max_depth, float* d2, float* sum_f, int32_t* sum_i, void* stream) {
+  constexpr bool surface = std::is_same<Args, SurfaceContactArgs>::value;
+  bool all = c && verts && cam_trans && slots && d2 && sum_f && sum_i && B > 0;
+  for (const void* p : own) all = all && p;
+  if (!all) return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "%s: max_hand %d outside 1..%d", who, K, ACRMI_MAX_HAND);
+  if (!contact_params_ok(contact_dist, max_depth))
+    return fail(c, ACRMI_EINVAL, "%s: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)", who);
+  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "%s: MANO faces not loaded (acrmi_load_faces)", who);
+  const int F = c->n_faces[0];
+  if (surface && (c->n_faces[1] != F || F > SURFACE_MAX_FACES))
+    return fail(c, ACRMI_EINVAL, "%s: the two sides have %d and %d faces (equal counts, at most %d)", who, F, c->n_faces[1],
+                SURFACE_MAX_FACES);
+  const long long n = (long long)B * K, n_pairs = n * K;
+  if (2 * n > 0x7fffffffll || n_pairs > 0x7fffffffll ||
+      !(surface ? surface_plan((int)(2 * n), 778, F, (int)n_pairs).ok : contact_plan((int)(2 * n), 778, (int)n_pairs).ok))
+    return fail(c, ACRMI_EINVAL, "%s: %d frames of %d x %d pairs are beyond 2^31 - 1 elements", who, B, K, K);
+  ON_DEVICE(c);
+  acrmi_ctx::ContactScratch& sc = c->*scratch;
+  if (n > sc.hands || (surface && F != sc.faces)) {
+    if (sc.ws) {
+      HIPCHK(c, hipDeviceSynchronize());
+      (void)hipFree(sc.ws);
+      sc = {};
+    }
+    HIPCHK(c, hipMalloc(&sc.ws, contact_head_bytes(n) + (surface ? surface_workspace_bytes((int)(2 * n), 778, F)
+                                                                 : contact_workspace_bytes((int)(2 * n), 778))));
+    sc.hands = n;
+    sc.faces = F;
+  }
+  int32_t* pairs = (int32_t*)sc.ws;
+  int32_t* mesh_topo = pairs + 2 * n_pairs;
+  int32_t* sign = mesh_topo + 2 * n;
+  hipError_t e = launch_contact_prep(slots, B, K, sign_host[0] < 0 ? -1 : 1, sign_host[1] < 0 ? -1 : 1, pairs, mesh_topo, sign,
+                                     (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "%s: prep: %s", who, hipGetErrorString(e));
+  static_cast<ContactFrame&>(a) =
+      ContactFrame{verts, cam_trans, {c->faces_topo[0], c->faces_topo[1]}, mesh_topo, pairs, contact_dist, max_depth, d2,
+                   (float4*)(sc.ws + contact_head_bytes(sc.hands)), sum_f, sum_i, (int)(2 * n), 778, F, (int)n_pairs};
+  if constexpr (!surface) a.sign = sign;
+  e = launch(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
 extern "C" {
 
 int acrmi_version(void) { return ACRMI_VERSION; }
@@ -78,8 +139,8 @@ void acrmi_destroy(acrmi_ctx* c) {
   release_weights(c);
   acrmi_streams_destroy(c->own_streams);
   if (c->render_ws) (void)hipFree(c->render_ws);
-  if (c->contact_ws) (void)hipFree(c->contact_ws);
-  if (c->surface_ws) (void)hipFree(c->surface_ws);
+  if (c->contact_ws.ws) (void)hipFree(c->contact_ws.ws);
+  if (c->surface_ws.ws) (void)hipFree(c->surface_ws.ws);
   if (c->region_hand_frame) (void)hipFree(c->region_hand_frame);
   for (int32_t* p : c->faces_topo)
     if (p) (void)hipFree(p);
@@ -943,95 +1004,24 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
 }
 
 // ---- contact between the hands of a row (csrc/contact.hip) ---------------------------------------------------------------
-// The context's contact scratch for n = B * K hand pairs: [pairs n*K*2 | mesh_topo 2n | sign 2n] int32 (sized for K =
-// ACRMI_MAX_HAND) and the P / N records of the 2n meshes behind them.  Allocates at the first call and when n grows.
-static size_t contact_head_bytes(long long n) {
-  return ((size_t)n * (2 * CONTACT_MAX_HAND + 4) * sizeof(int32_t) + 255) / 256 * 256;
-}
-
 int acrmi_contact(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, int K, const int32_t* sign_host,
                   float contact_dist, float max_depth, int32_t* nn, float* d2, float* s_out, float* sum_f, int32_t* sum_i,
                   void* stream) {
-  if (!c || !verts || !cam_trans || !slots || !nn || !d2 || !s_out || !sum_f || !sum_i || B <= 0)
-    return fail(c, ACRMI_EINVAL, "acrmi_contact: bad arguments");
-  if (K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "acrmi_contact: max_hand %d outside 1..%d", K, ACRMI_MAX_HAND);
-  if (!contact_params_ok(contact_dist, max_depth))
-    return fail(c, ACRMI_EINVAL, "acrmi_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
-  const long long n = (long long)B * K, n_pairs = n * K;
-  if (2 * n > 0x7fffffffll || n_pairs > 0x7fffffffll || !contact_plan((int)(2 * n), 778, (int)n_pairs).ok)
-    return fail(c, ACRMI_EINVAL, "acrmi_contact: %d frames of %d x %d pairs are beyond 2^31 - 1 elements", B, K, K);
-  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "acrmi_contact: MANO faces not loaded (acrmi_load_faces)");
-  ON_DEVICE(c);
-  if (n > c->contact_ws_hands) {
-    if (c->contact_ws) {
-      HIPCHK(c, hipDeviceSynchronize());
-      (void)hipFree(c->contact_ws);
-      c->contact_ws = nullptr;
-      c->contact_ws_hands = 0;
-    }
-    HIPCHK(c, hipMalloc(&c->contact_ws, contact_head_bytes(n) + contact_workspace_bytes((int)(2 * n), 778)));
-    c->contact_ws_hands = n;
-  }
-  int32_t* pairs = (int32_t*)c->contact_ws;
-  int32_t* mesh_topo = pairs + 2 * n_pairs;
-  int32_t* sign = mesh_topo + 2 * n;
-  const int sl = sign_host ? sign_host[0] : c->contact_sign[0], sr = sign_host ? sign_host[1] : c->contact_sign[1];
-  hipError_t e = launch_contact_prep(slots, B, K, sl < 0 ? -1 : 1, sr < 0 ? -1 : 1, pairs, mesh_topo, sign, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "acrmi_contact: prep: %s", hipGetErrorString(e));
   ContactArgs a{};
-  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1]; a.mesh_topo = mesh_topo;
-  a.sign = sign; a.pairs = pairs; a.contact_dist = contact_dist; a.max_depth = max_depth;
-  a.nn = nn; a.d2 = d2; a.side = s_out; a.sum_f = sum_f; a.sum_i = sum_i;
-  a.ws = (float4*)(c->contact_ws + contact_head_bytes(c->contact_ws_hands));
-  a.n_meshes = (int)(2 * n); a.n_verts = 778; a.n_faces = c->n_faces[0]; a.n_pairs = (int)n_pairs;
-  e = launch_contact(a, (hipStream_t)stream);
-  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "acrmi_contact: %s", hipGetErrorString(e));
+  a.nn = nn; a.side = s_out;
+  return contact_call(c, "acrmi_contact", &acrmi_ctx::contact_ws, launch_contact, a, {nn, s_out}, verts, cam_trans, slots, B, K,
+                      sign_host || !c ? sign_host : c->contact_sign, contact_dist, max_depth, d2, sum_f, sum_i, stream);
 }
 
-// The surface measure of the same pairs (csrc/surface_contact.hip): the prep kernel of acrmi_contact forms them from the slot
-// flags; the scratch is the context's own ([pairs | mesh_topo | sign] as above, then the P and face records of the 2n meshes).
+// The surface measure of the same pairs.  It has no orientation sign: the prep kernel's sign array is written and not read.
 int acrmi_surface_contact(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, int K,
                           float contact_dist, float max_depth, int32_t* face, float* d2, float* point, int32_t* cross, float* sum_f,
                           int32_t* sum_i, void* stream) {
-  if (!c || !verts || !cam_trans || !slots || !face || !d2 || !point || !cross || !sum_f || !sum_i || B <= 0)
-    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: bad arguments");
-  if (K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: max_hand %d outside 1..%d", K, ACRMI_MAX_HAND);
-  if (!contact_params_ok(contact_dist, max_depth))
-    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
-  if (!c->faces_topo[0] || !c->faces_topo[1])
-    return fail(c, ACRMI_ESTATE, "acrmi_surface_contact: MANO faces not loaded (acrmi_load_faces)");
-  const int F = c->n_faces[0];
-  if (c->n_faces[1] != F || F > SURFACE_MAX_FACES)
-    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: the two sides have %d and %d faces (equal counts, at most %d)", F,
-                c->n_faces[1], SURFACE_MAX_FACES);
-  const long long n = (long long)B * K, n_pairs = n * K;
-  if (2 * n > 0x7fffffffll || n_pairs > 0x7fffffffll || !surface_plan((int)(2 * n), 778, F, (int)n_pairs).ok)
-    return fail(c, ACRMI_EINVAL, "acrmi_surface_contact: %d frames of %d x %d pairs are beyond 2^31 - 1 elements", B, K, K);
-  ON_DEVICE(c);
-  if (n > c->surface_ws_hands || F != c->surface_ws_faces) {
-    if (c->surface_ws) {
-      HIPCHK(c, hipDeviceSynchronize());
-      (void)hipFree(c->surface_ws);
-      c->surface_ws = nullptr;
-      c->surface_ws_hands = 0;
-    }
-    HIPCHK(c, hipMalloc(&c->surface_ws, contact_head_bytes(n) + surface_workspace_bytes((int)(2 * n), 778, F)));
-    c->surface_ws_hands = n;
-    c->surface_ws_faces = F;
-  }
-  int32_t* pairs = (int32_t*)c->surface_ws;
-  int32_t* mesh_topo = pairs + 2 * n_pairs;
-  int32_t* sign = mesh_topo + 2 * n;
-  hipError_t e = launch_contact_prep(slots, B, K, 1, 1, pairs, mesh_topo, sign, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "acrmi_surface_contact: prep: %s", hipGetErrorString(e));
+  static const int32_t kNoSign[2] = {1, 1};
   SurfaceContactArgs a{};
-  a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1]; a.mesh_topo = mesh_topo;
-  a.pairs = pairs; a.contact_dist = contact_dist; a.max_depth = max_depth;
-  a.face = face; a.d2 = d2; a.point = point; a.cross = cross; a.sum_f = sum_f; a.sum_i = sum_i;
-  a.ws = (float4*)(c->surface_ws + contact_head_bytes(c->surface_ws_hands));
-  a.n_meshes = (int)(2 * n); a.n_verts = 778; a.n_faces = F; a.n_pairs = (int)n_pairs;
-  e = launch_surface_contact(a, (hipStream_t)stream);
-  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "acrmi_surface_contact: %s", hipGetErrorString(e));
+  a.face = face; a.cross = cross; a.point = point;
+  return contact_call(c, "acrmi_surface_contact", &acrmi_ctx::surface_ws, launch_surface_contact, a, {face, point, cross}, verts,
+                      cam_trans, slots, B, K, kNoSign, contact_dist, max_depth, d2, sum_f, sum_i, stream);
 }
 
 // ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------

@@ -126,15 +126,16 @@ struct acrmi_ctx {
   int region_hand_cap = 0;                // regions it holds
   // contact between the hands (acrmi_contact; csrc/contact_plan.h): host copies of what the orientation sign of a side's
   // topology is derived from (the side's template vertices and its faces; +1 until both are there), and the call's scratch
-  // (pairs, per-mesh topology index and sign, the P / N records), grown on demand
+  // (pairs, per-mesh topology index and sign, the measure's records: csrc/contact_plan.h, csrc/surface_contact_plan.h), grown on demand
   std::vector<float> v_template_host[2];
   std::vector<int32_t> faces_host[2];
   int contact_sign[2] = {1, 1};
-  char* contact_ws = nullptr;
-  long long contact_ws_hands = 0;      // B * K it holds
-  char* surface_ws = nullptr;          // acrmi_surface_contact's scratch (csrc/surface_contact_plan.h), grown on demand
-  long long surface_ws_hands = 0;      // B * K it holds
-  int surface_ws_faces = 0;            // ... of meshes with this many faces
+  struct ContactScratch {
+    char* ws = nullptr;
+    long long hands = 0;      // B * K it holds
+    int faces = 0;            // ... of meshes with this many faces (the surface measure's alone)
+  };
+  ContactScratch contact_ws, surface_ws;      // one per measure: calls of the two on two streams share no memory
   int last_batch = 0;          // batch of the last program run: whose centre maps the head buffers hold (acrmi_overlay)
   // multi-GPU: RCCL communicator created by acrmi_comm_init
   void* comm = nullptr;

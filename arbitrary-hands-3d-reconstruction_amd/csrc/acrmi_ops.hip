@@ -6,6 +6,7 @@
 #include "roi_plan.h"
 #include "track_plan.h"
 
+#include <initializer_list>
 #include <vector>
 
 // (poison: acrmi_decode_gated's range flag of an 'fp16x3' program; null for the stand-alone operator)
@@ -732,40 +733,52 @@ int acrmi_rasterize_views(const float* verts_dev, const float* trans_dev, int n_
                    ids_out_dev, ws_dev, stream);
 }
 
-// ---- contact and interpenetration between meshes (csrc/contact.hip, csrc/contact_plan.h) ----
+// ---- the two contact measures between meshes (csrc/contact.hip; csrc/contact_plan.h, csrc/surface_contact_plan.h) ----
 size_t acrmi_contact_workspace(int n_meshes, int n_verts) { return contact_workspace_bytes(n_meshes, n_verts); }
+size_t acrmi_surface_contact_workspace(int n_meshes, int n_verts, int n_faces) {
+  return surface_workspace_bytes(n_meshes, n_verts, n_faces);
+}
+
+// What both stateless entry points check, in this order: the sizes, the limits (max_faces 0: the measure has none on the
+// faces), the parameters; then - n_pairs == 0 is a success that touches nothing - the pointers (own: the measure's own
+// outputs), the workspace's alignment and the plan's verdict.
+static int check_mesh_contact(const char* who, const ContactFrame& f, int max_faces, std::initializer_list<const void*> own,
+                              bool plan_ok) {
+  if (f.n_meshes <= 0 || f.n_verts <= 0 || f.n_faces <= 0 || f.n_pairs < 0)
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d meshes, %d vertices, %d faces, %d pairs)", who, f.n_meshes, f.n_verts,
+                f.n_faces, f.n_pairs);
+  if (f.n_verts > CONTACT_MAX_VERTS || (max_faces && f.n_faces > max_faces))
+    return max_faces ? fail(nullptr, ACRMI_EINVAL, "%s: %d vertices and %d faces, at most %d and %d", who, f.n_verts, f.n_faces,
+                            CONTACT_MAX_VERTS, max_faces)
+                     : fail(nullptr, ACRMI_EINVAL, "%s: %d vertices, at most %d (the other mesh is held in LDS)", who, f.n_verts,
+                            CONTACT_MAX_VERTS);
+  if (!contact_params_ok(f.contact_dist, f.max_depth))
+    return fail(nullptr, ACRMI_EINVAL, "%s: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)", who);
+  if (f.n_pairs == 0) return ACRMI_OK;
+  bool all = f.verts && f.topo[0] && f.pairs && f.d2 && f.sum_f && f.sum_i && f.ws;
+  for (const void* p : own) all = all && p;
+  if (!all) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)f.ws & 15) != 0) return fail(nullptr, ACRMI_EINVAL, "%s: the workspace is not 16-byte aligned", who);
+  if (!plan_ok)
+    return max_faces ? fail(nullptr, ACRMI_EINVAL, "%s: %d pairs of %d vertices (or %d meshes of %d faces) are beyond 2^31 - 1 elements",
+                            who, f.n_pairs, f.n_verts, f.n_meshes, f.n_faces)
+                     : fail(nullptr, ACRMI_EINVAL, "%s: %d pairs of %d vertices (or %d meshes) are beyond 2^31 - 1 elements", who,
+                            f.n_pairs, f.n_verts, f.n_meshes);
+  return ACRMI_OK;
+}
 
 int acrmi_mesh_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
                        const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev, const int32_t* sign_dev,
                        const int32_t* pairs_dev, int n_pairs, float contact_dist, float max_depth, int32_t* nn_dev, float* d2_dev,
                        float* s_dev, float* sum_f_dev, int32_t* sum_i_dev, void* ws_dev, void* stream) {
-  if (n_meshes <= 0 || n_verts <= 0 || n_faces <= 0 || n_pairs < 0)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: bad sizes (%d meshes, %d vertices, %d faces, %d pairs)", n_meshes, n_verts,
-                n_faces, n_pairs);
-  if (n_verts > CONTACT_MAX_VERTS)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: %d vertices, at most %d (the other mesh is held in LDS)", n_verts,
-                CONTACT_MAX_VERTS);
-  if (!contact_params_ok(contact_dist, max_depth))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)");
-  if (n_pairs == 0) return ACRMI_OK;
-  if (!verts_dev || !topo_dev || !pairs_dev || !nn_dev || !d2_dev || !s_dev || !sum_f_dev || !sum_i_dev || !ws_dev)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: a null pointer");
-  if (((uintptr_t)ws_dev & 15) != 0) return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: the workspace is not 16-byte aligned");
-  if (!contact_plan(n_meshes, n_verts, n_pairs).ok)
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_mesh_contact: %d pairs of %d vertices (or %d meshes) are beyond 2^31 - 1 elements", n_pairs,
-                n_verts, n_meshes);
-  ContactArgs a{};
-  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
-  a.sign = sign_dev; a.pairs = pairs_dev; a.contact_dist = contact_dist; a.max_depth = max_depth;
-  a.nn = nn_dev; a.d2 = d2_dev; a.side = s_dev; a.sum_f = sum_f_dev; a.sum_i = sum_i_dev; a.ws = (float4*)ws_dev;
-  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_pairs = n_pairs;
-  hipError_t e = launch_contact(a, (hipStream_t)stream);
-  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "acrmi_mesh_contact: %s", hipGetErrorString(e));
-}
-
-// ---- the surface contact measure between meshes (csrc/surface_contact.hip, csrc/surface_contact_plan.h) ----
-size_t acrmi_surface_contact_workspace(int n_meshes, int n_verts, int n_faces) {
-  return surface_workspace_bytes(n_meshes, n_verts, n_faces);
+  const char* who = "acrmi_mesh_contact";
+  const ContactArgs a{{verts_dev, trans_dev, {topo_dev, topo2_dev}, mesh_topo_dev, pairs_dev, contact_dist, max_depth, d2_dev,
+                       (float4*)ws_dev, sum_f_dev, sum_i_dev, n_meshes, n_verts, n_faces, n_pairs},
+                      sign_dev, nn_dev, s_dev};
+  const int r = check_mesh_contact(who, a, 0, {nn_dev, s_dev}, contact_plan(n_meshes, n_verts, n_pairs).ok);
+  if (r != ACRMI_OK || n_pairs == 0) return r;
+  const hipError_t e = launch_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 
 int acrmi_mesh_surface_contact(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
@@ -774,28 +787,13 @@ int acrmi_mesh_surface_contact(const float* verts_dev, const float* trans_dev, i
                                float* d2_dev, float* point_dev, int32_t* cross_dev, float* sum_f_dev, int32_t* sum_i_dev,
                                void* ws_dev, void* stream) {
   const char* who = "acrmi_mesh_surface_contact";
-  if (n_meshes <= 0 || n_verts <= 0 || n_faces <= 0 || n_pairs < 0)
-    return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d meshes, %d vertices, %d faces, %d pairs)", who, n_meshes, n_verts, n_faces,
-                n_pairs);
-  if (n_verts > CONTACT_MAX_VERTS || n_faces > SURFACE_MAX_FACES)
-    return fail(nullptr, ACRMI_EINVAL, "%s: %d vertices and %d faces, at most %d and %d", who, n_verts, n_faces, CONTACT_MAX_VERTS,
-                SURFACE_MAX_FACES);
-  if (!contact_params_ok(contact_dist, max_depth))
-    return fail(nullptr, ACRMI_EINVAL, "%s: contact_dist must be finite and >= 0, max_depth >= 0 (+inf allowed)", who);
-  if (n_pairs == 0) return ACRMI_OK;
-  if (!verts_dev || !topo_dev || !pairs_dev || !face_dev || !d2_dev || !point_dev || !cross_dev || !sum_f_dev || !sum_i_dev || !ws_dev)
-    return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
-  if (((uintptr_t)ws_dev & 15) != 0) return fail(nullptr, ACRMI_EINVAL, "%s: the workspace is not 16-byte aligned", who);
-  if (!surface_plan(n_meshes, n_verts, n_faces, n_pairs).ok)
-    return fail(nullptr, ACRMI_EINVAL, "%s: %d pairs of %d vertices (or %d meshes of %d faces) are beyond 2^31 - 1 elements", who,
-                n_pairs, n_verts, n_meshes, n_faces);
-  SurfaceContactArgs a{};
-  a.verts = verts_dev; a.trans = trans_dev; a.topo[0] = topo_dev; a.topo[1] = topo2_dev; a.mesh_topo = mesh_topo_dev;
-  a.pairs = pairs_dev; a.contact_dist = contact_dist; a.max_depth = max_depth;
-  a.face = face_dev; a.d2 = d2_dev; a.point = point_dev; a.cross = cross_dev; a.sum_f = sum_f_dev; a.sum_i = sum_i_dev;
-  a.ws = (float4*)ws_dev;
-  a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_pairs = n_pairs;
-  hipError_t e = launch_surface_contact(a, (hipStream_t)stream);
+  const SurfaceContactArgs a{{verts_dev, trans_dev, {topo_dev, topo2_dev}, mesh_topo_dev, pairs_dev, contact_dist, max_depth, d2_dev,
+                              (float4*)ws_dev, sum_f_dev, sum_i_dev, n_meshes, n_verts, n_faces, n_pairs},
+                             face_dev, cross_dev, point_dev};
+  const int r = check_mesh_contact(who, a, SURFACE_MAX_FACES, {face_dev, point_dev, cross_dev},
+                                   surface_plan(n_meshes, n_verts, n_faces, n_pairs).ok);
+  if (r != ACRMI_OK || n_pairs == 0) return r;
+  const hipError_t e = launch_surface_contact(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 

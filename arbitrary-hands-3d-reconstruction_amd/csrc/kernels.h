@@ -467,42 +467,34 @@ hipError_t launch_render_region_prep(const float* slots, const float* offsets, c
                                      int H, int W, int slot_stride, int flag_at, const float* colors, int32_t* mesh_frame,
                                      int32_t* mesh_topo, float* rgb, float* mesh_view, hipStream_t s);
 
-// Contact and interpenetration between meshes (csrc/contact.hip, csrc/contact_plan.h).
-struct ContactArgs {
+// The two contact measures between meshes (csrc/contact.hip): what both read and write, then what each adds.
+struct ContactFrame {
   const float* verts;            // [M, n_verts, 3]
   const float* trans;            // [M, 3] or null
   const int32_t* topo[2];        // mesh topology blobs on the device; [1] may be null
   const int32_t* mesh_topo;      // [M] 0 / 1 = which blob, or null (all 0)
-  const int32_t* sign;           // [M] +1 / -1 orientation of the mesh's topology, or null (all +1)
   const int32_t* pairs;          // [n_pairs, 2] mesh indices; outside [0, M): the pair is skipped
   float contact_dist, max_depth;
-  int32_t* nn;                   // [n_pairs, 2, n_verts]
-  float *d2, *side;              // [n_pairs, 2, n_verts]
-  float* sum_f;                  // [n_pairs, CONTACT_SUM_F]
-  int32_t* sum_i;                // [n_pairs, CONTACT_SUM_I]
-  float4* ws;                    // contact_workspace_bytes(M, n_verts), 16-byte aligned
+  float* d2;                     // [n_pairs, 2, n_verts]
+  float4* ws;                    // contact_workspace_bytes / surface_workspace_bytes of the sizes, 16-byte aligned
+  float* sum_f;                  // [n_pairs, CONTACT_SUM_F or SURFACE_SUM_F]
+  int32_t* sum_i;                // [n_pairs, CONTACT_SUM_I or SURFACE_SUM_I]
   int n_meshes, n_verts, n_faces, n_pairs;
+};
+// Contact and interpenetration by the nearest vertex (csrc/contact_plan.h).
+struct ContactArgs : ContactFrame {
+  const int32_t* sign;           // [M] +1 / -1 orientation of the mesh's topology, or null (all +1)
+  int32_t* nn;                   // [n_pairs, 2, n_verts]
+  float* side;                   // [n_pairs, 2, n_verts]
 };
 hipError_t launch_contact(const ContactArgs& a, hipStream_t s);
 // acrmi_contact: slots [B,K,2,ACRMI_SLOT] on the device -> pairs [B*K*K,2], mesh_topo and sign [2*B*K]
 hipError_t launch_contact_prep(const float* slots, int B, int K, int sign_left, int sign_right, int32_t* pairs, int32_t* mesh_topo,
                                int32_t* sign, hipStream_t s);
-
-// The surface contact measure between meshes (csrc/surface_contact.hip, csrc/surface_contact_plan.h).
-struct SurfaceContactArgs {
-  const float* verts;            // [M, n_verts, 3]
-  const float* trans;            // [M, 3] or null
-  const int32_t* topo[2];        // mesh topology blobs on the device; [1] may be null
-  const int32_t* mesh_topo;      // [M] 0 / 1 = which blob, or null (all 0)
-  const int32_t* pairs;          // [n_pairs, 2] mesh indices; outside [0, M): the pair is skipped
-  float contact_dist, max_depth;
+// The surface contact measure (csrc/surface_contact_plan.h).
+struct SurfaceContactArgs : ContactFrame {
   int32_t *face, *cross;         // [n_pairs, 2, n_verts]
-  float* d2;                     // [n_pairs, 2, n_verts]
   float* point;                  // [n_pairs, 2, n_verts, 3]
-  float* sum_f;                  // [n_pairs, SURFACE_SUM_F]
-  int32_t* sum_i;                // [n_pairs, SURFACE_SUM_I]
-  float4* ws;                    // surface_workspace_bytes(M, n_verts, n_faces), 16-byte aligned
-  int n_meshes, n_verts, n_faces, n_pairs;
 };
 hipError_t launch_surface_contact(const SurfaceContactArgs& a, hipStream_t s);
 

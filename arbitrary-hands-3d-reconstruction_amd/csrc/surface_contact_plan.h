@@ -1,5 +1,5 @@
 // The surface contact measure between two meshes (acrmi_mesh_surface_contact, acrmi_surface_contact; DESIGN.md section 20;
-// the kernels are in csrc/surface_contact.hip): the distance from every vertex to the other mesh's SURFACE with the point on
+// the kernels are in csrc/contact.hip): the distance from every vertex to the other mesh's SURFACE with the point on
 // it, and containment by counting the crossings of a ray.  Here: the rule as functions shared by host and device, the launch
 // geometry, the limits and the workspace size.  Plain C++, no HIP: tools/surface_contact_check.cpp compiles it alone; ACRMI_HD
 // (csrc/roi_plan.h) is `__host__ __device__` when the translation unit is HIP.
@@ -40,7 +40,6 @@ namespace acrmi {
 constexpr int SURFACE_FACE_TILE = 256;        // faces of the other mesh staged in LDS at a time
 constexpr int SURFACE_FACE_BYTES = 48;        // a face record: three 16-byte rows (corner x, y, z, the sign of the edge leaving it)
 constexpr int SURFACE_MAX_FACES = 8000;       // = 2 * CONTACT_MAX_VERTS: a closed mesh has 2 V - 4 faces
-constexpr int SURFACE_REDUCE_THREADS = 256;   // the reduce kernel's block
 constexpr int SURFACE_SUM_F = 4;              // floats of a pair's summary: min d2 of direction 0, 1, depth2 of direction 0, 1
 constexpr int SURFACE_SUM_I = 8;              // ints: closest (i, face) of direction 0, of 1, contact count 0, 1, inside count 0, 1
 
@@ -114,13 +113,10 @@ ACRMI_HD inline bool surface_crosses(SurfaceVec p, SurfaceVec A, SurfaceVec B, S
   return covers && front;
 }
 
-struct SurfacePlan {
-  bool ok;              // false: the sizes are refused (ACRMI_EINVAL)
-  int chunks;           // blocks along i: ceil(n_verts / CONTACT_CHUNK)
+// contact_plan's fields with the chunking and the (pair, chunk, direction) grid as it states them; here lds_bytes is the pair
+// kernel's one tile of face records and ws_bytes the P records of every mesh, then the face records of every mesh.
+struct SurfacePlan : ContactPlan {
   int tiles;            // LDS tiles of the other mesh's faces: ceil(n_faces / SURFACE_FACE_TILE)
-  unsigned grid[3];     // the pair kernel's grid: (pair, chunk of i, direction)
-  size_t lds_bytes;     // its LDS: one tile of face records
-  size_t ws_bytes;      // the workspace: P records of every mesh, then the face records of every mesh
 };
 
 // Bytes of workspace: float4 P[n_meshes][n_verts], then three float4 per face [n_meshes][n_faces].
@@ -129,22 +125,19 @@ inline size_t surface_workspace_bytes(int n_meshes, int n_verts, int n_faces) {
   return (size_t)n_meshes * ((size_t)n_verts * 16 + (size_t)n_faces * SURFACE_FACE_BYTES);
 }
 
-// n_pairs >= 1.  Refused: n_verts outside 1..CONTACT_MAX_VERTS, n_faces outside 1..SURFACE_MAX_FACES, n_meshes < 1, more than
-// 2^31 - 1 output elements (n_pairs * 2 * n_verts * 3: the points) or records (n_meshes * n_verts, n_meshes * n_faces * 3).
+// n_pairs >= 1.  Refused: what contact_plan refuses (n_verts outside 1..CONTACT_MAX_VERTS, n_meshes < 1, n_meshes * n_verts
+// records beyond 2^31 - 1), n_faces outside 1..SURFACE_MAX_FACES, more than 2^31 - 1 output elements (n_pairs * 2 * n_verts * 3:
+// the points) or face records (n_meshes * n_faces * 3).
 inline SurfacePlan surface_plan(int n_meshes, int n_verts, int n_faces, int n_pairs) {
   SurfacePlan p{};
-  if (n_meshes < 1 || n_pairs < 1 || n_verts < 1 || n_verts > CONTACT_MAX_VERTS || n_faces < 1 || n_faces > SURFACE_MAX_FACES) return p;
-  if ((long long)n_pairs * 6 * n_verts > 0x7fffffffll || (long long)n_meshes * n_verts > 0x7fffffffll ||
+  if (n_faces < 1 || n_faces > SURFACE_MAX_FACES || (long long)n_pairs * 6 * n_verts > 0x7fffffffll ||
       (long long)n_meshes * n_faces * 3 > 0x7fffffffll)
     return p;
-  p.chunks = (n_verts + CONTACT_CHUNK - 1) / CONTACT_CHUNK;
+  static_cast<ContactPlan&>(p) = contact_plan(n_meshes, n_verts, n_pairs);
+  if (!p.ok) return p;
   p.tiles = (n_faces + SURFACE_FACE_TILE - 1) / SURFACE_FACE_TILE;
-  p.grid[0] = (unsigned)n_pairs;
-  p.grid[1] = (unsigned)p.chunks;
-  p.grid[2] = 2;
   p.lds_bytes = (size_t)SURFACE_FACE_TILE * SURFACE_FACE_BYTES;
   p.ws_bytes = surface_workspace_bytes(n_meshes, n_verts, n_faces);
-  p.ok = true;
   return p;
 }
 

@@ -880,20 +880,13 @@ class Engine(object):
             cam_trans = cam_trans.reshape(B * K, 2, 3)
         cam_trans = self._cam_trans(flat, cam_trans, B * K, focal_length, st)
         verts, slots = out['verts'].contiguous(), slots.contiguous()
-        if mode == 'surface':
-            raw = ops_mod.surface_contact_outputs(B * K * K, 778, self.device)
-            _lib.check(self.L.acrmi_surface_contact(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, contact_dist,
-                                                    max_depth, _ptr(raw['face']), _ptr(raw['d2']), _ptr(raw['point']),
-                                                    _ptr(raw['cross']), _ptr(raw['sum_f']), _ptr(raw['sum_i']), st), self.ctx)
-            self._contact_keep = (verts, slots, cam_trans)
-            return ops_mod.surface_contact_result(raw)
-        raw = ops_mod.contact_outputs(B * K * K, 778, self.device)
+        m = ops_mod.CONTACT_MEASURES[mode]
+        raw = ops_mod.measure_outputs(m, B * K * K, 778, self.device)
         sign = None if self._contact_sign_set is None else (C.c_int32 * 2)(*self._contact_sign_set)
-        _lib.check(self.L.acrmi_contact(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, sign, contact_dist, max_depth,
-                                        _ptr(raw['nn']), _ptr(raw['d2']), _ptr(raw['side']), _ptr(raw['sum_f']), _ptr(raw['sum_i']),
-                                        st), self.ctx)
+        _lib.check(getattr(self.L, m['ctx'])(self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), B, K, *((sign,) if m['sign'] else ()),
+                                             contact_dist, max_depth, *[_ptr(x) for x in raw.values()], st), self.ctx)
         self._contact_keep = (verts, slots, cam_trans)      # referenced until the next call has been queued
-        return ops_mod.contact_result(raw)
+        return ops_mod.measure_result(m, raw)
 
     def _regions(self, images, offsets, region_frame, n):
         """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->

@@ -1037,18 +1037,59 @@ def check_contact_params(contact_dist, max_depth):
     return contact_dist, max_depth
 
 
+SURFACE_FACE_TILE, SURFACE_MAX_FACES = 256, 8000      # = csrc/surface_contact_plan.h
+
+# The two measures (Engine.contact's modes), each described once.  outputs: the per-vertex tensors [n_pairs, 2, V] + tail, in the
+# order the entry points take them, ahead of sum_f / sum_i of the widths `sums`; summary: the views of the two summaries the
+# result adds; workspace / op / ctx: the workspace size, the stateless and the context entry point; sign: it takes the
+# orientation signs (ahead of the pairs / of contact_dist).
+CONTACT_MEASURES = {
+    'vertex': dict(
+        outputs=(('nn', (), torch.int32), ('d2', (), torch.float32), ('side', (), torch.float32)), sums=(4, 6), sign=True,
+        summary=lambda f, i: {'min_d2': f[:, 0], 'closest': i[:, 0:2], 'n_contact': i[:, 2:4], 'n_inside': i[:, 4:6],
+                              'depth2': f[:, 1:3]},
+        workspace=lambda L, M, V, F: L.acrmi_contact_workspace(M, V), op='acrmi_mesh_contact', ctx='acrmi_contact'),
+    'surface': dict(
+        outputs=(('face', (), torch.int32), ('d2', (), torch.float32), ('point', (3,), torch.float32), ('cross', (), torch.int32)),
+        sums=(4, 8), sign=False,
+        summary=lambda f, i: {'min_d2': f[:, 0:2], 'closest': i[:, 0:4].unflatten(1, (2, 2)), 'n_contact': i[:, 4:6],
+                              'n_inside': i[:, 6:8], 'depth2': f[:, 2:4]},
+        workspace=lambda L, M, V, F: L.acrmi_surface_contact_workspace(M, V, F), op='acrmi_mesh_surface_contact',
+        ctx='acrmi_surface_contact')}
+
+
+def measure_outputs(m, n_pairs, V, dev):
+    """The raw output tensors of measure m (an entry of CONTACT_MEASURES) for n_pairs pairs of V vertices, in the order its entry
+    points take them."""
+    raw = {name: torch.empty((n_pairs, 2, V) + tail, dtype=dt, device=dev) for name, tail, dt in m['outputs']}
+    raw['sum_f'] = torch.empty((n_pairs, m['sums'][0]), dtype=torch.float32, device=dev)
+    raw['sum_i'] = torch.empty((n_pairs, m['sums'][1]), dtype=torch.int32, device=dev)
+    return raw
+
+
+def measure_result(m, raw):
+    """The raw outputs -> the dict the measure's operator returns (views of the summaries, no copy, no host visit)."""
+    return dict({name: raw[name] for name, _, _ in m['outputs']}, **m['summary'](raw['sum_f'], raw['sum_i']))
+
+
 def contact_outputs(n_pairs, V, dev):
     """The raw output tensors of acrmi_mesh_contact / acrmi_contact for n_pairs pairs of V vertices."""
-    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-    return {'nn': new((n_pairs, 2, V), torch.int32), 'd2': new((n_pairs, 2, V), torch.float32),
-            'side': new((n_pairs, 2, V), torch.float32), 'sum_f': new((n_pairs, 4), torch.float32),
-            'sum_i': new((n_pairs, 6), torch.int32)}
+    return measure_outputs(CONTACT_MEASURES['vertex'], n_pairs, V, dev)
 
 
 def contact_result(raw):
     """The raw outputs -> the dict mesh_contact returns (views of the summaries, no copy, no host visit)."""
-    return {'nn': raw['nn'], 'd2': raw['d2'], 'side': raw['side'], 'min_d2': raw['sum_f'][:, 0], 'closest': raw['sum_i'][:, 0:2],
-            'n_contact': raw['sum_i'][:, 2:4], 'n_inside': raw['sum_i'][:, 4:6], 'depth2': raw['sum_f'][:, 1:3]}
+    return measure_result(CONTACT_MEASURES['vertex'], raw)
+
+
+def surface_contact_outputs(n_pairs, V, dev):
+    """The raw output tensors of acrmi_mesh_surface_contact / acrmi_surface_contact for n_pairs pairs of V vertices."""
+    return measure_outputs(CONTACT_MEASURES['surface'], n_pairs, V, dev)
+
+
+def surface_contact_result(raw):
+    """The raw outputs -> the dict mesh_surface_contact returns (views of the summaries, no copy, no host visit)."""
+    return measure_result(CONTACT_MEASURES['surface'], raw)
 
 
 def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, contact_dist=CONTACT_DIST,
@@ -1065,6 +1106,26 @@ def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, co
     'min_d2' [n] with 'closest' [n,2] = (i, j); 'n_contact', 'n_inside' int32 [n,2]; 'depth2' [n,2] = the largest d2 among the
     inside vertices (its square root: the penetration depth estimate).  A skipped pair: nn -1, d2 inf, side 0, zero counts,
     closest (-1, -1)."""
+    return _mesh_measure('vertex', verts, faces, pairs, trans, topo_index, sign, contact_dist, max_depth)
+
+
+def mesh_surface_contact(verts, faces, pairs, trans=None, topo_index=None, contact_dist=CONTACT_DIST, max_depth=CONTACT_MAX_DEPTH):
+    """The surface contact measure between pairs of meshes on the GPU (acrmi_mesh_surface_contact; DESIGN.md section 20): the
+    distance from every vertex to the other mesh's SURFACE (closest point of every triangle) and containment by the parity of
+    the crossings of the +Z ray, exact on a closed mesh.  Every vertex meets every face: it costs more than mesh_contact.
+    verts, faces, pairs, trans, topo_index, contact_dist, max_depth: as mesh_contact, with the same host checks; there is no
+    sign - the rule does not depend on the winding.  At most 4000 vertices and 8000 faces.
+    Returns device tensors, nothing is copied to the host, direction 0 = the vertices of a against b, 1 = those of b against
+    a: 'face' int32 [n,2,V] (the nearest face, -1: none), 'd2' [n,2,V] (squared distance to it), 'point' [n,2,V,3] (the point
+    on it), 'cross' int32 [n,2,V] (crossings; odd = inside); 'min_d2' [n,2] with 'closest' [n,2,2] = (i, face) per direction;
+    'n_contact', 'n_inside' int32 [n,2]; 'depth2' [n,2] = the largest d2 among the inside vertices.  A skipped pair: face -1,
+    d2 inf, point 0, cross 0, zero counts, closest (-1, -1)."""
+    return _mesh_measure('surface', verts, faces, pairs, trans, topo_index, None, contact_dist, max_depth)
+
+
+def _mesh_measure(mode, verts, faces, pairs, trans, topo_index, sign, contact_dist, max_depth):
+    """mesh_contact / mesh_surface_contact: the host checks, the outputs, the aligned workspace and the call."""
+    m = CONTACT_MEASURES[mode]
     _need_cuda(verts)
     if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
         raise ValueError('verts must be [M,V,3]')
@@ -1078,14 +1139,13 @@ def mesh_contact(verts, faces, pairs, trans=None, topo_index=None, sign=None, co
         sg = torch.as_tensor(sign).to(dev, torch.int32).contiguous()
         if sg.numel() != M:
             raise ValueError('sign must hold one int per mesh')
-    raw = contact_outputs(n, V, dev)
+    raw = measure_outputs(m, n, V, dev)
     L = _lib.lib()
-    ws = torch.empty(int(L.acrmi_contact_workspace(M, V)) + 16, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(m['workspace'](L, M, V, F)) + 16, dtype=torch.uint8, device=dev)
     ws_p = (ws.data_ptr() + 15) // 16 * 16
-    _lib.check(L.acrmi_mesh_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]), _p(ti), _p(sg), _p(pr), n,
-                                    contact_dist, max_depth, _p(raw['nn']), _p(raw['d2']), _p(raw['side']), _p(raw['sum_f']),
-                                    _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
-    return contact_result(raw)
+    _lib.check(getattr(L, m['op'])(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]), _p(ti), *((_p(sg),) if m['sign'] else ()),
+                                   _p(pr), n, contact_dist, max_depth, *[_p(x) for x in raw.values()], C.c_void_p(ws_p), _s(v)))
+    return measure_result(m, raw)
 
 
 def _contact_inputs(verts, faces, pairs, trans, topo_index):
@@ -1119,52 +1179,6 @@ def _contact_inputs(verts, faces, pairs, trans, topo_index):
         if ti.numel() != M or not pair:
             raise ValueError('topo_index needs a pair of topologies and one int per mesh')
     return v, t, (topos[0], topos[1] if pair else None, F), ti, pr
-
-
-SURFACE_FACE_TILE, SURFACE_MAX_FACES = 256, 8000      # = csrc/surface_contact_plan.h
-
-
-def surface_contact_outputs(n_pairs, V, dev):
-    """The raw output tensors of acrmi_mesh_surface_contact / acrmi_surface_contact for n_pairs pairs of V vertices."""
-    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-    return {'face': new((n_pairs, 2, V), torch.int32), 'd2': new((n_pairs, 2, V), torch.float32),
-            'point': new((n_pairs, 2, V, 3), torch.float32), 'cross': new((n_pairs, 2, V), torch.int32),
-            'sum_f': new((n_pairs, 4), torch.float32), 'sum_i': new((n_pairs, 8), torch.int32)}
-
-
-def surface_contact_result(raw):
-    """The raw outputs -> the dict mesh_surface_contact returns (views of the summaries, no copy, no host visit)."""
-    return {'face': raw['face'], 'd2': raw['d2'], 'point': raw['point'], 'cross': raw['cross'], 'min_d2': raw['sum_f'][:, 0:2],
-            'closest': raw['sum_i'][:, 0:4].unflatten(1, (2, 2)), 'n_contact': raw['sum_i'][:, 4:6],
-            'n_inside': raw['sum_i'][:, 6:8], 'depth2': raw['sum_f'][:, 2:4]}
-
-
-def mesh_surface_contact(verts, faces, pairs, trans=None, topo_index=None, contact_dist=CONTACT_DIST, max_depth=CONTACT_MAX_DEPTH):
-    """The surface contact measure between pairs of meshes on the GPU (acrmi_mesh_surface_contact; DESIGN.md section 20): the
-    distance from every vertex to the other mesh's SURFACE (closest point of every triangle) and containment by the parity of
-    the crossings of the +Z ray, exact on a closed mesh.  Every vertex meets every face: it costs more than mesh_contact.
-    verts, faces, pairs, trans, topo_index, contact_dist, max_depth: as mesh_contact, with the same host checks; there is no
-    sign - the rule does not depend on the winding.  At most 4000 vertices and 8000 faces.
-    Returns device tensors, nothing is copied to the host, direction 0 = the vertices of a against b, 1 = those of b against
-    a: 'face' int32 [n,2,V] (the nearest face, -1: none), 'd2' [n,2,V] (squared distance to it), 'point' [n,2,V,3] (the point
-    on it), 'cross' int32 [n,2,V] (crossings; odd = inside); 'min_d2' [n,2] with 'closest' [n,2,2] = (i, face) per direction;
-    'n_contact', 'n_inside' int32 [n,2]; 'depth2' [n,2] = the largest d2 among the inside vertices.  A skipped pair: face -1,
-    d2 inf, point 0, cross 0, zero counts, closest (-1, -1)."""
-    _need_cuda(verts)
-    if verts.dim() != 3 or verts.shape[-1] != 3 or verts.shape[0] < 1:
-        raise ValueError('verts must be [M,V,3]')
-    contact_dist, max_depth = check_contact_params(contact_dist, max_depth)
-    v, t, topos, ti, pr = _contact_inputs(verts, faces, pairs, trans, topo_index)
-    M, V, _ = v.shape
-    n, F = pr.shape[0], int(topos[2])
-    raw = surface_contact_outputs(n, V, v.device)
-    L = _lib.lib()
-    ws = torch.empty(int(L.acrmi_surface_contact_workspace(M, V, F)) + 16, dtype=torch.uint8, device=v.device)
-    ws_p = (ws.data_ptr() + 15) // 16 * 16
-    _lib.check(L.acrmi_mesh_surface_contact(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]), _p(ti), _p(pr), n, contact_dist,
-                                            max_depth, _p(raw['face']), _p(raw['d2']), _p(raw['point']), _p(raw['cross']),
-                                            _p(raw['sum_f']), _p(raw['sum_i']), C.c_void_p(ws_p), _s(v)))
-    return surface_contact_result(raw)
 
 
 # ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------

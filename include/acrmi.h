@@ -729,7 +729,7 @@ int acrmi_contact(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans
 
 /* ---------------------------------------------------------------------------------------
  * The SURFACE contact measure between two meshes (csrc/surface_contact_plan.h,
- * csrc/surface_contact.hip): the distance from every vertex to the other mesh's surface with the point on it, and
+ * csrc/contact.hip): the distance from every vertex to the other mesh's surface with the point on it, and
  * containment by counting ray crossings in a way that is exact on a closed mesh.  The measure above stays the default; this
  * one costs every vertex against every face.  All fp32, every operation rounded on its own, `/` correctly rounded:
  *  dot(a,b) = (ax*bx + ay*by) + az*bz; a cross component is (a*b) - (c*d); P_m[i] = verts[m,i] + trans[m] as above.

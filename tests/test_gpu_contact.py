@@ -2,49 +2,23 @@
 (tests/contact_ref.py) FOR EQUALITY: nn, the bits of d2 and side, and both summaries.  There is no tolerance anywhere in this
 file; the one thing not compared is the payload of a NaN (contact_ref.same_bits).  Then the engine level: Engine.contact,
 EnginePool.contact and forward_batch(contact=True) against the stand-alone operator on the same tensors."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
 
+import contact_cases as C
 import contact_ref as R
 from conftest import pkg
-from render_ref import ellipsoid
+from contact_cases import LATLON, PAIRS, eng, frames3, near_sd, placed, scene      # (eng, frames3, near_sd: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ('nn', 'd2', 'side', 'min_d2', 'closest', 'n_contact', 'n_inside', 'depth2')
-# lat-long spheres with exactly V = 2 + (nlat - 1) * nlon vertices: 5 (less than a wave), 64 (a wave), 257 (two chunks of 128
-# and one vertex), 778 (MANO's count: six chunks and ten vertices; 194 groups of four and two vertices in LDS)
-LATLON = {5: (2, 3), 64: (3, 31), 257: (16, 17), 778: (9, 97)}
-
-
-def host(res):
-    return {k: res[k].cpu().numpy() for k in KEYS}
-
-
-def assert_equal(got, want, what=''):
-    for k in ('nn', 'closest', 'n_contact', 'n_inside'):
-        assert got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), (what, k)
-    for k in ('d2', 'side', 'min_d2', 'depth2'):
-        assert R.same_bits(got[k], want[k]), (what, k, np.argwhere(got[k] != want[k])[:4])
-
-
-def scene(V, seed=0):
-    """Five meshes of V vertices: the two-sphere geometry of the issue (R = 0.05, centres (0, 0, 0.5) and (c, 0.003, 0.5) with
-    c = 0.06 and 0.12) and two clouds of random vertices over random faces -> (verts [5,V,3], (sphere faces, random faces),
-    topo_index)."""
-    nlat, nlon = LATLON[V]
-    g = np.random.default_rng(seed + V)
-    a, f = ellipsoid(nlat, nlon, (0.05,) * 3, (0, 0, 0.5))
-    b, _ = ellipsoid(nlat, nlon, (0.05,) * 3, (0.06, 0.003, 0.5))
-    c, _ = ellipsoid(nlat, nlon, (0.05,) * 3, (0.12, 0.003, 0.5))
-    assert a.shape[0] == V
-    rnd = (g.uniform(-0.07, 0.07, (2, V, 3)) + np.array((0.02, 0, 0.5))).astype(np.float32)
-    rf = g.integers(0, V, (len(f), 3))
-    return np.stack([a, b, c, rnd[0], rnd[1]]), (f, rf), [0, 0, 0, 1, 1]
-
-
-PAIRS = [[0, 1], [0, 2], [3, 4], [0, 3], [4, 1], [2, 2]]
+KEYS = C.KEYS['vertex']
+host = partial(C.host, keys=KEYS)
+assert_equal = partial(C.assert_equal, 'vertex')
+by_operator = partial(C.by_operator, 'vertex')
 
 
 @pytest.mark.parametrize('V', sorted(LATLON))
@@ -156,40 +130,19 @@ def test_determinism_and_batch_independence():
 
 
 # ---- engine level ---------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def near_sd():
-    return pkg('synth').make_state_dict(seed=10)      # (the checkpoint of tests/test_gpu_render.py: both hands are detected)
-
-
-@pytest.fixture(scope='module')
-def eng(near_sd, mano_tables):
-    e = pkg('engine').Engine(0)
-    e.load_state_dict(near_sd, max_batch=3)
-    e.load_mano(mano_tables)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope='module')
-def frames3():
-    return torch.from_numpy(pkg('synth').make_frames(3, seed=0)).cuda()
-
-
-def placed(B, K=1):
-    """cam_trans [B,K,2,3] that puts the hands of a row a few centimetres from each other, about 0.8 m from the camera."""
-    g = np.random.default_rng(B * 10 + K)
-    t = np.array((0, 0, 0.8), np.float32) + g.uniform(-0.03, 0.03, (B, K, 2, 3)).astype(np.float32)
-    return torch.from_numpy(t).cuda()
-
-
-def by_operator(ops, L, eng, out, K, cam_trans, mano_tables, **kw):
-    """ops.mesh_contact fed what Engine.contact reads, with the pairs built from the flags on the host."""
-    n = out['slots'].shape[0] * K
-    flags = out['slots'].reshape(n, 2, L.SLOT)[:, :, L.SLOT_FLAG].cpu().numpy()
-    pairs = R.frame_pairs(flags, K)
-    res = ops.mesh_contact(out['verts'].reshape(2 * n, 778, 3), (mano_tables['left']['faces'], mano_tables['right']['faces']), pairs,
-                           trans=cam_trans.reshape(2 * n, 3), topo_index=[0, 1] * n, sign=list(eng.contact_sign) * n, **kw)
-    return host(res), pairs
+def test_scratch_growth_and_the_two_modes_side_by_side(eng, mano_tables, frames3):
+    """The context's two scratch buffers, from the module engine's first calls on: the modes in the order vertex, surface,
+    vertex, surface at B = 1 (both allocate), B = 3 (both grow) and B = 1 again (both are reused, not shrunk), then once each
+    at max_hand = 2 (another carve-up of the same buffers), all on the current stream.  Every result equals the stateless
+    operator's on the same tensors - no tolerance: neither mode disturbs the other, and a regrown buffer serves as a first."""
+    ops, L = pkg('ops'), pkg('_lib')
+    for B, K in ((1, 1), (3, 1), (1, 1), (1, 2)):
+        out = eng.forward(frames3[:B], project=True, **({} if K == 1 else {'max_hand': K}))
+        ct = placed(B, K) if K > 1 else placed(B)[:, 0]
+        for mode in ('vertex', 'surface') * (2 if K == 1 else 1):
+            got = C.host(eng.contact(out, max_hand=K, cam_trans=ct, mode=mode), C.KEYS[mode])
+            want, _ = C.by_operator(mode, ops, L, eng, out, K, ct, mano_tables)
+            C.assert_equal(mode, got, want, (B, K, mode))
 
 
 def test_engine_contact_matches_the_operator(eng, mano_tables, frames3):
