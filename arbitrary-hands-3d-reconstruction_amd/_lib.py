@@ -95,7 +95,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_tracks_create', 'acrmi_tracks_destroy', 'acrmi_tracks_reset', 'acrmi_associate', 'acrmi_forward_tracks',
            'acrmi_assoc_step', 'acrmi_point_heads_multi', 'acrmi_contact_workspace', 'acrmi_mesh_contact', 'acrmi_contact',
            'acrmi_conv2d_group', 'acrmi_program_groups', 'acrmi_surface_contact_workspace', 'acrmi_mesh_surface_contact',
-           'acrmi_surface_contact']
+           'acrmi_surface_contact', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes', 'acrmi_pose_errors',
+           'acrmi_score_accumulate', 'acrmi_score_hands']
 
 _lib = None
 
@@ -243,11 +244,19 @@ def lib():
     L.acrmi_mesh_surface_contact.argtypes = [f32p, f32p, i32, i32, i32, vp, vp, vp, vp, i32, C.c_float, C.c_float, vp, f32p, f32p,
                                              vp, f32p, vp, vp, vp]
     L.acrmi_surface_contact.argtypes = [vp, f32p, f32p, f32p, i32, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, f32p, vp, vp]
+    L.acrmi_score_board_bytes.argtypes = [i32, i32, i32]
+    L.acrmi_score_board_bytes.restype = C.c_size_t
+    L.acrmi_score_pair_bytes.argtypes = [i32]
+    L.acrmi_score_pair_bytes.restype = C.c_size_t
+    L.acrmi_pose_errors.argtypes = [f32p, f32p, u8p, i32, i32, i32, f32p, f32p, f32p, vp, i32, f32p, f32p, f32p, f32p, vp, f32p, f32p, vp]
+    L.acrmi_score_accumulate.argtypes = [f32p, f32p, i32, i32, vp, i32, f32p, f32p, i32, C.c_double, vp, vp, vp]
+    L.acrmi_score_hands.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p, u8p, vp, i32, i32, i32, i32, C.c_double, vp,
+                                    f32p, f32p, f32p, vp, f32p, f32p, f32p, vp, f32p, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
                         'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy', 'acrmi_contact_workspace',
-                        'acrmi_surface_contact_workspace'):
+                        'acrmi_surface_contact_workspace', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes'):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -259,7 +259,7 @@ class ACR(object):
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
-                      track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
+                      track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None, board=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -304,8 +304,14 @@ class ACR(object):
         contact='surface' (DESIGN.md section 20): the same four keys from the surface measure (Engine.contact(mode='surface')):
         'contact_dist' - metres between the two SURFACES, the square root of the smaller min_d2 of the pair's two directions;
         'contact_verts' - the hand's own vertices within ops.CONTACT_DIST of the partner's surface; 'penetration' - metres,
-        the largest distance to the partner's surface among the hand's own vertices inside it (ray crossings)."""
+        the largest distance to the partner's surface among the hand's own vertices inside it (ray crossings).
+        gt=: ground truth as Engine.score takes it - {'joints': [B,(K,)2,21,3], 'verts', 'joint_valid',
+        'group'} - scored on the GPU behind the fused call.  Every hand dict gains 'mpjpe', 'pa_mpjpe', 'mpvpe', 'pa_mpvpe' (only
+        then): the hand's mean root-aligned and Procrustes-aligned joint and vertex errors in metres, nan for a hand without
+        truth (its group outside the board's, no counted point, no 'verts').  board= (needs gt=): an engine.ScoreBoard the
+        batch is added to, on the device; its summary() is the data set's score.  With boxes= a region is a row."""
         _check_contact(contact)
+        _check_score(gt, board)
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
@@ -313,7 +319,7 @@ class ACR(object):
         results, eng, out = self._fused_call(rgb_u8_frames, paths, offsets=offsets, point_heads=point_heads,
                                              batch_semantics=batch_semantics, streams=streams, max_streams=max_streams, K=K,
                                              tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                             multi_point_heads=multi_point_heads, contact=contact)
+                                             multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board)
         if render is None:
             return results
         if K != 1 or tracks is not None:      # the [B,K,...] shapes: K pairs per frame
@@ -327,7 +333,8 @@ class ACR(object):
         return results, _views(show_items, render, draw)
 
     def _fused_call(self, frames, paths, *, offsets=None, point_heads=True, batch_semantics=None, streams=None, max_streams=None,
-                    K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
+                    K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None,
+                    board=None):
         """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).  K = 1 without
         tracks: one hand of each side, `point_heads` is the switch and multi_point_heads is checked and without effect.
         K > 1 or tracks=: Engine.forward(max_hand=K) on the dense heads, or with multi_point_heads (K > 1) at the K best centres.
@@ -384,6 +391,8 @@ class ACR(object):
                                          focal_length=self.focal_length).view(*out['slots'].shape[:-1], 3)
         if contact:
             _add_contact(eng, out, K, 'surface' if contact == 'surface' else 'vertex')
+        if gt is not None:
+            _add_score(eng, out, K, gt, board)
         return results_from_out(out, paths), eng, out
 
     def _render_batch(self, eng, out, frames, offsets, bgr):
@@ -477,6 +486,22 @@ def _check_contact(value):
         raise ValueError("contact must be True, False or 'surface', not %r" % (value,))
 
 
+def _check_score(gt, board):
+    if gt is not None and (not isinstance(gt, dict) or gt.get('joints') is None):
+        raise ValueError("gt must be a dict with 'joints' (Engine.score says what else it may hold)")
+    if board is not None and gt is None:
+        raise ValueError('board= accumulates the scores of gt=: it needs gt=')
+    if board is not None and getattr(board, 'sets', None) != (21, 778):
+        raise ValueError('board must be an engine.ScoreBoard of the default point sets (21 joints, 778 vertices)')
+
+
+def _add_score(eng, out, K, gt, board):
+    """out['score'] = the per-hand rows of Engine.score of `out` against gt ({'joints': row_f [N,4], 'verts': row_f or None}),
+    added to `board` on the device when there is one."""
+    res = eng.score(out, gt, board=board, max_hand=K, cam_trans=out['cam_trans'])
+    out['score'] = {'joints': res['joints']['row_f'], 'verts': None if res['verts'] is None else res['verts']['row_f']}
+
+
 def _add_contact(eng, out, K, mode='vertex'):
     """out['contact'] = Engine.contact of `out` at the package's default parameters, with the parameters beside it."""
     from .. import ops
@@ -528,6 +553,10 @@ def results_from_out(out, paths):
     con = out.get('contact')      # with contact=True: every hand dict gains the four contact keys
     if con is not None:
         con = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in con.items()}
+    sc = out.get('score')      # with gt=: every hand dict gains the four score keys
+    if sc is not None:
+        from .. import score as score_mod
+        sc = {k: (None if v is None else v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in sc.items()}
     results = {}
     for b, path in enumerate(paths):
         hands = []
@@ -547,6 +576,8 @@ def results_from_out(out, paths):
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
                     if ids is not None:
                         hands[-1]['track_id'] = np.int32(ids[b, k, h])
+                    if sc is not None:
+                        hands[-1].update(score_mod.hand_score_keys(sc, (b * slots.shape[1] + k) * 2 + h))
                     where.append((k, h))
         if con is not None:
             index_of = {kh: n for n, kh in enumerate(where)}
@@ -571,7 +602,8 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
-                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False):
+                       max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False,
+                       gt=None, board=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -600,10 +632,12 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     tracks / track_gate / track_max_miss: as forward_batch; with boxes= a ValueError (ops.track_boxes follows a region).
     multi_point_heads: as forward_batch (without effect with boxes=: a region has one hand of each side).
     contact: as forward_batch.  With boxes= the two hands of a REGION are paired: every region has its own camera, so hands of
-    different regions are never paired, also when the regions lie in one frame."""
+    different regions are never paired, also when the regions lie in one frame.
+    gt / board: as forward_batch.  With boxes= a region is a row: gt['joints'] is [n,2,21,3] for n regions."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
     _check_contact(contact)
+    _check_score(gt, board)
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
@@ -613,7 +647,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         raise ValueError('region_views=True draws the views of regions: it needs boxes=')
     if boxes is not None:
         got = _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
-                               pixel_format, matrix, region_views, contact)
+                               pixel_format, matrix, region_views, contact, gt, board)
     else:
         if box_frame is not None:
             raise ValueError('box_frame says which frame each box is of: it needs boxes=')
@@ -625,7 +659,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
                                  max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                 multi_point_heads=multi_point_heads, contact=contact)
+                                 multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board)
     if to_nv12 is None:
         return got
     return got[0], _views_to_nv12(to_nv12, got[1])
@@ -712,7 +746,7 @@ def _region_views(self, eng, out, canvas, offsets, box_frame, items, bgr=True, c
 
 
 def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, streams, max_streams, pixel_format, matrix,
-                     region_views=False, contact=False):
+                     region_views=False, contact=False, gt=None, board=None):
     """forward_raw_batch with boxes."""
     from .. import _lib as S
     from .. import ops
@@ -728,7 +762,7 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     if len(paths) != n:
         raise ValueError('one path per region: %d paths, %d regions' % (len(paths), n))
     results, eng, out = self._fused_call(meta['image'], paths, offsets=meta['offsets'], point_heads=True, streams=streams,
-                                         max_streams=max_streams, contact=contact)
+                                         max_streams=max_streams, contact=contact, gt=gt, board=board)
     if not render:
         return results
     canvas = ops.nv12_to_bgr(frames, matrix) if pixel_format == 'nv12' else frames

@@ -1,6 +1,7 @@
 // libacrmi.so: context life cycle, options and the fused entry points of the C ABI declared in include/acrmi.h
 // (program replay: acrmi_program.hip; stand-alone operators: acrmi_ops.hip; RCCL: acrmi_comm.hip).
 #include "acrmi_ctx.h"
+#include "score_plan.h"
 #include "surface_contact_plan.h"      // and contact_plan.h
 
 #include <initializer_list>
@@ -1022,6 +1023,56 @@ int acrmi_surface_contact(acrmi_ctx* c, const float* verts, const float* cam_tra
   a.face = face; a.cross = cross; a.point = point;
   return contact_call(c, "acrmi_surface_contact", &acrmi_ctx::surface_ws, launch_surface_contact, a, {face, point, cross}, verts,
                       cam_trans, slots, B, K, kNoSign, contact_dist, max_depth, d2, sum_f, sum_i, stream);
+}
+
+// ---- the hands of a forward call against ground truth (csrc/score.hip; csrc/score_plan.h) --------------------------------
+int acrmi_score_hands(acrmi_ctx* c, const float* joints, const float* verts, const float* slots, const float* cam_trans,
+                      const float* gt_joints, const float* gt_verts, const uint8_t* joint_valid, const int32_t* group, int B, int K,
+                      int n_groups, int n_bins, double bin_width, void* board, float* j_e_ra, float* j_e_pa, float* j_row_f,
+                      int32_t* j_row_i, float* v_e_ra, float* v_e_pa, float* v_row_f, int32_t* v_row_i, float* pair_err,
+                      void* stream) {
+  const char* who = "acrmi_score_hands";
+  if (!c) return fail(c, ACRMI_EINVAL, "%s: ctx is NULL", who);
+  if (B <= 0 || K < 1 || K > ACRMI_MAX_HAND) return fail(c, ACRMI_EINVAL, "%s: %d frames, max_hand %d outside 1..%d", who, B, K, ACRMI_MAX_HAND);
+  if (!score_groups_ok(n_groups)) return fail(c, ACRMI_EINVAL, "%s: n_groups %d outside 1..%d", who, n_groups, SCORE_MAX_GROUPS);
+  if (board && !score_bins_ok(n_bins, bin_width))
+    return fail(c, ACRMI_EINVAL, "%s: n_bins in 1..%d, bin_width finite and > 0", who, SCORE_MAX_BINS);
+  const long long N = 2ll * B * K;
+  if (N > 0x7fffffffll || !score_sizes_ok(N, 778)) return fail(c, ACRMI_EINVAL, "%s: %d frames of %d pairs are beyond 2^31 - 1 elements", who, B, K);
+  if (!joints || !slots || !gt_joints || !j_e_ra || !j_e_pa || !j_row_f || !j_row_i || !pair_err ||
+      (gt_verts && (!verts || !v_e_ra || !v_e_pa || !v_row_f || !v_row_i)))
+    return fail(c, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)board & 7) != 0) return fail(c, ACRMI_EINVAL, "%s: the board is not 8-byte aligned", who);
+  ON_DEVICE(c);
+  const int root = c->center_idx;
+  ScoreArgs a{};
+  a.set[0] = ScoreSet{joints, gt_joints, joint_valid, nullptr, nullptr, nullptr, cam_trans, j_e_ra, j_e_pa, j_row_f, j_row_i, nullptr,
+                      pair_err, 21, root, 3, 0};
+  // the vertices on the joints' origins: the root joint's rows, 63 floats apart, good where that joint is valid (root < 0: no
+  // origins, like the joints)
+  a.set[1] = ScoreSet{verts, gt_verts, nullptr, root >= 0 ? joints + 3 * root : nullptr, root >= 0 ? gt_joints + 3 * root : nullptr,
+                      root >= 0 && joint_valid ? joint_valid + root : nullptr, cam_trans, v_e_ra, v_e_pa, v_row_f, v_row_i, nullptr,
+                      nullptr, 778, -1, 63, 21};
+  a.n_sets = gt_verts ? 2 : 1;
+  a.group = group;
+  a.group_side = 1;
+  a.flags = slots + ACRMI_SLOT_FLAG;
+  a.flag_stride = ACRMI_SLOT;
+  a.N = (int)N;
+  a.n_groups = n_groups;
+  hipError_t e = launch_pose_errors(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+  if (!board) return ACRMI_OK;
+  int64_t* b = (int64_t*)board;
+  int64_t* pair_board = b + (score_board_bytes(21, n_groups, n_bins) + score_board_bytes(778, n_groups, n_bins)) / 8;
+  for (int k = 0; k < a.n_sets; ++k) {
+    const ScoreSet& st = a.set[k];
+    const ScoreAccArgs acc{st.e_ra, st.e_pa, group, 1, a.flags, a.flag_stride, st.pair_err, a.N, st.n, n_groups, n_bins, bin_width,
+                           b + (k ? score_board_bytes(21, n_groups, n_bins) / 8 : 0), k ? nullptr : pair_board};
+    if ((e = launch_score_accumulate(acc, (hipStream_t)stream)) != hipSuccess)
+      return fail(c, ACRMI_EHIP, "%s: accumulate: %s", who, hipGetErrorString(e));
+  }
+  return ACRMI_OK;
 }
 
 // ---- key-point skeleton / centre heat maps over the frames (csrc/overlay.hip) ------------------------------------------

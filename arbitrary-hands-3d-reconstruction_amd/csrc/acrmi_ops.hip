@@ -4,6 +4,7 @@
 #include "surface_contact_plan.h"
 #include "conv_frame.h"   // conv_shape
 #include "roi_plan.h"
+#include "score_plan.h"
 #include "track_plan.h"
 
 #include <initializer_list>
@@ -794,6 +795,56 @@ int acrmi_mesh_surface_contact(const float* verts_dev, const float* trans_dev, i
                                    surface_plan(n_meshes, n_verts, n_faces, n_pairs).ok);
   if (r != ACRMI_OK || n_pairs == 0) return r;
   const hipError_t e = launch_surface_contact(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+// ---- scoring against ground truth (csrc/score.hip; csrc/score_plan.h) ----
+size_t acrmi_score_board_bytes(int n, int n_groups, int n_bins) { return score_board_bytes(n, n_groups, n_bins); }
+size_t acrmi_score_pair_bytes(int n_groups) { return score_pair_bytes(n_groups); }
+
+int acrmi_pose_errors(const float* pred_dev, const float* gt_dev, const uint8_t* valid_dev, int N, int n, int root,
+                      const float* origin_pred_dev, const float* origin_gt_dev, const float* trans_dev, const int32_t* group_dev,
+                      int n_groups, const float* flags_dev, float* e_ra_dev, float* e_pa_dev, float* row_f_dev, int32_t* row_i_dev,
+                      float* xform_dev, float* pair_err_dev, void* stream) {
+  const char* who = "acrmi_pose_errors";
+  if (N < 0 || n < 1 || n > SCORE_MAX_POINTS)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d rows of %d points (n in 1..%d)", who, N, n, SCORE_MAX_POINTS);
+  if (root < -1 || root >= n) return fail(nullptr, ACRMI_EINVAL, "%s: root %d outside -1..%d", who, root, n - 1);
+  if (!score_groups_ok(n_groups)) return fail(nullptr, ACRMI_EINVAL, "%s: n_groups %d outside 1..%d", who, n_groups, SCORE_MAX_GROUPS);
+  if (!score_sizes_ok(N, n)) return fail(nullptr, ACRMI_EINVAL, "%s: %d rows of %d points are beyond 2^31 - 1 elements", who, N, n);
+  if (N == 0) return ACRMI_OK;
+  if (!pred_dev || !gt_dev || !e_ra_dev || !e_pa_dev || !row_f_dev || !row_i_dev || (origin_pred_dev == nullptr) != (origin_gt_dev == nullptr))
+    return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  ScoreArgs a{};
+  a.set[0] = ScoreSet{pred_dev, gt_dev, valid_dev, origin_pred_dev, origin_gt_dev, nullptr, trans_dev, e_ra_dev, e_pa_dev,
+                      row_f_dev, row_i_dev, xform_dev, pair_err_dev, n, root, 3, 0};
+  a.n_sets = 1;
+  a.group = group_dev;
+  a.flags = flags_dev;
+  a.flag_stride = 1;
+  a.N = N;
+  a.n_groups = n_groups;
+  const hipError_t e = launch_pose_errors(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int acrmi_score_accumulate(const float* e_ra_dev, const float* e_pa_dev, int N, int n, const int32_t* group_dev, int n_groups,
+                           const float* flags_dev, const float* pair_err_dev, int n_bins, double bin_width, void* board_dev,
+                           void* pair_board_dev, void* stream) {
+  const char* who = "acrmi_score_accumulate";
+  if (N < 0 || n < 1 || n > SCORE_MAX_POINTS)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d rows of %d points (n in 1..%d)", who, N, n, SCORE_MAX_POINTS);
+  if (!score_groups_ok(n_groups)) return fail(nullptr, ACRMI_EINVAL, "%s: n_groups %d outside 1..%d", who, n_groups, SCORE_MAX_GROUPS);
+  if (!score_bins_ok(n_bins, bin_width))
+    return fail(nullptr, ACRMI_EINVAL, "%s: n_bins in 1..%d, bin_width finite and > 0", who, SCORE_MAX_BINS);
+  if (!score_sizes_ok(N, n)) return fail(nullptr, ACRMI_EINVAL, "%s: %d rows of %d points are beyond 2^31 - 1 elements", who, N, n);
+  if (N == 0) return ACRMI_OK;
+  if (!e_ra_dev || !e_pa_dev || !board_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)board_dev & 7) != 0 || ((uintptr_t)pair_board_dev & 7) != 0)
+    return fail(nullptr, ACRMI_EINVAL, "%s: the board is not 8-byte aligned", who);
+  const ScoreAccArgs a{e_ra_dev, e_pa_dev, group_dev, 0, flags_dev, 1, pair_err_dev, N, n, n_groups, n_bins, bin_width,
+                       (int64_t*)board_dev, (int64_t*)pair_board_dev};
+  const hipError_t e = launch_score_accumulate(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 

@@ -498,6 +498,44 @@ struct SurfaceContactArgs : ContactFrame {
 };
 hipError_t launch_surface_contact(const SurfaceContactArgs& a, hipStream_t s);
 
+// Scoring against ground truth (csrc/score.hip; the rule: csrc/score_plan.h).
+struct ScoreSet {                // one point set of a pose-errors launch
+  const float *P, *G;            // [N, n, 3] prediction, truth
+  const uint8_t* valid;          // [N, n] or null
+  const float *oP, *oG;          // origin rows (row stride o_stride floats) read when root < 0, or null
+  const uint8_t* o_valid;        // with them: the origins of row r are good only when o_valid[r * o_valid_stride] != 0; or null
+  const float* trans;            // [N, 3] or null
+  float *e_ra, *e_pa;            // [N, n]
+  float* row_f;                  // [N, SCORE_ROW_F]
+  int32_t* row_i;                // [N, SCORE_ROW_I]
+  float* xform;                  // [N, SCORE_XFORM] or null
+  float* pair_err;               // [N / 2] or null
+  int n, root, o_stride, o_valid_stride;
+};
+struct ScoreArgs {
+  ScoreSet set[2];
+  int n_sets;
+  const int32_t* group;          // [N] or null: group_side ? row & 1 : 0
+  int group_side;
+  const float* flags;            // flag of row r at flags[r * flag_stride], or null
+  int flag_stride;
+  int N, n_groups;
+};
+hipError_t launch_pose_errors(const ScoreArgs& a, hipStream_t s);
+struct ScoreAccArgs {
+  const float *e_ra, *e_pa;      // [N, n]
+  const int32_t* group;
+  int group_side;
+  const float* flags;
+  int flag_stride;
+  const float* pair_err;         // [N / 2] or null
+  int N, n, n_groups, n_bins;
+  double bin_width;
+  int64_t* board;                // score_board_bytes
+  int64_t* pair_board;           // score_pair_bytes, or null
+};
+hipError_t launch_score_accumulate(const ScoreAccArgs& a, hipStream_t s);
+
 // Key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views").
 struct SkeletonArgs {
   const float* kps;              // [n_hands, 21, 2] MANO joint order; pixels of the image, or (normalized) [-1, 1] of the 512 canvas

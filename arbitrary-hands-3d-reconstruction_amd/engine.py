@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops as ops_mod, packer
+from . import _lib, ops as ops_mod, packer, score as score_mod
 from .ops import HAND_COLORS_RGB
 
 
@@ -140,6 +140,90 @@ def track_args(tracks, track_table, streams, table, K, B):
         raise ValueError('tracks= smooths every track with its own filter: not together with streams= / table=')
     ops_mod.check_track_table(track_table, K)
     return ops_mod.track_stream_ids(tracks, track_table, B)
+
+
+def score_truth(gt, lead, device):
+    """The ground truth of Engine.score as the library reads it: {'joints' fp32 lead + [21,3], 'verts' fp32 lead + [778,3] or
+    None, 'joint_valid' uint8 lead + [21] or None, 'group' int32 lead or None}, contiguous on `device`.  Tensors that already
+    are what is asked for are passed through untouched (no kernel is queued for them)."""
+    if not isinstance(gt, dict) or gt.get('joints') is None:
+        raise ValueError("gt must be a dict with 'joints'")
+    res = {}
+    for key, dtype, tail in (('joints', torch.float32, (21, 3)), ('verts', torch.float32, (778, 3)),
+                             ('joint_valid', torch.uint8, (21,)), ('group', torch.int32, ())):
+        t = gt.get(key)
+        if t is not None:
+            t = torch.as_tensor(t)
+            if tuple(t.shape) != tuple(lead) + tail:
+                raise ValueError("gt['%s'] must be %s, got %s" % (key, list(tuple(lead) + tail), list(t.shape)))
+            t = ops_mod._score_arg(t, device, dtype, t.shape, key, as_bool=key == 'joint_valid')
+        res[key] = t
+    return res
+
+
+class ScoreBoard(object):
+    """A device-resident running score: per point set and group the per-point error sums and counts, a
+    histogram of the root-aligned errors, the rows scored and missed, and per pair of groups the MRRPE sums.  The caller owns
+    it; Engine.score / EnginePool.score / ACR.forward_batch(board=) add batches to it without visiting the host, and
+    `summary()` is the one host visit.  sets / names: the point sets, by default the 21 joints and the 778 vertices of a hand;
+    n_groups: by default 2, the side; n_bins bins of bin_width metres (defaults 100 x 0.5 mm: parameters, not measurements) for
+    the PCK curve.  Boards of several devices or ranks are summed by the caller (`words`)."""
+
+    def __init__(self, device=0, sets=(21, 778), names=('joints', 'verts'), n_groups=2, n_bins=score_mod.N_BINS,
+                 bin_width=score_mod.BIN_WIDTH):
+        self.sets, self.n_groups, self.n_bins, self.bin_width = score_mod.check_board_params(sets, n_groups, n_bins, bin_width)
+        if len(names) != len(self.sets):
+            raise ValueError('one name per point set')
+        self.names = tuple(names)
+        self.device = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
+        self._offsets, self._pair_at, total = score_mod.board_layout(self.sets, self.n_groups, self.n_bins)
+        L = _lib.lib()
+        assert total * 8 == sum(L.acrmi_score_board_bytes(n, self.n_groups, self.n_bins) for n in self.sets) + \
+            L.acrmi_score_pair_bytes(self.n_groups)
+        self.words = torch.zeros(total, dtype=torch.int64, device=self.device)
+        self._event = None      # recorded behind the last call that touched the board, on whichever stream it ran
+
+    def set_words(self, k):
+        """The board of point set k (a view)."""
+        return self.words[self._offsets[k]:self._offsets[k] + score_mod.group_words(self.sets[k], self.n_bins) * self.n_groups]
+
+    def pair_words(self):
+        return self.words[self._pair_at:]
+
+    def order_on(self, stream):
+        """Makes `stream` (a torch stream) wait for the last call that touched the board: calls from several streams update
+        it in the order they were made."""
+        if self._event is not None:
+            stream.wait_event(self._event)
+
+    def touched_on(self, stream):
+        self._event = torch.cuda.Event()
+        self._event.record(stream)
+
+    def add(self, k, res, group=None, flags=None):
+        """Adds an ops.pose_errors result over point set k (with its pair_err, if it has one) on the current stream."""
+        st = torch.cuda.current_stream(self.device)
+        self.order_on(st)
+        ops_mod.score_accumulate(self.set_words(k), self.pair_words() if res.get('pair_err') is not None else None, res,
+                                 self.n_groups, self.n_bins, self.bin_width, group=group, flags=flags)
+        self.touched_on(st)
+
+    def reset(self):
+        st = torch.cuda.current_stream(self.device)
+        self.order_on(st)
+        self.words.zero_()
+        self.touched_on(st)
+
+    def arrays(self):
+        """The board on the host (score.board_arrays): the host waits for the calls queued so far."""
+        self.order_on(torch.cuda.current_stream(self.device))
+        return score_mod.board_arrays(self.words.cpu().numpy(), self.sets, self.n_groups, self.n_bins)
+
+    def summary(self):
+        """The one host visit: MPJPE, PA-MPJPE, MPVPE, PA-MPVPE and MRRPE in metres, per-joint tables, the PCK curve and its
+        AUC, rows scored and missed - per group and over all (score.summarize says what is where)."""
+        sets, pairs = self.arrays()
+        return score_mod.summarize(sets, pairs, self.names, self.bin_width)
 
 
 class Engine(object):
@@ -888,6 +972,56 @@ class Engine(object):
         self._contact_keep = (verts, slots, cam_trans)      # referenced until the next call has been queued
         return ops_mod.measure_result(m, raw)
 
+    def score(self, out, gt, board=None, max_hand=1, cam_trans=None, focal_length=1265., n_groups=None, stream=None):
+        """Scores the hands of `out` (what `forward(..., project=True[, max_hand=K])` returned) against ground truth on the GPU
+        (acrmi_score_hands).  gt: {'joints': [B,(K,)2,21,3], 'verts': [B,(K,)2,778,3] (optional),
+        'joint_valid': [B,(K,)2,21] (optional), 'group': int32 [B,(K,)2] (optional, default the side: 0 left, 1 right)}, device
+        tensors in metres, in the frame of out['joints'].  A row is a hand: scored where its slot's flag is set (read on the
+        device), a miss where it is not, not looked at where its group is outside [0, n_groups).  The joints are aligned on the
+        context's centre joint (set_center_idx), the vertices on the same joint; Procrustes alignment is per point set.
+        cam_trans [B,(K,)2,3]: as `contact` obtains it; the absolute root error and the MRRPE terms of the pairs (left rank k,
+        right rank k) need it.  board: a ScoreBoard of the default point sets to add the batch to (n_groups is then the
+        board's).  Nothing waits for the host.  Returns {'joints': what ops.pose_errors returns over the B*K*2 rows, 'verts':
+        the same or None, 'pair_err': [B*K]}.  stream: as `forward`."""
+        K = check_max_hand(max_hand)
+        slots = out['slots']
+        B = slots.shape[0]
+        lead = tuple(slots.shape[:-1])
+        if lead not in ((B, K, 2),) + (((B, 2),) if K == 1 else ()) or tuple(out['joints'].shape) != lead + (21, 3):
+            raise ValueError('out does not hold %d rows of %d hand pairs' % (B, K))
+        if board is not None:
+            if board.sets != (21, 778) or board.device != self.device:
+                raise ValueError('board must be a ScoreBoard of sets (21, 778) on %s' % (self.device,))
+            if n_groups is not None and int(n_groups) != board.n_groups:
+                raise ValueError('the board has %d groups (n_groups=%d)' % (board.n_groups, n_groups))
+        G = board.n_groups if board is not None else (2 if n_groups is None else int(n_groups))
+        N, dev = B * K * 2, self.device
+        truth = score_truth(gt, lead, dev)
+        gj, gv, jv, gr = (truth[k] for k in ('joints', 'verts', 'joint_valid', 'group'))
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        tst = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+        flat = out if len(lead) == 2 else {k: out[k].flatten(0, 1) for k in ('joints', 'pj2d', 'cam_trans') if out.get(k) is not None}
+        if cam_trans is not None:
+            cam_trans = cam_trans.reshape(B * K, 2, 3)
+        if cam_trans is not None or out.get('cam_trans') is not None or out.get('pj2d') is not None:
+            cam_trans = self._cam_trans(flat, cam_trans, B * K, focal_length, st)
+        joints, slots = out['joints'].contiguous(), slots.contiguous()
+        verts = out['verts'].contiguous() if gv is not None else None
+        rj = ops_mod.score_outputs(N, 21, dev, pairs=True)
+        rv = ops_mod.score_outputs(N, 778, dev) if gv is not None else None
+        if board is not None:
+            board.order_on(tst)
+        _lib.check(self.L.acrmi_score_hands(
+            self.ctx, _ptr(joints), _ptr(verts), _ptr(slots), _ptr(cam_trans), _ptr(gj), _ptr(gv), _ptr(jv), _ptr(gr), B, K, G,
+            board.n_bins if board is not None else 1, board.bin_width if board is not None else 1.0,
+            _ptr(board.words) if board is not None else None, *[_ptr(rj[k]) for k in ('e_ra', 'e_pa', 'row_f', 'row_i')],
+            *[_ptr(rv[k]) if rv is not None else None for k in ('e_ra', 'e_pa', 'row_f', 'row_i')], _ptr(rj['pair_err']), st), self.ctx)
+        if board is not None:
+            board.touched_on(tst)
+        self._score_keep = (joints, verts, slots, cam_trans, gj, gv, jv, gr)      # referenced until the next call has been queued
+        return {'joints': ops_mod.score_result(rj), 'verts': None if rv is None else ops_mod.score_result(rv),
+                'pair_err': rj['pair_err']}
+
     def _regions(self, images, offsets, region_frame, n):
         """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->
         (src, offsets, region_frame) on the device."""
@@ -1171,6 +1305,23 @@ class EnginePool(object):
         rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
         return self._on_ticket(ticket, 'contact', prepare, keep='_contact_keep',
                                call=lambda eng, raw, t: eng.contact(out, max_hand=K, stream=raw, **t, **rest))
+
+    def score(self, ticket, gt, board=None, **kw):
+        """Engine.score of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True) and collect(), like contact().  max_hand is the ticket's.  A board shared by the pool's contexts is
+        updated in the order of the calls, as the stream table is.  Returns what Engine.score returns."""
+        out = ticket['out']
+        K = out['slots'].shape[1] if out['slots'].dim() == 4 else 1
+
+        def prepare(eng):      # (every conversion here: Engine.score then queues nothing on the caller's stream)
+            t = {'gt': score_truth(gt, tuple(out['slots'].shape[:-1]), self.device)}
+            if kw.get('cam_trans') is not None:
+                t['cam_trans'] = kw['cam_trans'].to(self.device, torch.float32).contiguous()
+            return t
+
+        rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
+        return self._on_ticket(ticket, 'score', prepare, keep='_score_keep',
+                               call=lambda eng, raw, t: eng.score(out, board=board, max_hand=K, stream=raw, **t, **rest))
 
     def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
         """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

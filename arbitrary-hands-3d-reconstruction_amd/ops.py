@@ -1181,6 +1181,85 @@ def _contact_inputs(verts, faces, pairs, trans, topo_index):
     return v, t, (topos[0], topos[1] if pair else None, F), ti, pr
 
 
+# ---- scoring against ground truth (csrc/score.hip) -------------------------------------------------
+def score_outputs(N, n, dev, xform=False, pairs=False):
+    """The raw output tensors of acrmi_pose_errors for N rows of n points, in the order it takes them."""
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    return {'e_ra': f(N, n), 'e_pa': f(N, n), 'row_f': f(N, 4), 'row_i': torch.empty(N, 2, dtype=torch.int32, device=dev),
+            'xform': f(N, 8) if xform else None, 'pair_err': f(N // 2) if pairs else None}
+
+
+def score_result(raw):
+    """The raw outputs -> the dict pose_errors returns (views, no copy, no host visit)."""
+    rf, ri = raw['row_f'], raw['row_i']
+    res = {'e_ra': raw['e_ra'], 'e_pa': raw['e_pa'], 'row_f': rf, 'row_i': ri, 'mean_ra': rf[:, 0], 'mean_pa': rf[:, 1],
+           'scale': rf[:, 2], 'root_err': rf[:, 3], 'n_ra': ri[:, 0], 'n_pa': ri[:, 1]}
+    res.update({k: raw[k] for k in ('xform', 'pair_err') if raw.get(k) is not None})
+    return res
+
+
+def pose_errors(pred, gt, valid=None, root=-1, origin=None, group=None, flags=None, trans=None, n_groups=1, xform=False,
+                pairs=False):
+    """Errors of predicted against true points on the GPU (acrmi_pose_errors; the rule: DESIGN.md section 21): per point the
+    root-aligned error and the error after the best similarity transform (Procrustes, Horn's quaternion method, six Jacobi
+    sweeps), fp64 arithmetic on fp32 inputs.  pred, gt [N,n,3] device fp32 (a row = one hand, n <= 4000); valid [N,n] (non-zero =
+    the point counts) or None; root: the index of the point both sets are centred on, or -1: then origin = (pred origins
+    [N,3], gt origins [N,3]) or None = no alignment.  group int32 [N] with n_groups: a row is scored when its group is in [0,
+    n_groups) and its flag (flags fp32 [N], None = all set) is > 0.5.  trans [N,3]: the camera translation of every row, for
+    the absolute root error and - pairs=True, rows 2p and 2p + 1 the left and right hand of pair p - the MRRPE terms.
+    Returns device tensors, nothing is copied to the host: 'e_ra', 'e_pa' [N,n] (-1 = not counted), 'row_f' [N,4] = ('mean_ra',
+    'mean_pa', 'scale', 'root_err'), 'row_i' int32 [N,2] = ('n_ra', 'n_pa'), and with xform=True 'xform' [N,8] (quaternion w x y
+    z, scale, translation: pred -> gt), with pairs=True 'pair_err' [N // 2]."""
+    _need_cuda(pred)
+    if pred.dim() != 3 or pred.shape[-1] != 3 or tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError('pred and gt must be [N,n,3], shaped alike')
+    dev = pred.device
+    N, n, _ = pred.shape
+    if not 1 <= n <= 4000:
+        raise ValueError('n = %d: 1..4000 points' % n)
+    root = int(root)
+    if not -1 <= root < n:
+        raise ValueError('root %d outside -1..%d' % (root, n - 1))
+    f32 = lambda t, shape, name: _score_arg(t, dev, torch.float32, shape, name)
+    p, g = pred.to(dev, torch.float32).contiguous(), gt.to(dev, torch.float32).contiguous()
+    v = _score_arg(valid, dev, torch.uint8, (N, n), 'valid', as_bool=True)
+    if origin is not None and len(origin) != 2:
+        raise ValueError('origin is a pair (pred origins, gt origins), each [N,3]')
+    o = [None, None] if origin is None else [f32(t, (N, 3), 'origin') for t in origin]
+    t, fl = f32(trans, (N, 3), 'trans'), f32(flags, (N,), 'flags')
+    gr = _score_arg(group, dev, torch.int32, (N,), 'group')
+    raw = score_outputs(N, n, dev, xform, pairs)
+    _lib.check(_lib.lib().acrmi_pose_errors(_p(p), _p(g), _p(v), N, n, root, _p(o[0]), _p(o[1]), _p(t), _p(gr), int(n_groups), _p(fl),
+                                            *[_p(x) for x in raw.values()], _s(p)))
+    return score_result(raw)
+
+
+def _score_arg(t, dev, dtype, shape, name, as_bool=False):
+    """An optional argument of the scoring calls on the device, contiguous, of `dtype` and `shape` (None stays None)."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError('%s must be %s, got %s' % (name, list(shape), list(t.shape)))
+    if as_bool and t.dtype != torch.uint8:
+        t = t != 0
+    return t.to(dev, dtype).contiguous()
+
+
+def score_accumulate(board, pair_board, res, n_groups, n_bins, bin_width, group=None, flags=None, stream=None):
+    """Adds the rows of one pose_errors result `res` to a board (acrmi_score_accumulate): board / pair_board are int64 device
+    tensors of acrmi_score_board_bytes / acrmi_score_pair_bytes (pair_board may be None); group and flags as pose_errors took
+    them.  Asynchronous; engine.ScoreBoard is the object that owns such buffers."""
+    e = res['e_ra']
+    N, n = e.shape
+    dev = e.device
+    gr = _score_arg(group, dev, torch.int32, (N,), 'group')
+    fl = _score_arg(flags, dev, torch.float32, (N,), 'flags')
+    _lib.check(_lib.lib().acrmi_score_accumulate(_p(e), _p(res['e_pa']), N, n, _p(gr), int(n_groups), _p(fl), _p(res.get('pair_err')),
+                                                 int(n_bins), float(bin_width), _p(board), _p(pair_board),
+                                                 _s(e) if stream is None else C.c_void_p(stream)))
+
+
 # ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------
 # mano/skeleton.txt (first 21 rows) of the reference: five fingers of four joints, tip to base, then the wrist (no parent)
 SKELETON_PARENTS = (1, 2, 3, 20, 5, 6, 7, 20, 9, 10, 11, 20, 13, 14, 15, 20, 17, 18, 19, 20, -1)

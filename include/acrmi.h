@@ -782,6 +782,73 @@ int acrmi_surface_contact(acrmi_ctx* ctx, const float* verts_dev, const float* c
                           int32_t* cross_dev, float* sum_f_dev, int32_t* sum_i_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Scoring against ground truth (csrc/score_plan.h, csrc/score.hip): MPJPE / MPVPE root-aligned and
+ * Procrustes-aligned, per point and per row, and a device-resident BOARD of running sums (per-joint tables, a histogram for
+ * the PCK curve, MRRPE) that the host visits once, at the end.  The reference ships no evaluation code.
+ * Inputs fp32, arithmetic fp64 with every operation rounded on its own; outputs are the fp64 value rounded to fp32.  A row is
+ * one hand, a point set n <= 4000 points.
+ *  counted   point i counts when valid[i] != 0 (or there is no valid array) and the six coordinates of P[i] (prediction) and
+ *            G[i] (truth) are finite.  A row is SCORED when group[row] is in [0, n_groups) and its flag is > 0.5 (no flags:
+ *            every row is flagged; no groups: group 0); a MISS when the group is in range and the flag is not set - counted
+ *            per group, enters no error; a group out of range (negative, >= n_groups, INT_MIN): the row is not looked at.  A
+ *            row that is not scored has -1 in its per-point outputs and in row_f, and zero counts.
+ *  origins   oP, oG = P[root], G[root] when root >= 0, else the rows of the two origin arrays, else zero; GOOD when the root
+ *            point is counted / the six values are finite.
+ *  e_ra      |(P[i] - oP) - (G[i] - oG)| of a counted point of a row with good origins; |d| = sqrt((dx*dx + dy*dy) + dz*dz).
+ *  sums      over the points: thread t of T (64 when n <= 64, else 256) adds its points t, t + T, ... in ascending order (a
+ *            point that does not count adds +0), then the fixed tree for (s = T/2; s >= 1; s /= 2) v[t] += v[t + s], t < s.
+ *  e_pa      over the c counted points: means muP, muG; Pc = P - muP, Gc = G - muG; S[a][b] = sum Pc_a Gc_b; vP = sum
+ *            (Pcx*Pcx + Pcy*Pcy) + Pcz*Pcz; Horn's (1987) symmetric 4 x 4 matrix N of S; cyclic Jacobi on N, pairs (0,1) (0,2)
+ *            (0,3) (1,2) (1,3) (2,3), exactly 6 sweeps, no convergence test: a zero a_pq is skipped, else theta = (a_qq - a_pp)
+ *            / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) with sign(0) = +1 (an overflowing theta^2 gives t =
+ *            0), c = 1 / sqrt(t^2 + 1), s = t c, a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, a_rp' = c a_rp - s a_rq, a_rq' = s a_rp
+ *            + c a_rq, the eigenvector columns alike.  The quaternion (w, x, y, z) is the eigenvector of the largest diagonal
+ *            element, the lowest index on a tie; R is built from it; scale = lambda / vP;
+ *            e_pa[i] = |(scale * (R Pc[i]) + muG) - G[i]|.  Only with c >= 3 and vP > 0.
+ *  row_f     [N,4]: mean e_ra, mean e_pa (the sum of the fp64 errors over their count; -1 without one), scale (-1 without
+ *            e_pa), |(oP + trans) - oG| (-1 without a finite trans or good origins).   row_i [N,2]: the two counts.
+ *  xform     [N,8], optional: quaternion, scale, translation muG - scale * (R muP) (zeros with scale -1 without e_pa).
+ *  pair_err  [N/2], optional: rows 2p, 2p + 1 are the left and right hand of pair p; |((oP_R + t_R) - (oP_L + t_L)) - (oG_R -
+ *            oG_L)| when both are scored, have good origins and a finite trans, else -1 (the MRRPE term).
+ *  board     of one point set, 8-byte words, per group: sum_ra[n], sum_pa[n] fp64, cnt_ra[n], cnt_pa[n] int64, hist[n_bins + 1]
+ *            int64 of the set's e_ra (bin min(n_bins, (int64)((double)e / bin_width)); -1 and NaN are never binned), rows
+ *            scored, rows missed.  The pair board: per (left group, right group) the pair_err sum fp64 and count int64.  A
+ *            call continues from the board's values and adds the fp32 outputs >= 0, converted to double, in ascending row
+ *            order: 2B rows in one call equal two calls of B rows bit for bit.  No floating-point atomics, no atomics on
+ *            global memory, one writer per element.  The defaults of the Python layer, 100 bins of 0.5 mm, are parameters.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of the board of a set of n points (0 for sizes outside n 1..4000, n_groups 1..16, n_bins 1..4096), of the pair board. */
+size_t acrmi_score_board_bytes(int n, int n_groups, int n_bins);
+size_t acrmi_score_pair_bytes(int n_groups);
+/* pred_dev, gt_dev [N,n,3] fp32; valid_dev [N,n] bytes or NULL; root in -1..n-1; origin_pred_dev / origin_gt_dev [N,3] (both or
+ * neither; read when root < 0); trans_dev [N,3] or NULL; group_dev [N] int32 or NULL; flags_dev [N] fp32 or NULL.  Outputs
+ * e_ra_dev, e_pa_dev [N,n], row_f_dev [N,4], row_i_dev [N,2], optional xform_dev [N,8] and pair_err_dev [N/2].  N * n * 3 at
+ * most 2^31 - 1.  Pointers and sizes are checked before any GPU call (ACRMI_EINVAL); N == 0 is success and touches nothing. */
+int acrmi_pose_errors(const float* pred_dev, const float* gt_dev, const uint8_t* valid_dev, int N, int n, int root,
+                      const float* origin_pred_dev, const float* origin_gt_dev, const float* trans_dev, const int32_t* group_dev,
+                      int n_groups, const float* flags_dev, float* e_ra_dev, float* e_pa_dev, float* row_f_dev, int32_t* row_i_dev,
+                      float* xform_dev, float* pair_err_dev, void* stream);
+/* Adds the rows of one acrmi_pose_errors call to a board: e_ra_dev, e_pa_dev, pair_err_dev (or NULL) as it wrote them, group_dev
+ * and flags_dev as it took them; board_dev acrmi_score_board_bytes(), pair_board_dev acrmi_score_pair_bytes() or NULL, both 8-byte
+ * aligned, zeroed by the caller before the first call.  n_bins 1..4096, bin_width finite and > 0. */
+int acrmi_score_accumulate(const float* e_ra_dev, const float* e_pa_dev, int N, int n, const int32_t* group_dev, int n_groups,
+                           const float* flags_dev, const float* pair_err_dev, int n_bins, double bin_width, void* board_dev,
+                           void* pair_board_dev, void* stream);
+/* The outputs of the forward calls against truth: joints_dev [B,K,2,21,3], verts_dev [B,K,2,778,3], slots_dev
+ * [B,K,2,ACRMI_SLOT], cam_trans_dev [B,K,2,3] or NULL (then no root error and no MRRPE); gt_joints_dev like joints_dev,
+ * gt_verts_dev like verts_dev or NULL, joint_valid_dev [B,K,2,21] bytes or NULL, group_dev [B,K,2] int32 or NULL = the side.
+ * Row = hand, flag = ACRMI_SLOT_FLAG.  Both point sets in one call: the joints with root = the context's centre index (< 0: no
+ * alignment), the vertices on the joints' origins; pairs are (left rank k, right rank k).  Outputs j_* as acrmi_pose_errors
+ * over n = 21, v_* over n = 778 (ignored without gt_verts_dev), pair_err_dev [B*K].  board_dev NULL, or the board of n = 21, then
+ * the board of n = 778, then the pair board, to which the call is added. */
+int acrmi_score_hands(acrmi_ctx* ctx, const float* joints_dev, const float* verts_dev, const float* slots_dev,
+                      const float* cam_trans_dev, const float* gt_joints_dev, const float* gt_verts_dev,
+                      const uint8_t* joint_valid_dev, const int32_t* group_dev, int B, int K, int n_groups, int n_bins,
+                      double bin_width, void* board_dev, float* j_e_ra_dev, float* j_e_pa_dev, float* j_row_f_dev,
+                      int32_t* j_row_i_dev, float* v_e_ra_dev, float* v_e_pa_dev, float* v_row_f_dev, int32_t* v_row_i_dev,
+                      float* pair_err_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Key-point skeleton and centre heat-map views: acr/visualization.py:228-300 (Visualizer.visulize_result_live with
  * show_items 'pj2d' / 'centermap', vis_keypoints, make_heatmaps), drawn on the device.  Nothing of PIL or cv2 is used; the
  * rules are (DESIGN.md "Key-point and heat-map views"):
