@@ -96,7 +96,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_assoc_step', 'acrmi_point_heads_multi', 'acrmi_contact_workspace', 'acrmi_mesh_contact', 'acrmi_contact',
            'acrmi_conv2d_group', 'acrmi_program_groups', 'acrmi_surface_contact_workspace', 'acrmi_mesh_surface_contact',
            'acrmi_surface_contact', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes', 'acrmi_pose_errors',
-           'acrmi_score_accumulate', 'acrmi_score_hands']
+           'acrmi_score_accumulate', 'acrmi_score_hands', 'acrmi_vertex_colors', 'acrmi_contact_values',
+           'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored']
 
 _lib = None
 
@@ -252,6 +253,13 @@ def lib():
     L.acrmi_score_accumulate.argtypes = [f32p, f32p, i32, i32, vp, i32, f32p, f32p, i32, C.c_double, vp, vp, vp]
     L.acrmi_score_hands.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p, u8p, vp, i32, i32, i32, i32, C.c_double, vp,
                                     f32p, f32p, f32p, vp, f32p, f32p, f32p, vp, f32p, vp]
+    L.acrmi_vertex_colors.argtypes = [f32p, vp, f32p, i32, i32, C.c_float, C.c_float, i32, f32p, u8p, i32, f32p, vp]
+    L.acrmi_contact_values.argtypes = [f32p, f32p, vp, i32, i32, i32, C.c_float, f32p, vp, vp]
+    L.acrmi_rasterize_colored.argtypes = [f32p, f32p, i32, i32, i32, vp, vp, vp, vp, f32p, f32p, f32p, i32, C.c_float, C.c_float,
+                                          u8p, u8p, i32, i32, i32, vp, vp, vp]
+    L.acrmi_render_colored.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, f32p, C.c_float, C.c_float, u8p, u8p, i32, i32, vp, vp]
+    L.acrmi_render_regions_colored.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, vp, f32p, C.c_float, C.c_float, u8p, u8p, i32,
+                                               i32, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',

@@ -20,6 +20,9 @@ The other views of Visualizer.visulize_result_live (acr/visualization.py:228-254
     views['pj2d'], views['centermap']                      # frames like the input; the centre view as [2 (left, right), ...]
 'pj2d' = the 21 projected key points of each hand as a coloured skeleton, 'centermap' = the left and right centre heat
 maps in false colour over the frame.  The 'j3d' plot and video or image files stay out of scope.
+Two views the reference does not have colour the meshes per VERTEX: 'contact' (with contact=) by the
+distance to the other hand, 'error' (with gt= that holds 'verts') by the error against truth -
+    results, views = acr.forward_batch(rgb512, paths, contact=True, render=rgb512, show_items=('mesh', 'contact'))
 """
 import logging
 
@@ -33,7 +36,24 @@ from .utils import (create_OneEuroFilter, get_remove_keys, img_preprocess, justi
                     reorganize_results, save_results, smooth_results)
 
 
-SHOW_ITEMS = ('mesh', 'pj2d', 'centermap', 'org_img')      # the views of acr/visualization.py:174-254 that are built
+# the views of acr/visualization.py:174-254 that are built, and the two per-vertex colour views
+SHOW_ITEMS = ('mesh', 'pj2d', 'centermap', 'org_img', 'contact', 'error')
+COLOR_ITEMS = ('contact', 'error')      # the meshes coloured per vertex: Engine.contact_colors / Engine.error_colors
+
+
+def check_color_items(items, contact=False, gt=None, where=None):
+    """The two per-vertex colour views among `items` need what they show: 'contact' the contact measure (contact=True or
+    'surface'), 'error' ground-truth vertices (gt= with 'verts').  where: the entry point that does not build them at all.
+    ValueError before anything runs."""
+    for name in items or ():
+        if name not in COLOR_ITEMS:
+            continue
+        if where is not None:
+            raise ValueError('show_items: %r is a view of forward_batch / forward_raw_batch without boxes=, not of %s' % (name, where))
+        if name == 'contact' and not contact:
+            raise ValueError("show_items: 'contact' colours the hands by the contact measure: it needs contact=True or contact='surface'")
+        if name == 'error' and (not isinstance(gt, dict) or gt.get('verts') is None):
+            raise ValueError("show_items: 'error' colours the hands by their vertex errors: it needs gt= with 'verts'")
 
 
 def check_show_items(show_items):
@@ -127,7 +147,9 @@ class ACR(object):
             print('no hand detected!')
             results = {path: {}}
         if self.renderer == 'hip':
-            self.rendering = self._views_single(bgr_frame, outputs, check_show_items(self.show_items))
+            items = check_show_items(self.show_items)
+            check_color_items(items, where='forward')
+            self.rendering = self._views_single(bgr_frame, outputs, items)
         return results
 
     def _forward_multi_single(self, bgr_frame, path):
@@ -274,7 +296,11 @@ class ACR(object):
         The return value is then (results, rendered); `results` is what it is without `render`.
         show_items: names from SHOW_ITEMS - the views to draw over `render` instead of the meshes alone; the return value is
         then (results, {name: frames}): 'mesh' as above, 'pj2d' the key-point skeletons, 'centermap' the left and right centre
-        heat maps as [2,B,H,W,3] (a list of [2,H_i,W_i,3] for a list of frames), 'org_img' the frames themselves.
+        heat maps as [2,B,H,W,3] (a list of [2,H_i,W_i,3] for a list of frames), 'org_img' the frames themselves; 'contact'
+        (needs contact=) the meshes coloured per vertex by the distance to the nearest hand of the other side - near is hot, 0.02
+        m and beyond blue, a vertex inside the other hand magenta - and 'error' (needs gt= with 'verts') by the root-aligned
+        vertex error, 0.02 m and beyond red (Engine.contact_colors / error_colors; the 0.02 m are parameters of the picture;
+        DESIGN.md section 22).  A hand without a partner, or without truth, keeps its flat colour.
         streams (needs -t): the video stream (camera) of each frame, ints in [0, max_streams), -1 = do not smooth this frame -
         every frame is smoothed with the One-Euro state of ITS stream (acr/main.py:69-83 per video) instead of the batch being
         one video; the state lives in a table of max_streams streams (default 256, fixed when the first such call creates
@@ -315,6 +341,7 @@ class ACR(object):
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
+        check_color_items(show_items, contact, gt)
         K = int(self.hands_per_side if max_hand is None else max_hand)
         results, eng, out = self._fused_call(rgb_u8_frames, paths, offsets=offsets, point_heads=point_heads,
                                              batch_semantics=batch_semantics, streams=streams, max_streams=max_streams, K=K,
@@ -322,12 +349,13 @@ class ACR(object):
                                              multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board)
         if render is None:
             return results
+        _add_vertex_colors(eng, out, K, show_items, render_bgr)
         if K != 1 or tracks is not None:      # the [B,K,...] shapes: K pairs per frame
             return results, _multi_views(self, eng, out, render, offsets, render_bgr, show_items)
 
         def draw(name):
-            if name == 'mesh':
-                return self._render_batch(eng, out, render, offsets, render_bgr)
+            if name == 'mesh' or name in COLOR_ITEMS:
+                return self._render_batch(eng, out, render, offsets, render_bgr, vertex_colors=out.get(('vertex_colors', name)))
             return self._overlay_batch(eng, out, render, name, offsets, render_bgr)
 
         return results, _views(show_items, render, draw)
@@ -395,11 +423,15 @@ class ACR(object):
             _add_score(eng, out, K, gt, board)
         return results_from_out(out, paths), eng, out
 
-    def _render_batch(self, eng, out, frames, offsets, bgr):
-        """The meshes over a tensor of frames (Engine.render) or a list of frames of different sizes."""
+    def _render_batch(self, eng, out, frames, offsets, bgr, vertex_colors=None):
+        """The meshes over a tensor of frames (Engine.render) or a list of frames of different sizes; vertex_colors
+        [B,2,778,3]: coloured per vertex."""
+        src = out if vertex_colors is None else dict(out, vertex_colors=vertex_colors)
+
         def draw(imgs, idx, place):
-            sub, off = _frames_of(out, offsets, idx, ('slots', 'verts', 'cam_trans'))
-            return eng.render(sub, imgs, offsets=off, focal_length=float(self.focal_length), bgr=bgr)
+            sub, off = _frames_of(src, offsets, idx, ('slots', 'verts', 'cam_trans', 'vertex_colors'))
+            kw = {} if vertex_colors is None else {'vertex_colors': sub['vertex_colors']}
+            return eng.render(sub, imgs, offsets=off, focal_length=float(self.focal_length), bgr=bgr, **kw)
 
         return _per_size(frames, draw, count=out['slots'].shape[0])
 
@@ -499,6 +531,7 @@ def _add_score(eng, out, K, gt, board):
     """out['score'] = the per-hand rows of Engine.score of `out` against gt ({'joints': row_f [N,4], 'verts': row_f or None}),
     added to `board` on the device when there is one."""
     res = eng.score(out, gt, board=board, max_hand=K, cam_trans=out['cam_trans'])
+    out['score_result'] = res      # (the per-vertex errors: the 'error' view)
     out['score'] = {'joints': res['joints']['row_f'], 'verts': None if res['verts'] is None else res['verts']['row_f']}
 
 
@@ -508,6 +541,16 @@ def _add_contact(eng, out, K, mode='vertex'):
     kw = {} if mode == 'vertex' else {'mode': mode}
     out['contact'] = dict(eng.contact(out, max_hand=K, cam_trans=out['cam_trans'], **kw), contact_dist=ops.CONTACT_DIST,
                           max_depth=ops.CONTACT_MAX_DEPTH)
+
+
+def _add_vertex_colors(eng, out, K, items, bgr):
+    """out[('vertex_colors', name)] [B,(K,)2,778,3] for the per-vertex colour views among `items`, at the package's default
+    parameters, from what _add_contact / _add_score left on `out`."""
+    for name in items or ():
+        if name == 'contact':
+            out[('vertex_colors', name)] = eng.contact_colors(out['contact'], out, max_hand=K, max_depth=out['contact']['max_depth'], bgr=bgr)
+        elif name == 'error':
+            out[('vertex_colors', name)] = eng.error_colors(out['score_result'], out, max_hand=K, bgr=bgr)
 
 
 def _contact_keys(con, b, k, h, K, index_of):
@@ -594,7 +637,8 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
     if len(frames) != B:
         raise ValueError('one frame to draw into per input frame')
     rows = (_whole_frame_offsets(B) if offsets is None else torch.as_tensor(offsets).to(torch.float32)).repeat_interleave(K, 0)
-    flat = {k: out[k].flatten(0, 1) for k in ('slots', 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans') if out.get(k) is not None}
+    flat = {k: out[k].flatten(0, 1) for k in ('slots', 'verts', 'joints', 'pj2d', 'pj2d_org', 'cam_trans') +
+            tuple(('vertex_colors', name) for name in COLOR_ITEMS) if out.get(k) is not None}
     # the centre maps are the frame's, not a pair's: drawn per frame, with pair 0's slots standing for the frame
     return _region_views(self, eng, flat, frames, rows, torch.arange(B).repeat_interleave(K), items, bgr=bgr,
                          centermap=lambda: self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, 'centermap', offsets, bgr))
@@ -633,11 +677,15 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     multi_point_heads: as forward_batch (without effect with boxes=: a region has one hand of each side).
     contact: as forward_batch.  With boxes= the two hands of a REGION are paired: every region has its own camera, so hands of
     different regions are never paired, also when the regions lie in one frame.
-    gt / board: as forward_batch.  With boxes= a region is a row: gt['joints'] is [n,2,21,3] for n regions."""
+    gt / board: as forward_batch.  With boxes= a region is a row: gt['joints'] is [n,2,21,3] for n regions.
+    show_items 'contact' / 'error' (DESIGN.md section 22): as forward_batch, also with render_format='nv12'; with boxes= - and
+    in track_raw_batch - a ValueError: the two views over regions are not built at this layer (Engine.render_regions takes
+    vertex_colors=)."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
     _check_contact(contact)
     _check_score(gt, board)
+    check_color_items(check_show_items(show_items), contact, gt, where=None if boxes is None else 'forward_raw_batch(boxes=)')
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
@@ -736,8 +784,9 @@ def _region_views(self, eng, out, canvas, offsets, box_frame, items, bgr=True, c
 
         def draw(imgs, idx, place):
             region_frame = _local_frames(frame_of, place)
-            if name == 'mesh':
-                return eng.render_regions(out, imgs, offsets, region_frame, focal_length=float(self.focal_length), bgr=bgr)
+            if name == 'mesh' or name in COLOR_ITEMS:
+                kw = {} if name == 'mesh' else {'vertex_colors': out[('vertex_colors', name)]}
+                return eng.render_regions(out, imgs, offsets, region_frame, focal_length=float(self.focal_length), bgr=bgr, **kw)
             return eng.overlay_regions(out, imgs, name, offsets, region_frame, bgr=bgr)
 
         return _per_size(canvas, draw, pair=name == 'centermap')
@@ -752,6 +801,7 @@ def _forward_regions(self, frames, paths, boxes, box_frame, render, show_items, 
     from .. import ops
     from .utils import img_preprocess_gpu
     items = check_show_items(show_items)
+    check_color_items(items, where='forward_raw_batch(boxes=)')
     if render and not region_views:
         bad = [name for name in (items or ['mesh']) if name not in ('pj2d', 'org_img')]
         if bad:
@@ -798,6 +848,7 @@ def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=No
     and returned in input order.  render_format='nv12': as forward_raw_batch."""
     from .. import ops
     items = check_show_items(show_items)
+    check_color_items(items, where='track_raw_batch')
     to_nv12, matrix = _check_render_args(frames, items, render, render_format, pixel_format, matrix)
     scale, min_size = ops.check_track_args(scale, min_size)
     frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)

@@ -3,6 +3,7 @@
 #include "acrmi_ctx.h"
 #include "score_plan.h"
 #include "surface_contact_plan.h"      // and contact_plan.h
+#include "vertex_color_plan.h"
 
 #include <initializer_list>
 #include <type_traits>
@@ -976,23 +977,25 @@ static const float kHandColors[6] = {0.46f, 0.59f, 0.64f, 0.94f, 0.71f, 0.53f};
 // the n_meshes hands the prep kernel described in sc, drawn into n_frames frames; one of view / mesh_view (or neither)
 static hipError_t render_launch(const acrmi_ctx* c, const RenderScratch& sc, const float* verts, const float* cam_trans,
                                 const float* view, const float* mesh_view, float focal, float visible_weight, const uint8_t* img_in,
-                                uint8_t* img_out, int32_t* ids_out, int n_meshes, int n_frames, int H, int W, hipStream_t stream) {
+                                uint8_t* img_out, int32_t* ids_out, int n_meshes, int n_frames, int H, int W, hipStream_t stream,
+                                const float* vcol = nullptr) {
   RenderArgs a{};
   a.verts = verts; a.trans = cam_trans; a.topo[0] = c->faces_topo[0]; a.topo[1] = c->faces_topo[1];
   a.mesh_topo = sc.mesh_topo; a.mesh_frame = sc.mesh_frame; a.rgb = sc.rgb; a.view = view; a.mesh_view = mesh_view;
   a.focal = focal; a.visible_weight = visible_weight; a.img_in = img_in; a.img_out = img_out; a.ids_out = ids_out;
-  a.ws = sc.ws;
+  a.ws = sc.ws; a.vcol = vcol;
   a.n_meshes = n_meshes; a.n_verts = 778; a.n_faces = c->n_faces[0]; a.n_frames = n_frames; a.H = H; a.W = W;
   return launch_render(a, stream);
 }
 
-int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
-                 const float* colors_host, float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out, int H,
-                 int W, int32_t* ids_out, void* stream) {
+// acrmi_render / acrmi_render_colored (colored: vcol must be there; B * 2 * 778 * 3 colours within 2^31 - 1)
+static int render_call(acrmi_ctx* c, const char* who, bool colored, const float* vcol, const float* verts, const float* cam_trans,
+                       const float* slots, int B, const float* offsets, const float* colors_host, float focal, float visible_weight,
+                       const uint8_t* img_in, uint8_t* img_out, int H, int W, int32_t* ids_out, void* stream) {
   if (!c || !verts || !cam_trans || !slots || !img_in || !img_out || B <= 0 || H <= 0 || W <= 0 || !(focal > 0.f) ||
-      !(visible_weight >= 0.f && visible_weight <= 1.f))
-    return fail(c, ACRMI_EINVAL, "acrmi_render: bad arguments");
-  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "acrmi_render: MANO faces not loaded (acrmi_load_faces)");
+      !(visible_weight >= 0.f && visible_weight <= 1.f) || (colored && (!vcol || !vertex_color_sizes_ok(2ll * B, 778))))
+    return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "%s: MANO faces not loaded (acrmi_load_faces)", who);
   ON_DEVICE(c);
   RenderScratch sc;
   if (int r = render_scratch(c, B, &sc)) return r;
@@ -1000,8 +1003,22 @@ int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const
                                     sc.mesh_frame, sc.mesh_topo, sc.rgb, sc.view, (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render prep: %s", hipGetErrorString(e));
   e = render_launch(c, sc, verts, cam_trans, offsets ? sc.view : nullptr, nullptr, focal, visible_weight, img_in, img_out, ids_out,
-                    2 * B, B, H, W, (hipStream_t)stream);
+                    2 * B, B, H, W, (hipStream_t)stream, vcol);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render: %s", hipGetErrorString(e));
+}
+
+int acrmi_render(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
+                 const float* colors_host, float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out, int H,
+                 int W, int32_t* ids_out, void* stream) {
+  return render_call(c, "acrmi_render", false, nullptr, verts, cam_trans, slots, B, offsets, colors_host, focal, visible_weight,
+                     img_in, img_out, H, W, ids_out, stream);
+}
+
+int acrmi_render_colored(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int B, const float* offsets,
+                         const float* colors_host, const float* vcol, float focal, float visible_weight, const uint8_t* img_in,
+                         uint8_t* img_out, int H, int W, int32_t* ids_out, void* stream) {
+  return render_call(c, "acrmi_render_colored", true, vcol, verts, cam_trans, slots, B, offsets, colors_host, focal,
+                     visible_weight, img_in, img_out, H, W, ids_out, stream);
 }
 
 // ---- contact between the hands of a row (csrc/contact.hip) ---------------------------------------------------------------
@@ -1136,15 +1153,15 @@ int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d,
 }
 
 // ---- views over regions (DESIGN.md "Views over regions") ------------------------------------------------------------------
-int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int n, const float* offsets,
-                         const int32_t* region_frame, const float* colors_host, float focal, float visible_weight,
-                         const uint8_t* img_in, uint8_t* img_out, int n_frames, int H, int W, int32_t* ids_out, void* stream) {
-  if (!c || !verts || !cam_trans || !slots || !offsets || !region_frame || !img_in || !img_out || n <= 0 || n_frames <= 0 ||
+static int render_regions_call(acrmi_ctx* c, const char* who, bool colored, const float* vcol, const float* verts,
+                               const float* cam_trans, const float* slots, int n, const float* offsets, const int32_t* region_frame,
+                               const float* colors_host, float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out,
+                               int n_frames, int H, int W, int32_t* ids_out, void* stream) {
+  if ((colored && (!vcol || n <= 0 || !vertex_color_sizes_ok(2ll * n, 778))) || !c || !verts || !cam_trans || !slots || !offsets || !region_frame || !img_in || !img_out || n <= 0 || n_frames <= 0 ||
       n_frames > OVERLAY_MAX_FRAMES || H <= 0 || W <= 0 || H > OVERLAY_MAX_DIM || W > OVERLAY_MAX_DIM || !(focal > 0.f) ||
       !(visible_weight >= 0.f && visible_weight <= 1.f) || n > 0x3fffffff || (c->n_faces[0] > 0 && 2ll * n * c->n_faces[0] > 0x7fffffffll))
-    return fail(c, ACRMI_EINVAL, "acrmi_render_regions: bad arguments");
-  if (!c->faces_topo[0] || !c->faces_topo[1])
-    return fail(c, ACRMI_ESTATE, "acrmi_render_regions: MANO faces not loaded (acrmi_load_faces)");
+    return fail(c, ACRMI_EINVAL, "%s: bad arguments", who);
+  if (!c->faces_topo[0] || !c->faces_topo[1]) return fail(c, ACRMI_ESTATE, "%s: MANO faces not loaded (acrmi_load_faces)", who);
   ON_DEVICE(c);
   RenderScratch sc;
   if (int r = render_scratch(c, n, &sc)) return r;
@@ -1153,8 +1170,23 @@ int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_tran
                                            (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, ACRMI_EHIP, "render region prep: %s", hipGetErrorString(e));
   e = render_launch(c, sc, verts, cam_trans, nullptr, sc.view, focal, visible_weight, img_in, img_out, ids_out, 2 * n, n_frames, H, W,
-                    (hipStream_t)stream);
+                    (hipStream_t)stream, vcol);
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "render regions: %s", hipGetErrorString(e));
+}
+
+int acrmi_render_regions(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int n, const float* offsets,
+                         const int32_t* region_frame, const float* colors_host, float focal, float visible_weight,
+                         const uint8_t* img_in, uint8_t* img_out, int n_frames, int H, int W, int32_t* ids_out, void* stream) {
+  return render_regions_call(c, "acrmi_render_regions", false, nullptr, verts, cam_trans, slots, n, offsets, region_frame, colors_host,
+                             focal, visible_weight, img_in, img_out, n_frames, H, W, ids_out, stream);
+}
+
+int acrmi_render_regions_colored(acrmi_ctx* c, const float* verts, const float* cam_trans, const float* slots, int n,
+                                 const float* offsets, const int32_t* region_frame, const float* colors_host, const float* vcol,
+                                 float focal, float visible_weight, const uint8_t* img_in, uint8_t* img_out, int n_frames, int H,
+                                 int W, int32_t* ids_out, void* stream) {
+  return render_regions_call(c, "acrmi_render_regions_colored", true, vcol, verts, cam_trans, slots, n, offsets, region_frame,
+                             colors_host, focal, visible_weight, img_in, img_out, n_frames, H, W, ids_out, stream);
 }
 
 int acrmi_overlay_regions(acrmi_ctx* c, int what, const float* slots, const float* pj2d_org, int n, const float* offsets,

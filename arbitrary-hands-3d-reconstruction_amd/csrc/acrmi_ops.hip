@@ -6,6 +6,7 @@
 #include "roi_plan.h"
 #include "score_plan.h"
 #include "track_plan.h"
+#include "vertex_color_plan.h"
 
 #include <initializer_list>
 #include <vector>
@@ -697,8 +698,8 @@ static int rasterize(const char* who, bool per_mesh, const float* verts_dev, con
                      int n_faces, const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
                      const int32_t* mesh_frame_dev, const float* rgb_dev, const float* view_dev, float focal,
                      float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int n_frames, int H, int W,
-                     int32_t* ids_out_dev, void* ws_dev, void* stream) {
-  if ((per_mesh && !view_dev) ||
+                     int32_t* ids_out_dev, void* ws_dev, void* stream, const float* vcol_dev = nullptr, bool colored = false) {
+  if ((per_mesh && !view_dev) || (colored && (!vcol_dev || !vertex_color_sizes_ok(n_meshes, n_verts))) ||
       !verts_dev || !topo_dev || !mesh_frame_dev || !rgb_dev || !img_in_dev || !img_out_dev || !ws_dev || n_meshes <= 0 ||
       n_verts <= 0 || n_verts > RENDER_MAX_VERTS || n_faces <= 0 || n_frames <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384 ||
       (long long)n_meshes * n_faces > 0x7fffffffll || n_frames > 65535 || !(focal > 0.f) ||
@@ -710,6 +711,7 @@ static int rasterize(const char* who, bool per_mesh, const float* verts_dev, con
   a.focal = focal; a.visible_weight = visible_weight;
   a.img_in = img_in_dev; a.img_out = img_out_dev; a.ids_out = ids_out_dev; a.ws = (char*)ws_dev;
   a.n_meshes = n_meshes; a.n_verts = n_verts; a.n_faces = n_faces; a.n_frames = n_frames; a.H = H; a.W = W;
+  a.vcol = vcol_dev;
   hipError_t e = launch_render(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "rasterize: %s", hipGetErrorString(e));
 }
@@ -732,6 +734,52 @@ int acrmi_rasterize_views(const float* verts_dev, const float* trans_dev, int n_
   return rasterize("acrmi_rasterize_views", true, verts_dev, trans_dev, n_meshes, n_verts, n_faces, topo_dev, topo2_dev,
                    mesh_topo_dev, mesh_frame_dev, rgb_dev, view_dev, focal, visible_weight, img_in_dev, img_out_dev, n_frames, H, W,
                    ids_out_dev, ws_dev, stream);
+}
+
+int acrmi_rasterize_colored(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                            const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                            const int32_t* mesh_frame_dev, const float* rgb_dev, const float* vcol_dev, const float* view_dev,
+                            int view_per_mesh, float focal, float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev,
+                            int n_frames, int H, int W, int32_t* ids_out_dev, void* ws_dev, void* stream) {
+  return rasterize("acrmi_rasterize_colored", view_per_mesh != 0, verts_dev, trans_dev, n_meshes, n_verts, n_faces, topo_dev,
+                   topo2_dev, mesh_topo_dev, mesh_frame_dev, rgb_dev, view_dev, focal, visible_weight, img_in_dev, img_out_dev,
+                   n_frames, H, W, ids_out_dev, ws_dev, stream, vcol_dev, true);
+}
+
+// ---- per-vertex colours (csrc/vertex_color.hip; csrc/vertex_color_plan.h) ----
+int acrmi_vertex_colors(const float* values_dev, const int32_t* flags_dev, const float* base_rgb_dev, int M, int V, float lo,
+                        float hi, int reverse, const float* flag_rgb_host, const uint8_t* lut_host, int bgr, float* vcol_dev,
+                        void* stream) {
+  const char* who = "acrmi_vertex_colors";
+  if (M < 0 || V < 1) return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d meshes of %d vertices)", who, M, V);
+  if (!vertex_color_range_ok(lo, hi)) return fail(nullptr, ACRMI_EINVAL, "%s: lo and hi must be finite, hi > lo", who);
+  if (!vertex_color_sizes_ok(M, V)) return fail(nullptr, ACRMI_EINVAL, "%s: %d meshes of %d vertices are beyond 2^31 - 1 elements", who, M, V);
+  if (M == 0) return ACRMI_OK;
+  if (!values_dev || !base_rgb_dev || !flag_rgb_host || !vcol_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  VertexColorArgs a{};
+  a.values = values_dev; a.flags = flags_dev; a.base_rgb = base_rgb_dev; a.vcol = vcol_dev; a.lo = lo; a.hi = hi;
+  a.flag_rgb[0] = flag_rgb_host[0]; a.flag_rgb[1] = flag_rgb_host[1]; a.flag_rgb[2] = flag_rgb_host[2];
+  a.reverse = reverse != 0; a.M = M; a.V = V;
+  if (lut_host) std::memcpy(a.lut, lut_host, 768);
+  else heatmap_default_lut(bgr != 0, a.lut);
+  const hipError_t e = launch_vertex_colors(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int acrmi_contact_values(const float* d2_dev, const float* s_dev, const int32_t* cross_dev, int B, int K, int V, float max_depth,
+                         float* value_dev, int32_t* flag_dev, void* stream) {
+  const char* who = "acrmi_contact_values";
+  if (B < 0 || K < 1 || K > ACRMI_MAX_HAND || V < 1)
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d rows, %d hands per side in 1..%d, %d vertices)", who, B, K, ACRMI_MAX_HAND, V);
+  if (!(max_depth >= 0.f)) return fail(nullptr, ACRMI_EINVAL, "%s: max_depth must be >= 0 (+inf allowed)", who);
+  if (!contact_values_sizes_ok(B, K, V)) return fail(nullptr, ACRMI_EINVAL, "%s: %d rows of %d x %d pairs of %d vertices are beyond 2^31 - 1 elements", who, B, K, K, V);
+  if ((s_dev != nullptr) == (cross_dev != nullptr))
+    return fail(nullptr, ACRMI_EINVAL, "%s: exactly one of s_dev (nearest-vertex measure) and cross_dev (surface measure)", who);
+  if (B == 0) return ACRMI_OK;
+  if (!d2_dev || !value_dev || !flag_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  const ContactValuesArgs a{d2_dev, s_dev, cross_dev, max_depth, value_dev, flag_dev, B, K, V};
+  const hipError_t e = launch_contact_values(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 
 // ---- the two contact measures between meshes (csrc/contact.hip; csrc/contact_plan.h, csrc/surface_contact_plan.h) ----

@@ -453,6 +453,8 @@ struct RenderArgs {
   char* ws;                      // render_workspace_bytes(M, n_faces)
   size_t ws_box_off, ws_rec_off; // (launch_render fills these)
   int n_meshes, n_verts, n_faces, n_frames, H, W;
+  const float* vcol;             // [M, n_verts, 3] base colour per VERTEX in [0,1], channel order of the image, or null: `rgb`.
+                                 // Last, so that the flat kernels read every other field where they always did.
 };
 constexpr int RENDER_MAX_VERTS = 4000;      // 16 bytes of LDS per vertex in the setup kernel
 long long mesh_topology_ints(int n_faces, int n_verts);
@@ -466,6 +468,29 @@ hipError_t launch_render_prep(const float* slots, const float* offsets, int B, i
 hipError_t launch_render_region_prep(const float* slots, const float* offsets, const int32_t* region_frame, int n, int n_frames,
                                      int H, int W, int slot_stride, int flag_at, const float* colors, int32_t* mesh_frame,
                                      int32_t* mesh_topo, float* rgb, float* mesh_view, hipStream_t s);
+
+// Per-vertex colours (csrc/vertex_color.hip; the rule: csrc/vertex_color_plan.h).
+struct VertexColorArgs {
+  const float* values;           // [M, V]
+  const int32_t* flags;          // [M, V] or null
+  const float* base_rgb;         // [M, 3]
+  float* vcol;                   // [M, V, 3]
+  float lo, hi;
+  float flag_rgb[3];
+  int reverse, M, V;
+  uint8_t lut[768];              // [256][3] in the image's channel order
+};
+hipError_t launch_vertex_colors(const VertexColorArgs& a, hipStream_t s);
+struct ContactValuesArgs {
+  const float* d2;               // [B*K*K, 2, V]
+  const float* s;                // the same shape (nearest-vertex measure), or null
+  const int32_t* cross;          // the same shape (surface measure), or null: exactly one of the two
+  float max_depth;
+  float* value;                  // [B, K, 2, V]
+  int32_t* flag;                 // [B, K, 2, V]
+  int B, K, V;
+};
+hipError_t launch_contact_values(const ContactValuesArgs& a, hipStream_t s);
 
 // The two contact measures between meshes (csrc/contact.hip): what both read and write, then what each adds.
 struct ContactFrame {

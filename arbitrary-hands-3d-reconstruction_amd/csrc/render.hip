@@ -11,6 +11,8 @@
 //                        -> their triangle boxes tested 256 at a time and compacted IN ORDER (ballot + mbcnt) into a list in
 //                        LDS -> every thread walks the list for its own pixel: exact coverage in int64, fp32 depth (1/Z,
 //                        larger wins, strict > so the lower global face id wins a tie), shade, blend, store.
+//                        With a colour per vertex (RenderArgs::vcol) its second instantiation takes the
+//                        base colour of a covered pixel from the three vertices of the winning triangle instead of rgb[mesh].
 // The depth buffer is a register per pixel; there are no atomics on global memory, so the result is deterministic.
 #include "kernels.h"
 #include "region_view_plan.h"
@@ -27,11 +29,13 @@ constexpr int LIST_CAP = 1024;        // compacted face ids held in LDS between 
 constexpr float SNAP = 256.f;         // sub-pixel units per pixel
 constexpr float SNAP_MAX = 4194304.f; // 2^22: largest snapped coordinate a triangle may carry
 constexpr float Z_NEAR = 0.05f;       // metres; a triangle with a vertex at or in front of it is dropped whole
+constexpr uint32_t NB_SWAPPED = 8u;   // TriRecord::nb
 
 struct TriRecord {   // 80 bytes; edge k is the one OPPOSITE vertex k (its value / area = the barycentric weight of vertex k)
   int32_t A[3], B[3];
   int32_t c_lo[3], c_hi[3];   // C of A*x + B*y + C, MINUS 1 on the edges that do not own their pixels (top-left rule)
-  uint32_t nb;                // bit k: edge k carries that -1
+  uint32_t nb;                // bit k (0..2): edge k carries that -1; bit 3: vertices 1 and 2 are the face's in the blob SWAPPED
+                              // (re-oriented to positive area) - read by the per-vertex colour path alone
   float inv_area;             // 1 / (twice the area, sub-pixel units squared)
   float iz[3], sz[3];         // 1/Z and shade/Z at the vertices
 };
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(256) void render_setup_kernel(RenderArgs a) {
     bool ok = siz[i0] > 0.f && siz[i1] > 0.f && siz[i2] > 0.f;
     if (ok) {
       long long area = (long long)(sx[i1] - sx[i0]) * (sy[i2] - sy[i0]) - (long long)(sy[i1] - sy[i0]) * (sx[i2] - sx[i0]);
-      if (area < 0) { const int t = i1; i1 = i2; i2 = t; area = -area; }
+      if (area < 0) { const int t = i1; i1 = i2; i2 = t; area = -area; r.nb = NB_SWAPPED; }
       ok = area != 0;
       if (ok) {
         const int vi[3] = {i0, i1, i2};
@@ -202,6 +206,35 @@ __device__ inline void shade_list(const TriRecord* __restrict__ recs, const int*
   }
 }
 
+// The base colour of a covered pixel from the colours of its visible triangle's vertices: the record's
+// barycentrics recomputed for this pixel - the same operations in the same order as shade_list, so d is the depth value that won -
+// and the face's three indices from the topology blob, vertices 1 and 2 exchanged when the record was re-oriented.
+// Bounds: gid < n_meshes * n_faces names a record the setup kernel wrote for a drawn mesh; the indices come from a blob that
+// acrmi_mesh_topology validated (each in [0, n_verts)), so vcol is read inside [n_meshes, n_verts, 3] whatever the colours hold.
+__device__ inline void vertex_base_color(const RenderArgs& a, const TriRecord* __restrict__ recs, int gid, int px, int py, float* base) {
+  const TriRecord& r = recs[gid];
+  float b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const long long C = (long long)(((unsigned long long)(uint32_t)r.c_hi[k] << 32) | (uint32_t)r.c_lo[k]);
+    const long long e = (long long)r.A[k] * px + ((long long)r.B[k] * py + C);
+    b[k] = (float)(e + ((r.nb >> k) & 1)) * r.inv_area;
+  }
+  const float w0 = b[0] * r.iz[0], w1 = b[1] * r.iz[1], w2 = b[2] * r.iz[2];
+  const float d = (w0 + w1) + w2;
+  const int mesh = gid / a.n_faces, f = gid - mesh * a.n_faces;
+  const int32_t* topo = (a.mesh_topo && a.mesh_topo[mesh] == 1 && a.topo[1]) ? a.topo[1] : a.topo[0];
+  const int32_t* face = topo + 2 + 3 * f;
+  const bool swapped = (r.nb & NB_SWAPPED) != 0;
+  const int i0 = face[0], i1 = swapped ? face[2] : face[1], i2 = swapped ? face[1] : face[2];
+  const float* vc = a.vcol + (size_t)mesh * a.n_verts * 3;
+  const float *c0 = vc + 3 * i0, *c1 = vc + 3 * i1, *c2 = vc + 3 * i2;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) base[c] = ((w0 * c0[c] + w1 * c1[c]) + w2 * c2[c]) / d;
+}
+
+// COLOR: the base colour of a pixel comes from a.vcol (vertex_base_color) instead of a.rgb; everything else is the same code.
+template <bool COLOR>
 __global__ __launch_bounds__(256) void render_tile_kernel(RenderArgs a) {
   __shared__ int s_list[LIST_CAP];
   __shared__ int s_mesh[256];
@@ -270,7 +303,14 @@ __global__ __launch_bounds__(256) void render_tile_kernel(RenderArgs a) {
     }
     return;
   }
-  const float* rgb = a.rgb + (size_t)(st.id / a.n_faces) * 3;
+  float vbase[3];
+  const float* rgb;
+  if (COLOR) {
+    vertex_base_color(a, recs, st.id, px, py, vbase);
+    rgb = vbase;
+  } else {
+    rgb = a.rgb + (size_t)(st.id / a.n_faces) * 3;
+  }
   const float w = a.visible_weight, iw = 1.f - w;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -316,7 +356,8 @@ hipError_t launch_render(const RenderArgs& a0, hipStream_t s) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int tiles = ((a.W + TILE - 1) / TILE) * ((a.H + TILE - 1) / TILE);
-  hipLaunchKernelGGL(render_tile_kernel, dim3(tiles, a.n_frames), dim3(256), 0, s, a);
+  if (a.vcol) hipLaunchKernelGGL(render_tile_kernel<true>, dim3(tiles, a.n_frames), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(render_tile_kernel<false>, dim3(tiles, a.n_frames), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -854,8 +854,14 @@ class Engine(object):
         return offsets
 
     def _render(self, out, src, n, name, offsets, region_frame, cam_trans, focal_length, visible_weight, colors, bgr, dst,
-                return_ids, stream):
-        """acrmi_render (region_frame None) / acrmi_render_regions of the n frames / regions of `out` over src."""
+                return_ids, stream, vertex_colors=None):
+        """acrmi_render (region_frame None) / acrmi_render_regions of the n frames / regions of `out` over src; with
+        vertex_colors [n,2,778,3] their _colored forms."""
+        vcol = None
+        if vertex_colors is not None:
+            if not vertex_colors.is_cuda or tuple(vertex_colors.shape) != (n, 2, 778, 3):
+                raise ValueError('vertex_colors must be [%d,2,778,3] on the device' % n)
+            vcol = vertex_colors.to(self.device, torch.float32).contiguous()
         N, H, W, _ = src.shape
         st = _stream(self.device) if stream is None else C.c_void_p(stream)
         cam_trans = self._cam_trans(out, cam_trans, n, focal_length, st)
@@ -864,13 +870,15 @@ class Engine(object):
         ids = torch.empty(N, H, W, dtype=torch.int32, device=self.device) if return_ids else None
         verts, slots = out['verts'].contiguous(), out['slots'].contiguous()
         head = (self.ctx, _ptr(verts), _ptr(cam_trans), _ptr(slots), n, _ptr(offsets))
-        tail = (None if col is None else col.ctypes.data_as(C.c_void_p), float(focal_length), float(visible_weight), _ptr(src),
-                _ptr(dst))
+        tail = ((None if col is None else col.ctypes.data_as(C.c_void_p),) + (() if vcol is None else (_ptr(vcol),)) +
+                (float(focal_length), float(visible_weight), _ptr(src), _ptr(dst)))
         if region_frame is None:
-            _lib.check(self.L.acrmi_render(*head, *tail, H, W, _ptr(ids), st), self.ctx)
+            call = self.L.acrmi_render if vcol is None else self.L.acrmi_render_colored
+            _lib.check(call(*head, *tail, H, W, _ptr(ids), st), self.ctx)
         else:
-            _lib.check(self.L.acrmi_render_regions(*head, _ptr(region_frame), *tail, N, H, W, _ptr(ids), st), self.ctx)
-        self._render_keep = (verts, slots, cam_trans, offsets, region_frame, src)      # referenced until the next call has been queued
+            call = self.L.acrmi_render_regions if vcol is None else self.L.acrmi_render_regions_colored
+            _lib.check(call(*head, _ptr(region_frame), *tail, N, H, W, _ptr(ids), st), self.ctx)
+        self._render_keep = (verts, slots, cam_trans, offsets, region_frame, src, vcol)      # referenced until the next call has been queued
         return (dst, ids) if return_ids else dst
 
     def _overlay(self, out, src, n, name, what, kps_key, offsets, region_frame, bgr, dst, stream):
@@ -902,7 +910,7 @@ class Engine(object):
         return dst
 
     def render(self, out, images, offsets=None, cam_trans=None, focal_length=1265., visible_weight=0.9, colors=None,
-               bgr=False, dst=None, return_ids=False, stream=None):
+               bgr=False, dst=None, return_ids=False, stream=None, vertex_colors=None):
         """The hands of `out` (what `forward(..., project=True)` returned: slots, verts, joints, pj2d) drawn over `images`
         (acrmi_render; the reference's Visualizer 'mesh' view, acr/visualization.py:100-218, conventions in DESIGN.md
         "Rendering").  images uint8 [B,H,W,3] on the device: the 512 x 512 network input when offsets is None, else the
@@ -910,13 +918,15 @@ class Engine(object):
         slot's flag is set.  cam_trans [B,2,3]: computed from out['joints'] / out['pj2d'] (acrmi_cam_trans) when None.
         colors [2,3] left / right in the images' channel order (default: the reference's, RGB or - bgr=True - BGR).
         dst: uint8 tensor like images to draw into (may be `images` itself: in place).  Returns the frames, or (frames,
-        ids int32 [B,H,W] = (2 * frame + hand) * F + face, -1 where no hand is) with return_ids.  stream: as `forward`."""
+        ids int32 [B,H,W] = (2 * frame + hand) * F + face, -1 where no hand is) with return_ids.  stream: as `forward`.
+        vertex_colors [B,2,778,3] device fp32 (contact_colors / error_colors / ops.vertex_colors): a base colour per vertex in
+        the images' channel order instead of `colors` (acrmi_render_colored)."""
         src = self._check_frames(images, 'images', 'B')
         B = src.shape[0]
         if tuple(out['verts'].shape) != (B, 2, 778, 3) or tuple(out['slots'].shape) != (B, 2, _lib.SLOT):
             raise ValueError('out does not hold the results of %d frames' % B)
         return self._render(out, src, B, 'images', self._frame_offsets(offsets, B), None, cam_trans, focal_length, visible_weight,
-                            colors, bgr, dst, return_ids, stream)
+                            colors, bgr, dst, return_ids, stream, vertex_colors)
 
     def overlay(self, out, images, what, offsets=None, bgr=False, dst=None, stream=None):
         """The reference's other two views of a result over `images` (acrmi_overlay; acr/visualization.py:228-300, rules in
@@ -1030,19 +1040,89 @@ class Engine(object):
         return src, o.to(self.device, torch.float32).contiguous(), rf.to(self.device, torch.int32).contiguous()
 
     def render_regions(self, out, frames, offsets, region_frame, cam_trans=None, focal_length=1265., visible_weight=0.9,
-                       colors=None, bgr=False, dst=None, return_ids=False, stream=None):
+                       colors=None, bgr=False, dst=None, return_ids=False, stream=None, vertex_colors=None):
         """`render` for the results of a forward on n REGIONS of interest (acrmi_render_regions; DESIGN.md "Views over
         regions"): the hands of region i are drawn into frame region_frame[i] of `frames` (uint8 [N,H,W,3] on the device),
         mapped by the view of ITS `offsets` row; all hands of all regions of a frame go through one depth-tested pass.
         offsets [n,10] and region_frame [n] may be device tensors (out['offsets'] of track_step is one): the kernels read
         them, nothing here waits for the device.  A region whose window has no pixel, whose scale is not > 0 or whose
-        frame index is outside [0, N) draws nothing.  The other arguments as `render`; ids = (2 * region + hand) * F + face."""
+        frame index is outside [0, N) draws nothing.  The other arguments as `render` (vertex_colors [n,2,778,3]:
+        acrmi_render_regions_colored); ids = (2 * region + hand) * F + face."""
         n = out['slots'].shape[0]
         if tuple(out['verts'].shape) != (n, 2, 778, 3) or tuple(out['slots'].shape) != (n, 2, _lib.SLOT):
             raise ValueError('out does not hold the results of %d regions' % n)
         src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
         return self._render(out, src, n, 'frames', offsets, region_frame, cam_trans, focal_length, visible_weight, colors, bgr, dst,
-                            return_ids, stream)
+                            return_ids, stream, vertex_colors)
+
+    # ---- per-vertex colours: the contact and error views (DESIGN.md section 22) -----------------------------------------------
+    def _hand_base(self, lead, colors, bgr, tst):
+        """The flat colours `render` would give the hands of `lead` = (B,(K,)2) -> [hands,3] on the device, on torch stream tst."""
+        col = self._colors(colors, bgr)
+        col = np.asarray(HAND_COLORS_RGB, np.float32) if col is None else col
+        cache = self.__dict__.setdefault('_hand_base_cache', {})
+        pair = cache.get(col.tobytes())
+        if pair is None:      # six scalar fills, once per pair of colours: no copy from the host, so nothing waits for it
+            if len(cache) >= 16:
+                cache.clear()
+            with torch.cuda.stream(tst):
+                pair = torch.empty(2, 3, dtype=torch.float32, device=self.device)
+                for h in range(2):
+                    for c in range(3):
+                        pair[h, c] = float(col[h, c])
+            cache[col.tobytes()] = pair
+        with torch.cuda.stream(tst):
+            return pair.repeat(int(np.prod(lead[:-1])), 1)
+
+    def _lead(self, out, K):
+        slots = out['slots']
+        B = slots.shape[0]
+        lead = tuple(slots.shape[:-1])
+        if lead not in ((B, K, 2),) + (((B, 2),) if K == 1 else ()):
+            raise ValueError('out does not hold %d rows of %d hand pairs' % (B, K))
+        return B, lead
+
+    def contact_colors(self, con, out, max_hand=1, far=0.02, max_depth=None, colors=None, bgr=False, flag_color=ops_mod.FLAG_COLOR,
+                       lut=None, stream=None):
+        """What `contact(out, max_hand=K[, mode=])` returned -> a colour per vertex for `render(..., vertex_colors=)`, on the GPU
+        (acrmi_contact_values + acrmi_vertex_colors): every vertex by its distance to the nearest hand of
+        the OTHER side in its row, near is hot (the default jet reversed: 0 m red, `far` and beyond blue); a vertex inside the
+        other hand (the measure's own rule, within max_depth - default ops.CONTACT_MAX_DEPTH) takes flag_color; a hand without
+        a computed pair keeps the flat colour `render` gives it (colors / bgr as there).  far = 0.02 m is a PARAMETER of the
+        picture, not a measurement.  Returns fp32 [B,(K,)2,778,3] shaped like out['slots']; nothing waits for the host."""
+        K = check_max_hand(max_hand)
+        B, lead = self._lead(out, K)
+        lo, hi = ops_mod.check_color_range(0.0, far)
+        tst = torch.cuda.current_stream(self.device) if stream is None else torch.cuda.ExternalStream(stream, device=self.device)
+        st = tst.cuda_stream
+        cv = ops_mod.contact_values(con, B, K, max_depth=max_depth, stream=st)
+        V = cv['value'].shape[-1]
+        vcol = ops_mod.vertex_colors(cv['value'].view(-1, V), lo, hi, flags=cv['flag'].view(-1, V), base=self._hand_base(lead, colors, bgr, tst),
+                                     flag_color=flag_color, lut=lut, reverse=True, bgr=bgr, stream=st)
+        return vcol.view(*lead, V, 3)
+
+    def error_colors(self, sc, out, max_hand=1, kind='ra', hi=0.02, colors=None, bgr=False, lut=None, stream=None):
+        """What `score(out, gt, max_hand=K)` returned (gt with 'verts') -> a colour per vertex for `render(..., vertex_colors=)`
+        (acrmi_vertex_colors): every vertex by its error against truth, kind='ra' root-aligned, 'pa'
+        Procrustes-aligned - 0 m blue, `hi` and beyond red (the default jet).  A hand that scoring did not count, and a
+        vertex without an error, keeps the flat colour `render` gives it (colors / bgr as there): its -1 becomes NaN by a torch
+        operation on the device.  hi = 0.02 m is a PARAMETER of the picture, not a measurement.  Returns fp32
+        [B,(K,)2,778,3] shaped like out['slots']; nothing waits for the host."""
+        if kind not in ('ra', 'pa'):
+            raise ValueError("kind must be 'ra' or 'pa', not %r" % (kind,))
+        K = check_max_hand(max_hand)
+        B, lead = self._lead(out, K)
+        if not isinstance(sc, dict) or sc.get('verts') is None:
+            raise ValueError("sc holds no per-vertex errors: score(out, gt) with gt['verts']")
+        e = sc['verts']['e_' + kind]
+        if tuple(e.shape) != (B * K * 2, 778) or not e.is_cuda:
+            raise ValueError('sc does not hold the scores of %d rows of %d hand pairs' % (B, K))
+        lo, hi = ops_mod.check_color_range(0.0, hi)
+        tst = torch.cuda.current_stream(self.device) if stream is None else torch.cuda.ExternalStream(stream, device=self.device)
+        with torch.cuda.stream(tst):
+            values = e.masked_fill(e < 0, float('nan'))
+        vcol = ops_mod.vertex_colors(values, lo, hi, base=self._hand_base(lead, colors, bgr, tst), lut=lut, bgr=bgr, stream=tst.cuda_stream)
+        return vcol.view(*lead, 778, 3)
 
     def overlay_regions(self, out, frames, what, offsets, region_frame, bgr=False, dst=None, stream=None):
         """`overlay` for the results of a forward on n REGIONS (acrmi_overlay_regions; DESIGN.md "Views over regions").

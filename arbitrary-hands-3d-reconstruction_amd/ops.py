@@ -939,7 +939,7 @@ def _topology_on(t, n_verts, device):
 
 
 def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None, view=None, focal_length=1265.,
-                  visible_weight=0.9, out=None, return_ids=False, topo_index=None, mesh_view=None):
+                  visible_weight=0.9, out=None, return_ids=False, topo_index=None, mesh_view=None, vertex_colors=None):
     """Draws M meshes over N equal-sized frames on the GPU (acrmi_rasterize; the reference's Visualizer 'mesh' view,
     acr/visualization.py:100-218, with the conventions of DESIGN.md "Rendering").
     verts [M,V,3] device fp32 (metres, camera axes); trans [M,3] added to them (cam_trans) or None.
@@ -951,6 +951,9 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
     canvas (view_from_offsets) or None = the 512 network input.  mesh_view [M,4]: such a row per MESH instead (exclusive with
     view; meshes of several regions of interest in one frame, DESIGN.md "Views over regions") - the depth that is compared
     is then mesh_view[m,0] / Z, one virtual camera per frame, and a mesh whose scale is not > 0 is not drawn.
+    vertex_colors [M,V,3] device fp32 (what ops.vertex_colors returns): a base colour in [0,1] per VERTEX, in the images'
+    channel order, interpolated perspective-correctly over every triangle (acrmi_rasterize_colored); it
+    replaces `colors` for every mesh of the call, with view= and with mesh_view=.
     out: uint8 tensor like images (may BE images: in place).
     Returns out, or (out, ids int32 [N,H,W]: mesh * F + face of the visible triangle, -1 = none) with return_ids."""
     if view is not None and mesh_view is not None:
@@ -994,6 +997,12 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
         vw = torch.as_tensor(mesh_view, dtype=torch.float32).to(dev).contiguous()
         if tuple(vw.shape) != (M, 4):
             raise ValueError('mesh_view must be [M,4]')
+    vc = None
+    if vertex_colors is not None:
+        _need_cuda(vertex_colors)
+        if tuple(vertex_colors.shape) != (M, V, 3):
+            raise ValueError('vertex_colors must be [M,V,3]')
+        vc = vertex_colors.to(dev, torch.float32).contiguous()
     src = images.contiguous()
     if out is None:
         out = torch.empty_like(src)
@@ -1003,11 +1012,107 @@ def render_meshes(verts, faces, images, mesh_frame=None, trans=None, colors=None
     L = _lib.lib()
     ws = torch.empty(int(L.acrmi_render_workspace(M, F)) + 256, dtype=torch.uint8, device=dev)
     ws_p = (ws.data_ptr() + 255) // 256 * 256
-    call = L.acrmi_rasterize if mesh_view is None else L.acrmi_rasterize_views
-    _lib.check(call(_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(mf), _p(c),
-                    _p(vw), float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids),
-                    C.c_void_p(ws_p), _s(src)))
+    head = (_p(v), _p(t), M, V, F, _p(topos[0]), _p(topos[1]) if pair else None, _p(ti), _p(mf), _p(c))
+    tail = (float(focal_length), float(visible_weight), _p(src), _p(out), N, H, W, _p(ids), C.c_void_p(ws_p), _s(src))
+    if vc is not None:
+        _lib.check(L.acrmi_rasterize_colored(*head, _p(vc), _p(vw), int(mesh_view is not None), *tail))
+    else:
+        call = L.acrmi_rasterize if mesh_view is None else L.acrmi_rasterize_views
+        _lib.check(call(*head, _p(vw), *tail))
     return (out, ids) if return_ids else out
+
+
+# ---- per-vertex colours: the contact and error views (csrc/vertex_color.hip) ------------------------
+FLAG_COLOR = (1.0, 0.0, 1.0)      # magenta: no entry of the default table, in either channel order
+
+
+def check_color_range(lo, hi):
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo) or not (abs(lo) <= 3.4028234e38 and abs(hi) <= 3.4028234e38):
+        raise ValueError('lo and hi must be finite fp32 values with hi > lo')
+    return lo, hi
+
+
+def _lut_arg(lut):
+    if lut is None:
+        return None
+    t = np.ascontiguousarray(np.asarray(lut.cpu() if isinstance(lut, torch.Tensor) else lut))
+    if t.dtype != np.uint8 or t.shape != (256, 3):
+        raise ValueError('lut must be uint8 [256,3]')
+    return t
+
+
+def vertex_colors(values, lo, hi, flags=None, base=None, flag_color=FLAG_COLOR, lut=None, reverse=False, bgr=False, out=None,
+                  stream=None):
+    """A scalar per vertex -> a colour per vertex for render_meshes(vertex_colors=) on the GPU (acrmi_vertex_colors; DESIGN.md
+    section 22).  values [M,V] device fp32; flags [M,V] device int32 or None.  Per vertex: flag != 0 -> flag_color; else a NaN
+    value -> base (the mesh keeps its flat colour there); else t = (v - lo) / (hi - lo) clamped to [0,1], entry int(t * 255)
+    of the table - 255 minus it with reverse=True - divided by 255.  base [M,3] or [3] (default: the reference's right-hand
+    colour, as render_meshes), flag_color [3], in the images' channel order; lut uint8 [256,3] in that order, None = the
+    default jet of overlay_tables(bgr).  lo, hi: finite, hi > lo (ValueError).  Returns fp32 [M,V,3] on the device of values;
+    nothing waits for the host."""
+    _need_cuda(values, flags, out)
+    if values.dim() != 2 or values.shape[1] < 1:
+        raise ValueError('values must be [M,V]')
+    lo, hi = check_color_range(lo, hi)
+    dev = values.device
+    M, V = values.shape
+    if M * V * 3 > 0x7fffffff:
+        raise ValueError('%d meshes of %d vertices are beyond 2^31 - 1 colour values' % (M, V))
+    val = values.to(dev, torch.float32).contiguous()
+    fl = None
+    if flags is not None:
+        if tuple(flags.shape) != (M, V):
+            raise ValueError('flags must be [M,V] like values')
+        fl = flags.to(dev, torch.int32).contiguous()
+    b = torch.as_tensor(HAND_COLORS_RGB[1] if base is None else base, dtype=torch.float32)
+    if b.numel() not in (3, 3 * M):
+        raise ValueError('base must be [M,3] or [3]')
+    b = (b.reshape(1, 3).repeat(M, 1) if b.numel() == 3 and M != 1 else b.reshape(M, 3)).to(dev).contiguous()
+    fc = np.ascontiguousarray(np.asarray(flag_color, np.float32))
+    if fc.shape != (3,):
+        raise ValueError('flag_color must be [3]')
+    table = _lut_arg(lut)
+    if out is None:
+        out = torch.empty(M, V, 3, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, V, 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous fp32 tensor [M,V,3] on the device of values')
+    st = _s(val) if stream is None else C.c_void_p(stream)
+    _lib.check(_lib.lib().acrmi_vertex_colors(_p(val), _p(fl), _p(b), M, V, lo, hi, int(bool(reverse)), fc.ctypes.data_as(C.c_void_p),
+                                              None if table is None else table.ctypes.data_as(C.c_void_p), int(bool(bgr)), _p(out), st))
+    return out
+
+
+def contact_values(con, B, K=1, max_depth=None, stream=None):
+    """What mesh_contact / mesh_surface_contact (or Engine.contact) returned for the B * K * K pairs of B rows at K hands per side
+    (pair (b*K + i)*K + j = left rank i, right rank j; direction 0 = the left hand) -> per HAND and vertex, on the GPU
+    (acrmi_contact_values): 'value' fp32 [B,K,2,V] = metres to the nearest hand of the other side in the
+    row (NaN when no pair of the hand was computed), 'flag' int32 [B,K,2,V] = 1 where the vertex is inside one of them by the
+    measure's own rule (side < 0, respectively crossings odd) within max_depth.  con: a dict with 'd2' [B*K*K,2,V] and 'side'
+    (nearest-vertex measure) or 'cross' (surface measure).  Nothing waits for the host."""
+    d2 = con['d2']
+    surface = con.get('cross') is not None
+    other = con['cross'] if surface else con.get('side')
+    if other is None:
+        raise ValueError("con must hold 'd2' and one of 'side' (mesh_contact) and 'cross' (mesh_surface_contact)")
+    _need_cuda(d2, other)
+    B, K = int(B), int(K)
+    if B < 0 or not 1 <= K <= _lib.MAX_HAND:
+        raise ValueError('B >= 0 and K in 1..%d' % _lib.MAX_HAND)
+    if d2.dim() != 3 or d2.shape[0] != B * K * K or d2.shape[1] != 2 or d2.shape[2] < 1 or tuple(other.shape) != tuple(d2.shape):
+        raise ValueError('d2 and %s must be [%d,2,V]' % ('cross' if surface else 'side', B * K * K))
+    max_depth = float(CONTACT_MAX_DEPTH if max_depth is None else max_depth)      # (a parameter, not a measurement)
+    if not max_depth >= 0:
+        raise ValueError('max_depth must be >= 0 (inf allowed)')
+    dev, V = d2.device, d2.shape[2]
+    d2 = d2.to(dev, torch.float32).contiguous()
+    other = other.to(dev, torch.int32 if surface else torch.float32).contiguous()
+    value = torch.empty(B, K, 2, V, dtype=torch.float32, device=dev)
+    flag = torch.empty(B, K, 2, V, dtype=torch.int32, device=dev)
+    st = _s(d2) if stream is None else C.c_void_p(stream)
+    _lib.check(_lib.lib().acrmi_contact_values(_p(d2), None if surface else _p(other), _p(other) if surface else None, B, K, V,
+                                               max_depth, _p(value), _p(flag), st))
+    return {'value': value, 'flag': flag}
 
 
 # ---- contact and interpenetration between meshes (csrc/contact.hip; DESIGN.md section 19) --------------------------------

@@ -942,6 +942,57 @@ int acrmi_overlay_regions(acrmi_ctx* ctx, int what, const float* slots_dev, cons
                           const float* offsets_dev, const int32_t* region_frame_dev, int bgr, const uint8_t* img_in_dev,
                           uint8_t* out_dev, uint8_t* out2_dev, int n_frames, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-vertex colours: the contact and error views (csrc/vertex_color_plan.h, csrc/vertex_color.hip,
+ * csrc/render.hip).  The reference has no such view.  All fp32, every operation rounded on its own, `/` and sqrt correctly
+ * rounded.
+ *  raster   with vcol [n_meshes,n_verts,3] (base colours in [0,1], the image's channel order) the base colour of a covered pixel
+ *           replaces rgb[mesh] for every mesh of the call.  v0, v1, v2 = the vertices of the pixel's visible triangle after
+ *           its re-orientation to positive area, b_k their barycentrics from the integer edge values, iz_k their depth values:
+ *             w_k = b_k * iz_k;  d = (w_0 + w_1) + w_2 (the depth value);
+ *             base_c = ((w_0 * vcol[v0][c] + w_1 * vcol[v1][c]) + w_2 * vcol[v2][c]) / d;
+ *             out_c = uint8(clamp(floor(((w * 255) * base_c) * shade + (1 - w) * img_c), 0, 255)).
+ *           Shade, coverage, depth test, tie rule and ids are those of acrmi_rasterize; a NaN colour gives 0; no colour value
+ *           moves a store, and vcol is read only at vertex indices of the (validated) topology blobs.
+ *  colours  per vertex: flag != 0 -> the flag colour; else a NaN value -> base_rgb[mesh]; else t = (v - lo) / (hi - lo) clamped
+ *           to [0,1] (infinities clamp), i = (int)(t * 255), with `reverse` 255 - i, colour_c = (float)lut[i][c] / 255.
+ *  values   what acrmi_contact / acrmi_surface_contact wrote for B rows at K hands per side -> per hand (b, k, side) and vertex:
+ *           the partners in ascending rank are, for left rank k, the pairs (b*K + k)*K + j in direction 0, for right rank k the
+ *           pairs (b*K + i)*K + k in direction 1; m2 = the smallest d2 over them (strict < from +inf: NaN and +inf never win),
+ *           value = sqrt(m2), NaN when m2 stayed +inf (no computed pair); flag = 1 when in any partner pair d2 <= m*m (m =
+ *           max_depth) and s < 0, respectively cross odd - the INSIDE rules above.
+ * No atomics, no host visit: deterministic; a row alone equals the row in a batch.
+ * ------------------------------------------------------------------------------------- */
+/* values_dev [M,V] fp32, flags_dev [M,V] int32 or NULL (no vertex flagged), base_rgb_dev [M,3], flag_rgb_host [3], lut_host
+ * [256][3] bytes in the image's channel order or NULL = the default table of acrmi_overlay_tables (flipped when bgr != 0), the
+ * way acrmi_draw_heatmaps takes its table; vcol_dev [M,V,3] out.  lo, hi finite, hi > lo; M * V * 3 at most 2^31 - 1; checked
+ * with the pointers before any GPU call (ACRMI_EINVAL).  M == 0 is success and touches nothing. */
+int acrmi_vertex_colors(const float* values_dev, const int32_t* flags_dev, const float* base_rgb_dev, int M, int V, float lo,
+                        float hi, int reverse, const float* flag_rgb_host, const uint8_t* lut_host, int bgr, float* vcol_dev,
+                        void* stream);
+/* d2_dev [B*K*K,2,V] and exactly one of s_dev fp32 (acrmi_contact) and cross_dev int32 (acrmi_surface_contact), shaped alike;
+ * K in 1..ACRMI_MAX_HAND; max_depth >= 0 (+inf allowed); outputs value_dev fp32 and flag_dev int32 [B,K,2,V].  B * K * K * 2 * V at
+ * most 2^31 - 1.  Checked before any GPU call; B == 0 is success and touches nothing. */
+int acrmi_contact_values(const float* d2_dev, const float* s_dev, const int32_t* cross_dev, int B, int K, int V, float max_depth,
+                         float* value_dev, int32_t* flag_dev, void* stream);
+/* acrmi_rasterize with vcol_dev [n_meshes,n_verts,3] (not NULL; rgb_dev is still required and not read for a colour);
+ * view_per_mesh == 0: view_dev [n_frames,4] or NULL as acrmi_rasterize; != 0: view_dev [n_meshes,4] as acrmi_rasterize_views. */
+int acrmi_rasterize_colored(const float* verts_dev, const float* trans_dev, int n_meshes, int n_verts, int n_faces,
+                            const int32_t* topo_dev, const int32_t* topo2_dev, const int32_t* mesh_topo_dev,
+                            const int32_t* mesh_frame_dev, const float* rgb_dev, const float* vcol_dev, const float* view_dev,
+                            int view_per_mesh, float focal, float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev,
+                            int n_frames, int H, int W, int32_t* ids_out_dev, void* ws_dev, void* stream);
+/* acrmi_render with vcol_dev [B,2,778,3] (not NULL). */
+int acrmi_render_colored(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int B,
+                         const float* offsets_dev, const float* colors_host, const float* vcol_dev, float focal,
+                         float visible_weight, const uint8_t* img_in_dev, uint8_t* img_out_dev, int H, int W, int32_t* ids_out_dev,
+                         void* stream);
+/* acrmi_render_regions with vcol_dev [n,2,778,3] (not NULL). */
+int acrmi_render_regions_colored(acrmi_ctx* ctx, const float* verts_dev, const float* cam_trans_dev, const float* slots_dev, int n,
+                                 const float* offsets_dev, const int32_t* region_frame_dev, const float* colors_host,
+                                 const float* vcol_dev, float focal, float visible_weight, const uint8_t* img_in_dev,
+                                 uint8_t* img_out_dev, int n_frames, int H, int W, int32_t* ids_out_dev, void* stream);
+
 /* Multi-GPU (replaces nn.DataParallel's scatter/gather, acr/main.py:61): frames are sharded by the caller, one
  * process per GPU; the only collective is ONE all-gather per batch of each rank's flat result buffer
  * [slots | verts | joints] over RCCL/xGMI.  recv_dev holds n_ranks * n_floats floats, rank-major.
