@@ -24,6 +24,7 @@ ASSOC_STATE = 41  # ACRMI_ASSOC_STATE
 SLOT_FLAG, SLOT_FLATIND, SLOT_SCORE, SLOT_CAM, SLOT_POSES, SLOT_BETAS, SLOT_PARAMS = 0, 1, 2, 3, 6, 54, 64
 E_INVAL, E_HIP, E_STATE, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5
 OVERLAY_SKELETON, OVERLAY_CENTERMAP = 0, 1      # acrmi_overlay `what`
+SEGM_NONE = 255      # ACRMI_SEGM_NONE: the label of a pixel the canvas does not cover
 
 
 class BufferDesc(C.Structure):
@@ -97,7 +98,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_conv2d_group', 'acrmi_program_groups', 'acrmi_surface_contact_workspace', 'acrmi_mesh_surface_contact',
            'acrmi_surface_contact', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes', 'acrmi_pose_errors',
            'acrmi_score_accumulate', 'acrmi_score_hands', 'acrmi_vertex_colors', 'acrmi_contact_values',
-           'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored']
+           'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored', 'acrmi_segm_tables',
+           'acrmi_segm_labels', 'acrmi_segm_stats_ws_ints', 'acrmi_segm_stats', 'acrmi_segment']
 
 _lib = None
 
@@ -260,11 +262,19 @@ def lib():
     L.acrmi_render_colored.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, f32p, C.c_float, C.c_float, u8p, u8p, i32, i32, vp, vp]
     L.acrmi_render_regions_colored.argtypes = [vp, f32p, f32p, f32p, i32, f32p, vp, vp, f32p, C.c_float, C.c_float, u8p, u8p, i32,
                                                i32, i32, vp, vp]
+    L.acrmi_segm_tables.argtypes = [i32, i32, u8p]
+    L.acrmi_segm_labels.argtypes = [f32p, C.c_longlong, i32, i32, i32, i32, i32, f32p, f32p, C.c_float, u8p, i32, u8p, u8p, u8p,
+                                    i32, i32, vp]
+    L.acrmi_segm_stats_ws_ints.argtypes = [i32, i32, i32]
+    L.acrmi_segm_stats_ws_ints.restype = C.c_size_t
+    L.acrmi_segm_stats.argtypes = [u8p, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.acrmi_segment.argtypes = [vp, i32, f32p, C.c_float, u8p, i32, u8p, u8p, u8p, i32, i32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
                         'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy', 'acrmi_contact_workspace',
-                        'acrmi_surface_contact_workspace', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes'):
+                        'acrmi_surface_contact_workspace', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes',
+                        'acrmi_segm_stats_ws_ints'):
             fn.restype = C.c_int
     _lib = L
     return L

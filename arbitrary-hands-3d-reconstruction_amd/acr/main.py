@@ -23,6 +23,9 @@ maps in false colour over the frame.  The 'j3d' plot and video or image files st
 Two views the reference does not have colour the meshes per VERTEX: 'contact' (with contact=) by the
 distance to the other hand, 'error' (with gt= that holds 'verts') by the error against truth -
     results, views = acr.forward_batch(rgb512, paths, contact=True, render=rgb512, show_items=('mesh', 'contact'))
+The network's own hand-part segmentation is the view 'segm' - the part labels in colour over the frame -
+and, with masks=True / masks='iou', three more keys of every hand dict: 'mask_area', 'mask_box', 'mask_iou' -
+    results, views = acr.forward_raw_batch(bgr_frames, paths, render=True, show_items=('mesh', 'segm'), masks='iou')
 """
 import logging
 
@@ -39,6 +42,7 @@ from .utils import (create_OneEuroFilter, get_remove_keys, img_preprocess, justi
 # the views of acr/visualization.py:174-254 that are built, and the two per-vertex colour views
 SHOW_ITEMS = ('mesh', 'pj2d', 'centermap', 'org_img', 'contact', 'error')
 COLOR_ITEMS = ('contact', 'error')      # the meshes coloured per vertex: Engine.contact_colors / Engine.error_colors
+MAP_ITEMS = ('segm',)                   # views of the network's other maps: the part segmentation (Engine.segment)
 
 
 def check_color_items(items, contact=False, gt=None, where=None):
@@ -57,14 +61,32 @@ def check_color_items(items, contact=False, gt=None, where=None):
 
 
 def check_show_items(show_items):
-    """None stays None; else the list of view names, ValueError for one that is not in SHOW_ITEMS."""
+    """None stays None; else the list of view names, ValueError for one that is not in SHOW_ITEMS or MAP_ITEMS."""
     if show_items is None:
         return None
     items = [show_items] if isinstance(show_items, str) else list(show_items)
     for name in items:
-        if name not in SHOW_ITEMS:
-            raise ValueError('show_items: %r is not one of %s' % (name, SHOW_ITEMS))
+        if name not in SHOW_ITEMS and name not in MAP_ITEMS:
+            raise ValueError('show_items: %r is not one of %s' % (name, SHOW_ITEMS + MAP_ITEMS))
     return items
+
+
+def check_masks(masks, where=None):
+    """masks= of forward_batch / forward_raw_batch: False, True or 'iou'; where: the entry point that does not build them."""
+    if not isinstance(masks, bool) and not (isinstance(masks, str) and masks == 'iou'):
+        raise ValueError("masks must be True, False or 'iou', not %r" % (masks,))
+    if masks and where is not None:
+        raise ValueError('masks= over regions is not built (%s): the part segmentation is a map per region, and overlapping '
+                         'regions of a frame would need a winner rule' % where)
+    return masks
+
+
+def check_map_items(items, where):
+    """'segm' among `items` over regions (`where`) is a ValueError before anything runs."""
+    for name in items or ():
+        if name in MAP_ITEMS:
+            raise ValueError('show_items: %r over regions is not built (%s): the part segmentation is a map per region, and '
+                             'overlapping regions of a frame would need a winner rule' % (name, where))
 
 
 class ACR(object):
@@ -176,7 +198,7 @@ class ACR(object):
 
     def _views_single(self, bgr_frame, outputs, items):
         """`rendering` of one forward(): 'mesh' -> 'mesh_rendering_orgimgs' (the reference's key), 'pj2d' -> [frame],
-        'centermap' -> [(left, right)], 'org_img' -> [frame]; uint8 [H,W,3] BGR numpy, original size."""
+        'centermap' -> [(left, right)], 'segm' -> [frame], 'org_img' -> [frame]; uint8 [H,W,3] BGR numpy, original size."""
         from .. import ops
         views = {}
         frame = np.ascontiguousarray(np.asarray(bgr_frame, np.uint8))
@@ -202,6 +224,13 @@ class ACR(object):
                 img = torch.from_numpy(frame)[None].to(maps.device)
                 both = ops.draw_heatmaps(maps, img, view=ops.view_from_offsets(outputs['meta_data']['offsets'][:1]), bgr=True)
                 views['centermap'] = [(both[0, 0].cpu().numpy(), both[1, 0].cpu().numpy())]
+            elif name == 'segm':
+                if outputs is None or outputs.get('segms') is None:
+                    views['segm'] = [frame.copy()]
+                    continue
+                logits = outputs['segms'][:1].permute(0, 2, 3, 1).float().contiguous()      # NCHW -> [1,h,w,33]
+                img = torch.from_numpy(frame)[None].to(logits.device)
+                views['segm'] = [ops.draw_segm(logits, img, offsets=outputs['meta_data']['offsets'][:1], bgr=True)[0].cpu().numpy()]
         return views
 
     def _render_single(self, bgr_frame, outputs):
@@ -281,7 +310,8 @@ class ACR(object):
     @torch.no_grad()
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
-                      track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None, board=None):
+                      track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None, board=None,
+                      masks=False):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -335,9 +365,18 @@ class ACR(object):
         'group'} - scored on the GPU behind the fused call.  Every hand dict gains 'mpjpe', 'pa_mpjpe', 'mpvpe', 'pa_mpvpe' (only
         then): the hand's mean root-aligned and Procrustes-aligned joint and vertex errors in metres, nan for a hand without
         truth (its group outside the board's, no counted point, no 'verts').  board= (needs gt=): an engine.ScoreBoard the
-        batch is added to, on the device; its summary() is the data set's score.  With boxes= a region is a row."""
+        batch is added to, on the device; its summary() is the data set's score.  With boxes= a region is a row.
+        show_items 'segm' (DESIGN.md section 23): the network's hand-part segmentation in colour over the frames
+        (Engine.segment), like 'centermap' a view of the frame, not of a hand.
+        masks=True: every hand dict gains 'mask_area' - the pixels the segmentation gives the hand's SIDE - and 'mask_box' - the
+        smallest (l, t, r, b) around them, r and b exclusive, zeros when there are none - at the resolution of the frames given
+        to `render`, else on the 512 x 512 canvas.  The map has no instances: with max_hand > 1 every hand of a side carries its
+        side's values.  masks='iou': also 'mask_iou', the intersection over union of the side's mask and the side's drawn
+        silhouette (the rasteriser's ids over the same frames, or over a scratch canvas) - a check of the reconstruction against
+        image evidence that needs no ground truth; nan when both are empty."""
         _check_contact(contact)
         _check_score(gt, board)
+        check_masks(masks)
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
             raise ValueError('show_items needs the frames to draw over (render=)')
@@ -346,7 +385,8 @@ class ACR(object):
         results, eng, out = self._fused_call(rgb_u8_frames, paths, offsets=offsets, point_heads=point_heads,
                                              batch_semantics=batch_semantics, streams=streams, max_streams=max_streams, K=K,
                                              tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                             multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board)
+                                             multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board,
+                                             masks=masks, mask_frames=render, mask_offsets=offsets)
         if render is None:
             return results
         _add_vertex_colors(eng, out, K, show_items, render_bgr)
@@ -356,13 +396,15 @@ class ACR(object):
         def draw(name):
             if name == 'mesh' or name in COLOR_ITEMS:
                 return self._render_batch(eng, out, render, offsets, render_bgr, vertex_colors=out.get(('vertex_colors', name)))
+            if name in MAP_ITEMS:
+                return self._segm_batch(eng, out, render, offsets, render_bgr)
             return self._overlay_batch(eng, out, render, name, offsets, render_bgr)
 
         return results, _views(show_items, render, draw)
 
     def _fused_call(self, frames, paths, *, offsets=None, point_heads=True, batch_semantics=None, streams=None, max_streams=None,
                     K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None,
-                    board=None):
+                    board=None, masks=False, mask_frames=None, mask_offsets=None):
         """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).  K = 1 without
         tracks: one hand of each side, `point_heads` is the switch and multi_point_heads is checked and without effect.
         K > 1 or tracks=: Engine.forward(max_hand=K) on the dense heads, or with multi_point_heads (K > 1) at the K best centres.
@@ -421,6 +463,8 @@ class ACR(object):
             _add_contact(eng, out, K, 'surface' if contact == 'surface' else 'vertex')
         if gt is not None:
             _add_score(eng, out, K, gt, board)
+        if masks:
+            _add_masks(self, eng, out, masks == 'iou', mask_frames, mask_offsets)
         return results_from_out(out, paths), eng, out
 
     def _render_batch(self, eng, out, frames, offsets, bgr, vertex_colors=None):
@@ -452,6 +496,20 @@ class ACR(object):
             return ops.draw_heatmaps(sub['maps'], imgs, view=None if off is None else ops.view_from_offsets(off), bgr=bgr)
 
         return _per_size(frames, draw, count=B, pair=what == 'centermap')
+
+    def _segm_batch(self, eng, out, frames, offsets, bgr):
+        """'segm' over a tensor of frames (Engine.segment) or a list of frames of different sizes."""
+        from .. import ops
+        B = out['slots'].shape[0]
+
+        def draw(imgs, idx, place):
+            if idx is None:
+                return eng.segment(B, images=imgs, offsets=offsets, bgr=bgr, labels=False)['view']
+            # the context's map is that of the whole batch: a subset goes through the stand-alone operator
+            sub, off = _frames_of({'logits': _segm_logits(eng, B)}, offsets, idx, ('logits',))
+            return ops.draw_segm(sub['logits'], imgs, offsets=off, bgr=bgr)
+
+        return _per_size(frames, draw, count=B)
 
 
 def _whole_frame_offsets(B):
@@ -535,6 +593,66 @@ def _add_score(eng, out, K, gt, board):
     out['score'] = {'joints': res['joints']['row_f'], 'verts': None if res['verts'] is None else res['verts']['row_f']}
 
 
+def _segm_logits(eng, B):
+    """The part logits of the last program run, NHWC [B,256,256,33]: a view of the context's buffer, not a copy."""
+    return eng.buffer(eng.program['heads'].segm_buf, B, 33)
+
+
+def _mask_ids(self, eng, out, imgs, offsets, idx, place):
+    """The rasteriser's ids of the hands of `out` over imgs [n,H,W,3] (the frames idx of a _per_size group; drawn into a scratch
+    copy): (2 * row + hand) * F + face, so the left hand of every pair is the even mesh."""
+    focal = float(self.focal_length)
+    if out['slots'].dim() == 3:
+        sub, off = _frames_of(out, offsets, idx, ('slots', 'verts', 'cam_trans'))
+        return eng.render(sub, imgs, offsets=off, focal_length=focal, return_ids=True)[1]
+    B, K = out['slots'].shape[:2]      # K pairs per frame: pair k of frame b is region b * K + k with the frame's own row
+    flat = {k: out[k].flatten(0, 1) for k in ('slots', 'verts', 'cam_trans')}
+    region_frame = _local_frames(torch.arange(B).repeat_interleave(K), place)
+    return eng.render_regions(flat, imgs, torch.as_tensor(offsets).to(torch.float32).repeat_interleave(K, 0), region_frame,
+                              focal_length=focal, return_ids=True)[1]
+
+
+def _add_masks(self, eng, out, iou, frames, offsets):
+    """out['masks'] = the statistics of the part segmentation per frame, {'counts': [B,33], 'boxes': [B,2,4], 'agree': [B,2,3]
+    or None} (ops.segm_stats): at the resolution of `frames` (a tensor [B,H,W,3] or a list of B frames) under their offsets
+    rows, else on the 512 x 512 canvas; iou: with the rasteriser's ids of the same frames."""
+    from .. import ops
+    B = out['slots'].shape[0]
+    offsets = _whole_frame_offsets(B) if offsets is None else offsets
+    dev = out['slots'].device
+    n_faces = eng._faces['left'].shape[0] if iou and eng._faces.get('left') is not None else None
+    if iou and n_faces is None:
+        raise ValueError("masks='iou' compares the masks with the drawn meshes: it needs the MANO faces (mano tables with 'faces')")
+
+    def one(imgs, idx, place):
+        if imgs is None and iou:
+            imgs = torch.zeros(B, 512, 512, 3, dtype=torch.uint8, device=dev)      # a scratch canvas for the rasteriser
+        ids = _mask_ids(self, eng, out, imgs, offsets, idx, place) if iou else None
+        if idx is None:
+            st = eng.segment(B, images=imgs, offsets=offsets, stats=True, ids=ids, labels=False, draw=False)
+        else:
+            sub, off = _frames_of({'logits': _segm_logits(eng, B)}, offsets, idx, ('logits',))
+            st = ops.segm_stats(ops.segm_labels(sub['logits'], imgs.shape[1:3], offsets=off), 33, ids=ids, n_faces=n_faces)
+        n = st['counts'].shape[0]
+        agree = st['agree'].view(n, 6) if iou else torch.zeros(n, 6, dtype=torch.int32, device=dev)
+        return torch.cat([st['counts'], st['boxes'].view(n, 8), agree], 1)      # one row per frame
+
+    rows = one(None, None, None) if frames is None else _per_size(frames, one, count=B)
+    rows = (torch.stack(list(rows)) if isinstance(rows, (list, tuple)) else rows).cpu().numpy()
+    out['masks'] = {'counts': rows[:, :33], 'boxes': rows[:, 33:41].reshape(B, 2, 4), 'agree': rows[:, 41:].reshape(B, 2, 3) if iou else None}
+
+
+def mask_keys(ms, b, h):
+    """The mask keys of a hand of side h (0 left, 1 right) in frame b from out['masks']: its SIDE's values."""
+    counts = ms['counts'][b]
+    keys = {'mask_area': np.int32(counts[1:17].sum() if h == 1 else counts[17:33].sum()), 'mask_box': ms['boxes'][b, h].astype(np.int32)}
+    if ms['agree'] is not None:
+        inter, mask, sil = (int(v) for v in ms['agree'][b, h])
+        union = mask + sil - inter
+        keys['mask_iou'] = np.float32(inter / union) if union > 0 else np.float32(np.nan)
+    return keys
+
+
 def _add_contact(eng, out, K, mode='vertex'):
     """out['contact'] = Engine.contact of `out` at the package's default parameters, with the parameters beside it."""
     from .. import ops
@@ -596,6 +714,7 @@ def results_from_out(out, paths):
     con = out.get('contact')      # with contact=True: every hand dict gains the four contact keys
     if con is not None:
         con = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in con.items()}
+    ms = out.get('masks')      # with masks=: every hand dict gains its side's mask keys
     sc = out.get('score')      # with gt=: every hand dict gains the four score keys
     if sc is not None:
         from .. import score as score_mod
@@ -621,6 +740,8 @@ def results_from_out(out, paths):
                         hands[-1]['track_id'] = np.int32(ids[b, k, h])
                     if sc is not None:
                         hands[-1].update(score_mod.hand_score_keys(sc, (b * slots.shape[1] + k) * 2 + h))
+                    if ms is not None:
+                        hands[-1].update(mask_keys(ms, b, h))
                     where.append((k, h))
         if con is not None:
             index_of = {kh: n for n, kh in enumerate(where)}
@@ -641,13 +762,14 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
             tuple(('vertex_colors', name) for name in COLOR_ITEMS) if out.get(k) is not None}
     # the centre maps are the frame's, not a pair's: drawn per frame, with pair 0's slots standing for the frame
     return _region_views(self, eng, flat, frames, rows, torch.arange(B).repeat_interleave(K), items, bgr=bgr,
-                         centermap=lambda: self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, 'centermap', offsets, bgr))
+                         centermap=lambda: self._overlay_batch(eng, {'slots': out['slots'][:, 0]}, frames, 'centermap', offsets, bgr),
+                         segm=lambda: self._segm_batch(eng, out, frames, offsets, bgr))
 
 
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
                        max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False,
-                       gt=None, board=None):
+                       gt=None, board=None, masks=False):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -680,12 +802,18 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     gt / board: as forward_batch.  With boxes= a region is a row: gt['joints'] is [n,2,21,3] for n regions.
     show_items 'contact' / 'error' (DESIGN.md section 22): as forward_batch, also with render_format='nv12'; with boxes= - and
     in track_raw_batch - a ValueError: the two views over regions are not built at this layer (Engine.render_regions takes
-    vertex_colors=)."""
+    vertex_colors=).
+    show_items 'segm' and masks=: as forward_batch, the masks at the frames' own resolution with
+    render=True, also with render_format='nv12'; with boxes= - and 'segm' in track_raw_batch - a ValueError: views and masks
+    over regions are not built (several overlapping regions of a frame would need a winner rule)."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
     _check_contact(contact)
     _check_score(gt, board)
     check_color_items(check_show_items(show_items), contact, gt, where=None if boxes is None else 'forward_raw_batch(boxes=)')
+    check_masks(masks, where=None if boxes is None else 'forward_raw_batch(boxes=)')
+    if boxes is not None:
+        check_map_items(check_show_items(show_items), 'forward_raw_batch(boxes=)')
     if boxes is not None and tracks is not None:
         raise ValueError('tracks= with boxes= is not implemented: a region is one person (DESIGN.md section 18)')
     if boxes is not None and int(self.hands_per_side if max_hand is None else max_hand) != 1:
@@ -707,7 +835,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
                                  max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                 multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board)
+                                 multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board, masks=masks)
     if to_nv12 is None:
         return got
     return got[0], _views_to_nv12(to_nv12, got[1])
@@ -770,17 +898,22 @@ def _nv12_views(frames, pixel_format, matrix):
     return view, row6
 
 
-def _region_views(self, eng, out, canvas, offsets, box_frame, items, bgr=True, centermap=None):
+def _region_views(self, eng, out, canvas, offsets, box_frame, items, bgr=True, centermap=None, segm=None):
     """The views `items` (None: the meshes alone, not in a dict) of the n regions of `out` over their frames `canvas` - a
     tensor [N,H,W,3], or a list of frames of different sizes, drawn per size and returned in input order; 'centermap' is
     [2,N,H,W,3], respectively a list of [2,H_i,W_i,3].  offsets: the regions' rows, on the host or on the device.  bgr: the
-    frames' channel order.  centermap: a function that draws that view instead of Engine.overlay_regions."""
+    frames' channel order.  centermap: a function that draws that view instead of Engine.overlay_regions; segm: the function
+    that draws 'segm' (a view of whole frames: there is none over regions)."""
     n = out['slots'].shape[0]
     frame_of = torch.arange(n) if box_frame is None else torch.as_tensor(np.asarray(box_frame)).long()
 
     def one(name):
         if name == 'centermap' and centermap is not None:
             return centermap()
+        if name in MAP_ITEMS:
+            if segm is None:
+                check_map_items([name], 'region views')
+            return segm()
 
         def draw(imgs, idx, place):
             region_frame = _local_frames(frame_of, place)
@@ -849,6 +982,7 @@ def _track_raw_batch(self, frames, paths, boxes=None, box_frame=None, streams=No
     from .. import ops
     items = check_show_items(show_items)
     check_color_items(items, where='track_raw_batch')
+    check_map_items(items, 'track_raw_batch')
     to_nv12, matrix = _check_render_args(frames, items, render, render_format, pixel_format, matrix)
     scale, min_size = ops.check_track_args(scale, min_size)
     frame_hw = ops.region_frame_sizes(frames, box_frame, pixel_format)

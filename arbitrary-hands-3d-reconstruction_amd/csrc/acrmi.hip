@@ -1152,6 +1152,24 @@ int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d,
   return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "overlay: %s", hipGetErrorString(e));
 }
 
+// ---- the part segmentation of the last program run (csrc/segm.hip) -----------------------------------
+int acrmi_segment(acrmi_ctx* c, int B, const float* offsets, float weight, const uint8_t* colors_host, int bgr,
+                  const uint8_t* img_in, uint8_t* out, uint8_t* labels, int H, int W, void* stream) {
+  const char* who = "acrmi_segment";
+  if (!c) return fail(c, ACRMI_EINVAL, "%s: ctx is NULL", who);
+  if (B <= 0) return fail(c, ACRMI_EINVAL, "%s: B = %d", who, B);
+  if (!c->have_program || c->last_batch <= 0) return fail(c, ACRMI_ESTATE, "%s: no program has run", who);
+  if (B != c->last_batch)
+    return fail(c, ACRMI_ESTATE, "%s: the resident segmentation is that of a batch of %d, not %d", who, c->last_batch, B);
+  const int id = c->heads.segm_buf;
+  const acrmi_buffer_desc& d = c->bufs[id];
+  if (d.dtype != ACRMI_DT_F32) return fail(c, ACRMI_ESTATE, "%s: the segmentation buffer is not fp32", who);
+  ON_DEVICE(c);
+  // 33 classes (background + 16 parts of each hand: what attpool reads from this buffer) at the buffer's own geometry and stride
+  return segm_labels_call(c, who, (const float*)c->buf_ptr[id], (long long)d.h * d.w * d.cs, d.cs, B, d.h, d.w, 33, nullptr, offsets,
+                          weight, colors_host, bgr, img_in, out, labels, H, W, stream);
+}
+
 // ---- views over regions (DESIGN.md "Views over regions") ------------------------------------------------------------------
 static int render_regions_call(acrmi_ctx* c, const char* who, bool colored, const float* vcol, const float* verts,
                                const float* cam_trans, const float* slots, int n, const float* offsets, const int32_t* region_frame,

@@ -188,3 +188,7 @@ int decode_maps_impl(const float* l_center, const float* r_center, int center_cs
                      int params_cs, const float* l_prior, const float* r_prior, int prior_cs, int B, float conf_thresh,
                      const int32_t* prior_gate, const unsigned* poison, float* slots, void* stream,
                      int max_hand = 0 /* > 0: the top-K decode, slots [B,max_hand,2,ACRMI_SLOT] */);      // acrmi_ops.hip
+// acrmi_segm_labels for `who`: the argument checks, then the launch; errors go to c (null: the stand-alone operators')
+int segm_labels_call(acrmi_ctx* c, const char* who, const float* logits, long long frame_stride, int pix_stride, int n, int h, int w,
+                     int C, const float* view, const float* offsets, float weight, const uint8_t* colors_host, int bgr,
+                     const uint8_t* img_in, uint8_t* out, uint8_t* labels, int H, int W, void* stream);      // acrmi_ops.hip

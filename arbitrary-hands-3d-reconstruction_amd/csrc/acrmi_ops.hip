@@ -5,6 +5,7 @@
 #include "conv_frame.h"   // conv_shape
 #include "roi_plan.h"
 #include "score_plan.h"
+#include "segm_plan.h"
 #include "track_plan.h"
 #include "vertex_color_plan.h"
 
@@ -960,3 +961,61 @@ int acrmi_draw_region_heatmaps(const float* maps_l_dev, const float* maps_r_dev,
 }
 
 }  // extern "C"
+
+// ---- the part segmentation as an output (csrc/segm.hip; csrc/segm_plan.h) ----
+int acrmi_segm_tables(int bgr, int C, uint8_t* colors_host) {
+  if (!segm_classes_ok(C) || !colors_host)
+    return fail(nullptr, ACRMI_EINVAL, "acrmi_segm_tables: C = %d must be odd and in %d..%d, colors_host not NULL", C, SEGM_MIN_C, SEGM_MAX_C);
+  segm_default_colors(bgr != 0, C, colors_host);
+  return ACRMI_OK;
+}
+
+int segm_labels_call(acrmi_ctx* c, const char* who, const float* logits, long long frame_stride, int pix_stride, int n, int h, int w,
+                     int C, const float* view, const float* offsets, float weight, const uint8_t* colors_host, int bgr,
+                     const uint8_t* img_in, uint8_t* out, uint8_t* labels, int H, int W, void* stream) {
+  if (!segm_classes_ok(C)) return fail(c, ACRMI_EINVAL, "%s: C = %d must be odd and in %d..%d", who, C, SEGM_MIN_C, SEGM_MAX_C);
+  if (pix_stride < C) return fail(c, ACRMI_EINVAL, "%s: pix_stride %d is less than the %d classes of a cell", who, pix_stride, C);
+  if (!segm_dim_ok(h) || !segm_dim_ok(w) || !segm_dim_ok(H) || !segm_dim_ok(W) || n < 0 || n > SEGM_MAX_FRAMES)
+    return fail(c, ACRMI_EINVAL, "%s: bad sizes (%d frames of %d x %d from maps of %d x %d; each in 1..%d, at most %d frames)", who, n,
+                H, W, h, w, SEGM_MAX_DIM, SEGM_MAX_FRAMES);
+  if (frame_stride < (long long)h * w * pix_stride)
+    return fail(c, ACRMI_EINVAL, "%s: frame_stride %lld is less than %d x %d cells of %d floats", who, frame_stride, h, w, pix_stride);
+  if (!(weight >= 0.f && weight <= 1.f)) return fail(c, ACRMI_EINVAL, "%s: weight must be in [0, 1]", who);
+  if (view && offsets) return fail(c, ACRMI_EINVAL, "%s: view_dev or offsets_dev, not both", who);
+  if (!out && !labels) return fail(c, ACRMI_EINVAL, "%s: neither out_dev nor labels_dev: nothing to write", who);
+  if (out && !img_in) return fail(c, ACRMI_EINVAL, "%s: out_dev needs img_in_dev", who);
+  if (n == 0) return ACRMI_OK;
+  if (!logits) return fail(c, ACRMI_EINVAL, "%s: logits_dev is NULL", who);
+  SegmArgs a{};
+  a.logits = logits; a.frame_stride = frame_stride; a.pix_stride = pix_stride; a.C = C; a.n = n; a.h = h; a.w = w; a.H = H; a.W = W;
+  a.view = view; a.offsets = offsets; a.weight = weight; a.img_in = img_in; a.out = out; a.labels = labels;
+  if (colors_host) std::memcpy(a.colors, colors_host, 3 * (size_t)C);
+  else segm_default_colors(bgr != 0, C, a.colors);
+  const hipError_t e = launch_segm(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(c, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int acrmi_segm_labels(const float* logits_dev, long long frame_stride, int pix_stride, int n, int h, int w, int C,
+                      const float* view_dev, const float* offsets_dev, float weight, const uint8_t* colors_host, int bgr,
+                      const uint8_t* img_in_dev, uint8_t* out_dev, uint8_t* labels_dev, int H, int W, void* stream) {
+  return segm_labels_call(nullptr, "acrmi_segm_labels", logits_dev, frame_stride, pix_stride, n, h, w, C, view_dev, offsets_dev, weight,
+                          colors_host, bgr, img_in_dev, out_dev, labels_dev, H, W, stream);
+}
+
+size_t acrmi_segm_stats_ws_ints(int n, int H, int W) { return segm_stats_ws_ints(n, H, W); }
+
+int acrmi_segm_stats(const uint8_t* labels_dev, const int32_t* ids_dev, int n_faces, int n, int H, int W, int C,
+                     int32_t* counts_dev, int32_t* boxes_dev, int32_t* agree_dev, int32_t* ws_dev, void* stream) {
+  const char* who = "acrmi_segm_stats";
+  if (!segm_classes_ok(C)) return fail(nullptr, ACRMI_EINVAL, "%s: C = %d must be odd and in %d..%d", who, C, SEGM_MIN_C, SEGM_MAX_C);
+  if (!segm_dim_ok(H) || !segm_dim_ok(W) || n < 0 || n > SEGM_MAX_FRAMES)
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad sizes (%d frames of %d x %d; each in 1..%d, at most %d frames)", who, n, H, W,
+                SEGM_MAX_DIM, SEGM_MAX_FRAMES);
+  if ((ids_dev != nullptr) != (agree_dev != nullptr)) return fail(nullptr, ACRMI_EINVAL, "%s: agree_dev goes with ids_dev", who);
+  if (ids_dev && n_faces <= 0) return fail(nullptr, ACRMI_EINVAL, "%s: ids_dev needs n_faces > 0", who);
+  if (n == 0) return ACRMI_OK;
+  if (!labels_dev || !counts_dev || !boxes_dev || !ws_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  const SegmStatsArgs a{labels_dev, ids_dev, n_faces, n, H, W, C, counts_dev, boxes_dev, agree_dev, ws_dev};
+  const hipError_t e = launch_segm_stats(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}

@@ -611,4 +611,29 @@ struct RegionHeatmapArgs {
 };
 hipError_t launch_region_heatmap(const RegionHeatmapArgs& a, hipStream_t s);
 
+// The part segmentation as an output (csrc/segm.hip; csrc/segm_plan.h).
+struct SegmArgs {
+  const float* logits;           // [n, h, w, pix_stride] fp32, C classes per cell
+  long long frame_stride;        // floats between the maps of two frames
+  int pix_stride, C;
+  int n, h, w, H, W;
+  const float* view;             // [n, 4] or null
+  const float* offsets;          // [n, 10]: the view is taken from these rows instead (null: `view`, or none)
+  float weight;
+  const uint8_t* img_in;         // [n, H, W, 3], with `out`
+  uint8_t* out;                  // the drawn view, may be img_in; or null
+  uint8_t* labels;               // [n, H, W]; or null
+  int wide, wide_labels, vec;    // (launch_segm fills these)
+  uint8_t colors[192];           // [C][3] in the image's channel order
+};
+hipError_t launch_segm(const SegmArgs& a, hipStream_t s);
+struct SegmStatsArgs {
+  const uint8_t* labels;         // [n, H, W]
+  const int32_t* ids;            // [n, H, W] of the rasteriser, or null
+  int n_faces, n, H, W, C;
+  int32_t *counts, *boxes, *agree;      // [n, C], [n, 2, 4], [n, 2, 3] (null without ids)
+  int32_t* ws;                   // segm_stats_ws_ints(n, H, W)
+};
+hipError_t launch_segm_stats(const SegmStatsArgs& a, hipStream_t s);
+
 }  // namespace acrmi

@@ -20,7 +20,9 @@
 // aligned, byte by byte otherwise.  A thread reads and writes only its own pixels, so drawing in place is safe; there are
 // no atomics on global memory, so the result is deterministic.
 #include "kernels.h"
+#include "px_rows.h"          // load_px, store_px, get_byte, set_byte, dword_rows
 #include "region_view_plan.h"
+#include "segm_plan.h"        // Tap, map_tap
 
 #include <hip/hip_fp16.h>
 
@@ -64,35 +66,6 @@ __device__ inline bool prim_covers(const Prim& r, int x, int y) {
   cr = cr < 0 ? -cr : cr;
   if (cr >= CROSS_LIMIT) return false;
   return 4 * cr * cr <= r.lim;
-}
-
-// 4 pixels of one row <-> 3 dwords: channel c of pixel j is byte 3 j + c
-__device__ inline void load_px(const uint8_t* p, bool wide, int n, uint32_t d[3]) {
-  if (wide) {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
-    return;
-  }
-  d[0] = d[1] = d[2] = 0;
-#pragma unroll
-  for (int k = 0; k < 12; ++k)
-    if (k < 3 * n) d[k >> 2] |= (uint32_t)p[k] << ((k & 3) * 8);
-}
-
-__device__ inline void store_px(uint8_t* p, bool wide, int n, const uint32_t d[3]) {
-  if (wide) {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-    q[0] = d[0]; q[1] = d[1]; q[2] = d[2];
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 12; ++k)
-    if (k < 3 * n) p[k] = (uint8_t)(d[k >> 2] >> ((k & 3) * 8));
-}
-
-__device__ inline uint32_t get_byte(const uint32_t d[3], int k) { return (d[k >> 2] >> ((k & 3) * 8)) & 0xffu; }
-__device__ inline void set_byte(uint32_t d[3], int k, uint32_t v) {
-  d[k >> 2] = (d[k >> 2] & ~(0xffu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
 }
 
 }  // namespace
@@ -241,19 +214,6 @@ __global__ __launch_bounds__(256) void skeleton_kernel(SkeletonArgs a) {
 
 // ---- heat maps --------------------------------------------------------------------------------------------------------
 namespace {
-
-struct Tap { int i0, i1; float l0, l1; };
-
-// source position of canvas coordinate c on a map of n cells (scale m = n / 512): the half-pixel-centre bilinear rule
-__device__ inline Tap map_tap(float c, float m, int n) {
-  const float s = fmaxf(c * m - 0.5f, 0.f);
-  Tap t;
-  t.i0 = min((int)s, n - 1);
-  t.i1 = min(t.i0 + 1, n - 1);
-  t.l1 = s - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
 
 __device__ inline float map_load(const void* p, int dtype, size_t at) {
   if (dtype == 0) return static_cast<const float*>(p)[at];
@@ -525,8 +485,6 @@ void heatmap_default_lut(bool bgr, uint8_t* out768) {
       out768[i * 3 + (bgr ? 2 - c : c)] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
     }
 }
-
-static bool dword_rows(const void* p, int W) { return W % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 hipError_t launch_skeleton(const SkeletonArgs& a0, hipStream_t s) {
   SkeletonArgs a = a0;

@@ -1134,6 +1134,66 @@ class Engine(object):
         src, offsets, region_frame = self._regions(frames, offsets, region_frame, n)
         return self._overlay(out, src, n, 'frames', what, 'pj2d_org', offsets, region_frame, bgr, dst, stream)
 
+    # ---- the part segmentation as an output -------------------------------------------------------------
+    def segment(self, out_or_B, images=None, offsets=None, bgr=False, dst=None, labels=True, stats=False, ids=None, stream=None,
+                weight=0.7, colors=None, draw=True):
+        """The hand-part segmentation of the LAST program run of this context (it must be the forward that produced `out`) as
+        labels, as a view, and as mask statistics (acrmi_segment + acrmi_segm_stats).  out_or_B: what
+        `forward` returned, or its batch size.  images uint8 [B,H,W,3] on the device: the frames the labels are made for and the
+        view is drawn over - the 512 x 512 network input when offsets is None, else the original frames the `offsets` rows
+        [B,10] describe; without images the labels are 512 x 512 under the identity view.  Returns a dict of device tensors:
+        'labels' uint8 [B,H,W] (labels=True, or with stats) - 0 background, 1..16 the right hand's parts, 17..32 the left
+        hand's, 255 where the canvas does not cover the frame; 'view' uint8 [B,H,W,3] (with images; dst: tensor to draw
+        into, may be `images`; bgr, weight, colors [33,3]: as ops.draw_segm); with stats=True 'counts' int32 [B,33] and 'boxes'
+        int32 [B,2,4] (ops.segm_stats), and with ids - int32 [B,H,W] of `render(..., return_ids=True)` over the same frames -
+        'agree' int32 [B,2,3] = (intersection, mask, silhouette) per side.  draw=False: `images` only say which frames the labels
+        are made for, no view is drawn.  The map has no instances: with max_hand > 1 the hands of a side share its mask.
+        stream: as `forward`.  Nothing waits for the host."""
+        B = int(out_or_B['slots'].shape[0]) if isinstance(out_or_B, dict) else int(out_or_B)
+        if ids is not None and not stats:
+            raise ValueError('ids= is compared with the masks by stats=True')
+        src = None
+        H = W = 512
+        if images is not None:
+            src = self._check_frames(images, 'images', 'B')
+            if src.shape[0] != B:
+                raise ValueError('images must hold the %d frames of the batch' % B)
+            H, W = src.shape[1:3]
+        if dst is not None and (images is None or not draw):
+            raise ValueError('dst is the view drawn over images=')
+        if not (labels or stats or (images is not None and draw)):
+            raise ValueError('nothing to make: labels=False and stats=False without a view to draw')
+        offsets = self._frame_offsets(offsets, B)
+        if ids is not None and (ids.dtype != torch.int32 or tuple(ids.shape) != (B, H, W) or not ids.is_cuda):
+            raise ValueError('ids must be int32 [%d,%d,%d] on the device' % (B, H, W))
+        tab = None
+        if colors is not None:
+            tab = np.ascontiguousarray(np.asarray(colors.cpu() if hasattr(colors, 'cpu') else colors))
+            if tab.shape != (33, 3) or tab.dtype != np.uint8:
+                raise ValueError('colors must be uint8 [33,3]')
+        tst = torch.cuda.current_stream(self.device) if stream is None else torch.cuda.ExternalStream(stream, device=self.device)
+        res = {}
+        with torch.cuda.stream(tst):
+            if src is not None and draw:
+                res['view'] = self._dst(dst, src, (B, H, W, 3), 'images')
+            if labels or stats:
+                res['labels'] = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.acrmi_segment(self.ctx, B, _ptr(offsets), float(weight), None if tab is None else tab.ctypes.data_as(C.c_void_p),
+                                        int(bool(bgr)), _ptr(src) if draw else None, _ptr(res.get('view')), _ptr(res.get('labels')), H, W,
+                                        C.c_void_p(tst.cuda_stream)), self.ctx)
+        if stats:
+            n_faces = None
+            if ids is not None:
+                if self._faces.get('left') is None:
+                    raise _lib.AcrmiError('ids= needs the MANO faces the ids were rendered with (load_faces)')
+                n_faces = self._faces['left'].shape[0]
+            with torch.cuda.stream(tst):
+                res.update(ops_mod.segm_stats(res['labels'], 33, ids=ids, n_faces=n_faces, stream=tst.cuda_stream))
+        self._segment_keep = (offsets, src, ids, dict(res))      # referenced until the next call has been queued
+        if not labels:
+            res.pop('labels', None)
+        return res
+
 
     def profile_ops(self, img):
         img = self._check_img(img)
@@ -1370,6 +1430,16 @@ class EnginePool(object):
         """Engine.overlay_regions of the ticket's batch on the ticket's stream, like overlay()."""
         return self._view(ticket, 'overlay_regions', '_overlay_keep', self._region_frames(ticket, frames, offsets, region_frame),
                           what=what, **kw)
+
+    def segment(self, ticket, images=None, offsets=None, ids=None, **kw):
+        """Engine.segment of the ticket's batch on the ticket's stream, behind its forward: call between submit() and
+        collect(), like overlay().  `images`, `offsets` and `ids` as the caller's current stream left them.  Returns what
+        Engine.segment returns."""
+        def prepare(eng):
+            return {'images': None if images is None else images.contiguous(),
+                    'offsets': None if offsets is None else offsets.to(self.device, torch.float32).contiguous(),
+                    'ids': None if ids is None else ids.contiguous()}
+        return self._view(ticket, 'segment', '_segment_keep', prepare, **kw)
 
     def contact(self, ticket, **kw):
         """Engine.contact of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

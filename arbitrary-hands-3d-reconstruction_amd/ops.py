@@ -1523,3 +1523,122 @@ def draw_region_heatmaps(maps, images, offsets, region_frame, weight=0.7, bgr=Fa
                                                      None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
                                                      _p(src), _p(left), _p(right), N, H, W, _s(src)))
     return dst
+
+
+# ---- the part segmentation as an output (csrc/segm_plan.h) ----------------------------------------
+SEGM_NONE = _lib.SEGM_NONE
+
+
+def segm_colors(classes=33, bgr=False):
+    """The default colours of the 'segm' view, uint8 [classes,3] (acrmi_segm_tables): right parts on the upper half of the heat
+    maps' jet, left parts on the lower half, row 0 (background, never drawn) zero."""
+    tab = np.zeros((int(classes), 3), np.uint8)
+    _lib.check(_lib.lib().acrmi_segm_tables(int(bool(bgr)), int(classes), tab.ctypes.data_as(C.c_void_p)))
+    return tab
+
+
+def _segm_logits(logits, classes):
+    """logits NHWC [N,h,w,cs] fp32 on the device, possibly a channel slice of a wider buffer -> (tensor, classes, pix_stride,
+    frame_stride)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32:
+        raise ValueError('logits must be a float32 tensor [N,h,w,C] (NHWC)')
+    _need_cuda(logits)
+    N, h, w, cs = logits.shape
+    st = logits.stride()
+    if st[3] != 1 or (w > 1 and st[1] != w * st[2]) or st[2] < cs or (N > 1 and st[0] < h * w * st[2]):
+        logits = logits.contiguous()
+        st = logits.stride()
+    return logits, int(cs if classes is None else classes), int(st[2]), int(st[0]) if N > 1 else int(max(st[0], h * w * st[2]))
+
+
+def _segm_call(logits, classes, hw, images, view, offsets, weight, bgr, colors, dst, labels, stream=None):
+    logits, Cn, ps, fs = _segm_logits(logits, classes)
+    N, h, w, _ = logits.shape
+    dev = logits.device
+    src = out = None
+    if images is not None:
+        _check_images(images)
+        _need_cuda(images)
+        if images.shape[0] != N:
+            raise ValueError('one image per frame of logits')
+        src = images.contiguous()
+        H, W = src.shape[1:3]
+        if dst is None:
+            out = torch.empty_like(src)
+        else:
+            _check_dst(dst, src)
+            out = dst
+    else:
+        H, W = (512, 512) if hw is None else (int(hw[0]), int(hw[1]))
+    if view is not None and offsets is not None:
+        raise ValueError('view or offsets, not both')
+    vw = off = None
+    if view is not None:
+        vw = torch.as_tensor(view, dtype=torch.float32).to(dev).contiguous()
+        if tuple(vw.shape) != (N, 4):
+            raise ValueError('view must be [N,4]')
+    if offsets is not None:
+        off = torch.as_tensor(offsets, dtype=torch.float32).to(dev).contiguous()
+        if tuple(off.shape) != (N, 10):
+            raise ValueError('offsets must be [N,10]')
+    tab = None
+    if colors is not None:
+        tab = np.ascontiguousarray(np.asarray(colors.cpu() if hasattr(colors, 'cpu') else colors))
+        if tab.shape != (Cn, 3) or tab.dtype != np.uint8:
+            raise ValueError('colors must be uint8 [%d,3]' % Cn)
+    lab = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if labels else None
+    _lib.check(_lib.lib().acrmi_segm_labels(_p(logits), fs, ps, N, h, w, Cn, _p(vw), _p(off), float(weight),
+                                            None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)), _p(src), _p(out),
+                                            _p(lab), H, W, _s(logits) if stream is None else C.c_void_p(stream)))
+    return out, lab
+
+
+def segm_labels(logits, hw=None, view=None, offsets=None, classes=None):
+    """Part logits -> a label per pixel of N frames of hw = (H, W) pixels (default 512 x 512) on the GPU (acrmi_segm_labels;
+    DESIGN.md section 23): the bilinear LOGITS of every class at the pixel's canvas coordinate, then the strict arg-max (the
+    lowest class wins a tie, a NaN never wins) - not nearest labels.  logits device fp32 NHWC [N,h,w,C] (a channel slice of
+    a wider buffer is read in place; classes: the first `classes` channels, default all), C odd in 3..63.  view [N,4]
+    (view_from_offsets) or offsets [N,10]: where the 512 canvas the map covers sits in the frames; neither: it is the whole
+    frame.  Label 0 = background, 1 .. (C-1)/2 the right hand's parts, the rest the left hand's; SEGM_NONE (255) where the
+    canvas does not cover the pixel.  Returns uint8 [N,H,W]."""
+    return _segm_call(logits, classes, hw, None, view, offsets, 0.7, False, None, None, True)[1]
+
+
+def draw_segm(logits, images, view=None, offsets=None, weight=0.7, bgr=False, colors=None, dst=None, labels=False, classes=None):
+    """The part labels of segm_labels in colour over N frames, in the same launch (acrmi_segm_labels): a pixel with a hand
+    part's label becomes floor(weight * colour[label] + (1 - weight) * pixel), every other pixel stays byte for byte.  images
+    uint8 [N,H,W,3] device; colors uint8 [C,3] in the images' channel order (default segm_colors(C, bgr)); dst: tensor like
+    images to draw into (may BE images).  Returns the frames, or (frames, labels uint8 [N,H,W]) with labels=True."""
+    if images is None:
+        raise ValueError('images: the frames to draw over')
+    out, lab = _segm_call(logits, classes, None, images, view, offsets, weight, bgr, colors, dst, labels)
+    return (out, lab) if labels else out
+
+
+def segm_stats(labels, classes=33, ids=None, n_faces=None, stream=None):
+    """Statistics of label maps uint8 [N,H,W] on the GPU (acrmi_segm_stats) -> {'counts': int32 [N,C]
+    pixels per label (255 is not counted), 'boxes': int32 [N,2,4] the smallest (l, t, r, b) around each side's pixels (side 0
+    left, 1 right; r, b exclusive; zeros when the side has none)}, and with ids - int32 [N,H,W] of render(...,
+    return_ids=True) for the same frames, n_faces the faces of a mesh - 'agree': int32 [N,2,3] = (pixels in mask and silhouette,
+    mask pixels, silhouette pixels) per side.  Integers only; IoU = inter / (mask + sil - inter) is the caller's division."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3:
+        raise ValueError('labels must be a uint8 tensor [N,H,W]')
+    _need_cuda(labels, ids)
+    lab = labels.contiguous()
+    N, H, W = lab.shape
+    dev = lab.device
+    if ids is not None:
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (N, H, W):
+            raise ValueError('ids must be int32 [N,H,W] like labels')
+        if n_faces is None or int(n_faces) <= 0:
+            raise ValueError('ids needs n_faces, the number of faces of a mesh')
+        ids = ids.contiguous()
+    L = _lib.lib()
+    ws = torch.empty(max(int(L.acrmi_segm_stats_ws_ints(N, H, W)), 1), dtype=torch.int32, device=dev)
+    res = {'counts': torch.empty(N, int(classes), dtype=torch.int32, device=dev),
+           'boxes': torch.empty(N, 2, 4, dtype=torch.int32, device=dev)}
+    if ids is not None:
+        res['agree'] = torch.empty(N, 2, 3, dtype=torch.int32, device=dev)
+    _lib.check(L.acrmi_segm_stats(_p(lab), _p(ids), int(n_faces or 0), N, H, W, int(classes), _p(res['counts']), _p(res['boxes']),
+                                  _p(res.get('agree')), _p(ws), _s(lab) if stream is None else C.c_void_p(stream)))
+    return res

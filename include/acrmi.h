@@ -993,6 +993,57 @@ int acrmi_render_regions_colored(acrmi_ctx* ctx, const float* verts_dev, const f
                                  const float* vcol_dev, float focal, float visible_weight, const uint8_t* img_in_dev,
                                  uint8_t* img_out_dev, int n_frames, int H, int W, int32_t* ids_out_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The hand-part segmentation as an output (the rule once in csrc/segm_plan.h; csrc/segm.hip).  The
+ * network computes C = 33 part logits per cell of a 256 x 256 map (backbone.hand_segm, the reference's `segms`); the reference
+ * turns them into labels with map2labels (acr/model.py:397-401) and draws nothing.  All fp32, every operation rounded on its
+ * own:
+ *  canvas  of pixel (x, y): cx = (x + 0.5 - ox) / sx with the frame's view row (sx, sy, ox, oy) - given, or taken from its
+ *          `offsets` row as acrmi_render does - and cx = (x + 0.5) * (512 / W) without one.  A pixel with cx or cy outside
+ *          [0, 512), and every pixel of a frame with sx or sy not > 0, is NOT COVERED.
+ *  taps    s = max(cx * (w / 512) - 0.5, 0), i0 = min(int(s), w - 1), i1 = min(i0 + 1, w - 1), l1 = s - i0, l0 = 1 - l1, the
+ *          same in y with h: acrmi_draw_heatmaps' rule with the map's own h, w
+ *  value   v_c = ly0 (lx0 a_c + lx1 b_c) + ly1 (lx0 c_c + lx1 d_c) for every class c: bilinear logits, not nearest labels
+ *  label   best = v_0, label = 0; for c = 1 .. C - 1 in order, c is taken when v_c > best (strict: the lowest class wins a
+ *          tie, a NaN never wins).  A pixel that is not covered gets ACRMI_SEGM_NONE.  C is odd, 3 <= C <= 63; class 0 is
+ *          background, classes 1 .. (C-1)/2 are the RIGHT hand's parts, the rest the LEFT hand's (acr/model.py:141-144).
+ *          Which part is which bone is not known: the reference ships no list.
+ *  view    for 1 <= label < C: out = floor(weight * colour[label] + (1 - weight) * img); every other pixel keeps the input
+ *          byte for byte.  Default colours: right part p = label - 1 takes the heat maps' LUT[128 + 8 p], left part p =
+ *          label - 1 - (C-1)/2 takes LUT[127 - 8 p] (index clamped into the table), flipped for BGR.
+ *  stats   counts[c] = pixels of label c (ACRMI_SEGM_NONE is not counted); box of side s (0 left, 1 right) = the smallest
+ *          (l, t, r, b) around its pixels, r and b exclusive as acrmi_roi's, zeros when it has none; agree of side s =
+ *          (pixels in both, mask pixels, silhouette pixels) with the silhouette = pixels whose rasteriser id is >= 0 and
+ *          ((id / n_faces) & 1) == s.  Integers only: IoU = inter / (mask + sil - inter) is the caller's division.
+ * No atomics on global memory; a frame alone equals the frame in a batch; in place = out of place; nothing is zeroed by the
+ * caller.  Arguments are checked before any device call (ACRMI_EINVAL); n == 0 is a success that touches nothing.
+ * ------------------------------------------------------------------------------------- */
+#define ACRMI_SEGM_NONE 255
+/* Pure host: the default colours of C classes, colors_host [C][3] in RGB order or flipped (bgr != 0); row 0 is zero. */
+int acrmi_segm_tables(int bgr, int C, uint8_t* colors_host);
+/* logits_dev fp32: cell (y, x) of frame i starts at element i * frame_stride + (y * w + x) * pix_stride and holds C classes;
+ * pix_stride >= C, frame_stride >= h * w * pix_stride (when pix_stride is a multiple of 4 whole cells of pix_stride floats
+ * are read).  At most one of view_dev [n,4] and offsets_dev [n,10].  out_dev uint8 [n,H,W,3] or NULL: the view over
+ * img_in_dev (needed with out_dev only; they may be the same buffer); labels_dev uint8 [n,H,W] or NULL; one of the two at
+ * least.  weight in [0,1]; colors_host [C][3] in the image's channel order, NULL = the default (flipped when bgr != 0).
+ * h, w, H, W <= 16384, n <= 65535.  ONE launch reads the logits once. */
+int acrmi_segm_labels(const float* logits_dev, long long frame_stride, int pix_stride, int n, int h, int w, int C,
+                      const float* view_dev, const float* offsets_dev, float weight, const uint8_t* colors_host, int bgr,
+                      const uint8_t* img_in_dev, uint8_t* out_dev, uint8_t* labels_dev, int H, int W, void* stream);
+/* int32 words of acrmi_segm_stats' workspace (0 for sizes it would refuse). */
+size_t acrmi_segm_stats_ws_ints(int n, int H, int W);
+/* labels_dev uint8 [n,H,W]; ids_dev int32 [n,H,W] (what acrmi_render / acrmi_rasterize wrote for the same frames, with its
+ * n_faces > 0) or NULL; counts_dev int32 [n,C], boxes_dev int32 [n,2,4], agree_dev int32 [n,2,3] - with ids_dev, else NULL;
+ * ws_dev: acrmi_segm_stats_ws_ints(n, H, W) int32, nothing in it needs to be set. */
+int acrmi_segm_stats(const uint8_t* labels_dev, const int32_t* ids_dev, int n_faces, int n, int H, int W, int C,
+                     int32_t* counts_dev, int32_t* boxes_dev, int32_t* agree_dev, int32_t* ws_dev, void* stream);
+/* acrmi_segm_labels on the context's own segmentation buffer as the last program run left it, which must have been at batch
+ * B (geometry and channel stride as acrmi_buffer_ptr reports them; the buffer is fp32 in every storage type); offsets_dev
+ * [B,10] or NULL (the 512 x 512 network input, or any frame the canvas fills).  ACRMI_ESTATE before a program has run or
+ * after one at another batch size, as acrmi_overlay(ACRMI_OVERLAY_CENTERMAP). */
+int acrmi_segment(acrmi_ctx* ctx, int B, const float* offsets_dev, float weight, const uint8_t* colors_host, int bgr,
+                  const uint8_t* img_in_dev, uint8_t* out_dev, uint8_t* labels_dev, int H, int W, void* stream);
+
 /* Multi-GPU (replaces nn.DataParallel's scatter/gather, acr/main.py:61): frames are sharded by the caller, one
  * process per GPU; the only collective is ONE all-gather per batch of each rank's flat result buffer
  * [slots | verts | joints] over RCCL/xGMI.  recv_dev holds n_ranks * n_floats floats, rank-major.
