@@ -1120,9 +1120,7 @@ static hipError_t skeleton_launch(const float* kps, const float* slots, const in
 // What HeatmapArgs and RegionHeatmapArgs share: the maps are the head buffers the last program run left for n frames (NHWC,
 // channel 0, the buffer's channel stride between two cells); a 16-bit storage program's are converted to fp32 as the kernels
 // stage them in LDS.
-extern "C++" {
-template <class Args>
-static int heatmap_fill(acrmi_ctx* c, const char* who, Args& a, int n, const float* offsets, int bgr, const uint8_t* img_in,
+static int heatmap_fill(acrmi_ctx* c, const char* who, HeatmapBase& a, int n, const float* offsets, int bgr, const uint8_t* img_in,
                         uint8_t* out, uint8_t* out2, int H, int W) {
   if (n != c->last_batch)
     return fail(c, ACRMI_ESTATE, "%s: the resident centre maps are those of a batch of %d, not %d", who, c->last_batch, n);
@@ -1135,7 +1133,6 @@ static int heatmap_fill(acrmi_ctx* c, const char* who, Args& a, int n, const flo
   heatmap_default_lut(bgr != 0, a.lut);
   return ACRMI_OK;
 }
-}      // extern "C++"
 
 int acrmi_overlay(acrmi_ctx* c, int what, const float* slots, const float* pj2d, int B, const float* offsets, int bgr,
                   const uint8_t* img_in, uint8_t* out, uint8_t* out2, int H, int W, void* stream) {

@@ -924,19 +924,30 @@ int acrmi_draw_skeletons(const float* kps_dev, const int32_t* hand_frame_dev, in
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_skeletons: %s", hipGetErrorString(e));
 }
 
+// What acrmi_draw_heatmaps and acrmi_draw_region_heatmaps check and fill alike: n fp32 maps (pairs) of h x w drawn over
+// n_frames frames; own_ok = the caller's own pointers are there.
+static int heatmap_args(const char* who, HeatmapBase& a, bool own_ok, const float* maps_l, const float* maps_r, long long frame_stride,
+                        int n, int h, int w, float weight, const uint8_t* lut_host, int bgr, const uint8_t* img_in, uint8_t* out_l,
+                        uint8_t* out_r, int n_frames, int H, int W) {
+  if (!own_ok || !maps_l || !img_in || !out_l || (maps_r != nullptr) != (out_r != nullptr) || out_l == out_r ||
+      (out_r && out_r == img_in) || n <= 0 || !overlay_image_ok(n_frames, H, W) || h <= 0 || w <= 0 || h > OVERLAY_MAX_DIM ||
+      w > OVERLAY_MAX_DIM || frame_stride < (long long)h * w || !(weight >= 0.f && weight <= 1.f))
+    return fail(nullptr, ACRMI_EINVAL, "%s: bad arguments", who);
+  a.maps[0] = maps_l; a.maps[1] = maps_r; a.frame_stride = frame_stride; a.pix_stride = 1; a.dtype = ACRMI_DT_F32;
+  a.n = n; a.h = h; a.w = w; a.H = H; a.W = W; a.weight = weight; a.img_in = img_in; a.out[0] = out_l; a.out[1] = out_r;
+  if (lut_host) std::memcpy(a.lut, lut_host, 768);
+  else heatmap_default_lut(bgr != 0, a.lut);
+  return ACRMI_OK;
+}
+
 int acrmi_draw_heatmaps(const float* maps_l_dev, const float* maps_r_dev, long long frame_stride, int n, int h, int w,
                         const float* view_dev, float weight, const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev,
                         uint8_t* out_l_dev, uint8_t* out_r_dev, int H, int W, void* stream) {
-  if (!maps_l_dev || !img_in_dev || !out_l_dev || (maps_r_dev != nullptr) != (out_r_dev != nullptr) || out_l_dev == out_r_dev ||
-      (out_r_dev && out_r_dev == img_in_dev) || !overlay_image_ok(n, H, W) || h <= 0 || w <= 0 || h > OVERLAY_MAX_DIM ||
-      w > OVERLAY_MAX_DIM || frame_stride < (long long)h * w || !(weight >= 0.f && weight <= 1.f))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_draw_heatmaps: bad arguments");
   HeatmapArgs a{};
-  a.maps[0] = maps_l_dev; a.maps[1] = maps_r_dev; a.frame_stride = frame_stride; a.pix_stride = 1; a.dtype = ACRMI_DT_F32;
-  a.n = n; a.h = h; a.w = w; a.H = H; a.W = W; a.view = view_dev; a.weight = weight; a.img_in = img_in_dev;
-  a.out[0] = out_l_dev; a.out[1] = out_r_dev;
-  if (lut_host) std::memcpy(a.lut, lut_host, 768);
-  else heatmap_default_lut(bgr != 0, a.lut);
+  if (int r = heatmap_args("acrmi_draw_heatmaps", a, true, maps_l_dev, maps_r_dev, frame_stride, n, h, w, weight, lut_host, bgr,
+                           img_in_dev, out_l_dev, out_r_dev, n, H, W))
+    return r;
+  a.view = view_dev;
   hipError_t e = launch_heatmap(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_heatmaps: %s", hipGetErrorString(e));
 }
@@ -945,17 +956,11 @@ int acrmi_draw_region_heatmaps(const float* maps_l_dev, const float* maps_r_dev,
                                const float* offsets_dev, const int32_t* region_frame_dev, float weight,
                                const uint8_t* lut_host, int bgr, const uint8_t* img_in_dev, uint8_t* out_l_dev,
                                uint8_t* out_r_dev, int n_frames, int H, int W, void* stream) {
-  if (!maps_l_dev || !offsets_dev || !region_frame_dev || !img_in_dev || !out_l_dev ||
-      (maps_r_dev != nullptr) != (out_r_dev != nullptr) || out_l_dev == out_r_dev || (out_r_dev && out_r_dev == img_in_dev) ||
-      n <= 0 || !overlay_image_ok(n_frames, H, W) || h <= 0 || w <= 0 || h > OVERLAY_MAX_DIM || w > OVERLAY_MAX_DIM ||
-      frame_stride < (long long)h * w || !(weight >= 0.f && weight <= 1.f))
-    return fail(nullptr, ACRMI_EINVAL, "acrmi_draw_region_heatmaps: bad arguments");
   RegionHeatmapArgs a{};
-  a.maps[0] = maps_l_dev; a.maps[1] = maps_r_dev; a.frame_stride = frame_stride; a.pix_stride = 1; a.dtype = ACRMI_DT_F32;
-  a.n = n; a.h = h; a.w = w; a.n_frames = n_frames; a.H = H; a.W = W; a.offsets = offsets_dev; a.region_frame = region_frame_dev;
-  a.weight = weight; a.img_in = img_in_dev; a.out[0] = out_l_dev; a.out[1] = out_r_dev;
-  if (lut_host) std::memcpy(a.lut, lut_host, 768);
-  else heatmap_default_lut(bgr != 0, a.lut);
+  if (int r = heatmap_args("acrmi_draw_region_heatmaps", a, offsets_dev && region_frame_dev, maps_l_dev, maps_r_dev, frame_stride,
+                           n, h, w, weight, lut_host, bgr, img_in_dev, out_l_dev, out_r_dev, n_frames, H, W))
+    return r;
+  a.offsets = offsets_dev; a.region_frame = region_frame_dev; a.n_frames = n_frames;
   hipError_t e = launch_region_heatmap(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "draw_region_heatmaps: %s", hipGetErrorString(e));
 }

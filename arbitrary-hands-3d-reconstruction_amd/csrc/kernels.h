@@ -573,19 +573,21 @@ struct SkeletonArgs {
   int wide;                      // (launch_skeleton fills this)
   uint8_t colors[64];            // [21][3] in the image's channel order
 };
-struct HeatmapArgs {
-  const void* maps[2];           // left / right; [1] null = one view
-  long long frame_stride;        // elements between the maps of two frames
+struct HeatmapBase {             // what the heat maps over frames and over regions share
+  const void* maps[2];           // left / right, one pair per frame or region; [1] null = one view
+  long long frame_stride;        // elements between the maps of two frames (regions)
   int pix_stride;                // elements between two cells of a row (1; the channel stride of a head buffer)
   int dtype;                     // 0 fp32, 1 f16, 2 bf16 (ACRMI_DT_*)
-  int n, h, w, H, W;
-  const float* view;             // [n, 4] scale x, scale y, shift x, shift y, or null
-  const float* offsets;          // [n, 10] the view is taken from these rows instead (null: `view`, or none)
+  int n, h, w, H, W;             // frames (regions), map size, frame size
+  const float* offsets;          // [n, 10]
   float weight;
-  const uint8_t* img_in;         // [n, H, W, 3]
+  const uint8_t* img_in;         // [frames, H, W, 3]
   uint8_t* out[2];
-  int wide;                      // (launch_heatmap fills this)
+  int wide;                      // (the launcher fills this)
   uint8_t lut[768];              // [256][3] in the image's channel order
+};
+struct HeatmapArgs : HeatmapBase {
+  const float* view;             // [n, 4] scale x, scale y, shift x, shift y; null: the view is taken from `offsets`, or none
 };
 constexpr int OVERLAY_MAX_DIM = 16384, OVERLAY_MAX_FRAMES = 65535, OVERLAY_MAX_WIDTH = 11, OVERLAY_MAX_RAD = 255;
 extern const uint8_t kSkeletonRGB[21][3];
@@ -595,19 +597,9 @@ hipError_t launch_skeleton(const SkeletonArgs& a, hipStream_t s);
 hipError_t launch_heatmap(const HeatmapArgs& a, hipStream_t s);
 // Heat maps of REGIONS composed over their frames (DESIGN.md "Views over regions"): region i's maps tint the pixels of its
 // window in frame region_frame[i]; where windows overlap the larger colour index wins.
-struct RegionHeatmapArgs {
-  const void* maps[2];           // as HeatmapArgs, one pair per region
-  long long frame_stride;
-  int pix_stride, dtype;
-  int n, h, w;                   // regions, map size
-  int n_frames, H, W;
-  const float* offsets;          // [n, 10]
+struct RegionHeatmapArgs : HeatmapBase {
   const int32_t* region_frame;   // [n]
-  float weight;
-  const uint8_t* img_in;         // [n_frames, H, W, 3]
-  uint8_t* out[2];
-  int wide;                      // (launch_region_heatmap fills this)
-  uint8_t lut[768];
+  int n_frames;
 };
 hipError_t launch_region_heatmap(const RegionHeatmapArgs& a, hipStream_t s);
 

@@ -16,13 +16,15 @@
 //                     other the part of their two maps the tile's share of the window samples is staged, and every thread
 //                     keeps the LARGEST colour index of each of its pixels per side in registers; after the last region
 //                     the image is read once, blended once and written to both outputs.
+// The two heat-map kernels take the frame's view, coverage, taps, value, the footprint of a tile and the blend from
+// csrc/map_view_plan.h, where the rule is stated once (csrc/segm.hip draws by it too).
 // Pixels move as 4 pixels = 3 dwords per thread and row when the row length is a multiple of 4 and the buffers are dword
 // aligned, byte by byte otherwise.  A thread reads and writes only its own pixels, so drawing in place is safe; there are
 // no atomics on global memory, so the result is deterministic.
 #include "kernels.h"
 #include "px_rows.h"          // load_px, store_px, get_byte, set_byte, dword_rows
+#include "map_view_plan.h"    // the map-sampling rule of the heat maps
 #include "region_view_plan.h"
-#include "segm_plan.h"        // Tap, map_tap
 
 #include <hip/hip_fp16.h>
 
@@ -222,6 +224,33 @@ __device__ inline float map_load(const void* p, int dtype, size_t at) {
   return __uint_as_float((uint32_t)bits << 16);      // bf16
 }
 
+// the cells of footprint fp (which fits MAP_CAP) of the `views` maps that start at element fb -> s_map, as fp32
+__device__ inline void stage_maps(float (*s_map)[MAP_CAP], const HeatmapBase& a, int views, size_t fb, const MapFootprint& fp, int tid) {
+  for (int v = 0; v < views; ++v)
+    for (int t = tid; t < fp.fw * fp.fh; t += 256) {
+      const int r = t / fp.fw, c = t - r * fp.fw;
+      s_map[v][t] = map_load(a.maps[v], a.dtype, fb + ((size_t)(fp.iy + r) * a.w + fp.ix + c) * a.pix_stride);
+    }
+}
+
+// the colour index of a covered pixel from its taps: the four cells from s_map (one map's staged footprint) or, not staged,
+// from `map` at element fb; bilinear value * 255 truncated, as .byte() does; NaN -> 0
+__device__ inline int color_index(const float* s_map, bool staged, const MapFootprint& fp, const void* map, const HeatmapBase& a,
+                                  size_t fb, const Tap& ty, const Tap& tx) {
+  float p00, p01, p10, p11;
+  if (staged) {
+    const int r0 = (ty.i0 - fp.iy) * fp.fw - fp.ix, r1 = (ty.i1 - fp.iy) * fp.fw - fp.ix;
+    p00 = s_map[r0 + tx.i0]; p01 = s_map[r0 + tx.i1]; p10 = s_map[r1 + tx.i0]; p11 = s_map[r1 + tx.i1];
+  } else {
+    const size_t r0 = (size_t)ty.i0 * a.w, r1 = (size_t)ty.i1 * a.w;
+    p00 = map_load(map, a.dtype, fb + (r0 + tx.i0) * a.pix_stride);
+    p01 = map_load(map, a.dtype, fb + (r0 + tx.i1) * a.pix_stride);
+    p10 = map_load(map, a.dtype, fb + (r1 + tx.i0) * a.pix_stride);
+    p11 = map_load(map, a.dtype, fb + (r1 + tx.i1) * a.pix_stride);
+  }
+  return (int)fminf(fmaxf(map_value(ty, tx, p00, p01, p10, p11) * 255.f, 0.f), 255.f);
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
@@ -233,48 +262,17 @@ __global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
   const int views = a.maps[1] ? 2 : 1;
   for (int t = tid; t < 768; t += 256) s_lut[t] = a.lut[t];
 
-  // the frame's viewport: canvas coordinate of pixel x = (x + 0.5 - ox) / sx, or (x + 0.5) * (512 / W) without one
-  const bool has_view = a.view || a.offsets;
-  float sx = 1.f, sy = 1.f, ox = 0.f, oy = 0.f;
-  if (a.view) {
-    sx = a.view[f * 4]; sy = a.view[f * 4 + 1]; ox = a.view[f * 4 + 2]; oy = a.view[f * 4 + 3];
-  } else if (a.offsets) {      // as ops.view_from_offsets / render_prep_kernel
-    float row[4];
-    region_view_row(a.offsets + (size_t)f * 10, row);
-    sx = row[0]; sy = row[1]; ox = row[2]; oy = row[3];
-  }
+  const MapView vw = map_frame_view(a.view, a.offsets, f);      // the `view` row, else region_view_row(the `offsets` row), else none
   const float kx = 512.f / (float)a.W, ky = 512.f / (float)a.H;
   const float mx = (float)a.w / 512.f, my = (float)a.h / 512.f;
-  auto canvas_x = [&](int x) { return has_view ? ((float)x + 0.5f - ox) / sx : ((float)x + 0.5f) * kx; };
-  auto canvas_y = [&](int y) { return has_view ? ((float)y + 0.5f - oy) / sy : ((float)y + 0.5f) * ky; };
-  const bool frame_ok = sx > 0.f && sy > 0.f;      // (false for NaN) a viewport that does not face the canvas draws nothing
-
-  // what this tile samples: the map coordinate is monotone in the pixel coordinate, so the taps of the first and the last
-  // pixel (clamped into the canvas) bound those of every pixel between them
-  const float cx_a = canvas_x(X0), cx_b = canvas_x(min(X0 + TW, a.W) - 1);
-  const float cy_a = canvas_y(Y0), cy_b = canvas_y(min(Y0 + TH, a.H) - 1);
-  const bool tile_ok = frame_ok && cx_b >= 0.f && cx_a < 512.f && cy_b >= 0.f && cy_a < 512.f;
-  int ix_lo = 0, iy_lo = 0, fw = 0, fh = 0;
-  bool staged = false;
-  if (tile_ok) {
-    ix_lo = map_tap(fminf(fmaxf(cx_a, 0.f), 512.f), mx, a.w).i0;
-    iy_lo = map_tap(fminf(fmaxf(cy_a, 0.f), 512.f), my, a.h).i0;
-    fw = map_tap(fminf(fmaxf(cx_b, 0.f), 512.f), mx, a.w).i1 - ix_lo + 1;
-    fh = map_tap(fminf(fmaxf(cy_b, 0.f), 512.f), my, a.h).i1 - iy_lo + 1;
-    staged = fw * fh <= MAP_CAP;
-    if (staged) {
-      for (int v = 0; v < views; ++v)
-        for (int t = tid; t < fw * fh; t += 256) {
-          const int r = t / fw, c = t - r * fw;
-          s_map[v][t] = map_load(a.maps[v], a.dtype,
-                                 (size_t)f * a.frame_stride + ((size_t)(iy_lo + r) * a.w + ix_lo + c) * a.pix_stride);
-        }
-    }
-  }
+  // what this tile samples (the same for every thread), staged when it fits
+  const MapFootprint fp = map_footprint(X0, min(X0 + TW, a.W), Y0, min(Y0 + TH, a.H), vw, a.H, a.W, a.h, a.w);
+  const bool staged = map_staged(fp, 1, MAP_CAP);
+  const size_t fb = (size_t)f * a.frame_stride;
+  if (staged) stage_maps(s_map, a, views, fb, fp, tid);
   __syncthreads();
   if (xt >= a.W) return;
   const int n = min(PX, a.W - xt);
-  const float wgt = a.weight, iw = 1.f - a.weight;
 #pragma unroll
   for (int rr = 0; rr < ROWS; ++rr) {
     const int y = yt + ROW_STEP * rr;
@@ -284,36 +282,21 @@ __global__ __launch_bounds__(256) void heatmap_kernel(HeatmapArgs a) {
     load_px(a.img_in + at, a.wide, n, d);
 #pragma unroll
     for (int k = 0; k < 3; ++k) o[0][k] = o[1][k] = d[k];
-    const float cy = canvas_y(y);
-    if (tile_ok && cy >= 0.f && cy < 512.f) {
+    const float cy = map_canvas(y, vw.has, vw.sy, vw.oy, ky);
+    if (fp.any && cy >= 0.f && cy < 512.f) {
       const Tap ty = map_tap(cy, my, a.h);
 #pragma unroll
       for (int j = 0; j < PX; ++j) {
-        const float cx = canvas_x(xt + j);
-        if (!(cx >= 0.f && cx < 512.f)) continue;
+        const float cx = map_canvas(xt + j, vw.has, vw.sx, vw.ox, kx);
+        if (!map_covered(cx, cy, vw.sx, vw.sy)) continue;
         const Tap tx = map_tap(cx, mx, a.w);
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
           if (v >= views) continue;
-          float p00, p01, p10, p11;
-          if (staged) {
-            const float* m = s_map[v];
-            const int r0 = (ty.i0 - iy_lo) * fw - ix_lo, r1 = (ty.i1 - iy_lo) * fw - ix_lo;
-            p00 = m[r0 + tx.i0]; p01 = m[r0 + tx.i1]; p10 = m[r1 + tx.i0]; p11 = m[r1 + tx.i1];
-          } else {
-            const size_t fb = (size_t)f * a.frame_stride, r0 = (size_t)ty.i0 * a.w, r1 = (size_t)ty.i1 * a.w;
-            p00 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i0) * a.pix_stride);
-            p01 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i1) * a.pix_stride);
-            p10 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i0) * a.pix_stride);
-            p11 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i1) * a.pix_stride);
-          }
-          const float val = ty.l0 * (tx.l0 * p00 + tx.l1 * p01) + ty.l1 * (tx.l0 * p10 + tx.l1 * p11);
-          const int idx = (int)fminf(fmaxf(val * 255.f, 0.f), 255.f);      // truncates, as .byte() does; NaN -> 0
+          const int idx = color_index(s_map[v], staged, fp, a.maps[v], a, fb, ty, tx);
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float img = (float)get_byte(d, 3 * j + c);
-            set_byte(o[v], 3 * j + c, (uint32_t)floorf(wgt * (float)s_lut[idx * 3 + c] + iw * img));
-          }
+          for (int c = 0; c < 3; ++c)
+            set_byte(o[v], 3 * j + c, map_blend(a.weight, (int)s_lut[idx * 3 + c], (int)get_byte(d, 3 * j + c)));
         }
       }
     }
@@ -367,64 +350,33 @@ __global__ __launch_bounds__(256) void region_heatmap_kernel(RegionHeatmapArgs a
     for (int k = 0; k < total; ++k) {      // (everything up to the per-pixel part is the same for every thread)
       const int i = __builtin_amdgcn_readfirstlane(s_list[k]);
       const RegionView rv = region_view(a.offsets + (size_t)i * 10, f, a.n_frames, a.H, a.W);
-      // the tile's share of the window: not empty, and inside the frame (region_view_plan.h)
+      const MapView vw = {true, rv.sx, rv.sy, rv.ox, rv.oy};
+      // the tile's share of the window: not empty, and inside the frame (region_view_plan.h); what it samples, staged when it fits
       const int wx0 = max(X0, rv.x0), wx1 = min(X1, rv.x1), wy0 = max(Y0, rv.y0), wy1 = min(Y1, rv.y1);
-      auto canvas_x = [&](int x) { return ((float)x + 0.5f - rv.ox) / rv.sx; };
-      auto canvas_y = [&](int y) { return ((float)y + 0.5f - rv.oy) / rv.sy; };
-      // what it samples: as heatmap_kernel, the taps of its first and last pixel bound those of every pixel between them
-      const float cx_a = canvas_x(wx0), cx_b = canvas_x(wx1 - 1), cy_a = canvas_y(wy0), cy_b = canvas_y(wy1 - 1);
-      const bool tile_ok = cx_b >= 0.f && cx_a < 512.f && cy_b >= 0.f && cy_a < 512.f;      // (false for NaN)
+      const MapFootprint fp = map_footprint(wx0, wx1, wy0, wy1, vw, a.H, a.W, a.h, a.w);
+      const bool staged = map_staged(fp, 1, MAP_CAP);
       const size_t fb = (size_t)i * a.frame_stride;
-      int ix_lo = 0, iy_lo = 0, fw = 0, fh = 0;
-      bool staged = false;
-      if (tile_ok) {
-        ix_lo = map_tap(fminf(fmaxf(cx_a, 0.f), 512.f), mx, a.w).i0;
-        iy_lo = map_tap(fminf(fmaxf(cy_a, 0.f), 512.f), my, a.h).i0;
-        fw = map_tap(fminf(fmaxf(cx_b, 0.f), 512.f), mx, a.w).i1 - ix_lo + 1;
-        fh = map_tap(fminf(fmaxf(cy_b, 0.f), 512.f), my, a.h).i1 - iy_lo + 1;
-        staged = fw * fh <= MAP_CAP;
-        if (staged) {
-          for (int v = 0; v < views; ++v)
-            for (int t = tid; t < fw * fh; t += 256) {
-              const int r = t / fw, c = t - r * fw;
-              s_map[v][t] = map_load(a.maps[v], a.dtype, fb + ((size_t)(iy_lo + r) * a.w + ix_lo + c) * a.pix_stride);
-            }
-        }
-      }
+      if (staged) stage_maps(s_map, a, views, fb, fp, tid);
       __syncthreads();
-      if (tile_ok) {
+      if (fp.any) {
 #pragma unroll
         for (int rr = 0; rr < ROWS; ++rr) {
           const int y = yt + ROW_STEP * rr;
           if (y < wy0 || y >= wy1) continue;
-          const float cy = canvas_y(y);
+          const float cy = map_canvas(y, true, vw.sy, vw.oy, 0.f);
           if (!(cy >= 0.f && cy < 512.f)) continue;
           const Tap ty = map_tap(cy, my, a.h);
 #pragma unroll
           for (int j = 0; j < PX; ++j) {
             const int x = xt + j;
             if (x < wx0 || x >= wx1) continue;
-            const float cx = canvas_x(x);
-            if (!(cx >= 0.f && cx < 512.f)) continue;
+            const float cx = map_canvas(x, true, vw.sx, vw.ox, 0.f);
+            if (!map_covered(cx, cy, vw.sx, vw.sy)) continue;
             const Tap tx = map_tap(cx, mx, a.w);
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
               if (v >= views) continue;
-              float p00, p01, p10, p11;
-              if (staged) {
-                const float* m = s_map[v];
-                const int r0 = (ty.i0 - iy_lo) * fw - ix_lo, r1 = (ty.i1 - iy_lo) * fw - ix_lo;
-                p00 = m[r0 + tx.i0]; p01 = m[r0 + tx.i1]; p10 = m[r1 + tx.i0]; p11 = m[r1 + tx.i1];
-              } else {
-                const size_t r0 = (size_t)ty.i0 * a.w, r1 = (size_t)ty.i1 * a.w;
-                p00 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i0) * a.pix_stride);
-                p01 = map_load(a.maps[v], a.dtype, fb + (r0 + tx.i1) * a.pix_stride);
-                p10 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i0) * a.pix_stride);
-                p11 = map_load(a.maps[v], a.dtype, fb + (r1 + tx.i1) * a.pix_stride);
-              }
-              const float val = ty.l0 * (tx.l0 * p00 + tx.l1 * p01) + ty.l1 * (tx.l0 * p10 + tx.l1 * p11);
-              const int idx = (int)fminf(fmaxf(val * 255.f, 0.f), 255.f);      // truncates, as .byte() does; NaN -> 0
-              best[v][rr][j] = max(best[v][rr][j], idx);
+              best[v][rr][j] = max(best[v][rr][j], color_index(s_map[v], staged, fp, a.maps[v], a, fb, ty, tx));
             }
           }
         }
@@ -435,7 +387,6 @@ __global__ __launch_bounds__(256) void region_heatmap_kernel(RegionHeatmapArgs a
 
   if (xt >= a.W) return;
   const int n = min(PX, a.W - xt);
-  const float wgt = a.weight, iw = 1.f - a.weight;
 #pragma unroll
   for (int rr = 0; rr < ROWS; ++rr) {
     const int y = yt + ROW_STEP * rr;
@@ -452,10 +403,8 @@ __global__ __launch_bounds__(256) void region_heatmap_kernel(RegionHeatmapArgs a
         const int idx = best[v][rr][j];
         if (idx < 0) continue;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float img = (float)get_byte(d, 3 * j + c);
-          set_byte(o[v], 3 * j + c, (uint32_t)floorf(wgt * (float)s_lut[idx * 3 + c] + iw * img));
-        }
+        for (int c = 0; c < 3; ++c)
+          set_byte(o[v], 3 * j + c, map_blend(a.weight, (int)s_lut[idx * 3 + c], (int)get_byte(d, 3 * j + c)));
       }
     store_px(a.out[0] + at, a.wide, n, o[0]);
     if (views == 2) store_px(a.out[1] + at, a.wide, n, o[1]);
@@ -475,15 +424,10 @@ void skeleton_default_colors(bool bgr, uint8_t* out63) {
     for (int c = 0; c < 3; ++c) out63[i * 3 + c] = kSkeletonRGB[i][bgr ? 2 - c : c];
 }
 
-// The piece-wise linear "jet": with t = i / 255, red = clamp(1.5 - |4 t - 3|), green = clamp(1.5 - |4 t - 2|), blue =
-// clamp(1.5 - |4 t - 1|), clamped to [0, 1] and scaled to bytes by floor(255 v + 0.5).  255 v + 0.5 = 383 - |4 i - 255 k|
-// (k = 3, 2, 1) is an integer, so the table is exact integer arithmetic: byte = clamp(383 - |4 i - 255 k|, 0, 255).
+// the piece-wise linear "jet" of csrc/map_view_plan.h
 void heatmap_default_lut(bool bgr, uint8_t* out768) {
   for (int i = 0; i < 256; ++i)
-    for (int c = 0; c < 3; ++c) {
-      const int k = 3 - c, d = 4 * i - 255 * k, v = 383 - (d < 0 ? -d : d);
-      out768[i * 3 + (bgr ? 2 - c : c)] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
-    }
+    for (int c = 0; c < 3; ++c) out768[i * 3 + (bgr ? 2 - c : c)] = (uint8_t)map_jet(i, c);
 }
 
 hipError_t launch_skeleton(const SkeletonArgs& a0, hipStream_t s) {
@@ -493,16 +437,20 @@ hipError_t launch_skeleton(const SkeletonArgs& a0, hipStream_t s) {
   return hipGetLastError();
 }
 
+static int heatmap_wide(const HeatmapBase& a) {
+  return dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
+}
+
 hipError_t launch_heatmap(const HeatmapArgs& a0, hipStream_t s) {
   HeatmapArgs a = a0;
-  a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
+  a.wide = heatmap_wide(a);
   hipLaunchKernelGGL(heatmap_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_region_heatmap(const RegionHeatmapArgs& a0, hipStream_t s) {
   RegionHeatmapArgs a = a0;
-  a.wide = dword_rows(a.img_in, a.W) && dword_rows(a.out[0], a.W) && (!a.maps[1] || dword_rows(a.out[1], a.W));
+  a.wide = heatmap_wide(a);
   hipLaunchKernelGGL(region_heatmap_kernel, dim3((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.n_frames), dim3(256), 0, s, a);
   return hipGetLastError();
 }

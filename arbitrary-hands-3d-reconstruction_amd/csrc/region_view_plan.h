@@ -6,7 +6,7 @@
 // A region has an `offsets` row o = [padded h, padded w, ct, cr, cb, cl, pt, pr, pb, pl] (csrc/roi_plan.h) and a frame index;
 // the frames are H x W.  Everything is fp32, every operation rounded on its own (the library is built with -ffp-contract=off).
 //   view     (sx, sy, ox, oy) = (o[0] / 512, o[1] / 512, o[5] - o[9], o[2] - o[6]): frame x = canvas x * sx + ox, the map of
-//            pj2d -> pj2d_org (csrc/mano.hip), of render_prep_kernel, heatmap_kernel and ops.view_from_offsets
+//            pj2d -> pj2d_org (csrc/mano.hip), of render_prep_kernel, map_frame_view (csrc/map_view_plan.h) and ops.view_from_offsets
 //   window   l = o[5], t = o[2], r = W - o[3], b = H - o[4], each clamped into [0, W] / [0, H] with a clamp that sends NaN to 0;
 //            pixel x belongs to the window when its centre does: l <= x + 0.5 < r, that is x0 <= x < x1 with
 //            x0 = ceil(l - 0.5), x1 = ceil(r - 0.5) - for the whole numbers the pre-processing writes, x0 = l and x1 = r

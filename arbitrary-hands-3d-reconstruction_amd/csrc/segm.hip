@@ -1,5 +1,6 @@
 // The hand-part segmentation as an output: label maps at the frames' resolution, the 'segm' view, and
-// the statistics of the masks.  The rule is csrc/segm_plan.h, stated once for the host and the device.
+// the statistics of the masks.  The rule is csrc/segm_plan.h, on the map sampling of csrc/map_view_plan.h that the heat-map
+// views share, each stated once for the host and the device.
 //
 //   segm_kernel        one 256-thread block per (SEGM_TW x SEGM_TH pixel tile, frame), every thread 4 pixels of one row.  The
 //                      cells of the logits the tile samples are staged in LDS - whole cells in 16-byte pieces when the
@@ -15,7 +16,6 @@
 // safe.  No atomics on global memory: the results are the same words on every run, and a frame's do not depend on its batch.
 #include "kernels.h"
 #include "px_rows.h"
-#include "region_view_plan.h"
 #include "segm_plan.h"
 
 #include <climits>
@@ -38,12 +38,12 @@ __device__ inline int label_of(const float* pa, const float* pb, const float* pc
   for (int k = 0; k < C; k += 4) {
     const float4 a = *reinterpret_cast<const float4*>(pa + k), b = *reinterpret_cast<const float4*>(pb + k);
     const float4 c = *reinterpret_cast<const float4*>(pc + k), d = *reinterpret_cast<const float4*>(pd + k);
-    const float v0 = segm_value(ty, tx, a.x, b.x, c.x, d.x);
+    const float v0 = map_value(ty, tx, a.x, b.x, c.x, d.x);
     if (k == 0) best = v0;
     else segm_take(v0, k, best, label);
-    if (k + 1 < C) segm_take(segm_value(ty, tx, a.y, b.y, c.y, d.y), k + 1, best, label);
-    if (k + 2 < C) segm_take(segm_value(ty, tx, a.z, b.z, c.z, d.z), k + 2, best, label);
-    if (k + 3 < C) segm_take(segm_value(ty, tx, a.w, b.w, c.w, d.w), k + 3, best, label);
+    if (k + 1 < C) segm_take(map_value(ty, tx, a.y, b.y, c.y, d.y), k + 1, best, label);
+    if (k + 2 < C) segm_take(map_value(ty, tx, a.z, b.z, c.z, d.z), k + 2, best, label);
+    if (k + 3 < C) segm_take(map_value(ty, tx, a.w, b.w, c.w, d.w), k + 3, best, label);
   }
   return label;
 }
@@ -59,24 +59,15 @@ __global__ __launch_bounds__(256) void segm_kernel(SegmArgs a) {
   const int xt = X0 + PX * (tid % TXN), y = Y0 + tid / TXN;
   if (tid < 3 * a.C) s_col[tid] = a.colors[tid];
 
-  const bool has_view = a.view || a.offsets;
-  float sx = 1.f, sy = 1.f, ox = 0.f, oy = 0.f;
-  if (a.view) {
-    sx = a.view[f * 4]; sy = a.view[f * 4 + 1]; ox = a.view[f * 4 + 2]; oy = a.view[f * 4 + 3];
-  } else if (a.offsets) {
-    float row[4];
-    region_view_row(a.offsets + (size_t)f * 10, row);
-    sx = row[0]; sy = row[1]; ox = row[2]; oy = row[3];
-  }
+  const MapView v = map_frame_view(a.view, a.offsets, f);
   const float kx = 512.f / (float)a.W, ky = 512.f / (float)a.H;
   const float mx = (float)a.w / 512.f, my = (float)a.h / 512.f;
 
   // what this tile samples (the same for every thread), staged when it fits
-  const SegmFootprint fp = segm_footprint(X0, min(X0 + SEGM_TW, a.W), Y0, min(Y0 + SEGM_TH, a.H), has_view, sx, sy, ox, oy, a.H, a.W,
-                                          a.h, a.w);
+  const MapFootprint fp = map_footprint(X0, min(X0 + SEGM_TW, a.W), Y0, min(Y0 + SEGM_TH, a.H), v, a.H, a.W, a.h, a.w);
   const bool vec = a.vec != 0;
   const int cell = segm_cell_floats(a.C, vec);
-  const bool staged = segm_staged(fp, cell);
+  const bool staged = map_staged(fp, cell, SEGM_LDS_FLOATS);
   const float* frame = a.logits + (size_t)f * a.frame_stride;
   if (staged) {
     if (vec) {
@@ -100,14 +91,14 @@ __global__ __launch_bounds__(256) void segm_kernel(SegmArgs a) {
   int lab[PX];
 #pragma unroll
   for (int j = 0; j < PX; ++j) lab[j] = SEGM_NONE;
-  const float cy = segm_canvas(y, has_view, sy, oy, ky);
+  const float cy = map_canvas(y, v.has, v.sy, v.oy, ky);
   if (fp.any && cy >= 0.f && cy < 512.f) {
     const Tap ty = map_tap(cy, my, a.h);
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
       if (j >= n) continue;
-      const float cx = segm_canvas(xt + j, has_view, sx, ox, kx);
-      if (!segm_covered(cx, cy, sx, sy)) continue;
+      const float cx = map_canvas(xt + j, v.has, v.sx, v.ox, kx);
+      if (!map_covered(cx, cy, v.sx, v.sy)) continue;
       const Tap tx = map_tap(cx, mx, a.w);
       if (staged) {
         const int r0 = (ty.i0 - fp.iy) * fp.fw - fp.ix, r1 = (ty.i1 - fp.iy) * fp.fw - fp.ix;
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(256) void segm_kernel(SegmArgs a) {
       if (!(lab[j] >= 1 && lab[j] < a.C)) continue;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        set_byte(d, 3 * j + c, segm_blend(a.weight, (int)s_col[3 * lab[j] + c], (int)get_byte(d, 3 * j + c)));
+        set_byte(d, 3 * j + c, map_blend(a.weight, (int)s_col[3 * lab[j] + c], (int)get_byte(d, 3 * j + c)));
     }
     store_px(a.out + 3 * px, a.wide, n, d);
   }

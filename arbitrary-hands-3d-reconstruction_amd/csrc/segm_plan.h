@@ -4,12 +4,9 @@
 //
 // The logits are a map of h x w cells of C classes (NHWC; a cell is pix_stride floats, a frame frame_stride floats); the
 // frames are H x W.  Everything is fp32, every operation rounded on its own (the library is built with -ffp-contract=off).
-//   canvas   of pixel x: (x + 0.5 - ox) / sx under a view row (sx, sy, ox, oy) - given, or region_view_row of an `offsets`
-//            row - and (x + 0.5) * (512 / W) without one: steps 1-2 of DESIGN.md section 10.  A pixel is COVERED when its
-//            frame has sx > 0 and sy > 0 (false for NaN) and 0 <= cx < 512 and 0 <= cy < 512.
-//   taps     map_tap(cx, w / 512, w), map_tap(cy, h / 512, h): the half-pixel-centre bilinear rule of the heat-map views
-//   value    v_c = ly0 * (lx0 * a_c + lx1 * b_c) + ly1 * (lx0 * c_c + lx1 * d_c) for every class: bilinear LOGITS, not nearest
-//            labels; a non-finite cell propagates as the formula says
+// The frame's view, the canvas coordinate, COVERED, the taps, the footprint of a tile, the jet and the blend are the heat-map
+// views' own: csrc/map_view_plan.h.  What is segmentation's:
+//   value    map_value of every class c, v_c: bilinear LOGITS, not nearest labels
 //   label    best = v_0, label = 0; for c = 1 .. C-1 in order, c is taken when v_c > best - strict: the lowest class wins a
 //            tie and a NaN never wins (a NaN in class 0 keeps label 0).  A pixel that is not covered: SEGM_NONE = 255.
 //   sides    C is odd, 3 <= C <= 63.  Class 0 is background, classes 1 .. (C-1)/2 are the RIGHT hand's parts and the rest the
@@ -34,7 +31,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "roi_plan.h"      // ACRMI_HD
+#include "map_view_plan.h"      // Tap, map_value, map_jet, ...; ACRMI_HD
 
 namespace acrmi {
 
@@ -52,32 +49,6 @@ constexpr int SEGM_STATS_ROWS = 16;
 constexpr int SEGM_STATS_REC = 80;                // 64 counts, 2 x (min x, min y, max x, max y), 2 x (intersection, silhouette), 4 unused
 constexpr int SEGM_REC_BOX = 64, SEGM_REC_AGREE = 72;
 
-struct Tap { int i0, i1; float l0, l1; };
-
-// source position of canvas coordinate c on a map of n cells (scale m = n / 512): the half-pixel-centre bilinear rule
-ACRMI_HD inline Tap map_tap(float c, float m, int n) {
-  const float s = fmaxf(c * m - 0.5f, 0.f);
-  Tap t;
-  t.i0 = (int)s < n - 1 ? (int)s : n - 1;
-  t.i1 = t.i0 + 1 < n - 1 ? t.i0 + 1 : n - 1;
-  t.l1 = s - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// canvas coordinate of pixel x: s, o = the view's scale and shift along this axis, k = 512 / (the frame's size along it)
-ACRMI_HD inline float segm_canvas(int x, bool has_view, float s, float o, float k) {
-  return has_view ? ((float)x + 0.5f - o) / s : ((float)x + 0.5f) * k;
-}
-
-ACRMI_HD inline bool segm_covered(float cx, float cy, float sx, float sy) {
-  return sx > 0.f && sy > 0.f && cx >= 0.f && cx < 512.f && cy >= 0.f && cy < 512.f;
-}
-
-ACRMI_HD inline float segm_value(const Tap& ty, const Tap& tx, float a, float b, float c, float d) {
-  return ty.l0 * (tx.l0 * a + tx.l1 * b) + ty.l1 * (tx.l0 * c + tx.l1 * d);
-}
-
 // one step of the arg-max: class c with value v against the best so far
 ACRMI_HD inline void segm_take(float v, int c, float& best, int& label) {
   if (v > best) { best = v; label = c; }
@@ -85,9 +56,9 @@ ACRMI_HD inline void segm_take(float v, int c, float& best, int& label) {
 
 // the label of one covered pixel from its four cells (C floats each)
 ACRMI_HD inline int segm_label(const float* a, const float* b, const float* c, const float* d, const Tap& ty, const Tap& tx, int C) {
-  float best = segm_value(ty, tx, a[0], b[0], c[0], d[0]);
+  float best = map_value(ty, tx, a[0], b[0], c[0], d[0]);
   int label = 0;
-  for (int k = 1; k < C; ++k) segm_take(segm_value(ty, tx, a[k], b[k], c[k], d[k]), k, best, label);
+  for (int k = 1; k < C; ++k) segm_take(map_value(ty, tx, a[k], b[k], c[k], d[k]), k, best, label);
   return label;
 }
 
@@ -96,12 +67,6 @@ ACRMI_HD inline bool segm_dim_ok(int v) { return v > 0 && v <= SEGM_MAX_DIM; }
 
 // 1 = right, 0 = left, -1 = background, SEGM_NONE or no label at all
 ACRMI_HD inline int segm_side(int label, int C) { return label < 1 || label >= C ? -1 : (label <= (C - 1) / 2 ? 1 : 0); }
-
-// the jet of the heat-map views (csrc/overlay.hip heatmap_default_lut): channel c (0 = red) of entry i
-ACRMI_HD inline int segm_jet(int i, int c) {
-  const int d = 4 * i - 255 * (3 - c), v = 383 - (d < 0 ? -d : d);
-  return v < 0 ? 0 : v > 255 ? 255 : v;
-}
 
 // jet entry of a label (1 <= label < C)
 ACRMI_HD inline int segm_color_index(int label, int C) {
@@ -114,39 +79,11 @@ ACRMI_HD inline int segm_color_index(int label, int C) {
 ACRMI_HD inline void segm_default_colors(bool bgr, int C, uint8_t* colors) {
   for (int c = 0; c < 3; ++c) colors[c] = 0;
   for (int l = 1; l < C; ++l)
-    for (int c = 0; c < 3; ++c) colors[3 * l + (bgr ? 2 - c : c)] = (uint8_t)segm_jet(segm_color_index(l, C), c);
-}
-
-ACRMI_HD inline uint8_t segm_blend(float weight, int colour, int img) {
-  return (uint8_t)floorf(weight * (float)colour + (1.f - weight) * (float)img);
-}
-
-// What a tile of pixels [X0, X1) x [Y0, Y1) (not empty, inside the frame) samples.  The canvas coordinate is monotone in the
-// pixel coordinate and the taps are monotone in the canvas coordinate, so the taps of the first and of the last pixel (clamped
-// into the canvas) bound those of every covered pixel between them.  any = 0: no pixel of the tile is covered.
-struct SegmFootprint { int any, ix, iy, fw, fh; };
-
-ACRMI_HD inline SegmFootprint segm_footprint(int X0, int X1, int Y0, int Y1, bool has_view, float sx, float sy, float ox, float oy,
-                                             int H, int W, int h, int w) {
-  SegmFootprint f = {0, 0, 0, 0, 0};
-  const float kx = 512.f / (float)W, ky = 512.f / (float)H;
-  const float cx_a = segm_canvas(X0, has_view, sx, ox, kx), cx_b = segm_canvas(X1 - 1, has_view, sx, ox, kx);
-  const float cy_a = segm_canvas(Y0, has_view, sy, oy, ky), cy_b = segm_canvas(Y1 - 1, has_view, sy, oy, ky);
-  if (!(sx > 0.f && sy > 0.f && cx_b >= 0.f && cx_a < 512.f && cy_b >= 0.f && cy_a < 512.f)) return f;      // (false for NaN)
-  const float mx = (float)w / 512.f, my = (float)h / 512.f;
-  f.any = 1;
-  f.ix = map_tap(fminf(fmaxf(cx_a, 0.f), 512.f), mx, w).i0;
-  f.iy = map_tap(fminf(fmaxf(cy_a, 0.f), 512.f), my, h).i0;
-  f.fw = map_tap(fminf(fmaxf(cx_b, 0.f), 512.f), mx, w).i1 - f.ix + 1;
-  f.fh = map_tap(fminf(fmaxf(cy_b, 0.f), 512.f), my, h).i1 - f.iy + 1;
-  return f;
+    for (int c = 0; c < 3; ++c) colors[3 * l + (bgr ? 2 - c : c)] = (uint8_t)map_jet(segm_color_index(l, C), c);
 }
 
 // floats of a staged cell: whole 16-byte pieces when the cells can be read so (vec), else the C classes
 ACRMI_HD inline int segm_cell_floats(int C, bool vec) { return vec ? (C + 3) & ~3 : C; }
-ACRMI_HD inline bool segm_staged(const SegmFootprint& f, int cell_floats) {
-  return f.any && (long long)f.fw * f.fh * cell_floats <= SEGM_LDS_FLOATS;
-}
 
 // ---- statistics ----
 ACRMI_HD inline int segm_stats_chunks(int H) { return (H + SEGM_STATS_ROWS - 1) / SEGM_STATS_ROWS; }

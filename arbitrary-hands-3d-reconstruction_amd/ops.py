@@ -1435,6 +1435,17 @@ def draw_skeletons(kps, images, hand_frame=None, colors=None, line_width=3, circ
     return dst
 
 
+def _maps_arg(maps, images, n, per, rows=None):
+    """The maps of draw_heatmaps / draw_region_heatmaps, checked -> (fp32, contiguous, on the images' device; pointer to the
+    right maps or None; whether there are two per row)."""
+    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() not in (3, 4) or \
+            (maps.dim() == 4 and maps.shape[1] != 2) or maps.shape[0] < 1 or (rows is not None and maps.shape[0] != rows):
+        raise ValueError('maps must be a float tensor [%s,2,h,w] or [%s,h,w] with one row per %s' % (n, n, per))
+    m = maps.to(images.device, torch.float32).contiguous()      # (16-bit maps convert exactly)
+    two = m.dim() == 4
+    return m, C.c_void_p(m.data_ptr() + 4 * m.shape[-2] * m.shape[-1]) if two else None, two
+
+
 def draw_heatmaps(maps, images, view=None, weight=0.7, bgr=False, lut=None):
     """Heat maps in false colour over N frames on the GPU (acrmi_draw_heatmaps; the reference's 'centermap' view,
     acr/visualization.py:246-300: bilinear to the frame, * 255 truncated to a byte, colour table, weight * colour +
@@ -1444,28 +1455,19 @@ def draw_heatmaps(maps, images, view=None, weight=0.7, bgr=False, lut=None):
     None = it is the whole frame.  lut: uint8 [256,3] in the images' channel order (default: the library's, flipped with
     bgr=True).  Returns uint8 [2,N,H,W,3] for [N,2,h,w] maps, [N,H,W,3] for [N,h,w]."""
     _check_images(images)
-    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() not in (3, 4) or \
-            (maps.dim() == 4 and maps.shape[1] != 2) or maps.shape[0] != images.shape[0]:
-        raise ValueError('maps must be a float tensor [N,2,h,w] or [N,h,w] with one row per image')
+    m, right, two = _maps_arg(maps, images, 'N', 'image', images.shape[0])
     _need_cuda(maps, images)
     dev = images.device
     N, H, W, _ = images.shape
-    m = maps.to(dev, torch.float32).contiguous()      # (16-bit maps convert exactly)
     h, w = m.shape[-2:]
-    two = m.dim() == 4
     vw = None
     if view is not None:
         vw = torch.as_tensor(view, dtype=torch.float32).to(dev).contiguous()
         if tuple(vw.shape) != (N, 4):
             raise ValueError('view must be [N,4]')
-    tab = None
-    if lut is not None:
-        tab = np.ascontiguousarray(np.asarray(lut.cpu() if hasattr(lut, 'cpu') else lut))
-        if tab.shape != (256, 3) or tab.dtype != np.uint8:
-            raise ValueError('lut must be uint8 [256,3]')
+    tab = _lut_arg(lut)
     src = images.contiguous()
     out = torch.empty((2 if two else 1, N, H, W, 3), dtype=torch.uint8, device=dev)
-    right = C.c_void_p(m.data_ptr() + 4 * h * w) if two else None
     _lib.check(_lib.lib().acrmi_draw_heatmaps(_p(m), right, (2 if two else 1) * h * w, N, h, w, _p(vw), float(weight),
                                               None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
                                               _p(src), _p(out[0]), _p(out[1]) if two else None, H, W, _s(src)))
@@ -1494,23 +1496,15 @@ def draw_region_heatmaps(maps, images, offsets, region_frame, weight=0.7, bgr=Fa
     pixel is the input byte for byte.  weight, bgr, lut: as draw_heatmaps.  dst: uint8 [2,N,H,W,3] (or [N,H,W,3] for [n,h,w]
     maps) to draw into; dst[0] (dst) may BE images.  Returns uint8 [2,N,H,W,3], or [N,H,W,3] for [n,h,w] maps."""
     _check_images(images)
-    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() not in (3, 4) or \
-            (maps.dim() == 4 and maps.shape[1] != 2) or maps.shape[0] < 1:
-        raise ValueError('maps must be a float tensor [n,2,h,w] or [n,h,w] with one row per region')
+    m, rp, two = _maps_arg(maps, images, 'n', 'region')
     n, o, rf = check_regions(offsets, region_frame, maps.shape[0])
     _need_cuda(maps, images)
     dev = images.device
     N, H, W, _ = images.shape
-    m = maps.to(dev, torch.float32).contiguous()
     h, w = m.shape[-2:]
-    two = m.dim() == 4
     o = o.to(dev, torch.float32).contiguous()
     rf = rf.to(dev, torch.int32).contiguous()
-    tab = None
-    if lut is not None:
-        tab = np.ascontiguousarray(np.asarray(lut.cpu() if hasattr(lut, 'cpu') else lut))
-        if tab.shape != (256, 3) or tab.dtype != np.uint8:
-            raise ValueError('lut must be uint8 [256,3]')
+    tab = _lut_arg(lut)
     src = images.contiguous()
     shape = (2, N, H, W, 3) if two else (N, H, W, 3)
     if dst is None:
@@ -1518,7 +1512,6 @@ def draw_region_heatmaps(maps, images, offsets, region_frame, weight=0.7, bgr=Fa
     elif dst.dtype != torch.uint8 or tuple(dst.shape) != shape or not dst.is_contiguous() or dst.device != dev:
         raise ValueError('dst must be a contiguous uint8 tensor %s on the images\' device' % (shape,))
     left, right = (dst[0], dst[1]) if two else (dst, None)
-    rp = C.c_void_p(m.data_ptr() + 4 * h * w) if two else None
     _lib.check(_lib.lib().acrmi_draw_region_heatmaps(_p(m), rp, (2 if two else 1) * h * w, n, h, w, _p(o), _p(rf), float(weight),
                                                      None if tab is None else tab.ctypes.data_as(C.c_void_p), int(bool(bgr)),
                                                      _p(src), _p(left), _p(right), N, H, W, _s(src)))

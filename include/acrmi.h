@@ -994,7 +994,8 @@ int acrmi_render_regions_colored(acrmi_ctx* ctx, const float* verts_dev, const f
                                  uint8_t* img_out_dev, int n_frames, int H, int W, int32_t* ids_out_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * The hand-part segmentation as an output (the rule once in csrc/segm_plan.h; csrc/segm.hip).  The
+ * The hand-part segmentation as an output (the rule once in csrc/segm_plan.h, on the map sampling
+ * of csrc/map_view_plan.h that the heat-map views share; csrc/segm.hip).  The
  * network computes C = 33 part logits per cell of a 256 x 256 map (backbone.hand_segm, the reference's `segms`); the reference
  * turns them into labels with map2labels (acr/model.py:397-401) and draws nothing.  All fp32, every operation rounded on its
  * own:

@@ -3,8 +3,11 @@ written out in include/acrmi.h).  No GPU, no torch: the yardstick csrc/overlay.h
 
 Skeleton: integers only (numpy int64; with |k| < 16384 and pixel coordinates < 16384 every term fits: u.d and u x d are
 below 2^32, |d|^2 below 2^32, 4 (u x d)^2 below 2^38 once |u x d| >= 2^18 is rejected, w^2 |d|^2 below 2^39 for w <= 11).
-Heat map: np.float32 arrays throughout, so every operation is rounded on its own, in the order the rule states."""
+Heat map: np.float32 arrays throughout, so every operation is rounded on its own, in the order the rule states; canvas, taps,
+value, jet and blend are tests/map_view_ref.py's, which segm_ref shares."""
 import numpy as np
+
+from map_view_ref import blend, canvas, jet as jet_lut, taps, value
 
 PARENTS = (1, 2, 3, 20, 5, 6, 7, 20, 9, 10, 11, 20, 13, 14, 15, 20, 17, 18, 19, 20, -1)
 MAPPER = (4, 3, 2, 1, 8, 7, 6, 5, 12, 11, 10, 9, 16, 15, 14, 13, 20, 19, 18, 17, 0)
@@ -112,13 +115,6 @@ def draw_skeletons(kps, images, hand_frame=None, colors=None, line_width=3, circ
 
 
 # ---- heat maps --------------------------------------------------------------------------------------------------------
-def jet_lut(bgr=False):
-    """byte = clamp(383 - |4 i - 255 k|, 0, 255), k = 3, 2, 1 for red, green, blue."""
-    i = np.arange(256, dtype=np.int64)
-    lut = np.stack([np.clip(383 - np.abs(4 * i - 255 * k), 0, 255) for k in (3, 2, 1)], 1).astype(np.uint8)
-    return np.ascontiguousarray(lut[:, ::-1]) if bgr else lut
-
-
 def jet_lut_formula():
     """The same table from the stated formula in exact rationals: floor(255 clamp(3/2 - |4 t - k|, 0, 1) + 1/2), t = i / 255
     (in floating point t is inexact and the half-way values fall either way)."""
@@ -133,47 +129,24 @@ def jet_lut_formula():
     return lut
 
 
-def _canvas(n, scale_or_none, shift, size):
-    x = np.arange(n, dtype=F)
-    if scale_or_none is None:
-        return (x + F(0.5)) * (F(512) / F(size))
-    with np.errstate(all='ignore'):
-        return (x + F(0.5) - F(shift)) / F(scale_or_none)
-
-
-def _taps(c, inside, n):
-    c = np.where(inside, c, F(0)).astype(F)
-    s = np.maximum(c * (F(n) / F(512)) - F(0.5), F(0))
-    i0 = np.minimum(s.astype(np.int64), n - 1)
-    i1 = np.minimum(i0 + 1, n - 1)
-    l1 = (s - i0.astype(F)).astype(F)
-    l0 = (F(1) - l1).astype(F)
-    return i0, i1, l0, l1
-
-
 def heatmap_index(m, H, W, view=None):
     """One map fp32 [h,w] -> (idx uint8 [H,W], inside bool [H,W]); view = (sx, sy, ox, oy) or None."""
     m = np.asarray(m, np.float32)
     h, w = m.shape
     if view is None:
-        cx, cy, ok = _canvas(W, None, 0, W), _canvas(H, None, 0, H), True
+        cx, cy, ok = canvas(W), canvas(H), True
     else:
         sx, sy, ox, oy = (F(v) for v in view)
-        cx, cy = _canvas(W, sx, ox, W), _canvas(H, sy, oy, H)
+        cx, cy = canvas(W, (sx, ox)), canvas(H, (sy, oy))
         ok = bool(sx > 0) and bool(sy > 0)
     with np.errstate(invalid='ignore'):
         in_x = (cx >= 0) & (cx < 512) & ok
         in_y = (cy >= 0) & (cy < 512) & ok
-    x0, x1, lx0, lx1 = _taps(cx, in_x, w)
-    y0, y1, ly0, ly1 = _taps(cy, in_y, h)
-    a, b = m[y0][:, x0], m[y0][:, x1]
-    c, d = m[y1][:, x0], m[y1][:, x1]
+    v = value(m, taps(np.where(in_y, cy, F(0)), h), taps(np.where(in_x, cx, F(0)), w))
     with np.errstate(all='ignore'):
-        v = ly0[:, None] * (lx0[None] * a + lx1[None] * b) + ly1[:, None] * (lx0[None] * c + lx1[None] * d)
         t = v * F(255)
         t = np.where(np.isnan(t), F(0), t)
         idx = np.minimum(np.maximum(t, F(0)), F(255)).astype(np.uint8)      # truncates
-    assert v.dtype == np.float32
     return idx, in_y[:, None] & in_x[None, :]
 
 
@@ -182,15 +155,10 @@ def draw_heatmaps(maps, images, view=None, weight=0.7, lut=None, bgr=False):
     images = np.asarray(images, np.uint8)
     lut = jet_lut(bgr) if lut is None else np.asarray(lut, np.uint8)
     n, H, W, _ = images.shape
-    wgt = F(weight)
-    iw = F(1) - wgt
     out = images.copy()
     for i in range(n):
         idx, inside = heatmap_index(maps[i], H, W, None if view is None else np.asarray(view, np.float32)[i])
-        col = lut[idx].astype(F)
-        o = np.floor(wgt * col + iw * images[i].astype(F))
-        assert o.dtype == np.float32
-        out[i] = np.where(inside[..., None], o.astype(np.uint8), images[i])
+        out[i] = np.where(inside[..., None], blend(weight, lut[idx], images[i]), images[i])
     return out
 
 

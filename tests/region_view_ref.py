@@ -14,6 +14,7 @@ import numpy as np
 
 import overlay_ref as O
 import render_ref as R
+from map_view_ref import blend, view_from_offsets
 
 F = np.float32
 
@@ -24,9 +25,7 @@ def _clamp(v, hi):
 
 
 def view_row(o):
-    o = np.asarray(o, F)
-    with np.errstate(all='ignore'):
-        return np.array([o[0] / F(512), o[1] / F(512), o[5] - o[9], o[2] - o[6]], F)
+    return view_from_offsets(np.asarray(o, F)[None])[0]
 
 
 def region_view(o, frame, n_frames, H, W):
@@ -143,12 +142,7 @@ def draw_region_heatmaps(maps, images, offsets, region_frame, weight=0.7, lut=No
     lut = O.jet_lut(bgr) if lut is None else np.asarray(lut, np.uint8)
     N, H, W, _ = images.shape
     idx = heatmap_indices(np.asarray(maps, F), offsets, region_frame, N, H, W)
-    wgt = F(weight)
-    iw = F(1) - wgt
-    col = lut[np.maximum(idx, 0)].astype(F)
-    o = np.floor(wgt * col + iw * images.astype(F))
-    assert o.dtype == np.float32
-    return np.where((idx >= 0)[..., None], o.astype(np.uint8), images)
+    return np.where((idx >= 0)[..., None], blend(weight, lut[np.maximum(idx, 0)], images), images)
 
 
 def roi_offsets(H, W, box):

@@ -1,35 +1,12 @@
 """The part segmentation as an output (csrc/segm_plan.h) restated in numpy: labels, the 'segm' view, the
 default colours and the mask statistics.  Everything is float32, every operation rounded on its own, in the order the rule
-gives; arrays are NHWC as the library takes them."""
+gives; arrays are NHWC as the library takes them.  The map sampling it shares with the heat-map views is tests/map_view_ref.py."""
 import numpy as np
+
+from map_view_ref import blend, canvas, jet, taps, value, view_from_offsets  # noqa: F401 (view_from_offsets, jet: for the tests)
 
 F32 = np.float32
 NONE = 255
-
-
-def view_from_offsets(o):
-    o = np.asarray(o, F32)
-    return np.stack([o[:, 0] / F32(512), o[:, 1] / F32(512), o[:, 5] - o[:, 9], o[:, 2] - o[:, 6]], 1).astype(F32)
-
-
-def canvas(n, size, view=None):
-    """Canvas coordinate of the pixels 0..size-1 along one axis; view = (scale, shift) or None."""
-    x = np.arange(size, dtype=F32) + F32(0.5)
-    with np.errstate(all='ignore'):
-        if view is None:
-            return (x * (F32(512) / F32(size))).astype(F32)
-        return ((x - F32(view[1])) / F32(view[0])).astype(F32)
-
-
-def tap(c, n):
-    """map_tap: (i0, i1, l0, l1) of canvas coordinates c (finite) on a map of n cells."""
-    m = F32(n) / F32(512)
-    s = np.maximum(c * m - F32(0.5), F32(0)).astype(F32)
-    i0 = np.minimum(s.astype(np.int64), n - 1)
-    i1 = np.minimum(i0 + 1, n - 1)
-    l1 = (s - i0.astype(F32)).astype(F32)
-    l0 = (F32(1) - l1).astype(F32)
-    return i0, i1, l0, l1
 
 
 def labels_one(logits, C, H, W, view=None):
@@ -39,20 +16,15 @@ def labels_one(logits, C, H, W, view=None):
     out = np.full((H, W), NONE, np.uint8)
     if view is not None and not (view[0] > 0 and view[1] > 0):
         return out
-    cx = canvas(w, W, None if view is None else (view[0], view[2]))
-    cy = canvas(h, H, None if view is None else (view[1], view[3]))
+    cx = canvas(W, None if view is None else (view[0], view[2]))
+    cy = canvas(H, None if view is None else (view[1], view[3]))
     with np.errstate(invalid='ignore'):
         okx, oky = (cx >= 0) & (cx < 512), (cy >= 0) & (cy < 512)
-    x0, x1, lx0, lx1 = tap(np.where(okx, cx, F32(0)), w)
-    y0, y1, ly0, ly1 = tap(np.where(oky, cy, F32(0)), h)
-    lx0, lx1, ly0, ly1 = lx0[None, :], lx1[None, :], ly0[:, None], ly1[:, None]
+    tx, ty = taps(np.where(okx, cx, F32(0)), w), taps(np.where(oky, cy, F32(0)), h)
     best = lab = None
     with np.errstate(all='ignore'):
         for c in range(C):
-            m = logits[:, :, c]
-            top = (lx0 * m[np.ix_(y0, x0)]).astype(F32) + (lx1 * m[np.ix_(y0, x1)]).astype(F32)
-            bot = (lx0 * m[np.ix_(y1, x0)]).astype(F32) + (lx1 * m[np.ix_(y1, x1)]).astype(F32)
-            v = ((ly0 * top.astype(F32)).astype(F32) + (ly1 * bot.astype(F32)).astype(F32)).astype(F32)
+            v = value(logits[:, :, c], ty, tx)
             if c == 0:
                 best, lab = v, np.zeros((H, W), np.uint8)
             else:
@@ -67,14 +39,6 @@ def labels_one(logits, C, H, W, view=None):
 def labels(logits, C, H, W, view=None):
     """logits [n,h,w,>=C] -> uint8 [n,H,W]; view [n,4] or None."""
     return np.stack([labels_one(logits[i], C, H, W, None if view is None else np.asarray(view, F32)[i]) for i in range(len(logits))])
-
-
-def jet(bgr=False):
-    """The heat-map views' default table [256,3]."""
-    i = np.arange(256)[:, None]
-    k = np.array([3, 2, 1])[None, :]
-    t = np.clip(383 - np.abs(4 * i - 255 * k), 0, 255).astype(np.uint8)
-    return t[:, ::-1].copy() if bgr else t
 
 
 def default_colors(C=33, bgr=False):
@@ -92,9 +56,7 @@ def draw(images, lab, C, colors=None, weight=0.7, bgr=False):
     col = default_colors(C, bgr) if colors is None else np.asarray(colors, np.uint8)
     out = np.array(images, np.uint8, copy=True)
     hand = (lab >= 1) & (lab < C)
-    w = F32(weight)
-    mixed = np.floor((w * col[np.minimum(lab, C - 1)].astype(F32)).astype(F32) + ((F32(1) - w) * out.astype(F32)).astype(F32))
-    out[hand] = mixed.astype(np.uint8)[hand]
+    out[hand] = blend(weight, col[np.minimum(lab, C - 1)], out)[hand]
     return out
 
 

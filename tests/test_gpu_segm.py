@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import overlay_ref as O
+import region_view_ref as V
 import segm_ref as SR
 from conftest import pkg
 from contact_cases import eng, frames3, near_sd      # (fixtures)
@@ -164,6 +166,66 @@ def test_video_frames_under_the_view_of_their_offsets_rows(H, W):
     out, lab = _gpu(logits, C, img, offsets=torch.from_numpy(off), bgr=True)
     print('%d x %d: %d of %d labels differ' % (H, W, int((lab != want).sum()), want.size))
     assert np.array_equal(lab, want) and np.array_equal(out, SR.draw(img, want, C, bgr=True))
+
+
+# ---- the map sampling the segmentation shares with the heat-map views (csrc/map_view_plan.h) ----------------------------------
+@pytest.mark.parametrize('partial', [False, True])
+@pytest.mark.parametrize('H,W', [(16, 16), (96, 158)])
+def test_both_sides_of_the_staging_capacity(H, W, partial):
+    """A 64 x 64 map (4096 cells: more than the heat maps' 48 * 48 and, at 33 classes, than the segmentation's 344) under
+    draw_heatmaps, draw_region_heatmaps and draw_segm, byte for byte the restatements.  Over 16 x 16 the one tile's footprint is
+    (nearly) the whole map: every tap is read from memory.  Over 96 x 158 the footprints fit and are staged; the width is no
+    multiple of 4: the byte path.  partial: a view under which the canvas leaves part of the frame out - it zooms in at 16 x 16
+    (canvas = 0.6 of the frame: still beyond the capacities) and out at 96 x 158 (1.5: still staged).  Already there at other
+    shapes, no view: test_gpu_overlay's 128 x 128 map over 96 x 96 (from memory), this file's 'net-unstaged' (16 x 16)."""
+    ops = pkg('ops')
+    h = w = 64
+    off = np.zeros((3, 10), F32)      # regions 0 and 1: one per frame; region 2 overlaps region 0 in frame 0
+    span = (0.6 if H == 16 else 1.5) if partial else 1.0
+    off[:, 0], off[:, 1] = span * W, span * H
+    if partial:
+        off[:, 5], off[:, 6] = W // 4, 3      # ox = W // 4, where the window starts too; oy = -3
+    off[2, 5] += 2
+    off[2, 3] = W // 8
+    frames = [0, 1, 0]
+    view = None if not partial else SR.view_from_offsets(off[:2])
+    maps, img = O.gaussian_maps(3, h, w, seed=H, peaks=4), _images(2, H, W, seed=W)
+    tm, ti = torch.from_numpy(maps).cuda(), torch.from_numpy(img).cuda()
+    got = ops.draw_heatmaps(tm[:2], ti, view=None if view is None else torch.from_numpy(view)).cpu().numpy()
+    want = O.draw_heatmaps(maps[:2], img, view)
+    assert np.array_equal(got, want) and (want != img).any()
+    if partial:
+        assert np.array_equal(got[:, :, :W // 4], img[:, :, :W // 4])      # outside the canvas: the input
+    got = ops.draw_region_heatmaps(tm, ti, torch.from_numpy(off), frames).cpu().numpy()
+    want = V.draw_region_heatmaps(maps, img, off, frames)
+    assert np.array_equal(got, want) and (want != img).any()
+    C = 33
+    logits = _logits(2, h, w, 36, C, seed=W)
+    want = SR.labels(logits, C, H, W, view)
+    out, lab = _gpu(logits, C, img, **({} if view is None else {'view': torch.from_numpy(view)}))
+    assert np.array_equal(lab, want) and np.array_equal(out, SR.draw(img, want, C)) and (out != img).any()
+    assert (want == SR.NONE).any() == partial
+
+
+def test_the_three_views_agree_on_coverage():
+    """A 40 x 56 map over a 97 x 203 zero image under a view that leaves part of the frame outside the canvas, weight 1 and a table
+    of 255: the pixels draw_heatmaps changes are those segm_labels gives a label and those draw_region_heatmaps changes for the
+    one region with that view's `offsets` row and a window that is the frame."""
+    ops = pkg('ops')
+    H, W = 97, 203
+    off = np.array([[128, 64, 0, 0, 0, 0, 10, 0, 0, 20]], F32)      # the window: the whole frame
+    view = SR.view_from_offsets(off)
+    assert view.tolist() == [[0.25, 0.125, -20.0, -10.0]]      # the canvas: x in [-20, 108), y in [-10, 54) of the frame
+    inside = np.zeros((H, W), bool)
+    inside[:54, :108] = True
+    img = torch.zeros(1, H, W, 3, dtype=torch.uint8).cuda()
+    maps = torch.from_numpy(O.gaussian_maps(1, 40, 56, seed=3)).cuda()
+    lut = torch.full((256, 3), 255, dtype=torch.uint8)
+    heat = ops.draw_heatmaps(maps, img, view=torch.from_numpy(view), weight=1.0, lut=lut).cpu().numpy()[0]
+    region = ops.draw_region_heatmaps(maps, img, torch.from_numpy(off), [0], weight=1.0, lut=lut).cpu().numpy()[0]
+    lab = _gpu(_logits(1, 40, 56, 3, 3, seed=1), 3, None, (H, W), view=torch.from_numpy(view))[1][0]
+    assert np.array_equal((heat != 0).any(-1), inside) and (heat[inside] == 255).all()
+    assert np.array_equal((region != 0).any(-1), inside) and np.array_equal(lab != SR.NONE, inside)
 
 
 # ---- statistics -------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
-// Stand-alone check of the part-segmentation rules (csrc/segm_plan.h): the taps on recorded values, the
-// strict arg-max with ties, NaN and infinities, the colour table against its stated formula, the footprint of a tile against
-// the taps of every one of its pixels (views that scale, shift, face away or hold NaN and infinities included), and the
+// Stand-alone check of the part-segmentation rules (csrc/segm_plan.h) and of the map sampling they share
+// with the heat-map views (csrc/map_view_plan.h): the taps on recorded values, the strict arg-max with ties, NaN and infinities,
+// the colour table against its stated formula, the footprint of a tile - the segmentation's and the heat maps', whole or clipped
+// by a region's window - against the taps of every one of its pixels (views that scale, shift, face away or hold NaN and
+// infinities included), and the
 // statistics records - a frame's pixels pushed through chunks and folded - against a plain restatement written in this file.
 // No GPU, no HIP:
 //   c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -35,29 +37,29 @@ int main() {
   {
     // a 512-pixel row over a 256-cell map without a view: pixel x sits at canvas x + 0.5, source (x + 0.5) / 2 - 0.5
     const float m = 256.f / 512.f;
-    Tap t = map_tap(segm_canvas(0, false, 1.f, 0.f, 1.f), m, 256);
+    Tap t = map_tap(map_canvas(0, false, 1.f, 0.f, 1.f), m, 256);
     EXPECT(t.i0 == 0 && t.i1 == 1 && t.l1 == 0.f && t.l0 == 1.f);      // clamped at the edge
-    t = map_tap(segm_canvas(1, false, 1.f, 0.f, 1.f), m, 256);
+    t = map_tap(map_canvas(1, false, 1.f, 0.f, 1.f), m, 256);
     EXPECT(t.i0 == 0 && t.i1 == 1 && t.l1 == 0.25f && t.l0 == 0.75f);
-    t = map_tap(segm_canvas(2, false, 1.f, 0.f, 1.f), m, 256);
+    t = map_tap(map_canvas(2, false, 1.f, 0.f, 1.f), m, 256);
     EXPECT(t.i0 == 0 && t.i1 == 1 && t.l1 == 0.75f && t.l0 == 0.25f);
-    t = map_tap(segm_canvas(511, false, 1.f, 0.f, 1.f), m, 256);
+    t = map_tap(map_canvas(511, false, 1.f, 0.f, 1.f), m, 256);
     EXPECT(t.i0 == 255 && t.i1 == 255 && t.l1 == 0.25f);      // both taps the last cell
     // a 256-pixel row over a 256-cell map: the pixel is the cell, l1 = 0
     for (int x = 0; x < 256; ++x) {
-      t = map_tap(segm_canvas(x, false, 1.f, 0.f, 2.f), m, 256);
+      t = map_tap(map_canvas(x, false, 1.f, 0.f, 2.f), m, 256);
       EXPECT(t.i0 == x && t.l1 == 0.f && t.l0 == 1.f);
     }
     // a view: scale 3.75, shift -420 (a 1920-wide frame padded to a square)
-    t = map_tap(segm_canvas(960, true, 3.75f, 0.f, 0.f), m, 256);
+    t = map_tap(map_canvas(960, true, 3.75f, 0.f, 0.f), m, 256);
     EXPECT(t.i0 == 127 && t.i1 == 128);
     t = map_tap(512.f, m, 256);      // the clamp of the footprint's far end
     EXPECT(t.i0 == 255 && t.i1 == 255);
     t = map_tap(0.f, m, 1);          // a map of one cell
     EXPECT(t.i0 == 0 && t.i1 == 0);
-    EXPECT(segm_covered(0.f, 511.9f, 1.f, 1.f) && !segm_covered(512.f, 0.f, 1.f, 1.f) && !segm_covered(-0.001f, 0.f, 1.f, 1.f));
-    EXPECT(!segm_covered(nan, 0.f, 1.f, 1.f) && !segm_covered(0.f, 0.f, 0.f, 1.f) && !segm_covered(0.f, 0.f, 1.f, -1.f) &&
-           !segm_covered(0.f, 0.f, nan, 1.f) && !segm_covered(inf, 0.f, 1.f, 1.f));
+    EXPECT(map_covered(0.f, 511.9f, 1.f, 1.f) && !map_covered(512.f, 0.f, 1.f, 1.f) && !map_covered(-0.001f, 0.f, 1.f, 1.f));
+    EXPECT(!map_covered(nan, 0.f, 1.f, 1.f) && !map_covered(0.f, 0.f, 0.f, 1.f) && !map_covered(0.f, 0.f, 1.f, -1.f) &&
+           !map_covered(0.f, 0.f, nan, 1.f) && !map_covered(inf, 0.f, 1.f, 1.f));
   }
 
   // ---- arg-max: strict, the lowest class wins a tie, a NaN never wins ----
@@ -114,7 +116,7 @@ int main() {
       for (int c = 0; c < 3; ++c) {
         double v255 = 382.5 - std::abs(4 * i - 255 * (3 - c));      // 255 (1.5 - |4 t - k|), exact in binary
         v255 = v255 < 0 ? 0 : v255 > 255 ? 255 : v255;
-        EXPECT(segm_jet(i, c) == (int)std::floor(v255 + 0.5));
+        EXPECT(map_jet(i, c) == (int)std::floor(v255 + 0.5));
       }
     uint8_t rgb[63 * 3], bgr[63 * 3];
     segm_default_colors(false, 33, rgb);
@@ -123,13 +125,13 @@ int main() {
     for (int l = 1; l < 33; ++l) {
       const int i = l <= 16 ? 128 + 8 * (l - 1) : 127 - 8 * (l - 17);
       EXPECT(i >= 0 && i <= 255 && segm_color_index(l, 33) == i);
-      for (int c = 0; c < 3; ++c) EXPECT(rgb[3 * l + c] == segm_jet(i, c) && bgr[3 * l + 2 - c] == rgb[3 * l + c]);
+      for (int c = 0; c < 3; ++c) EXPECT(rgb[3 * l + c] == map_jet(i, c) && bgr[3 * l + 2 - c] == rgb[3 * l + c]);
       for (int k = 1; k < l; ++k)      // no two parts share a colour
         EXPECT(rgb[3 * l] != rgb[3 * k] || rgb[3 * l + 1] != rgb[3 * k + 1] || rgb[3 * l + 2] != rgb[3 * k + 2]);
     }
     segm_default_colors(false, 63, rgb);      // the largest C: the index is clamped into the table, nothing is written beyond 63 rows
     EXPECT(segm_color_index(31, 63) == 255 && segm_color_index(62, 63) == 0 && segm_color_index(1, 3) == 128 && segm_color_index(2, 3) == 127);
-    EXPECT(segm_blend(0.7f, 255, 0) == 178 && segm_blend(0.7f, 0, 255) == 76 && segm_blend(1.f, 200, 13) == 200 && segm_blend(0.f, 200, 13) == 13);
+    EXPECT(map_blend(0.7f, 255, 0) == 178 && map_blend(0.7f, 0, 255) == 76 && map_blend(1.f, 200, 13) == 200 && map_blend(0.f, 200, 13) == 13);
   }
 
   // ---- footprint: it holds the taps of every covered pixel of the tile ----
@@ -140,35 +142,59 @@ int main() {
                           {true, -1.f, 1.f, 0.f, 0.f},  {true, nan, 1.f, 0.f, 0.f},     {true, 1.f, 1.f, nan, 0.f},
                           {true, 1.f, 1.f, inf, -inf},  {true, 0.f, 0.f, 0.f, 0.f},     {true, 1e-30f, 1e30f, 0.f, 0.f}};
     const int sizes[][4] = {{512, 512, 256, 256}, {97, 203, 256, 256}, {16, 16, 256, 256}, {333, 517, 40, 56}, {1080, 1920, 256, 256}, {64, 128, 8, 8}};
+    // the segmentation's tile, and the heat maps' - whole, and its share of a region's window, which ends between tile boundaries
+    const int tiles[][2] = {{SEGM_TW, SEGM_TH}, {128, 32}};
     for (const View& v : views)
-      for (const auto& sz : sizes) {
-        const int H = sz[0], W = sz[1], h = sz[2], w = sz[3];
-        const float kx = 512.f / (float)W, ky = 512.f / (float)H, mx = (float)w / 512.f, my = (float)h / 512.f;
-        for (int Y0 = 0; Y0 < H; Y0 += SEGM_TH * 5)
-          for (int X0 = 0; X0 < W; X0 += SEGM_TW * 3) {
-            const int X1 = std::min(X0 + SEGM_TW, W), Y1 = std::min(Y0 + SEGM_TH, H);
-            const SegmFootprint f = segm_footprint(X0, X1, Y0, Y1, v.has, v.sx, v.sy, v.ox, v.oy, H, W, h, w);
-            if (f.any) EXPECT(f.ix >= 0 && f.iy >= 0 && f.fw >= 1 && f.fh >= 1 && f.ix + f.fw <= w && f.iy + f.fh <= h);
-            for (int y = Y0; y < Y1; ++y)
-              for (int x = X0; x < X1; ++x) {
-                const float cx = segm_canvas(x, v.has, v.sx, v.ox, kx), cy = segm_canvas(y, v.has, v.sy, v.oy, ky);
-                if (!segm_covered(cx, cy, v.sx, v.sy)) continue;
-                EXPECT(f.any);
-                const Tap tx = map_tap(cx, mx, w), ty = map_tap(cy, my, h);
-                EXPECT(tx.i0 >= f.ix && tx.i1 < f.ix + f.fw && ty.i0 >= f.iy && ty.i1 < f.iy + f.fh);
+      for (const auto& sz : sizes)
+        for (const auto& tile : tiles)
+          for (int windowed = 0; windowed <= (tile[0] == 128); ++windowed) {
+            const int H = sz[0], W = sz[1], h = sz[2], w = sz[3], TW = tile[0], TH = tile[1];
+            const int wx0 = windowed ? W / 7 + 1 : 0, wx1 = windowed ? W - W / 5 - 1 : W;
+            const int wy0 = windowed ? H / 9 + 1 : 0, wy1 = windowed ? H - H / 3 - 1 : H;
+            const float kx = 512.f / (float)W, ky = 512.f / (float)H, mx = (float)w / 512.f, my = (float)h / 512.f;
+            const MapView mv = {v.has, v.sx, v.sy, v.ox, v.oy};
+            for (int T0 = 0; T0 < H; T0 += TH * 5)
+              for (int L0 = 0; L0 < W; L0 += TW * 3) {
+                const int X0 = std::max(L0, wx0), X1 = std::min({L0 + TW, W, wx1}), Y0 = std::max(T0, wy0), Y1 = std::min({T0 + TH, H, wy1});
+                if (X0 >= X1 || Y0 >= Y1) continue;
+                const MapFootprint f = map_footprint(X0, X1, Y0, Y1, mv, H, W, h, w);
+                if (f.any) EXPECT(f.ix >= 0 && f.iy >= 0 && f.fw >= 1 && f.fh >= 1 && f.ix + f.fw <= w && f.iy + f.fh <= h);
+                for (int y = Y0; y < Y1; ++y)
+                  for (int x = X0; x < X1; ++x) {
+                    const float cx = map_canvas(x, v.has, v.sx, v.ox, kx), cy = map_canvas(y, v.has, v.sy, v.oy, ky);
+                    if (!map_covered(cx, cy, v.sx, v.sy)) continue;
+                    EXPECT(f.any);
+                    const Tap tx = map_tap(cx, mx, w), ty = map_tap(cy, my, h);
+                    EXPECT(tx.i0 >= f.ix && tx.i1 < f.ix + f.fw && ty.i0 >= f.iy && ty.i1 < f.iy + f.fh);
+                  }
               }
           }
-      }
+    // the frame's view: the `view` row, else the row of `offsets`, else none
+    {
+      const float rows[8] = {9, 9, 9, 9, 2.f, 0.5f, 100.f, -7.f}, o[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1024, 256, 30, 0, 0, 100, 10, 0, 0, 40};
+      MapView m = map_frame_view(rows, o, 1);
+      EXPECT(m.has && m.sx == 2.f && m.sy == 0.5f && m.ox == 100.f && m.oy == -7.f);
+      m = map_frame_view(nullptr, o, 1);
+      EXPECT(m.has && m.sx == 2.f && m.sy == 0.5f && m.ox == 60.f && m.oy == 20.f);
+      m = map_frame_view(nullptr, nullptr, 1);
+      EXPECT(!m.has && m.sx == 1.f && m.sy == 1.f && m.ox == 0.f && m.oy == 0.f);
+    }
     // the network's own case fits the staged capacity, whole cells of 36 floats; a small image over the whole map does not
-    const SegmFootprint net = segm_footprint(64, 128, 16, 32, false, 1, 1, 0, 0, 512, 512, 256, 256);
-    EXPECT(net.ix == 31 && net.iy == 7 && net.fw == 34 && net.fh == 10 && segm_staged(net, 36));
+    const MapView whole = {false, 1.f, 1.f, 0.f, 0.f}, away = {true, 1.f, 1.f, 600.f, 0.f};
+    const MapFootprint net = map_footprint(64, 128, 16, 32, whole, 512, 512, 256, 256);
+    EXPECT(net.ix == 31 && net.iy == 7 && net.fw == 34 && net.fh == 10 && map_staged(net, 36, SEGM_LDS_FLOATS));
     EXPECT(segm_cell_floats(33, true) == 36 && segm_cell_floats(33, false) == 33 && segm_cell_floats(3, true) == 4 && segm_cell_floats(63, true) == 64);
-    const SegmFootprint edge = segm_footprint(0, 64, 0, 16, false, 1, 1, 0, 0, 512, 512, 256, 256);
+    const MapFootprint edge = map_footprint(0, 64, 0, 16, whole, 512, 512, 256, 256);
     EXPECT(edge.ix == 0 && edge.fw == 33 && edge.fh == 9);
-    const SegmFootprint small = segm_footprint(0, 16, 0, 16, false, 1, 1, 0, 0, 16, 16, 256, 256);
-    EXPECT(small.any && small.ix == 7 && small.fw == 242 && small.fh == 242 && !segm_staged(small, 36) && !segm_staged(small, 33));
-    const SegmFootprint none = segm_footprint(0, 64, 0, 16, true, 1.f, 1.f, 600.f, 0.f, 512, 512, 256, 256);
-    EXPECT(!none.any && !segm_staged(none, 36));
+    const MapFootprint small = map_footprint(0, 16, 0, 16, whole, 16, 16, 256, 256);
+    EXPECT(small.any && small.ix == 7 && small.fw == 242 && small.fh == 242 && !map_staged(small, 36, SEGM_LDS_FLOATS) &&
+           !map_staged(small, 33, SEGM_LDS_FLOATS));
+    const MapFootprint none = map_footprint(0, 64, 0, 16, away, 512, 512, 256, 256);
+    EXPECT(!none.any && !map_staged(none, 36, SEGM_LDS_FLOATS));
+    // the heat maps' capacity of 48 * 48 cells: a 64 x 64 map over a 16 x 16 image is beyond it, over the first tile of a 158 x 96 image within
+    const MapFootprint all = map_footprint(0, 16, 0, 16, whole, 16, 16, 64, 64), part = map_footprint(0, 128, 0, 32, whole, 96, 158, 64, 64);
+    EXPECT(all.ix == 1 && all.fw == 62 && all.fh == 62 && !map_staged(all, 1, 48 * 48));
+    EXPECT(part.ix == 0 && part.iy == 0 && part.fw == 53 && part.fh == 22 && map_staged(part, 1, 48 * 48));
   }
 
   // ---- statistics: pixels -> chunk records -> folded record -> outputs, against a plain count ----
