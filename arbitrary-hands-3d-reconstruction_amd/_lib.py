@@ -99,7 +99,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_surface_contact', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes', 'acrmi_pose_errors',
            'acrmi_score_accumulate', 'acrmi_score_hands', 'acrmi_vertex_colors', 'acrmi_contact_values',
            'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored', 'acrmi_segm_tables',
-           'acrmi_segm_labels', 'acrmi_segm_stats_ws_ints', 'acrmi_segm_stats', 'acrmi_segment']
+           'acrmi_segm_labels', 'acrmi_segm_stats_ws_ints', 'acrmi_segm_stats', 'acrmi_segment', 'acrmi_match_board_bytes',
+           'acrmi_match_hands', 'acrmi_match_gather', 'acrmi_match_accumulate']
 
 _lib = None
 
@@ -269,12 +270,18 @@ def lib():
     L.acrmi_segm_stats_ws_ints.restype = C.c_size_t
     L.acrmi_segm_stats.argtypes = [u8p, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.acrmi_segment.argtypes = [vp, i32, f32p, C.c_float, u8p, i32, u8p, u8p, u8p, i32, i32, vp]
+    L.acrmi_match_board_bytes.argtypes = []
+    L.acrmi_match_board_bytes.restype = C.c_size_t
+    L.acrmi_match_hands.argtypes = [f32p, f32p, u8p, u8p, f32p, i32, f32p, vp, i32, i32, i32, i32, i32, C.c_float, i32, vp, vp, f32p,
+                                    vp, vp, vp]
+    L.acrmi_match_gather.argtypes = [f32p, vp, i32, i32, i32, i32, f32p, vp]
+    L.acrmi_match_accumulate.argtypes = [vp, f32p, i32, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ('acrmi_last_error', 'acrmi_destroy', 'acrmi_buffer_ptr', 'acrmi_attpool_ws_floats',
                         'acrmi_render_workspace', 'acrmi_streams_destroy', 'acrmi_tracks_destroy', 'acrmi_contact_workspace',
                         'acrmi_surface_contact_workspace', 'acrmi_score_board_bytes', 'acrmi_score_pair_bytes',
-                        'acrmi_segm_stats_ws_ints'):
+                        'acrmi_segm_stats_ws_ints', 'acrmi_match_board_bytes'):
             fn.restype = C.c_int
     _lib = L
     return L

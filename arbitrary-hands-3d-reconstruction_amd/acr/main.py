@@ -311,7 +311,7 @@ class ACR(object):
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
                       track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None, board=None,
-                      masks=False):
+                      masks=False, match=None, match_gate=float('inf'), match_board=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -373,9 +373,19 @@ class ACR(object):
         to `render`, else on the 512 x 512 canvas.  The map has no instances: with max_hand > 1 every hand of a side carries its
         side's values.  masks='iou': also 'mask_iou', the intersection over union of the side's mask and the side's drawn
         silhouette (the rasteriser's ids over the same frames, or over a scratch canvas) - a check of the reconstruction against
-        image evidence that needs no ground truth; nan when both are empty."""
+        image evidence that needs no ground truth; nan when both are empty.
+        match='kp2d' | 'joints' (needs gt=): the decoded hands are matched to the annotated ones on the
+        GPU before they are scored (Engine.match): gt then leads with [B,G,2] for any G in 1..8, whatever max_hand is, and may
+        hold 'kp2d' [B,G,2,21,2] in the pixels of pj2d_org and 'valid' [B,G,2].  'kp2d' matches on pj2d_org against gt['kp2d'],
+        'joints' on joints + cam_trans against gt['joints']; match_gate is the largest mean distance of a pair (pixels /
+        metres; default inf: a parameter, not a measurement).  Every hand dict gains 'gt_index' - the annotated hand it was
+        matched to, -1 for a false positive - and 'match_cost'; the four score keys come from the matched truth, nan for an
+        unmatched hand; board= receives the rows in TRUTH order, so its 'missed' are the annotated hands nothing was matched
+        to and its MRRPE pairs are (left g, right g).  match_board=: an engine.MatchBoard the batch's TP / FP / FN are added to.
+        The 'error' view and boxes= are not built with match=."""
         _check_contact(contact)
         _check_score(gt, board)
+        _check_match(match, gt, match_gate, match_board, show_items)
         check_masks(masks)
         show_items = check_show_items(show_items)
         if show_items is not None and render is None:
@@ -386,7 +396,8 @@ class ACR(object):
                                              batch_semantics=batch_semantics, streams=streams, max_streams=max_streams, K=K,
                                              tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
                                              multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board,
-                                             masks=masks, mask_frames=render, mask_offsets=offsets)
+                                             masks=masks, mask_frames=render, mask_offsets=offsets, match=match,
+                                             match_gate=match_gate, match_board=match_board)
         if render is None:
             return results
         _add_vertex_colors(eng, out, K, show_items, render_bgr)
@@ -404,7 +415,8 @@ class ACR(object):
 
     def _fused_call(self, frames, paths, *, offsets=None, point_heads=True, batch_semantics=None, streams=None, max_streams=None,
                     K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None,
-                    board=None, masks=False, mask_frames=None, mask_offsets=None):
+                    board=None, masks=False, mask_frames=None, mask_offsets=None, match=None, match_gate=float('inf'),
+                    match_board=None):
         """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).  K = 1 without
         tracks: one hand of each side, `point_heads` is the switch and multi_point_heads is checked and without effect.
         K > 1 or tracks=: Engine.forward(max_hand=K) on the dense heads, or with multi_point_heads (K > 1) at the K best centres.
@@ -461,7 +473,9 @@ class ACR(object):
                                          focal_length=self.focal_length).view(*out['slots'].shape[:-1], 3)
         if contact:
             _add_contact(eng, out, K, 'surface' if contact == 'surface' else 'vertex')
-        if gt is not None:
+        if gt is not None and match is not None:
+            _add_match(eng, out, K, gt, board, match, match_gate, match_board)
+        elif gt is not None:
             _add_score(eng, out, K, gt, board)
         if masks:
             _add_masks(self, eng, out, masks == 'iou', mask_frames, mask_offsets)
@@ -593,6 +607,38 @@ def _add_score(eng, out, K, gt, board):
     out['score'] = {'joints': res['joints']['row_f'], 'verts': None if res['verts'] is None else res['verts']['row_f']}
 
 
+def _check_match(match, gt, match_gate, match_board, show_items=None):
+    """match= / match_gate= / match_board= of forward_batch: ValueError before anything runs."""
+    if match is None:
+        if match_board is not None:
+            raise ValueError('match_board= accumulates the counts of match=: it needs match=')
+        return
+    if match not in ('kp2d', 'joints'):
+        raise ValueError("match must be None, 'kp2d' or 'joints', not %r" % (match,))
+    if gt is None:
+        raise ValueError('match= matches the decoded hands to gt=: it needs gt=')
+    if match == 'kp2d' and gt.get('kp2d') is None:
+        raise ValueError("match='kp2d' compares pj2d_org with gt['kp2d']: gt does not hold it")
+    if not float(match_gate) >= 0:
+        raise ValueError('match_gate %r: finite and >= 0, or inf' % (match_gate,))
+    if match_board is not None and not hasattr(match_board, 'words'):
+        raise ValueError('match_board must be an engine.MatchBoard')
+    if 'error' in (show_items or ()):
+        raise ValueError("show_items: 'error' is not built with match=: the errors are in truth order")
+
+
+def _add_match(eng, out, K, gt, board, match, gate, match_board):
+    """Engine.match of `out` against gt, then Engine.score of the truth-ordered rows (added to `board` when there is one):
+    out['match'] = {'match' [B,K,2], 'cost' [B,K,2], 'G'}, out['score'] = the per-hand rows in TRUTH order."""
+    res = eng.match(out, gt, on='joints' if match == 'joints' else 'pj2d_org', gate=gate, max_hand=K, cam_trans=out['cam_trans'],
+                    board=match_board)
+    G = res['pred_of'].shape[1]
+    sc = eng.score(res['out'], res['gt'], board=board, max_hand=G, cam_trans=res['out']['cam_trans'])
+    out['match'] = {'match': res['match'], 'cost': res['cost'], 'G': G}
+    out['match_result'] = res
+    out['score'] = {'joints': sc['joints']['row_f'], 'verts': None if sc['verts'] is None else sc['verts']['row_f']}
+
+
 def _segm_logits(eng, B):
     """The part logits of the last program run, NHWC [B,256,256,33]: a view of the context's buffer, not a copy."""
     return eng.buffer(eng.program['heads'].segm_buf, B, 33)
@@ -719,6 +765,10 @@ def results_from_out(out, paths):
     if sc is not None:
         from .. import score as score_mod
         sc = {k: (None if v is None else v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in sc.items()}
+    mt = out.get('match')      # with match=: 'gt_index' and 'match_cost', and the score rows are in truth order
+    if mt is not None:
+        from .. import match as match_mod
+        mt = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in mt.items()}
     results = {}
     for b, path in enumerate(paths):
         hands = []
@@ -738,8 +788,13 @@ def results_from_out(out, paths):
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
                     if ids is not None:
                         hands[-1]['track_id'] = np.int32(ids[b, k, h])
+                    row = (b * slots.shape[1] + k) * 2 + h
+                    if mt is not None:
+                        hands[-1].update(match_mod.hand_match_keys(mt['match'], mt['cost'], row))
+                        g = int(mt['match'].reshape(-1)[row])      # the score row of the matched truth; none: nan
+                        row = (b * int(mt['G']) + g) * 2 + h if g >= 0 else None
                     if sc is not None:
-                        hands[-1].update(score_mod.hand_score_keys(sc, (b * slots.shape[1] + k) * 2 + h))
+                        hands[-1].update(score_mod.hand_score_keys(sc if row is not None else {}, row))
                     if ms is not None:
                         hands[-1].update(mask_keys(ms, b, h))
                     where.append((k, h))
@@ -769,7 +824,7 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
                        max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False,
-                       gt=None, board=None, masks=False):
+                       gt=None, board=None, masks=False, match=None, match_gate=float('inf'), match_board=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -805,11 +860,16 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     vertex_colors=).
     show_items 'segm' and masks=: as forward_batch, the masks at the frames' own resolution with
     render=True, also with render_format='nv12'; with boxes= - and 'segm' in track_raw_batch - a ValueError: views and masks
-    over regions are not built (several overlapping regions of a frame would need a winner rule)."""
+    over regions are not built (several overlapping regions of a frame would need a winner rule).
+    match / match_gate / match_board (DESIGN.md section 24): as forward_batch, gt['kp2d'] in the pixels of the original frames;
+    with boxes= a ValueError (a region is one person)."""
     from .utils import img_preprocess_gpu
     _check_multi_point_heads(multi_point_heads)
     _check_contact(contact)
     _check_score(gt, board)
+    _check_match(match, gt, match_gate, match_board, check_show_items(show_items))
+    if boxes is not None and match is not None:
+        raise ValueError('match= with boxes= is not implemented: a region is one person (DESIGN.md section 24)')
     check_color_items(check_show_items(show_items), contact, gt, where=None if boxes is None else 'forward_raw_batch(boxes=)')
     check_masks(masks, where=None if boxes is None else 'forward_raw_batch(boxes=)')
     if boxes is not None:
@@ -835,7 +895,8 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
         got = self.forward_batch(meta['image'], paths, offsets=meta['offsets'], render=canvas,
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
                                  max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
-                                 multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board, masks=masks)
+                                 multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board, masks=masks,
+                                 match=match, match_gate=match_gate, match_board=match_board)
     if to_nv12 is None:
         return got
     return got[0], _views_to_nv12(to_nv12, got[1])

@@ -3,6 +3,7 @@
 #include "contact_plan.h"
 #include "surface_contact_plan.h"
 #include "conv_frame.h"   // conv_shape
+#include "match_plan.h"
 #include "roi_plan.h"
 #include "score_plan.h"
 #include "segm_plan.h"
@@ -894,6 +895,57 @@ int acrmi_score_accumulate(const float* e_ra_dev, const float* e_pa_dev, int N, 
   const ScoreAccArgs a{e_ra_dev, e_pa_dev, group_dev, 0, flags_dev, 1, pair_err_dev, N, n, n_groups, n_bins, bin_width,
                        (int64_t*)board_dev, (int64_t*)pair_board_dev};
   const hipError_t e = launch_score_accumulate(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+// ---- matching decoded hands to ground truth (csrc/match.hip; csrc/match_plan.h) ----
+size_t acrmi_match_board_bytes(void) { return match_board_bytes(); }
+
+int acrmi_match_hands(const float* pred_dev, const float* truth_dev, const uint8_t* valid_dev, const uint8_t* truth_valid_dev,
+                      const float* flags_dev, int flag_stride, const float* trans_dev, const int32_t* group_dev, int B, int K, int G,
+                      int n, int D, float gate, int min_points, int32_t* match_dev, int32_t* pred_of_dev, float* cost_dev,
+                      int32_t* counts_dev, int32_t* group_out_dev, void* stream) {
+  const char* who = "acrmi_match_hands";
+  if (B < 0 || K < 1 || K > MATCH_MAX || G < 1 || G > MATCH_MAX)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d frames, K = %d, G = %d (K, G in 1..%d)", who, B, K, G, MATCH_MAX);
+  if (n < 1 || n > MATCH_MAX_POINTS || (D != 2 && D != 3))
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d points of %d coordinates (n in 1..%d, D 2 or 3)", who, n, D, MATCH_MAX_POINTS);
+  if (!match_sizes_ok(B, K, G, n, D)) return fail(nullptr, ACRMI_EINVAL, "%s: %d frames are beyond 2^31 - 1 elements", who, B);
+  if (!match_gate_ok(gate)) return fail(nullptr, ACRMI_EINVAL, "%s: gate must be finite and >= 0, or +inf", who);
+  if (min_points < 1 || min_points > n) return fail(nullptr, ACRMI_EINVAL, "%s: min_points %d outside 1..%d", who, min_points, n);
+  if (flags_dev && flag_stride < 1) return fail(nullptr, ACRMI_EINVAL, "%s: flag_stride %d < 1", who, flag_stride);
+  if (B == 0) return ACRMI_OK;
+  if (!pred_dev || !truth_dev || !match_dev || !pred_of_dev || !cost_dev || !counts_dev || !group_out_dev)
+    return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  const MatchArgs a{pred_dev, truth_dev, valid_dev, truth_valid_dev, flags_dev, (size_t)flag_stride, trans_dev, group_dev, B, K, G, n, D,
+                    gate, min_points, match_dev, pred_of_dev, cost_dev, counts_dev, group_out_dev};
+  const hipError_t e = launch_match(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int acrmi_match_gather(const float* src_dev, const int32_t* index_dev, int B, int Ks, int Kd, int W, float* dst_dev, void* stream) {
+  const char* who = "acrmi_match_gather";
+  if (!match_gather_sizes_ok(B, Ks, Kd, W))
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d frames, Ks = %d, Kd = %d (1..%d), W = %d (>= 1), at most 2^31 - 1 elements", who, B, Ks,
+                Kd, MATCH_MAX, W);
+  if (B == 0) return ACRMI_OK;
+  if (!src_dev || !index_dev || !dst_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)src_dev & 3) != 0 || ((uintptr_t)dst_dev & 3) != 0 || ((uintptr_t)index_dev & 3) != 0)
+    return fail(nullptr, ACRMI_EINVAL, "%s: a pointer is not 4-byte aligned", who);
+  const MatchGatherArgs a{src_dev, index_dev, dst_dev, 2ll * B * Kd, W, Ks, Kd};
+  const hipError_t e = launch_match_gather(a, (hipStream_t)stream);
+  return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int acrmi_match_accumulate(const int32_t* counts_dev, const float* cost_dev, int B, int K, void* board_dev, void* stream) {
+  const char* who = "acrmi_match_accumulate";
+  if (B < 0 || K < 1 || K > MATCH_MAX || 2ll * B * K > 0x7fffffffll)
+    return fail(nullptr, ACRMI_EINVAL, "%s: %d frames, K = %d (1..%d)", who, B, K, MATCH_MAX);
+  if (B == 0) return ACRMI_OK;
+  if (!counts_dev || !cost_dev || !board_dev) return fail(nullptr, ACRMI_EINVAL, "%s: a null pointer", who);
+  if (((uintptr_t)board_dev & 7) != 0) return fail(nullptr, ACRMI_EINVAL, "%s: the board is not 8-byte aligned", who);
+  const MatchAccArgs a{counts_dev, cost_dev, B, K, (int64_t*)board_dev};
+  const hipError_t e = launch_match_accumulate(a, (hipStream_t)stream);
   return e == hipSuccess ? ACRMI_OK : fail(nullptr, ACRMI_EHIP, "%s: %s", who, hipGetErrorString(e));
 }
 

@@ -561,6 +561,42 @@ struct ScoreAccArgs {
 };
 hipError_t launch_score_accumulate(const ScoreAccArgs& a, hipStream_t s);
 
+// Matching decoded hands to ground truth (csrc/match.hip; the rule: csrc/match_plan.h).
+struct MatchArgs {
+  const float* pred;             // [B, K, 2, n, D]
+  const float* truth;            // [B, G, 2, n, D]
+  const uint8_t* valid;          // [B, G, 2, n] or null
+  const uint8_t* truth_valid;    // [B, G, 2] or null
+  const float* flags;            // flag of prediction row r = (b * K + i) * 2 + s at flags[r * flag_stride], or null
+  size_t flag_stride;
+  const float* trans;            // [B, K, 2, D] or null
+  const int32_t* group;          // [B, G, 2] or null = the side
+  int B, K, G, n, D;
+  float gate;
+  int min_points;
+  int32_t* match;                // [B, K, 2]
+  int32_t* pred_of;              // [B, G, 2]
+  float* cost;                   // [B, K, 2]
+  int32_t* counts;               // [B, 2, 3]
+  int32_t* group_out;            // [B, G, 2]
+};
+hipError_t launch_match(const MatchArgs& a, hipStream_t s);
+struct MatchGatherArgs {
+  const float* src;              // [B, Ks, 2, W]
+  const int32_t* index;          // [B, Kd, 2]
+  float* dst;                    // [B, Kd, 2, W]
+  long long rows, W;             // rows = B * Kd * 2
+  int Ks, Kd;
+};
+hipError_t launch_match_gather(const MatchGatherArgs& a, hipStream_t s);
+struct MatchAccArgs {
+  const int32_t* counts;         // [B, 2, 3]
+  const float* cost;             // [B, K, 2]
+  int B, K;
+  int64_t* board;                // match_board_bytes
+};
+hipError_t launch_match_accumulate(const MatchAccArgs& a, hipStream_t s);
+
 // Key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views").
 struct SkeletonArgs {
   const float* kps;              // [n_hands, 21, 2] MANO joint order; pixels of the image, or (normalized) [-1, 1] of the 512 canvas

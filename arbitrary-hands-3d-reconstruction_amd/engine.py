@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops as ops_mod, packer, score as score_mod
+from . import _lib, match as match_mod, ops as ops_mod, packer, score as score_mod
 from .ops import HAND_COLORS_RGB
 
 
@@ -224,6 +224,64 @@ class ScoreBoard(object):
         AUC, rows scored and missed - per group and over all (score.summarize says what is where)."""
         sets, pairs = self.arrays()
         return score_mod.summarize(sets, pairs, self.names, self.bin_width)
+
+
+MATCH_GATHERED = ('slots', 'joints', 'verts', 'cam_trans', 'pj2d', 'pj2d_org')      # what Engine.match brings into truth order
+
+
+def match_truth(gt, on, B, device):
+    """The ground truth of Engine.match as the library reads it -> (G, {'points' fp32 [B,G,2,21,D], 'joint_valid' uint8
+    [B,G,2,21] or None, 'valid' uint8 [B,G,2] or None, 'group' int32 [B,G,2] or None}), contiguous on `device`.  The points are
+    gt['kp2d'] for on = 'pj2d_org' / 'pj2d' and gt['joints'] for on = 'joints'."""
+    if on not in match_mod.ON_KEYS:
+        raise ValueError('on must be one of %s, not %r' % (', '.join(match_mod.ON_KEYS), on))
+    key, D = ('joints', 3) if on == 'joints' else ('kp2d', 2)
+    if not isinstance(gt, dict) or gt.get(key) is None:
+        raise ValueError("on=%r compares with gt['%s']: gt must be a dict that holds it" % (on, key))
+    pts = torch.as_tensor(gt[key])
+    if pts.dim() != 5 or pts.shape[0] != B or tuple(pts.shape[2:]) != (2, 21, D) or not 1 <= pts.shape[1] <= match_mod.MAX_HANDS:
+        raise ValueError("gt['%s'] must be [%d,G,2,21,%d] with G in 1..%d, got %s" % (key, B, D, match_mod.MAX_HANDS, list(pts.shape)))
+    G = pts.shape[1]
+    lead = (B, G, 2)
+    res = {'points': ops_mod._score_arg(pts, device, torch.float32, pts.shape, key)}
+    for name, dtype, tail in (('joint_valid', torch.uint8, (21,)), ('valid', torch.uint8, ()), ('group', torch.int32, ())):
+        t = gt.get(name)
+        res[name] = None if t is None else ops_mod._score_arg(t, device, dtype, lead + tail, "gt['%s']" % name, as_bool=name != 'group')
+    return G, res
+
+
+class MatchBoard(object):
+    """A device-resident running detection count: per side the matched pairs (TP), the flagged
+    predictions left unmatched (FP), the valid truths left unmatched (FN) and the sum of the matched costs.  The caller owns it;
+    Engine.match / EnginePool.match / ACR.forward_batch(match_board=) add batches to it without visiting the host, and
+    `summary()` is the one host visit.  Boards of several devices or ranks are summed by the caller (`words`)."""
+
+    def __init__(self, device=0):
+        self.device = torch.device('cuda', device) if isinstance(device, int) else torch.device(device)
+        assert _lib.lib().acrmi_match_board_bytes() == match_mod.BOARD_WORDS * 8
+        self.words = torch.zeros(match_mod.BOARD_WORDS, dtype=torch.int64, device=self.device)
+        self._event = None      # recorded behind the last call that touched the board, on whichever stream it ran
+
+    order_on = ScoreBoard.order_on
+    touched_on = ScoreBoard.touched_on
+    reset = ScoreBoard.reset
+
+    def add(self, res, stream=None):
+        """Adds an ops.match_hands result ('counts' and 'cost') on the current stream (or on the raw stream given)."""
+        st = torch.cuda.current_stream(self.device) if stream is None else torch.cuda.ExternalStream(stream, device=self.device)
+        self.order_on(st)
+        ops_mod.match_accumulate(self.words, res['counts'], res['cost'], stream=stream)
+        self.touched_on(st)
+
+    def arrays(self):
+        """The board on the host (match.board_arrays): the host waits for the calls queued so far."""
+        self.order_on(torch.cuda.current_stream(self.device))
+        return match_mod.board_arrays(self.words.cpu().numpy())
+
+    def summary(self):
+        """The one host visit: TP, FP, FN, precision, recall, F1 and the mean match cost, per side and over all
+        (match.summarize says what is where)."""
+        return match_mod.summarize(self.arrays())
 
 
 class Engine(object):
@@ -1032,6 +1090,75 @@ class Engine(object):
         return {'joints': ops_mod.score_result(rj), 'verts': None if rv is None else ops_mod.score_result(rv),
                 'pair_err': rj['pair_err']}
 
+    def match(self, out, gt, on='pj2d_org', gate=float('inf'), min_points=1, max_hand=1, cam_trans=None, board=None,
+              focal_length=1265., stream=None):
+        """Matches the hands of `out` (what `forward(..., project=True[, max_hand=K])` returned) to ground truth on the GPU and
+        brings them into truth order (acrmi_match_hands, acrmi_match_gather).  gt: what `score` takes,
+        with leading [B,G,2] for any G in 1..8, and two more optional keys: 'kp2d' [B,G,2,21,2] in the units of out[on] (on =
+        'pj2d_org' / 'pj2d'), 'valid' [B,G,2] (non-zero = the annotated hand exists).  on='joints' compares out['joints'] +
+        cam_trans (as `score` obtains it) with gt['joints'], the frame `score`'s absolute root error assumes.  A prediction is
+        looked at where its slot's flag is set (read on the device); gt['joint_valid'] says which points count.  gate: the
+        largest mean distance of an allowed pair (pixels, normalized units or metres), min_points: the fewest counted points of
+        one - parameters, not measurements.  board: a MatchBoard to add the batch to.  Nothing waits for the host.  Returns
+        {'match' int32 [B,K,2], 'pred_of' int32 [B,G,2], 'cost' [B,K,2], 'counts' int32 [B,2,3], 'group' int32 [B,G,2], 'out':
+        the slots, joints, verts, cam_trans and pj2d* of `out` as [B,G,2,...] rows in truth order (zeros where a truth has no
+        prediction), 'gt': gt with 'group' replaced - ready for score(res['out'], res['gt'], max_hand=G)}.  stream: as
+        `forward`."""
+        K = check_max_hand(max_hand)
+        if on not in match_mod.ON_KEYS:
+            raise ValueError('on must be one of %s, not %r' % (', '.join(match_mod.ON_KEYS), on))
+        slots = out['slots']
+        B = slots.shape[0]
+        lead = tuple(slots.shape[:-1])
+        if lead not in ((B, K, 2),) + (((B, 2),) if K == 1 else ()) or out.get(on) is None:
+            raise ValueError('out does not hold %d rows of %d hand pairs with %r' % (B, K, on))
+        dev = self.device
+        G, truth = match_truth(gt, on, B, dev)
+        D = 3 if on == 'joints' else 2
+        gate, min_points = ops_mod.check_match_params(gate, min_points, 21)
+        if board is not None and (not isinstance(board, MatchBoard) or board.device != dev):
+            raise ValueError('board must be a MatchBoard on %s' % (dev,))
+        st = _stream(dev) if stream is None else C.c_void_p(stream)
+        tst = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+        trans = None
+        if on == 'joints' or cam_trans is not None:
+            flat = out if len(lead) == 2 else {k: out[k].flatten(0, 1) for k in ('joints', 'pj2d', 'cam_trans') if out.get(k) is not None}
+            if cam_trans is not None:
+                cam_trans = cam_trans.reshape(B * K, 2, 3)
+            if cam_trans is not None or out.get('cam_trans') is not None or out.get('pj2d') is not None:
+                cam_trans = self._cam_trans(flat, cam_trans, B * K, focal_length, st).view(B, K, 2, 3)
+            trans = cam_trans if on == 'joints' else None
+        slots = slots.contiguous().view(B, K, 2, _lib.SLOT)
+        pred = out[on].contiguous()
+        if tuple(pred.shape) != lead + (21, D) or pred.dtype != torch.float32:
+            raise ValueError("out['%s'] must be fp32 %s" % (on, list(lead + (21, D))))
+        raw = ops_mod.match_outputs(B, K, G, dev)
+        if board is not None:
+            board.order_on(tst)
+        _lib.check(self.L.acrmi_match_hands(
+            _ptr(pred), _ptr(truth['points']), _ptr(truth['joint_valid']), _ptr(truth['valid']),
+            C.c_void_p(slots.data_ptr() + 4 * _lib.SLOT_FLAG), _lib.SLOT, _ptr(trans), _ptr(truth['group']), B, K, G, 21, D, gate,
+            min_points, *[_ptr(raw[k]) for k in ('match', 'pred_of', 'cost', 'counts', 'group')], st))
+        if board is not None:
+            _lib.check(self.L.acrmi_match_accumulate(_ptr(raw['counts']), _ptr(raw['cost']), B, K, _ptr(board.words), st))
+            board.touched_on(tst)
+        rows, kept = {}, [slots, pred, trans, truth]
+        for key in MATCH_GATHERED:
+            src = cam_trans if key == 'cam_trans' and cam_trans is not None else out.get(key)
+            if src is None:
+                continue
+            src = src.to(dev, torch.float32).contiguous().view((B, K, 2) + tuple(src.shape[len(lead):]))
+            dst = torch.empty((B, G, 2) + tuple(src.shape[3:]), dtype=torch.float32, device=dev)
+            _lib.check(self.L.acrmi_match_gather(_ptr(src), _ptr(raw['pred_of']), B, K, G, int(np.prod(src.shape[3:], dtype=np.int64)),
+                                                 _ptr(dst), st))
+            rows[key] = dst
+            kept.append(src)
+        self._match_keep = tuple(kept)      # referenced until the next call has been queued
+        res = dict(raw)
+        res['out'] = rows
+        res['gt'] = dict(gt, group=raw['group'])
+        return res
+
     def _regions(self, images, offsets, region_frame, n):
         """images, offsets [n,10], region_frame [n] of the calls over regions, checked without reading device memory ->
         (src, offsets, region_frame) on the device."""
@@ -1472,6 +1599,25 @@ class EnginePool(object):
         rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
         return self._on_ticket(ticket, 'score', prepare, keep='_score_keep',
                                call=lambda eng, raw, t: eng.score(out, board=board, max_hand=K, stream=raw, **t, **rest))
+
+    def match(self, ticket, gt, on='pj2d_org', board=None, **kw):
+        """Engine.match of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with
+        project=True) and collect(), like score().  max_hand is the ticket's.  A board shared by the pool's contexts is updated
+        in the order of the calls.  Returns what Engine.match returns; a score() of its rows on the same ticket runs behind it."""
+        out = ticket['out']
+        K = out['slots'].shape[1] if out['slots'].dim() == 4 else 1
+
+        def prepare(eng):      # (every conversion here: Engine.match then converts nothing on the caller's stream)
+            _, truth = match_truth(gt, on, out['slots'].shape[0], self.device)
+            key = 'joints' if on == 'joints' else 'kp2d'
+            t = {'gt': dict(gt, **{key: truth['points']}, **{k: truth[k] for k in ('joint_valid', 'valid', 'group') if truth[k] is not None})}
+            if kw.get('cam_trans') is not None:
+                t['cam_trans'] = kw['cam_trans'].to(self.device, torch.float32).contiguous()
+            return t
+
+        rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
+        return self._on_ticket(ticket, 'match', prepare, keep='_match_keep',
+                               call=lambda eng, raw, t: eng.match(out, on=on, board=board, max_hand=K, stream=raw, **t, **rest))
 
     def track_boxes(self, ticket, frame_hw, scale=1.5, min_size=64, out=None):
         """ops.track_boxes of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

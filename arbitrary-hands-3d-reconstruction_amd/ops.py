@@ -1365,6 +1365,106 @@ def score_accumulate(board, pair_board, res, n_groups, n_bins, bin_width, group=
                                                  _s(e) if stream is None else C.c_void_p(stream)))
 
 
+# ---- matching decoded hands to ground truth (csrc/match.hip) ----------------------------------------
+def match_outputs(B, K, G, dev):
+    """The raw output tensors of acrmi_match_hands, in the order it takes them."""
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    return {'match': i(B, K, 2), 'pred_of': i(B, G, 2), 'cost': torch.empty(B, K, 2, dtype=torch.float32, device=dev),
+            'counts': i(B, 2, 3), 'group': i(B, G, 2)}
+
+
+def check_match_params(gate, min_points, n):
+    """gate finite and >= 0, or +inf; min_points an integer in 1..n; else ValueError.  -> (float, int)."""
+    gate = float(gate)
+    if not gate >= 0:
+        raise ValueError('gate %r: finite and >= 0, or inf' % (gate,))
+    if int(min_points) != min_points or not 1 <= min_points <= n:
+        raise ValueError('min_points %r: an integer in 1..%d' % (min_points, n))
+    return gate, int(min_points)
+
+
+def match_hands(pred, truth, flags=None, valid=None, truth_valid=None, trans=None, group=None, gate=float('inf'), min_points=1):
+    """The exact assignment of predicted to true hands per (frame, side) on the GPU (acrmi_match_hands; the rule: DESIGN.md
+    section 24): pred [B,K,2,n,D], truth [B,G,2,n,D] device fp32 (K, G in 1..8, n <= 256, D = 2 or 3); the cost of a pair is the
+    mean distance over its counted points, the matching has the most allowed pairs and among those the smallest cost sum.
+    flags fp32 [B,K,2] (a prediction is looked at when its flag is > 0.5; None = all; a strided view such as slots[..., 0] is
+    read in place), valid [B,G,2,n] (non-zero = the point counts), truth_valid [B,G,2], trans [B,K,2,D] (added to the
+    prediction), group int32 [B,G,2] (default the side), gate: the largest cost of an allowed pair, min_points: the fewest
+    counted points of one.  Returns device tensors, nothing is copied to the host: 'match' int32 [B,K,2] (the truth of each
+    prediction or -1), 'pred_of' int32 [B,G,2], 'cost' fp32 [B,K,2] (-1 = unmatched), 'counts' int32 [B,2,3] (TP, FP, FN per
+    side), 'group' int32 [B,G,2] (-1 where the truth is not valid)."""
+    _need_cuda(pred, truth)
+    if pred.dim() != 5 or truth.dim() != 5 or pred.shape[2] != 2 or tuple(truth.shape[2:]) != tuple(pred.shape[2:]) or \
+            truth.shape[0] != pred.shape[0]:
+        raise ValueError('pred must be [B,K,2,n,D] and truth [B,G,2,n,D]')
+    dev = pred.device
+    B, K, _, n, D = pred.shape
+    G = truth.shape[1]
+    if not (1 <= K <= 8 and 1 <= G <= 8 and 1 <= n <= 256 and D in (2, 3)):
+        raise ValueError('K = %d, G = %d in 1..8, n = %d in 1..256, D = %d in (2, 3)' % (K, G, n, D))
+    gate, min_points = check_match_params(gate, min_points, n)
+    p, t = pred.to(dev, torch.float32).contiguous(), truth.to(dev, torch.float32).contiguous()
+    v = _score_arg(valid, dev, torch.uint8, (B, G, 2, n), 'valid', as_bool=True)
+    tv = _score_arg(truth_valid, dev, torch.uint8, (B, G, 2), 'truth_valid', as_bool=True)
+    tr = _score_arg(trans, dev, torch.float32, (B, K, 2, D), 'trans')
+    gr = _score_arg(group, dev, torch.int32, (B, G, 2), 'group')
+    fl, stride = _match_flags(flags, B, K, dev)
+    raw = match_outputs(B, K, G, dev)
+    _lib.check(_lib.lib().acrmi_match_hands(_p(p), _p(t), _p(v), _p(tv), _p(fl), stride, _p(tr), _p(gr), B, K, G, n, D, gate, min_points,
+                                            *[_p(x) for x in raw.values()], _s(p)))
+    return raw
+
+
+def _match_flags(flags, B, K, dev):
+    """flags [B,K,2] -> (the tensor whose data pointer the library reads, the stride in floats between two flags).  An fp32
+    device view whose [B,K,2] elements lie a constant number of floats apart is read in place, anything else is copied."""
+    if flags is None:
+        return None, 1
+    flags = torch.as_tensor(flags)
+    if tuple(flags.shape) != (B, K, 2):
+        raise ValueError('flags must be %s, got %s' % ([B, K, 2], list(flags.shape)))
+    if flags.dtype == torch.float32 and flags.device == dev and B * K * 2 > 0:
+        st = flags.stride()
+        step = st[2]
+        if step >= 1 and st[1] == 2 * step and st[0] == 2 * K * step:
+            return flags, int(step)
+    return flags.to(dev, torch.float32).contiguous(), 1
+
+
+def match_gather(src, index):
+    """dst[b,q,s,...] = src[b, index[b,q,s], s, ...] on the GPU (acrmi_match_gather): src fp32 [B,Ks,2,...], index int32 [B,Kd,2]
+    -> [B,Kd,2,...]; an index outside [0, Ks) gives a row of zeros (every index is range-checked on the device)."""
+    _need_cuda(src, index)
+    if src.dim() < 3 or src.shape[2] != 2 or index.dim() != 3 or index.shape[0] != src.shape[0] or index.shape[2] != 2:
+        raise ValueError('src must be [B,Ks,2,...] and index [B,Kd,2]')
+    if src.dtype != torch.float32:
+        raise ValueError('src must be float32, got %s' % src.dtype)
+    B, Ks, Kd = src.shape[0], src.shape[1], index.shape[1]
+    tail = tuple(src.shape[3:])
+    W = 1
+    for d in tail:
+        W *= d
+    if not (1 <= Ks <= 8 and 1 <= Kd <= 8 and W >= 1):
+        raise ValueError('Ks = %d, Kd = %d in 1..8, rows of at least one float' % (Ks, Kd))
+    s, ix = src.contiguous(), index.to(src.device, torch.int32).contiguous()
+    dst = torch.empty((B, Kd, 2) + tail, dtype=torch.float32, device=src.device)
+    _lib.check(_lib.lib().acrmi_match_gather(_p(s), _p(ix), B, Ks, Kd, W, _p(dst), _s(s)))
+    return dst
+
+
+def match_accumulate(board_words, counts, cost, stream=None):
+    """Adds 'counts' [B,2,3] and 'cost' [B,K,2] of one match_hands result to a board (acrmi_match_accumulate): board_words an
+    int64 device tensor of acrmi_match_board_bytes.  Asynchronous; engine.MatchBoard is the object that owns such a buffer."""
+    _need_cuda(board_words, counts, cost)
+    if counts.dim() != 3 or tuple(counts.shape[1:]) != (2, 3) or cost.dim() != 3 or cost.shape[0] != counts.shape[0] or cost.shape[2] != 2:
+        raise ValueError('counts must be [B,2,3] and cost [B,K,2]')
+    if board_words.dtype != torch.int64 or board_words.numel() != 8 or not board_words.is_contiguous():
+        raise ValueError('board_words must be a contiguous int64 tensor of 8 words')
+    c, f = counts.to(torch.int32).contiguous(), cost.to(torch.float32).contiguous()
+    _lib.check(_lib.lib().acrmi_match_accumulate(_p(c), _p(f), c.shape[0], f.shape[1], _p(board_words),
+                                                 _s(c) if stream is None else C.c_void_p(stream)))
+
+
 # ---- key-point skeleton and heat-map views (csrc/overlay.hip; DESIGN.md "Key-point and heat-map views") ----------------
 # mano/skeleton.txt (first 21 rows) of the reference: five fingers of four joints, tip to base, then the wrist (no parent)
 SKELETON_PARENTS = (1, 2, 3, 20, 5, 6, 7, 20, 9, 10, 11, 20, 13, 14, 15, 20, 17, 18, 19, 20, -1)

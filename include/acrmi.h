@@ -849,6 +849,55 @@ int acrmi_score_hands(acrmi_ctx* ctx, const float* joints_dev, const float* vert
                       float* pair_err_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Matching decoded hands to ground truth (csrc/match_plan.h, csrc/match.hip): with max_hand = K a frame
+ * holds up to K hands of each side in the order of their centre confidence, which says nothing about the order of the
+ * annotations.  These calls find, per (frame b, side s), the exact assignment of predictions to truths on the device, gather
+ * rows into truth order - what acrmi_score_hands then takes unchanged - and count true positives, false positives and misses.
+ * A PROBLEM is one (b, s): predictions i = 0..K-1, truths g = 0..G-1, 1 <= K, G <= 8, independent of each other; point sets of
+ * n points (1 <= n <= 256) of D coordinates, D = 2 (pixels) or 3 (metres).  Inputs fp32, arithmetic fp64 with every operation
+ * rounded on its own.
+ *  cost      of the pair (i, g): point j counts when valid[b,g,s,j] != 0 (or there is no valid array) and all 2D coordinates
+ *            are finite.  P is the prediction plus trans[b,i,s] when trans is given, added in fp64.  d_j = sqrt(dx*dx + dy*dy)
+ *            for D = 2, sqrt((dx*dx + dy*dy) + dz*dz) for D = 3.  cost = (sum of d_j in ascending j, a point that does not
+ *            count adds +0) / count.
+ *  allowed   a pair is allowed when the prediction's flag is > 0.5 (read with a stride, so ACRMI_SLOT_FLAG of the slots goes in
+ *            as it is; NaN is not flagged; flags NULL: every prediction is flagged), truth_valid[b,g,s] != 0 (or NULL), count >=
+ *            min_points, and the cost is finite and <= (double)gate.  gate is finite and >= 0, or +inf; min_points in 1..n.
+ *  objective among one-to-one matchings of allowed pairs the most pairs, among those the smallest cost sum.
+ *  rule      the subset recurrence: state m = bitmask of used truths, value (cnt, sum); dp[0] = (0, +0.0), every other state
+ *            unreachable.  For i = 0..K-1 in order and every m: start from dp[m] (prediction i stays unmatched); then for g
+ *            ascending with bit g set in m, (i, g) allowed and dp[m ^ (1 << g)] reachable, the candidate (cnt + 1, sum +
+ *            cost[i][g]) replaces the current best only on a strict improvement: a larger cnt, or an equal cnt and a smaller
+ *            sum.  The choice (-1 or g) is recorded per (i, m).  The final state is the best over m ascending, strict
+ *            improvement again; backtrack from i = K-1 down.
+ *  outputs   match int32 [B,K,2]: the truth of each prediction or -1; pred_of int32 [B,G,2]: the inverse; cost fp32 [B,K,2]: the
+ *            matched pair's cost rounded to fp32, -1 when unmatched; counts int32 [B,2,3]: TP = matched pairs, FP = flagged
+ *            predictions left unmatched, FN = valid truths left unmatched; group int32 [B,G,2]: the caller's group (default
+ *            the side) where the truth is valid, else -1.
+ *  gather    dst[b,q,s,:] = src[b, index[b,q,s], s, :] for fp32 rows of any width W; an index outside [0, Ks) gives a row of
+ *            +0 bytes.  Every index is range-checked before it becomes an address.
+ *  board     8 words of 8 bytes, per side [TP, FP, FN int64 | matched-cost sum fp64].  A call continues from the board's values
+ *            and adds the counts and the fp32 costs >= 0, converted to double, in ascending frame order, one writer per element,
+ *            no atomics: 2B frames in one call equal two calls of B frames bit for bit.
+ * Anything outside the limits is refused with ACRMI_EINVAL before any GPU call and never clamped; B == 0 is success and
+ * touches nothing.
+ * ------------------------------------------------------------------------------------- */
+size_t acrmi_match_board_bytes(void);
+/* pred_dev [B,K,2,n,D], truth_dev [B,G,2,n,D] fp32; valid_dev [B,G,2,n] bytes or NULL; truth_valid_dev [B,G,2] bytes or NULL;
+ * flags_dev: the flag of prediction (b,i,s) at flags_dev[((b*K + i)*2 + s) * flag_stride], or NULL; trans_dev [B,K,2,D] or NULL;
+ * group_dev [B,G,2] int32 or NULL = the side.  B * max(K,G) * 2 * n * D at most 2^31 - 1. */
+int acrmi_match_hands(const float* pred_dev, const float* truth_dev, const uint8_t* valid_dev, const uint8_t* truth_valid_dev,
+                      const float* flags_dev, int flag_stride, const float* trans_dev, const int32_t* group_dev, int B, int K, int G,
+                      int n, int D, float gate, int min_points, int32_t* match_dev, int32_t* pred_of_dev, float* cost_dev,
+                      int32_t* counts_dev, int32_t* group_out_dev, void* stream);
+/* src_dev [B,Ks,2,W] fp32, index_dev [B,Kd,2] int32, dst_dev [B,Kd,2,W]; Ks, Kd in 1..8, W >= 1, pointers 4-byte aligned.
+ * 16-byte accesses when W % 4 == 0 and src_dev and dst_dev are 16-byte aligned, 4-byte accesses otherwise. */
+int acrmi_match_gather(const float* src_dev, const int32_t* index_dev, int B, int Ks, int Kd, int W, float* dst_dev, void* stream);
+/* Adds counts_dev [B,2,3] and cost_dev [B,K,2] of one acrmi_match_hands call to board_dev (acrmi_match_board_bytes(), 8-byte
+ * aligned, zeroed by the caller before the first call).  K only indexes cost_dev. */
+int acrmi_match_accumulate(const int32_t* counts_dev, const float* cost_dev, int B, int K, void* board_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Key-point skeleton and centre heat-map views: acr/visualization.py:228-300 (Visualizer.visulize_result_live with
  * show_items 'pj2d' / 'centermap', vis_keypoints, make_heatmaps), drawn on the device.  Nothing of PIL or cv2 is used; the
  * rules are (DESIGN.md "Key-point and heat-map views"):
