@@ -100,7 +100,7 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_score_accumulate', 'acrmi_score_hands', 'acrmi_vertex_colors', 'acrmi_contact_values',
            'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored', 'acrmi_segm_tables',
            'acrmi_segm_labels', 'acrmi_segm_stats_ws_ints', 'acrmi_segm_stats', 'acrmi_segment', 'acrmi_match_board_bytes',
-           'acrmi_match_hands', 'acrmi_match_gather', 'acrmi_match_accumulate']
+           'acrmi_match_hands', 'acrmi_match_gather', 'acrmi_match_accumulate', 'acrmi_mano_backward']
 
 _lib = None
 
@@ -149,6 +149,7 @@ def lib():
     L.acrmi_mano.argtypes = [vp, f32p, i32, f32p, i32, vp, i32, i32, f32p, f32p, f32p, f32p, i32, f32p, f32p, f32p,
                              f32p, vp]
     L.acrmi_mano_rotmat.argtypes = [vp, f32p, f32p, i32, vp, i32, i32, f32p, f32p, f32p, vp]
+    L.acrmi_mano_backward.argtypes = [vp, f32p, i32, f32p, i32, vp, i32, i32, f32p, f32p, f32p, f32p, f32p, vp]
     L.acrmi_heads.argtypes = [vp, f32p, i32, vp]
     L.acrmi_backbone_channels.argtypes = [vp]
     L.acrmi_check_range.argtypes = [vp, vp]

@@ -757,6 +757,34 @@ int acrmi_mano_rotmat(acrmi_ctx* c, const float* rotmats, const float* betas, in
   return mano_rows(c, "acrmi_mano_rotmat", m, betas, beta_stride, side, H, center_idx, verts, joints, center, stream);
 }
 
+int acrmi_mano_backward(acrmi_ctx* c, const float* poses, int pose_stride, const float* betas, int beta_stride,
+                        const int32_t* side, int H, int center_idx, const float* g_verts, const float* g_joints,
+                        const float* g_center, float* g_poses, float* g_betas, void* stream) {
+  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_mano_backward: ctx is NULL");
+  if (H < 0 || center_idx < -1 || center_idx > 20 || pose_stride < 48 || beta_stride < 10)
+    return fail(c, ACRMI_EINVAL, "acrmi_mano_backward: bad arguments (H >= 0, center_idx -1..20, pose_stride >= 48, beta_stride >= 10)");
+  if (H == 0) return ACRMI_OK;
+  if (!poses || !betas || !g_poses || !g_betas) return fail(c, ACRMI_EINVAL, "acrmi_mano_backward: NULL poses, betas or outputs");
+  if (!c->have_mano[0] && !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_mano_backward: MANO tables not loaded");
+  ON_DEVICE(c);
+  if (!g_verts && !g_joints && !g_center) {      // no cotangent at all: the gradients are zero
+    HIPCHK(c, hipMemsetAsync(g_poses, 0, (size_t)H * 48 * sizeof(float), (hipStream_t)stream));
+    HIPCHK(c, hipMemsetAsync(g_betas, 0, (size_t)H * 10 * sizeof(float), (hipStream_t)stream));
+    return ACRMI_OK;
+  }
+  ManoGradArgs m{};
+  // a context may hold one side only (a lone ManoLayer), as in acrmi_mano
+  m.t[0] = c->have_mano[0] ? c->mano[0] : c->mano[1];
+  m.t[1] = c->have_mano[1] ? c->mano[1] : c->mano[0];
+  m.poses = poses; m.pose_stride = pose_stride;
+  m.betas = betas; m.beta_stride = beta_stride;
+  m.side = side; m.H = H; m.center_idx = center_idx;
+  m.g_verts = g_verts; m.g_joints = g_joints; m.g_center = g_center;
+  m.g_poses = g_poses; m.g_betas = g_betas;
+  HIPCHK(c, launch_mano_backward(m, (hipStream_t)stream));
+  return ACRMI_OK;
+}
+
 // The last op that writes the backbone map (heads.backbone_buf) and the channels it leaves there: an op whose out_buf is the
 // map - or, in large-batch fp32 programs, the ACRMI_CONV_DUAL convolution whose SECOND output (aux_buf: the full-resolution HR
 // fuse sum of the last stage, written at channel 0) is the map.  first = the op behind it (-1: none), c0 = channels.

@@ -433,6 +433,18 @@ struct ManoArgs {
                                        // mano/manolayer.py:151-162): no Rodrigues, no hands_mean
 };
 hipError_t launch_mano(const ManoArgs& a, hipStream_t s);
+// The backward of the axis-angle mode (csrc/mano_grad.hip): cotangents in, gradients of poses and betas out.  Always the fp32
+// tables of t[].
+struct ManoGradArgs {
+  ManoTables t[2];
+  const float* poses; int pose_stride;
+  const float* betas; int beta_stride;
+  const int32_t* side;
+  int H, center_idx;
+  const float *g_verts, *g_joints, *g_center;   // [H,778,3], [H,21,3], [H,3]; each may be null = zeros
+  float *g_poses, *g_betas;                     // [H,48], [H,10]
+};
+hipError_t launch_mano_backward(const ManoGradArgs& a, hipStream_t s);
 hipError_t launch_cam_trans(const float* joints, const float* pj2d, int n, float focal, float img, float* out, hipStream_t s);
 
 // Mesh overlay (csrc/render.hip; DESIGN.md "Rendering"): M meshes of one vertex / face count drawn into N equal-sized frames.

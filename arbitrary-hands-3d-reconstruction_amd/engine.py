@@ -284,6 +284,29 @@ class MatchBoard(object):
         return match_mod.summarize(self.arrays())
 
 
+class ManoFunction(torch.autograd.Function):
+    """Engine.mano (axis-angle mode, no projection) with Engine.mano_backward as its backward: apply(engine, poses [H,48],
+    betas [H,10], side, center_idx) -> (verts, joints, center).  Once differentiable: a double backward raises torch's error."""
+
+    @staticmethod
+    def forward(ctx, engine, poses, betas, side, center_idx):
+        verts, joints, center, _ = engine.mano(poses.detach(), betas.detach(), side, center_idx=center_idx)
+        ctx.engine, ctx.center_idx = engine, center_idx
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(poses, betas, side)
+        if center_idx is None:
+            ctx.mark_non_differentiable(center)
+        return verts, joints, center
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_verts, g_joints, g_center):
+        poses, betas, side = ctx.saved_tensors
+        g_poses, g_betas = ctx.engine.mano_backward(poses, betas, side, ctx.center_idx, g_verts, g_joints, g_center)
+        return (None, g_poses.to(poses.dtype) if ctx.needs_input_grad[1] else None,
+                g_betas.to(betas.dtype) if ctx.needs_input_grad[2] else None, None, None)
+
+
 class Engine(object):
     def __init__(self, device=0):
         if not torch.cuda.is_available():
@@ -783,6 +806,60 @@ class Engine(object):
                                      _ptr(center), _ptr(cam), 3, _ptr(offsets), _ptr(vc), _ptr(pj), _ptr(org),
                                      _stream(dev)), self.ctx)
         return verts, joints, center, extra
+
+    @staticmethod
+    def check_mano_backward(poses, betas, side, center_idx, g_verts, g_joints, g_center):
+        """The argument rules of `mano_backward`, checked on shapes alone (no device needed); ValueError when one is broken."""
+        if poses.dim() != 2 or poses.shape[1] < 48:
+            raise ValueError('poses must be [H,48] axis-angle rows (or rows of at least 48 values, read in place), got %s'
+                             % (tuple(poses.shape),))
+        H = poses.shape[0]
+        if betas.dim() != 2 or betas.shape[0] != H or betas.shape[1] < 10:
+            raise ValueError('betas must be [H,10] with one row per pose, got %s' % (tuple(betas.shape),))
+        if side.numel() != H:
+            raise ValueError('side must hold one value (0 left, 1 right) per hand')
+        if center_idx is not None and not 0 <= int(center_idx) <= 20:
+            raise ValueError('center_idx must be None or one of the 21 joints, got %r' % (center_idx,))
+        for name, g, shape in (('g_verts', g_verts, (H, 778, 3)), ('g_joints', g_joints, (H, 21, 3))):
+            if g is not None and tuple(g.shape) != shape:
+                raise ValueError('%s must be %s, got %s' % (name, shape, tuple(g.shape)))
+        if g_center is not None and g_center.numel() != 3 * H:
+            raise ValueError('g_center must be [H,1,3] or [H,3], got %s' % (tuple(g_center.shape),))
+
+    def mano_backward(self, poses, betas, side, center_idx=9, g_verts=None, g_joints=None, g_center=None):
+        """The backward of `mano` in its axis-angle mode (acrmi_mano_backward): cotangents of verts [H,778,3], joints
+        [H,21,3] and center [H,1,3] (each may be None = zeros) -> (g_poses [H,48], g_betas [H,10]).  Device tensors,
+        queued on the current stream, no host visit.  float32 rows whose values are contiguous - `slots[:, 6:54]` of
+        [H,176] slot rows - are read in place; always the fp32 tables, also with set_mano_fp16."""
+        self.check_mano_backward(poses, betas, side, center_idx, g_verts, g_joints, g_center)
+        dev = self.device
+        H = poses.shape[0]
+
+        def rows(t, n):      # [H, >= n] -> a float32 device tensor whose rows can be read in place, and its row stride
+            t = t.to(dev, torch.float32)
+            if t.stride(1) != 1 or t.stride(0) < n:
+                t = t[:, :n].contiguous()
+            return t, max(t.stride(0), n)
+        poses, pose_stride = rows(poses, 48)
+        betas, beta_stride = rows(betas, 10)
+        g_poses = torch.empty(H, 48, dtype=torch.float32, device=dev)
+        g_betas = torch.empty(H, 10, dtype=torch.float32, device=dev)
+        if H == 0:
+            return g_poses, g_betas
+        side = side.to(dev, torch.int32).contiguous()
+        g = [None if t is None else t.to(dev, torch.float32).contiguous() for t in (g_verts, g_joints, g_center)]
+        _lib.check(self.L.acrmi_mano_backward(self.ctx, _ptr(poses), pose_stride, _ptr(betas), beta_stride, _ptr(side), H,
+                                              -1 if center_idx is None else int(center_idx), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                              _ptr(g_poses), _ptr(g_betas), _stream(dev)), self.ctx)
+        return g_poses, g_betas
+
+    def mano_autograd(self, poses, betas, side, center_idx=9):
+        """`mano` as a node of torch's autograd graph: (verts, joints, center) that carry gradients back to poses [H,48] and
+        betas [H,10] through `mano_backward`.  Once differentiable; side and center_idx are not differentiated."""
+        if poses.dim() != 2 or poses.shape[1] != 48 or betas.dim() != 2 or tuple(betas.shape) != (poses.shape[0], 10):
+            raise ValueError('poses must be [H,48] and betas [H,10], got %s and %s' % (tuple(poses.shape), tuple(betas.shape)))
+        return ManoFunction.apply(self, poses.to(self.device, torch.float32), betas.to(self.device, torch.float32),
+                                  side.to(self.device, torch.int32), center_idx)
 
     def forward(self, img, offsets=None, project=False, out=None, stream=None, streams=None, table=None, max_hand=1,
                 tracks=None, track_table=None, smooth=True):

@@ -5,6 +5,7 @@ such as the visualiser (acr/visualization.py:80,120); the arithmetic runs in lib
 import io
 import os
 import pickle
+import warnings
 
 import numpy as np
 import torch
@@ -85,6 +86,8 @@ def batch_rotprojs(rotmats):
 
 
 class ManoLayer(object):
+    _warned_rotmat = False      # a layer in rotmat mode warns once that it carries no gradient
+
     def __init__(self, center_idx=None, flat_hand_mean=True, ncomps=6, side='right', mano_root='model_data/mano/',
                  use_pca=True, root_rot_mode='axisang', joint_rot_mode='axisang', robust_rot=False, tables=None,
                  device=0):
@@ -144,6 +147,48 @@ class ManoLayer(object):
         eng.load_mano_side(self.side, self.tables())
         self._engine = eng
         self._dirty = False
+        self._dev = {}
+
+    def _on_device(self, name):
+        """A th_* buffer on the engine's device for the gradient path (uploaded once per sync)."""
+        if name not in self._dev:
+            self._dev[name] = getattr(self, name).to(self._engine.device, torch.float32)
+        return self._dev[name]
+
+    def _forward_grad(self, th_pose_coeffs, th_betas, th_trans, root_palm, share_betas):
+        """forward when an input asks for a gradient: the same function as torch ops on the device around the engine's
+        differentiable MANO node (Engine.mano_autograd), so that autograd carries the PCA map, share_betas, th_trans, the palm
+        root and its late alignment by itself."""
+        eng = self._engine
+        dev = eng.device
+        N = th_pose_coeffs.shape[0]
+        c = th_pose_coeffs.to(dev, torch.float32)
+        if self.use_pca:
+            pose = torch.cat([c[:, :3], c[:, 3:3 + self.ncomps].mm(self._on_device('th_selected_comps'))], 1)
+        else:
+            pose = c[:, :48]
+        if th_betas is None or th_betas.numel() == 1:
+            betas = self._on_device('th_betas').expand(N, 10)
+        else:
+            betas = th_betas.to(dev, torch.float32)
+            if bool(share_betas):
+                betas = betas.mean(0, keepdim=True).expand(N, 10)
+        use_trans = not (th_trans is None or bool(torch.norm(th_trans.detach().float()) == 0))
+        palm = bool(root_palm)
+        side = torch.full((N,), 0 if self.side == 'left' else 1, dtype=torch.int32, device=dev)
+        # as in forward: the palm root and th_trans take the kernel's outputs unaligned
+        verts, joints, center = eng.mano_autograd(pose, betas, side, None if (palm or use_trans) else self.center_idx)
+        if palm:
+            joints = torch.cat([((verts[:, 95] + verts[:, 22]) / 2).unsqueeze(1), joints[:, 1:]], 1)
+        if use_trans:
+            t = th_trans.to(dev, torch.float32).unsqueeze(1)
+            return verts + t, joints + t, t
+        if self.center_idx is None:
+            return verts, joints, None
+        if palm:
+            center = joints[:, self.center_idx].unsqueeze(1)
+            return verts - center, joints - center, center
+        return verts, joints, center
 
     def tables(self):
         return {'v_template': self.th_v_template[0].numpy(), 'shapedirs': self.th_shapedirs.numpy(),
@@ -154,11 +199,26 @@ class ManoLayer(object):
     def forward(self, th_pose_coeffs, th_betas=torch.zeros(1), th_trans=torch.zeros(1), root_palm=torch.Tensor([0]),
                 share_betas=torch.Tensor([0])):
         """-> (verts [N,778,3], joints [N,21,3], center_joint [N,1,3]) in metres (mano/manolayer.py:269-276)."""
+        rotmat = not self.use_pca and self.joint_rot_mode == 'rotmat'
+        wants_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                     for t in (th_pose_coeffs, th_betas, th_trans))
+        if wants_grad and not rotmat:
+            if th_pose_coeffs.dim() != 2 or th_pose_coeffs.shape[1] < 3 + self.ncomps:
+                raise ValueError('th_pose_coeffs must be [N,%d], got %s' % (3 + self.ncomps, tuple(th_pose_coeffs.shape)))
+            if not (th_betas is None or th_betas.numel() == 1) and tuple(th_betas.shape) != (th_pose_coeffs.shape[0], 10):
+                raise ValueError('th_betas must be [N,10], got %s' % (tuple(th_betas.shape),))
         if self._dirty or self._engine is None:
             self.sync(self._engine)
         eng = self._engine
         N = th_pose_coeffs.shape[0]
-        rotmat = not self.use_pca and self.joint_rot_mode == 'rotmat'
+        if wants_grad:
+            # gradients reach th_pose_coeffs (48 values or 3 + ncomps PCA coordinates), th_betas and th_trans
+            if not rotmat:
+                return self._forward_grad(th_pose_coeffs, th_betas, th_trans, root_palm, share_betas)
+            if not self._warned_rotmat:
+                self._warned_rotmat = True
+                warnings.warn("ManoLayer(joint_rot_mode='rotmat') carries no gradient: the rotations are projected onto SO(3) "
+                              "on the host; the outputs do not require grad")
         if rotmat:
             # mano/manolayer.py:151-162: [N,16,3,3] matrices, projected onto SO(3) one by one with a CPU SVD exactly as the
             # reference's batch_rotprojs does (:436-453, U V^T with the last column flipped when det < 0); the kernel takes the

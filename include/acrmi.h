@@ -266,6 +266,17 @@ int acrmi_mano(acrmi_ctx* ctx, const float* poses, int pose_stride, const float*
 int acrmi_mano_rotmat(acrmi_ctx* ctx, const float* rotmats, const float* betas, int beta_stride, const int32_t* side,
                       int H, int center_idx, float* verts, float* joints, float* center, void* stream);
 
+/* The backward of acrmi_mano's axis-angle mode: the gradient of (verts, joints, center) with respect to the poses and betas
+ * of every row, from the cotangents g_verts [H,778,3], g_joints [H,21,3], g_center [H,3] (device pointers; each may be NULL =
+ * zeros; all three NULL: zero gradients are written).  poses / betas / side / center_idx as in acrmi_mano (pose_stride >= 48,
+ * beta_stride >= 10, center_idx -1..20; with center_idx < 0 center is constant and g_center is not read).  Writes all of
+ * g_poses [H,48] and g_betas [H,10].  One workgroup per hand, fixed summation orders, no atomics: a row's result does not
+ * depend on the batch it is in.  Always differentiates the fp32 tables, also under ACRMI_OPT_MANO_FP16.  The rotation-matrix
+ * mode and the projection outputs have no backward.  ACRMI_ESTATE before a side's tables are loaded; H == 0 is a success. */
+int acrmi_mano_backward(acrmi_ctx* ctx, const float* poses, int pose_stride, const float* betas, int beta_stride,
+                        const int32_t* side, int H, int center_idx, const float* g_verts, const float* g_joints,
+                        const float* g_center, float* g_poses, float* g_betas, void* stream);
+
 /* acr/utils.py:430-472 + :474-519 (estimate_translation_np / estimate_translation, the reference's closed-form
  * least-squares branch, unit joint confidences): joints [n,21,3] and pj2d [n,21,2] (in [-1,1]; the 2-D targets are
  * (pj2d+1)*img_size/2) on the device -> cam_trans [n,3].  Solved in fp64 like the reference. */
