@@ -23,6 +23,8 @@ MAX_HAND = 8      # ACRMI_MAX_HAND
 ASSOC_STATE = 41  # ACRMI_ASSOC_STATE
 SLOT_FLAG, SLOT_FLATIND, SLOT_SCORE, SLOT_CAM, SLOT_POSES, SLOT_BETAS, SLOT_PARAMS = 0, 1, 2, 3, 6, 54, 64
 E_INVAL, E_HIP, E_STATE, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5
+# acrmi_mano_fit (csrc/mano_fit_plan.h): floats of a state row (acrmi_mano_fit_state_floats) and the steps of one launch
+FIT_STATE, FIT_MAX_STEPS = 196, 1024
 OVERLAY_SKELETON, OVERLAY_CENTERMAP = 0, 1      # acrmi_overlay `what`
 SEGM_NONE = 255      # ACRMI_SEGM_NONE: the label of a pixel the canvas does not cover
 
@@ -100,7 +102,8 @@ EXPORTS = ['acrmi_version', 'acrmi_last_error', 'acrmi_create', 'acrmi_destroy',
            'acrmi_score_accumulate', 'acrmi_score_hands', 'acrmi_vertex_colors', 'acrmi_contact_values',
            'acrmi_rasterize_colored', 'acrmi_render_colored', 'acrmi_render_regions_colored', 'acrmi_segm_tables',
            'acrmi_segm_labels', 'acrmi_segm_stats_ws_ints', 'acrmi_segm_stats', 'acrmi_segment', 'acrmi_match_board_bytes',
-           'acrmi_match_hands', 'acrmi_match_gather', 'acrmi_match_accumulate', 'acrmi_mano_backward']
+           'acrmi_match_hands', 'acrmi_match_gather', 'acrmi_match_accumulate', 'acrmi_mano_backward',
+           'acrmi_mano_fit', 'acrmi_mano_fit_state_floats']
 
 _lib = None
 
@@ -150,6 +153,10 @@ def lib():
                              f32p, vp]
     L.acrmi_mano_rotmat.argtypes = [vp, f32p, f32p, i32, vp, i32, i32, f32p, f32p, f32p, vp]
     L.acrmi_mano_backward.argtypes = [vp, f32p, i32, f32p, i32, vp, i32, i32, f32p, f32p, f32p, f32p, f32p, vp]
+    L.acrmi_mano_fit.argtypes = [vp, f32p, vp, i32, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_double, C.c_double,
+                                 C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, i32, i32, f32p, f32p, f32p, f32p,
+                                 f32p, f32p, vp]
+    L.acrmi_mano_fit_state_floats.argtypes = []
     L.acrmi_heads.argtypes = [vp, f32p, i32, vp]
     L.acrmi_backbone_channels.argtypes = [vp]
     L.acrmi_check_range.argtypes = [vp, vp]

@@ -311,7 +311,7 @@ class ACR(object):
     def forward_batch(self, rgb_u8_frames, paths, offsets=None, point_heads=True, batch_semantics=None, render=None,
                       render_bgr=False, show_items=None, streams=None, max_streams=None, max_hand=None, tracks=None,
                       track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None, board=None,
-                      masks=False, match=None, match_gate=float('inf'), match_board=None):
+                      masks=False, match=None, match_gate=float('inf'), match_board=None, refine=None):
         """Batched throughput path: uint8 [B,512,512,3] RGB (already pre-processed) -> per-image results.
         One fused call (backbone, heads, decode, MANO, projection) + one D2H of the packed results.
         The head maps are not part of these results, so by default the params/cam/prior towers run only at the
@@ -382,7 +382,14 @@ class ACR(object):
         matched to, -1 for a false positive - and 'match_cost'; the four score keys come from the matched truth, nan for an
         unmatched hand; board= receives the rows in TRUTH order, so its 'missed' are the annotated hands nothing was matched
         to and its MRRPE pairs are (left g, right g).  match_board=: an engine.MatchBoard the batch's TP / FP / FN are added to.
-        The 'error' view and boxes= are not built with match=."""
+        The 'error' view and boxes= are not built with match=.
+        refine=dict(kp2d=..., joints=..., weights=..., steps=..., lam_pose=..., lam_beta=..., lr=..., free=...) (DESIGN.md
+        section 26): Engine.refine runs behind the fused call - every flagged hand is fitted on the GPU, in one launch, to
+        kp2d [B,(K,)2,21,2] in the units of pj2d (the canvas, -1..1; 'kp2d_org' instead: pixels of the original frames, taken
+        through the inverse of pj2d_org's formula with `offsets`) and / or root-aligned joints [B,(K,)2,21,3], with the network's
+        own prediction as start and prior.  The pose, shape, camera and mesh keys of every hand dict then come from the refined
+        hand - as do the views, contact, scores and masks - and it gains 'fit_loss' (first and last evaluated step).  Without
+        refine= nothing changes by a byte."""
         _check_contact(contact)
         _check_score(gt, board)
         _check_match(match, gt, match_gate, match_board, show_items)
@@ -397,7 +404,7 @@ class ACR(object):
                                              tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
                                              multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board,
                                              masks=masks, mask_frames=render, mask_offsets=offsets, match=match,
-                                             match_gate=match_gate, match_board=match_board)
+                                             match_gate=match_gate, match_board=match_board, refine=refine)
         if render is None:
             return results
         _add_vertex_colors(eng, out, K, show_items, render_bgr)
@@ -416,7 +423,7 @@ class ACR(object):
     def _fused_call(self, frames, paths, *, offsets=None, point_heads=True, batch_semantics=None, streams=None, max_streams=None,
                     K=1, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False, gt=None,
                     board=None, masks=False, mask_frames=None, mask_offsets=None, match=None, match_gate=float('inf'),
-                    match_board=None):
+                    match_board=None, refine=None):
         """The fused call of forward_batch and its packaging -> (results, the engine, what the engine returned).  K = 1 without
         tracks: one hand of each side, `point_heads` is the switch and multi_point_heads is checked and without effect.
         K > 1 or tracks=: Engine.forward(max_hand=K) on the dense heads, or with multi_point_heads (K > 1) at the K best centres.
@@ -442,6 +449,7 @@ class ACR(object):
         eng = self.model.engine(B)
         if offsets is None:
             offsets = _whole_frame_offsets(B)
+        refine_kw = None if refine is None else _refine_args(refine, offsets)
         # coeff: smooth_coeff travels with a call that may smooth (a reloaded checkpoint builds a new context)
         if not multi:
             # frames of the batch = one video stream, in order; with `streams` the table holds the state and the frames are
@@ -468,6 +476,8 @@ class ACR(object):
             eng.set_batch_semantics('frame')
             eng.set_point_heads_multi(False)
         eng.check_range()      # 'fp16x3' only: an activation outside the f16 range is an error, not an empty result
+        if refine is not None:      # the hands that go on are the refined ones (Engine.refine)
+            out = eng.refine(out, max_hand=K, offsets=offsets, **refine_kw)
         # cam_trans for every slot (acr/utils.py:399-412): the device least-squares kernel on all hands
         out['cam_trans'] = ops.cam_trans(out['joints'].view(-1, 21, 3), out['pj2d'].view(-1, 21, 2),
                                          focal_length=self.focal_length).view(*out['slots'].shape[:-1], 3)
@@ -524,6 +534,28 @@ class ACR(object):
             return ops.draw_segm(sub['logits'], imgs, offsets=off, bgr=bgr)
 
         return _per_size(frames, draw, count=B)
+
+
+def _refine_args(refine, offsets):
+    """refine= of forward_batch / forward_raw_batch -> the keyword arguments of Engine.refine.  kp2d is in the units of pj2d (the
+    canvas, -1..1); 'kp2d_org' - key points in pixels of the original frames - is taken through the inverse of pj2d_org's
+    formula with the frames' offsets rows: pj2d = (org - (crop_left - pad_left, crop_top - pad_top)) * 2 / (pad_w, pad_h) - 1."""
+    kw = dict(refine)
+    unknown = set(kw) - {'kp2d', 'kp2d_org', 'joints', 'weights', 'steps', 'lam_pose', 'lam_beta', 'lr', 'free', 'dense'}
+    if unknown:
+        raise ValueError('refine= holds kp2d / kp2d_org / joints / weights / steps / lam_pose / lam_beta / lr / free / dense, not %s'
+                         % sorted(unknown))
+    org = kw.pop('kp2d_org', None)
+    if org is not None:
+        if kw.get('kp2d') is not None:
+            raise ValueError('refine=: kp2d or kp2d_org, not both')
+        org = torch.as_tensor(org)
+        of = torch.as_tensor(offsets).to(org.device, torch.float32)
+        of = of.reshape((of.shape[0],) + (1,) * (org.dim() - 2) + (10,))
+        pad = of[..., 0:2]
+        lt = torch.stack([of[..., 5] - of[..., 9], of[..., 2] - of[..., 6]], -1)
+        kw['kp2d'] = (org.to(torch.float32) - lt) * 2.0 / pad - 1.0
+    return kw
 
 
 def _whole_frame_offsets(B):
@@ -761,6 +793,9 @@ def results_from_out(out, paths):
     if con is not None:
         con = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in con.items()}
     ms = out.get('masks')      # with masks=: every hand dict gains its side's mask keys
+    fl = out.get('fit_loss')      # with refine=: every hand dict gains 'fit_loss' (first, last evaluated step)
+    if fl is not None:
+        fl = (fl.detach().cpu().numpy() if hasattr(fl, 'detach') else np.asarray(fl)).reshape(slots.shape[:3] + (2,))
     sc = out.get('score')      # with gt=: every hand dict gains the four score keys
     if sc is not None:
         from .. import score as score_mod
@@ -788,6 +823,8 @@ def results_from_out(out, paths):
                                   'hand_type': np.int32(h), 'detection_flag_cache': True})
                     if ids is not None:
                         hands[-1]['track_id'] = np.int32(ids[b, k, h])
+                    if fl is not None:
+                        hands[-1]['fit_loss'] = fl[b, k, h].astype(np.float32)
                     row = (b * slots.shape[1] + k) * 2 + h
                     if mt is not None:
                         hands[-1].update(match_mod.hand_match_keys(mt['match'], mt['cost'], row))
@@ -824,7 +861,7 @@ def _multi_views(self, eng, out, frames, offsets, bgr, items):
 def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=None, streams=None, max_streams=None,
                        pixel_format='bgr', matrix='cv601', boxes=None, box_frame=None, render_format='bgr', region_views=False,
                        max_hand=None, tracks=None, track_gate=None, track_max_miss=None, multi_point_heads=False, contact=False,
-                       gt=None, board=None, masks=False, match=None, match_gate=float('inf'), match_board=None):
+                       gt=None, board=None, masks=False, match=None, match_gate=float('inf'), match_board=None, refine=None):
     """BASELINE.json config 4: raw BGR uint8 frames [n,H,W,3] resident in HBM (e.g. 1080p video) - or a LIST of device frames
     [H_i,W_i,3] of different sizes (a folder of images, acr/main.py:144-205) - -> per-image results.  Pre-processing (white square pad + bicubic resize to 512) runs on the GPU (ops.preprocess),
     then the fused path; `offsets` carry the pad geometry so pj2d_org lands in original-frame pixels.
@@ -843,6 +880,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     rasteriser's viewport is per frame: DESIGN.md "Regions of interest") - unless region_views=True: then every view of
     SHOW_ITEMS is drawn over the source frames with one view per REGION (Engine.render_regions / overlay_regions, DESIGN.md
     "Views over regions"), the default view is 'mesh' as without boxes, and 'centermap' is [2,N,H,W,3] over the N frames.
+    refine=: as forward_batch ('kp2d_org' is in the pixels of these frames); not built over regions (boxes=).
     render_format='nv12' (with render=True): the drawn views come back as NV12 surfaces for a video encoder - a tensor
     [n,H*3/2,W] when all sizes agree, else a list; 'centermap' keeps its leading pair.  With pixel_format='nv12' every view is
     composed onto its source surface (ops.nv12_compose: new bytes only where something was drawn) and 'org_img' is the
@@ -881,6 +919,8 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
     to_nv12, matrix = _check_render_args(bgr_frames_dev, show_items, render, render_format, pixel_format, matrix)
     if region_views and boxes is None:
         raise ValueError('region_views=True draws the views of regions: it needs boxes=')
+    if boxes is not None and refine is not None:
+        raise ValueError('refine= over regions is not built (forward_raw_batch(boxes=))')
     if boxes is not None:
         got = _forward_regions(self, bgr_frames_dev, paths, boxes, box_frame, render, show_items, streams, max_streams,
                                pixel_format, matrix, region_views, contact, gt, board)
@@ -896,7 +936,7 @@ def _forward_raw_batch(self, bgr_frames_dev, paths, render=False, show_items=Non
                                  render_bgr=True, show_items=show_items, streams=streams, max_streams=max_streams,
                                  max_hand=max_hand, tracks=tracks, track_gate=track_gate, track_max_miss=track_max_miss,
                                  multi_point_heads=multi_point_heads, contact=contact, gt=gt, board=board, masks=masks,
-                                 match=match, match_gate=match_gate, match_board=match_board)
+                                 match=match, match_gate=match_gate, match_board=match_board, refine=refine)
     if to_nv12 is None:
         return got
     return got[0], _views_to_nv12(to_nv12, got[1])

@@ -1,6 +1,7 @@
 // libacrmi.so: context life cycle, options and the fused entry points of the C ABI declared in include/acrmi.h
 // (program replay: acrmi_program.hip; stand-alone operators: acrmi_ops.hip; RCCL: acrmi_comm.hip).
 #include "acrmi_ctx.h"
+#include "mano_fit_plan.h"
 #include "score_plan.h"
 #include "surface_contact_plan.h"      // and contact_plan.h
 #include "vertex_color_plan.h"
@@ -782,6 +783,39 @@ int acrmi_mano_backward(acrmi_ctx* c, const float* poses, int pose_stride, const
   m.g_verts = g_verts; m.g_joints = g_joints; m.g_center = g_center;
   m.g_poses = g_poses; m.g_betas = g_betas;
   HIPCHK(c, launch_mano_backward(m, (hipStream_t)stream));
+  return ACRMI_OK;
+}
+
+int acrmi_mano_fit_state_floats(void) { return FIT_STATE; }
+
+int acrmi_mano_fit(acrmi_ctx* c, float* state, const int32_t* side, int H, int center_idx, const float* y3, const float* w3,
+                   const float* y2, const float* w2, const float* yv, const float* wv, const float* prior, double lam_pose,
+                   double lam_beta, const double* lr5, double b1, double b2, double eps, int steps, int dense, float* poses,
+                   float* betas, float* trans, float* cam, float* loss, float* grad, void* stream) {
+  if (!c) return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: ctx is NULL");
+  if (H < 0 || !fit_steps_ok(steps) || !fit_center_ok(center_idx))
+    return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: bad arguments (H >= 0, steps 0..%d, center_idx -1..20)", FIT_MAX_STEPS);
+  if (!state || !lr5) return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: NULL state or learning rates");
+  if (!(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0 && eps >= 0.0 && lam_pose >= 0.0 && lam_beta >= 0.0))
+    return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: b1 and b2 must lie in [0, 1), eps and the regulariser weights must not be negative");
+  for (int g = 0; g < FIT_GROUPS; ++g)
+    if (!(lr5[g] >= 0.0)) return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: a learning rate is negative or NaN");
+  if (H == 0) return ACRMI_OK;
+  if (!poses || !betas || !trans || !cam || !loss) return fail(c, ACRMI_EINVAL, "acrmi_mano_fit: NULL outputs");
+  if (!c->have_mano[0] && !c->have_mano[1]) return fail(c, ACRMI_ESTATE, "acrmi_mano_fit: MANO tables not loaded");
+  ON_DEVICE(c);
+  ManoFitArgs m{};
+  // a context may hold one side only (a lone ManoLayer), as in acrmi_mano
+  m.t[0] = c->have_mano[0] ? c->mano[0] : c->mano[1];
+  m.t[1] = c->have_mano[1] ? c->mano[1] : c->mano[0];
+  m.state = state; m.side = side; m.H = H; m.center_idx = center_idx;
+  m.y3 = y3; m.w3 = w3; m.y2 = y2; m.w2 = w2; m.yv = yv; m.wv = wv; m.prior = prior;
+  m.lam_pose = lam_pose; m.lam_beta = lam_beta;
+  for (int g = 0; g < FIT_GROUPS; ++g) m.lr[g] = lr5[g];
+  m.b1 = b1; m.b2 = b2; m.eps = eps;
+  m.steps = steps; m.dense = dense;
+  m.poses = poses; m.betas = betas; m.trans = trans; m.cam = cam; m.loss = loss; m.grad = grad;
+  HIPCHK(c, launch_mano_fit(m, (hipStream_t)stream));
   return ACRMI_OK;
 }
 

@@ -445,6 +445,22 @@ struct ManoGradArgs {
   float *g_poses, *g_betas;                     // [H,48], [H,10]
 };
 hipError_t launch_mano_backward(const ManoGradArgs& a, hipStream_t s);
+// The fused fitter (csrc/mano_fit.hip; the rule is csrc/mano_fit_plan.h): `steps` Adam iterations per hand in one launch.
+struct ManoFitArgs {
+  ManoTables t[2];
+  float* state;                                 // [H, FIT_STATE]: read, and written when steps > 0
+  const int32_t* side;
+  int H, center_idx;
+  const float *y3, *w3;                         // [H,21,3], [H,21]; y3 null = no 3-D term, w3 null = ones
+  const float *y2, *w2;                         // [H,21,2], [H,21]
+  const float *yv, *wv;                         // [H,778,3], [H]; yv non-null selects the dense vertex level
+  const float* prior;                           // [H,58] or null = zeros
+  double lam_pose, lam_beta, lr[5], b1, b2, eps;
+  int steps, dense;                             // dense: the dense vertex level also without yv
+  float *poses, *betas, *trans, *cam, *loss;    // [H,48], [H,10], [H,3], [H,3], [H,2]
+  float* grad;                                  // [H,64] or null: the gradient of the last evaluated step
+};
+hipError_t launch_mano_fit(const ManoFitArgs& a, hipStream_t s);
 hipError_t launch_cam_trans(const float* joints, const float* pj2d, int n, float focal, float img, float* out, hipStream_t s);
 
 // Mesh overlay (csrc/render.hip; DESIGN.md "Rendering"): M meshes of one vertex / face count drawn into N equal-sized frames.

@@ -853,6 +853,163 @@ class Engine(object):
                                               _ptr(g_poses), _ptr(g_betas), _stream(dev)), self.ctx)
         return g_poses, g_betas
 
+    FIT_GROUPS = ('root', 'pose', 'betas', 'trans', 'cam')      # the learning-rate groups of mano_fit, in lr5's order
+
+    @staticmethod
+    def check_mano_fit(side, joints=None, kp2d=None, verts=None, w_joints=None, w_kp2d=None, w_verts=None, init=None,
+                       state=None, prior=None, lam_pose=0., lam_beta=0., lr=0.02, steps=100, center_idx=9,
+                       free=('root', 'pose', 'betas'), dense=False):
+        """The argument rules of `mano_fit`, checked on shapes alone (no device needed); ValueError when one is broken.
+        -> H, the number of hands."""
+        if side.dim() != 1:
+            raise ValueError('side must be [H] (0 left, 1 right), got %s' % (tuple(side.shape),))
+        H = side.shape[0]
+        for name, t, shape in (('joints', joints, (H, 21, 3)), ('kp2d', kp2d, (H, 21, 2)), ('verts', verts, (H, 778, 3)),
+                               ('w_joints', w_joints, (H, 21)), ('w_kp2d', w_kp2d, (H, 21)), ('w_verts', w_verts, (H,)),
+                               ('prior', prior, (H, 58)), ('state', state, (H, _lib.FIT_STATE))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError('%s must be %s, got %s' % (name, shape, tuple(t.shape)))
+        for w, t, name in ((w_joints, joints, 'joints'), (w_kp2d, kp2d, 'kp2d'), (w_verts, verts, 'verts')):
+            if w is not None and t is None:
+                raise ValueError('w_%s without %s' % (name, name))
+        if init is not None and state is not None:
+            raise ValueError('init starts a fresh fit, state continues one: not both')
+        if init is not None:
+            shapes = {'poses': (H, 48), 'betas': (H, 10), 'trans': (H, 3), 'cam': (H, 3)}
+            for k, t in init.items():
+                if k not in shapes:
+                    raise ValueError('init holds poses / betas / trans / cam, not %r' % (k,))
+                if tuple(t.shape) != shapes[k]:
+                    raise ValueError('init[%r] must be %s, got %s' % (k, shapes[k], tuple(t.shape)))
+        if not isinstance(steps, int) or not 0 <= steps <= _lib.FIT_MAX_STEPS:
+            raise ValueError('steps must be 0..%d per call (chain longer fits through state), got %r' % (_lib.FIT_MAX_STEPS, steps))
+        if center_idx is not None and not 0 <= int(center_idx) <= 20:
+            raise ValueError('center_idx must be None or one of the 21 joints, got %r' % (center_idx,))
+        for g in free:
+            if g not in Engine.FIT_GROUPS:
+                raise ValueError('free names groups of %s, got %r' % (Engine.FIT_GROUPS, g))
+        if isinstance(lr, dict):
+            for g, v in lr.items():
+                if g not in Engine.FIT_GROUPS or not float(v) >= 0:
+                    raise ValueError('lr is a float or a dict over %s of values >= 0, got %r: %r' % (Engine.FIT_GROUPS, g, v))
+            for g in free:
+                if g not in lr:
+                    raise ValueError('lr names no rate for the free group %r' % (g,))
+        elif not float(lr) >= 0:
+            raise ValueError('lr must be >= 0, got %r' % (lr,))
+        if not float(lam_pose) >= 0 or not float(lam_beta) >= 0:
+            raise ValueError('lam_pose and lam_beta must be >= 0')
+        return H
+
+    def mano_fit_state(self, H, init=None):
+        """A fresh state [H, FIT_STATE] for `mano_fit`: parameters from init (poses / betas / trans / cam; zeros and
+        cam = (1, 0, 0) where absent), m = v = 0, t = 0."""
+        dev = self.device
+        state = torch.zeros(H, _lib.FIT_STATE, dtype=torch.float32, device=dev)
+        state[:, 61] = 1.0
+        for k, at, n in (('poses', 0, 48), ('betas', 48, 10), ('trans', 58, 3), ('cam', 61, 3)):
+            if init is not None and k in init:
+                state[:, at:at + n] = init[k].to(dev, torch.float32)
+        return state
+
+    def mano_fit(self, side, joints=None, kp2d=None, verts=None, w_joints=None, w_kp2d=None, w_verts=None, init=None,
+                 state=None, prior=None, lam_pose=0., lam_beta=0., lr=0.02, steps=100, center_idx=9,
+                 free=('root', 'pose', 'betas'), dense=False, grad=False, betas_adam=(0.9, 0.999), eps=1e-8):
+        """Fits MANO pose, shape, translation and camera of H hands with `steps` Adam iterations in ONE launch
+        (acrmi_mano_fit) to any mix of joints [H,21,3] (against joints + trans), kp2d [H,21,2] (against
+        `mano`'s pj2d: root-aligned joints * s + (tx, ty)) and verts [H,778,3] (against verts + trans), plus
+        lam_pose |pose[3:48] - prior|^2 + lam_beta |betas - prior|^2 (prior [H,58] = pose | betas, None = zeros).
+        Weights w_joints / w_kp2d [H,21], w_verts [H]; missing ones are 1/21 per joint and 1/778: mean squared distances.
+        init (a dict of poses / betas / trans / cam) starts a fresh fit, state (a previous call's 'state') continues one -
+        chained calls equal one long call bit for bit.  free names the groups that move ('root', 'pose', 'betas', 'trans',
+        'cam'); lr is a float or a dict per group.  dense=True runs the dense vertex level also without verts.
+        -> {'poses' [H,48], 'betas' [H,10], 'trans' [H,3], 'cam' [H,3], 'loss' [H,2] (first and last evaluated step),
+        'state' [H,FIT_STATE][, 'grad' [H,64] with grad=True: the gradient of the last evaluated step]}.
+        Device tensors, queued on the current stream, no host visit."""
+        H = self.check_mano_fit(side, joints, kp2d, verts, w_joints, w_kp2d, w_verts, init, state, prior, lam_pose, lam_beta, lr,
+                                steps, center_idx, free, dense)
+        dev = self.device
+        f32 = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
+        state = self.mano_fit_state(H, init) if state is None else state.to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+        out = {'poses': torch.empty(H, 48, dtype=torch.float32, device=dev), 'betas': torch.empty(H, 10, dtype=torch.float32, device=dev),
+               'trans': torch.empty(H, 3, dtype=torch.float32, device=dev), 'cam': torch.empty(H, 3, dtype=torch.float32, device=dev),
+               'loss': torch.zeros(H, 2, dtype=torch.float32, device=dev), 'state': state}
+        if grad:
+            out['grad'] = torch.zeros(H, 64, dtype=torch.float32, device=dev)
+        if H == 0:
+            return out
+        joints, kp2d, verts, prior = f32(joints), f32(kp2d), f32(verts), f32(prior)
+        if joints is not None:
+            w_joints = torch.full((H, 21), 1.0 / 21, dtype=torch.float32, device=dev) if w_joints is None else f32(w_joints)
+        if kp2d is not None:
+            w_kp2d = torch.full((H, 21), 1.0 / 21, dtype=torch.float32, device=dev) if w_kp2d is None else f32(w_kp2d)
+        if verts is not None:
+            w_verts = torch.full((H,), 1.0 / 778, dtype=torch.float32, device=dev) if w_verts is None else f32(w_verts)
+        rate = lambda g: (float(lr.get(g, 0.0)) if isinstance(lr, dict) else float(lr)) if g in free else 0.0
+        lr5 = (C.c_double * 5)(*[rate(g) for g in self.FIT_GROUPS])
+        side = side.to(dev, torch.int32).contiguous()
+        _lib.check(self.L.acrmi_mano_fit(self.ctx, _ptr(state), _ptr(side), H, -1 if center_idx is None else int(center_idx),
+                                         _ptr(joints), _ptr(w_joints), _ptr(kp2d), _ptr(w_kp2d), _ptr(verts), _ptr(w_verts),
+                                         _ptr(prior), float(lam_pose), float(lam_beta), lr5, float(betas_adam[0]),
+                                         float(betas_adam[1]), float(eps), int(steps), 1 if dense else 0, _ptr(out['poses']),
+                                         _ptr(out['betas']), _ptr(out['trans']), _ptr(out['cam']), _ptr(out['loss']),
+                                         _ptr(out.get('grad')), _stream(dev)), self.ctx)
+        return out
+
+    def refine(self, out, kp2d=None, joints=None, weights=None, steps=50, lam_pose=1e-3, lam_beta=1e-3, max_hand=1, lr=0.02,
+               free=('root', 'pose', 'betas', 'cam'), offsets=None, dense=False):
+        """Test-time refinement of a forward's hands: every flagged hand of `out` (what `forward(...,
+        project=True[, max_hand=K])` returned) is fitted with `mano_fit` - `steps` Adam iterations in one launch - to kp2d
+        [B,(K,)2,21,2] in the units of out['pj2d'] (the canvas, -1..1) and / or joints [B,(K,)2,21,3] (root-aligned, metres),
+        starting from the slots' pose, betas and cam (SLOT_POSES, SLOT_BETAS, SLOT_CAM) with that same prediction as the
+        prior of lam_pose / lam_beta.  weights [B,(K,)2,21] (None: 1/21) apply to both targets; hands whose flag is off get
+        all-zero weights and keep their slot bytes.  The fitted values are written into a COPY of the slots and `mano` runs on
+        them with the projection (offsets [B,10]: also pj2d_org).  -> an `out` dict of the usual keys plus 'fit_loss'
+        [B,(K,)2,2] (first and last evaluated step; 0 for unflagged hands): render, overlay, contact and score take it.  Device
+        tensors, the current stream, no host visit."""
+        slots = out['slots']
+        K = check_max_hand(max_hand)
+        lead = tuple(slots.shape[:-1])
+        if slots.shape[-1] != _lib.SLOT or lead[-1] != 2 or not ((len(lead) == 2 and K == 1) or (len(lead) == 3 and lead[1] == K)):
+            raise ValueError('out does not hold slots [B,%s2,%d] of max_hand=%d' % ('K,' if K > 1 else '', _lib.SLOT, K))
+        if kp2d is None and joints is None:
+            raise ValueError('refine needs kp2d or joints')
+        for name, t, tail in (('kp2d', kp2d, (21, 2)), ('joints', joints, (21, 3)), ('weights', weights, (21,))):
+            if t is not None and tuple(t.shape) != lead + tail:
+                raise ValueError('%s must be %s, got %s' % (name, lead + tail, tuple(t.shape)))
+        dev = self.device
+        H = slots.numel() // _lib.SLOT
+        rows = slots.reshape(H, _lib.SLOT)
+        flat = lambda t, *tail: None if t is None else t.to(dev, torch.float32).reshape((H,) + tail)
+        side = (torch.arange(H, device=dev, dtype=torch.int32) & 1)      # slot order: left, right
+        on = rows[:, _lib.SLOT_FLAG] > 0.5
+        w = flat(weights, 21) if weights is not None else torch.full((H, 21), 1.0 / 21, dtype=torch.float32, device=dev)
+        w = w * on.unsqueeze(1).to(torch.float32)
+        init = {'poses': rows[:, _lib.SLOT_POSES:_lib.SLOT_POSES + 48], 'betas': rows[:, _lib.SLOT_BETAS:_lib.SLOT_BETAS + 10],
+                'cam': rows[:, _lib.SLOT_CAM:_lib.SLOT_CAM + 3]}
+        fit = self.mano_fit(side, joints=flat(joints, 21, 3), kp2d=flat(kp2d, 21, 2), w_joints=None if joints is None else w,
+                            w_kp2d=None if kp2d is None else w, init=init, prior=torch.cat([init['poses'], init['betas']], 1),
+                            lam_pose=lam_pose, lam_beta=lam_beta, lr=lr, steps=steps, center_idx=self.center_idx, free=free,
+                            dense=dense)
+        new = rows.clone()
+        keep = on.unsqueeze(1)
+        for key, at, n in (('poses', _lib.SLOT_POSES, 48), ('betas', _lib.SLOT_BETAS, 10), ('cam', _lib.SLOT_CAM, 3)):
+            new[:, at:at + n] = torch.where(keep, fit[key], rows[:, at:at + n])
+        off = None
+        if offsets is not None:
+            off = self._frame_offsets(offsets, lead[0]).repeat_interleave(H // lead[0], 0)
+        verts, jts, _, extra = self.mano(new[:, _lib.SLOT_POSES:_lib.SLOT_POSES + 48], new[:, _lib.SLOT_BETAS:_lib.SLOT_BETAS + 10],
+                                         side, center_idx=self.center_idx, cam=new[:, _lib.SLOT_CAM:_lib.SLOT_CAM + 3], offsets=off)
+        res = {k: v for k, v in out.items() if k not in ('cam_trans', 'pj2d_org')}
+        res['slots'] = new.reshape(slots.shape)
+        got = dict(extra, verts=verts, joints=jts)
+        for k, v in got.items():      # an unflagged hand keeps what the forward gave it
+            old = out.get(k)
+            v = v.reshape(lead + tuple(v.shape[1:]))
+            res[k] = v if old is None else torch.where(on.reshape(lead + (1, 1)), v, old.to(dev, torch.float32))
+        res['fit_loss'] = torch.where(keep, fit['loss'], torch.zeros((), dtype=torch.float32, device=dev)).reshape(lead + (2,))
+        return res
+
     def mano_autograd(self, poses, betas, side, center_idx=9):
         """`mano` as a node of torch's autograd graph: (verts, joints, center) that carry gradients back to poses [H,48] and
         betas [H,10] through `mano_backward`.  Once differentiable; side and center_idx are not differentiated."""
@@ -1676,6 +1833,29 @@ class EnginePool(object):
         rest = {k: v for k, v in kw.items() if k != 'cam_trans'}
         return self._on_ticket(ticket, 'score', prepare, keep='_score_keep',
                                call=lambda eng, raw, t: eng.score(out, board=board, max_hand=K, stream=raw, **t, **rest))
+
+    def refine(self, ticket, **kw):
+        """Engine.refine of the ticket's batch: call between submit() (with project=True) and collect().  max_hand is the
+        ticket's.  The fit is mostly torch's own ops around two launches, so it runs on the CALLER's current stream, which is
+        made to wait - on the device - for the ticket's forward; the ticket's stream is then ordered behind it, so that later
+        calls on the ticket and collect() see it.  Returns what Engine.refine returns (a new dict: the ticket's own `out` is
+        not changed)."""
+        i = ticket['slot']
+        if self._busy[i] is not ticket:
+            raise RuntimeError('refine() belongs between submit() and collect() of its ticket')
+        out = ticket['out']
+        K = out['slots'].shape[1] if out['slots'].dim() == 4 else 1
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ticket['event'])
+        res = self.engines[i].refine(out, max_hand=K, **kw)
+        done = torch.cuda.Event()
+        done.record(cur)
+        self.streams[i].wait_event(done)
+        after = torch.cuda.Event()
+        after.record(self.streams[i])
+        ticket['event'] = after
+        ticket.setdefault('kept', []).append((res, kw, None))
+        return res
 
     def match(self, ticket, gt, on='pj2d_org', board=None, **kw):
         """Engine.match of the ticket's batch on the ticket's stream, behind its forward: call between submit() (with

@@ -258,3 +258,28 @@ class ManoLayer(object):
         return verts, joints, center
 
     __call__ = forward
+
+    def fit(self, joints=None, kp2d=None, verts=None, steps=100, th_pose_coeffs=None, th_betas=None, th_trans=None, cam=None,
+            free=('root', 'pose', 'betas'), **kw):
+        """Fits this layer's hand to joints [N,21,3], kp2d [N,21,2] and / or verts [N,778,3] with `steps` Adam iterations in one
+        launch (Engine.mano_fit; its other arguments - weights, prior, lam_pose, lam_beta, lr, state, dense - pass through
+        **kw), starting from th_pose_coeffs [N,48] / th_betas / th_trans / cam where given (zeros, cam = (1, 0, 0) otherwise).
+        The function fitted is this layer's forward at its center_idx, with th_trans ADDED to the root-aligned outputs.
+        Axis-angle layers only.  -> (th_pose_coeffs [N,48], th_betas [N,10], th_trans [N,3], cam [N,3], loss [N,2])."""
+        if self.use_pca or self.joint_rot_mode != 'axisang':
+            raise ValueError("ManoLayer.fit fits the 48 axis-angle values: not with use_pca=True or joint_rot_mode='rotmat'")
+        given = [t for t in (joints, kp2d, verts) if t is not None]
+        if not given:
+            raise ValueError('ManoLayer.fit needs joints, kp2d or verts')
+        if self._dirty or self._engine is None:
+            self.sync(self._engine)
+        eng = self._engine
+        N = given[0].shape[0]
+        side = torch.full((N,), 0 if self.side == 'left' else 1, dtype=torch.int32, device=eng.device)
+        init = {k: t for k, t in (('poses', th_pose_coeffs), ('betas', th_betas), ('trans', th_trans), ('cam', cam)) if t is not None}
+        if 'state' in kw and kw['state'] is not None:
+            init = None
+        out = eng.mano_fit(side, joints=joints, kp2d=kp2d, verts=verts, init=init or None, steps=steps,
+                           center_idx=self.center_idx, free=free, **kw)
+        self.fit_state = out['state']
+        return out['poses'], out['betas'], out['trans'], out['cam'], out['loss']

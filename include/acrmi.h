@@ -277,6 +277,29 @@ int acrmi_mano_backward(acrmi_ctx* ctx, const float* poses, int pose_stride, con
                         const int32_t* side, int H, int center_idx, const float* g_verts, const float* g_joints,
                         const float* g_center, float* g_poses, float* g_betas, void* stream);
 
+/* The fused fitter: `steps` (0..1024) iterations of Adam per hand in ONE launch, on the 64 parameters of a
+ * hand - pose [48] (root rotation, articulation), betas [10], trans [3], cam [3] = (s, tx, ty) - against any mix of
+ *   y3 [H,21,3] with w3 [H,21]: J3 = joints + trans;   y2 [H,21,2] with w2 [H,21]: P2 = joints[:, :2] * s + (tx, ty), acrmi_mano's
+ *   pj2d;   yv [H,778,3] with wv [H]: V3 = verts + trans,
+ * (verts, joints) being acrmi_mano's axis-angle outputs at center_idx (-1..20), plus lam_pose |pose[3:48] - prior[3:48]|^2 +
+ * lam_beta |betas - prior[48:58]|^2 (prior [H,58], NULL = zeros).  A NULL target removes its term (its weights are then not
+ * read), NULL weights are ones, a weight that is exactly 0 removes its point (its target is not read into the arithmetic).
+ * state [H, acrmi_mano_fit_state_floats()] is the caller's: parameters [64] | m [64] | v [64] | t | loss of the last evaluated
+ * step | loss of the first | 0; a fresh fit starts from the caller's parameters with everything behind them zero, a later call
+ * continues it bit for bit.  lr5 (HOST, 5 doubles): the learning rates of root rotation, articulation, betas, trans, cam; 0
+ * freezes a group (parameters, m and v keep their bytes).  b1, b2, eps: torch.optim.Adam's (0.9, 0.999, 1e-8); no weight
+ * decay, no amsgrad.  yv != NULL or dense != 0 runs the dense vertex level (all 778 vertices, as acrmi_mano_backward),
+ * otherwise only the five fingertips are skinned and the pose blend table is never read.  Writes poses [H,48], betas [H,10],
+ * trans [H,3], cam [H,3], loss [H,2] (first and last evaluated step of the fit) and, when not NULL, grad [H,64]: the gradient
+ * of the last evaluated step (untouched when steps == 0, which only copies the state's parameters and losses out).  One
+ * workgroup per hand, fixed summation orders, no atomics; always the fp32 tables.  ACRMI_EINVAL for a NULL state, steps or
+ * center_idx out of range - before a device is touched; ACRMI_ESTATE without MANO tables; H == 0 is a success. */
+int acrmi_mano_fit(acrmi_ctx* ctx, float* state, const int32_t* side, int H, int center_idx, const float* y3, const float* w3,
+                   const float* y2, const float* w2, const float* yv, const float* wv, const float* prior, double lam_pose,
+                   double lam_beta, const double* lr5, double b1, double b2, double eps, int steps, int dense, float* poses,
+                   float* betas, float* trans, float* cam, float* loss, float* grad, void* stream);
+int acrmi_mano_fit_state_floats(void);
+
 /* acr/utils.py:430-472 + :474-519 (estimate_translation_np / estimate_translation, the reference's closed-form
  * least-squares branch, unit joint confidences): joints [n,21,3] and pj2d [n,21,2] (in [-1,1]; the 2-D targets are
  * (pj2d+1)*img_size/2) on the device -> cam_trans [n,3].  Solved in fp64 like the reference. */
