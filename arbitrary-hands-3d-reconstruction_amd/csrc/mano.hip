@@ -5,15 +5,11 @@
 // fingertips / joint reorder / root alignment.  Everything between the 58 input floats and the
 // 2397 output floats lives in LDS; the 1.46 MB of per-side tables are read coalesced
 // (blend-shape tables pre-transposed on the host) and stay L2 resident across hands.
-#include "kernels.h"
-#include "mano_plan.h"
+// The kinematic tree, the wave sum and the blend's application are csrc/mano_stages.h's; Rodrigues, the chain link and the
+// rest-pose removal are csrc/mano_grad_plan.h's float instantiations - the functions the backward and the fitter run in double.
+#include "mano_stages.h"
 
 namespace acrmi {
-
-__constant__ int c_parent[16] = {-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14};
-__constant__ int c_depth[16] = {0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3};
-__constant__ int c_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int c_tips[2][5] = ACRMI_MANO_TIPS;  // [left, right]
 
 // H16 = ACRMI_OPT_MANO_FP16 (BASELINE.json configs[4] "fp16 MANO LBS"): the blend-shape tables (shapedirs, posedirs)
 // and the skinning weights are read as f16 copies (0.73 instead of 1.46 MB of L2 traffic per side and hand), every
@@ -50,26 +46,13 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
     if (tid < 144) sR[tid / 9][tid % 9] = pose[tid];
   } else if (tid < 16) {
     // batch_rodrigues (mano/manolayer.py:423-434) + quat2mat (:396-421)
-    float ax = pose[3 * tid], ay = pose[3 * tid + 1], az = pose[3 * tid + 2];
+    float aa[3] = {pose[3 * tid], pose[3 * tid + 1], pose[3 * tid + 2]};
     if (tid > 0) {
-      ax += T.hands_mean[3 * (tid - 1)];
-      ay += T.hands_mean[3 * (tid - 1) + 1];
-      az += T.hands_mean[3 * (tid - 1) + 2];
+      aa[0] += T.hands_mean[3 * (tid - 1)];
+      aa[1] += T.hands_mean[3 * (tid - 1) + 1];
+      aa[2] += T.hands_mean[3 * (tid - 1) + 2];
     }
-    const float ex = ax + 1e-8f, ey = ay + 1e-8f, ez = az + 1e-8f;
-    const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float nx = ax / angle, ny = ay / angle, nz = az / angle;
-    const float half = angle * 0.5f;
-    const float sn = sinf(half);
-    float w = cosf(half), x = sn * nx, y = sn * ny, z = sn * nz;
-    const float qn = sqrtf(w * w + x * x + y * y + z * z);
-    w /= qn; x /= qn; y /= qn; z /= qn;
-    const float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-    const float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-    float* R = sR[tid];
-    R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;    R[2] = 2 * wy + 2 * xz;
-    R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;  R[5] = 2 * yz - 2 * wx;
-    R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;    R[8] = w2 - x2 - y2 + z2;
+    mano_rodrigues(aa, sR[tid]);
   }
   __syncthreads();
   if (tid < 135) {
@@ -91,7 +74,7 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
     const int j = o / 3, d = o % 3;
     float s = 0.f;
     for (int v = lane; v < NV; v += 64) s += T.jreg[j * NV + v] * sV[v * 3 + d];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) sJ[j][d] = s;
   }
   __syncthreads();
@@ -104,8 +87,8 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
   }
   // kinematic chain, three levels below the root (mano/manolayer.py:187-223)
   for (int level = 0; level < 4; ++level) {
-    if (tid < 16 && c_depth[tid] == level) {
-      const int j = tid, p = c_parent[j];
+    if (tid < 16 && mano_depth[tid] == level) {
+      const int j = tid, p = mano_parent[j];
       const float* R = sR[j];
       float* G = sG[j];
       if (p < 0) {
@@ -114,29 +97,16 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
           G[r * 4 + 3] = sJ[0][r];
         }
       } else {
-        const float* P = sG[p];
-        const float t0 = sJ[j][0] - sJ[p][0], t1 = sJ[j][1] - sJ[p][1], t2 = sJ[j][2] - sJ[p][2];
-        for (int r = 0; r < 3; ++r) {
-          const float p0 = P[r * 4], p1 = P[r * 4 + 1], p2 = P[r * 4 + 2], p3 = P[r * 4 + 3];
-          G[r * 4 + 0] = p0 * R[0] + p1 * R[3] + p2 * R[6];
-          G[r * 4 + 1] = p0 * R[1] + p1 * R[4] + p2 * R[7];
-          G[r * 4 + 2] = p0 * R[2] + p1 * R[5] + p2 * R[8];
-          G[r * 4 + 3] = p0 * t0 + p1 * t1 + p2 * t2 + p3;
-        }
+        const float t[3] = {sJ[j][0] - sJ[p][0], sJ[j][1] - sJ[p][1], sJ[j][2] - sJ[p][2]};
+        mano_link(sG[p], R, t, G);
       }
     }
     __syncthreads();
   }
-  if (tid < 16) {   // rest-pose removal: A = G - [0 | G.[J;0]]  (mano/manolayer.py:226-228)
-    const float* G = sG[tid];
-    float* A = sA[tid];
-    for (int r = 0; r < 3; ++r) {
-      A[r * 4] = G[r * 4]; A[r * 4 + 1] = G[r * 4 + 1]; A[r * 4 + 2] = G[r * 4 + 2];
-      A[r * 4 + 3] = G[r * 4 + 3] - (G[r * 4] * sJ[tid][0] + G[r * 4 + 1] * sJ[tid][1] + G[r * 4 + 2] * sJ[tid][2]);
-    }
-  }
+  if (tid < 16) mano_rest(sG[tid], sJ[tid], sA[tid]);   // A = G - [0 | G.[J;0]]  (mano/manolayer.py:226-228)
   __syncthreads();
-  // linear blend skinning (mano/manolayer.py:230-240)
+  // linear blend skinning (mano/manolayer.py:230-240).  Tm is mano_blend's sum (csrc/mano_stages.h) with the f16 pair decoded
+  // per weight; it stays written out here: through mano_blend this kernel, already at 256 + 256 registers, triples its scratch
   for (int v = v0 + tid; v < v1; v += 256) {
     float Tm[12];
 #pragma unroll
@@ -150,17 +120,13 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
 #pragma unroll
       for (int e = 0; e < 12; ++e) Tm[e] += sA[j][e] * w;
     }
-    const float x = sV[v * 3], y = sV[v * 3 + 1], z = sV[v * 3 + 2];
-    const float ox = Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3];
-    const float oy = Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7];
-    const float oz = Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11];
-    sV[v * 3] = ox; sV[v * 3 + 1] = oy; sV[v * 3 + 2] = oz;
+    mano_blend_apply(Tm, sV[v * 3], sV[v * 3 + 1], sV[v * 3 + 2], sV + v * 3);
   }
   __syncthreads();
   if (tid < 21) {   // joints: 16 chain translations + 5 fingertip vertices, reordered (:241-254)
-    const int src = c_reorder[tid];
+    const int src = mano_reorder[tid];
     for (int d = 0; d < 3; ++d)
-      sJtr[tid][d] = src < 16 ? sG[src][d * 4 + 3] : sV[c_tips[side][src - 16] * 3 + d];
+      sJtr[tid][d] = src < 16 ? sG[src][d * 4 + 3] : sV[mano_tips[side][src - 16] * 3 + d];
   }
   __syncthreads();
   if (tid < 3) sCenter[tid] = a.center_idx >= 0 ? sJtr[a.center_idx][tid] : 0.f;
@@ -185,8 +151,8 @@ __global__ __launch_bounds__(256) void mano_kernel(const ManoArgs a) {
     if (proj && a.verts_camed) a.verts_camed[(size_t)row * NV3 + i] = d == 2 ? v : v * cs + (d == 0 ? ctx : cty);
   }
   // joint j: a chain joint is written by slice 0, a fingertip by the slice that skinned its vertex
-  const int jsrc = tid < 63 ? c_reorder[tid / 3] : 0;
-  const int jtip = jsrc >= 16 ? c_tips[side][jsrc - 16] : -1;
+  const int jsrc = tid < 63 ? mano_reorder[tid / 3] : 0;
+  const int jtip = jsrc >= 16 ? mano_tips[side][jsrc - 16] : -1;
   if (tid < 63 && (jtip < 0 ? slice == 0 : (jtip >= v0 && jtip < v1))) {
     const int j = tid / 3, d = tid % 3;
     const float v = sJtr[j][d] - (d == 0 ? cx : (d == 1 ? cy : cz));

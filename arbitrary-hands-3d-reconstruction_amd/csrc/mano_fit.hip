@@ -4,10 +4,11 @@
 // Adam's m and v and the targets of the hand live in LDS for the whole launch; every step runs forward, loss and cotangents,
 // backward and the update without leaving the workgroup.
 //
-// The forward recompute and the walk back restate csrc/mano_grad.hip's statements (its kernel is not touched: acrmi_mano_backward
-// returns the bytes it returned before): the joint level in fp64, the vertex level in fp32, always the fp32 tables.  What the
-// fit needs beyond the backward's recompute - the root-aligned joints, the fingertips and, with a vertex target, the skinned
-// vertices - is computed with csrc/mano.hip's statements from the fp64 chain.
+// The forward recompute and the walk back are the backward's (csrc/mano_grad.hip): both kernels call the stages of
+// csrc/mano_stages.h - the joint level in fp64, the vertex level in fp32, always the fp32 tables.  What the fit needs beyond the
+// backward's recompute - the root-aligned joints, the fingertips and, with a vertex target, the skinned vertices - is the blend of
+// csrc/mano_stages.h applied to the fp64 chain's transforms.  This file keeps what is the fitter's alone: the prologue, the
+// sparse level's 15 coordinates, the loss with its cotangents and the Adam step.
 //
 // TWO VERTEX LEVELS (the template argument).  DENSE, with a vertex target (or dense=1): all 778 vertices as in the backward, the
 // 1.26 MB pose blend table is streamed twice per step.  SPARSE, without one: the only vertices that matter are the five
@@ -16,29 +17,12 @@
 // step then touches no global memory at all.
 //
 // Every sum has one fixed order (mano_fit_plan.h); no atomics; a hand's result does not depend on the batch it is in.
-#include "kernels.h"
 #include "mano_fit_plan.h"
-#include "mano_grad_plan.h"
-#include "mano_plan.h"
+#include "mano_stages.h"
 
 namespace acrmi {
 
-namespace {
-
-__constant__ int f_parent[16] = {-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14};
-__constant__ int f_depth[16] = {0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3, 1, 2, 3};
-__constant__ int f_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int f_tips[2][5] = ACRMI_MANO_TIPS;  // [left, right]
-
-template <typename T>
-__device__ inline T fit_wave_sum(T s) {
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  return s;      // lane 0 holds the sum
-}
-
 static_assert(FIT_THREADS == MANO_GRAD_THREADS, "the walk back is the backward's, thread for thread");
-
-}  // namespace
 
 // The sparse level fits two workgroups per CU into the register file without scratch; the dense level, which keeps the 16 joint
 // transforms in registers across its vertex loops, does not (864 bytes of scratch per lane when capped): one per CU.
@@ -82,6 +66,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
   __shared__ float sRed[4][4];       // per wave: the sums of the vertex cotangents [3] and of the squared residuals
   float (*sPart)[16][12] = reinterpret_cast<float (*)[16][12]>(sVd);      // dense: [MANO_GRAD_GROUPS][16][12]
   static_assert(!DENSE || sizeof(float) * MANO_GRAD_GROUPS * 16 * 12 <= sizeof(double) * NV3, "sPart lives in sVd");
+  const ManoJointLevel L = {sAA, sR, sJ, sG, sGA, sGG, sGJ, sGR, sA};
 
   float* st = a.state + (size_t)row * FIT_STATE;
   if (tid < FIT_PARAMS) {
@@ -103,7 +88,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
     if (tid >= 96 && tid < 117) sW2[tid - 96] = has2 ? (a.w2 ? a.w2[(size_t)row * 21 + tid - 96] : 1.f) : 0.f;
     if (tid >= 128 && tid < 128 + FIT_PARAMS)
       sPrior[tid - 128] = (a.prior && tid - 128 < FIT_PRIOR) ? a.prior[(size_t)row * FIT_PRIOR + tid - 128] : 0.f;
-    if (tid < 80) sW[tid / 16][tid % 16] = T.weights[f_tips[side][tid / 16] * 16 + tid % 16];
+    if (tid < 80) sW[tid / 16][tid % 16] = T.weights[mano_tips[side][tid / 16] * 16 + tid % 16];
     if constexpr (DENSE) {
       if (hasV)
         for (int i = tid; i < NV3; i += FIT_THREADS) sYV[i] = a.yv[(size_t)row * NV3 + i];
@@ -114,7 +99,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
         const float* col = k == 0 ? T.v_template : T.shapedirs_t + (size_t)(k - 1) * NV3;
         double s = 0.0;
         for (int v = lane; v < NV; v += 64) s += (double)T.jreg[j * NV + v] * (double)col[v * 3 + d];
-        s = fit_wave_sum(s);
+        s = wave_sum(s);
         if (lane == 0) {
           if (k == 0) sJT[jd] = s;
           else sJD[(k - 1) * 48 + jd] = s;
@@ -122,58 +107,24 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
       }
       for (int i = tid; i < 135 * 15; i += FIT_THREADS) {
         const int k = i / 15, c = i % 15;
-        sPD[i] = T.posedirs_t[(size_t)k * NV3 + f_tips[side][c / 3] * 3 + c % 3];
+        sPD[i] = T.posedirs_t[(size_t)k * NV3 + mano_tips[side][c / 3] * 3 + c % 3];
       }
       if (tid < 150) {
         const int k = tid / 15, c = tid % 15;
-        sSD[tid] = T.shapedirs_t[(size_t)k * NV3 + f_tips[side][c / 3] * 3 + c % 3];
+        sSD[tid] = T.shapedirs_t[(size_t)k * NV3 + mano_tips[side][c / 3] * 3 + c % 3];
       }
-      if (tid < 15) sVT[tid] = T.v_template[f_tips[side][tid / 3] * 3 + tid % 3];
+      if (tid < 15) sVT[tid] = T.v_template[mano_tips[side][tid / 3] * 3 + tid % 3];
     }
   }
   __syncthreads();
 
   for (int step = 1; step <= steps; ++step) {
-    // ---- forward: the backward's recompute (csrc/mano_grad.hip), then csrc/mano.hip's tips, joints and root alignment ----
-    if (tid < 16) {
-      double aa[3] = {sP[3 * tid], sP[3 * tid + 1], sP[3 * tid + 2]};
-      if (tid > 0) {
-        aa[0] += T.hands_mean[3 * (tid - 1)];
-        aa[1] += T.hands_mean[3 * (tid - 1) + 1];
-        aa[2] += T.hands_mean[3 * (tid - 1) + 2];
-      }
-      sAA[tid][0] = aa[0]; sAA[tid][1] = aa[1]; sAA[tid][2] = aa[2];
-      mano_rodrigues(aa, sR[tid]);
-    }
+    // ---- forward: the recompute both levels share with the backward (csrc/mano_stages.h), then csrc/mano.hip's tips, joints
+    // and root alignment ----
+    mano_rotations(L, sP, T.hands_mean, tid);
     const float* sBeta = sP + FIT_BETAS;
     if constexpr (DENSE) {
-      __syncthreads();
-      if (tid < 135) {
-        const int k9 = tid % 9;
-        sPoseMap[tid] = (float)(sR[1 + tid / 9][k9] - ((k9 == 0 || k9 == 4 || k9 == 8) ? 1.0 : 0.0));
-      }
-      for (int i = tid; i < NV3; i += FIT_THREADS) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 10; ++k) s += (double)T.shapedirs_t[k * NV3 + i] * (double)sBeta[k];
-        s += (double)T.v_template[i];
-        sVd[i] = s;
-        sV[i] = (float)s;
-      }
-      __syncthreads();
-      for (int o = wave * 12; o < wave * 12 + 12; ++o) {
-        const int j = o / 3, d = o % 3;
-        double s = 0.0;
-        for (int v = lane; v < NV; v += 64) s += (double)T.jreg[j * NV + v] * sVd[v * 3 + d];
-        s = fit_wave_sum(s);
-        if (lane == 0) sJ[j][d] = s;
-      }
-      __syncthreads();
-      for (int i = tid; i < NV3; i += FIT_THREADS) {
-        float s = 0.f;
-        for (int k = 0; k < 135; ++k) s += T.posedirs_t[k * NV3 + i] * sPoseMap[k];
-        sV[i] += s;
-      }
+      mano_dense_forward(T, L, sBeta, sPoseMap, sVd, sV, tid, lane, wave);
     } else {
       if (tid >= 192 && tid < 192 + 48) {      // J = J_template + J_dirs . betas
         const int jd = tid - 192;
@@ -191,10 +142,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
         sV[i] = (float)s;
       }
       __syncthreads();
-      if (tid < 135) {
-        const int k9 = tid % 9;
-        sPoseMap[tid] = (float)(sR[1 + tid / 9][k9] - ((k9 == 0 || k9 == 4 || k9 == 8) ? 1.0 : 0.0));
-      }
+      mano_pose_map(L, sPoseMap, tid);
       __syncthreads();
       if (tid < 15) {
         float s = 0.f;
@@ -202,47 +150,17 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
         sV[tid] += s;
       }
     }
-    for (int level = 0; level < 4; ++level) {
-      if (tid < 16 && f_depth[tid] == level) {
-        const int j = tid, p = f_parent[j];
-        if (p < 0) {
-          for (int r = 0; r < 3; ++r) {
-            sG[j][r * 4 + 0] = sR[j][r * 3]; sG[j][r * 4 + 1] = sR[j][r * 3 + 1]; sG[j][r * 4 + 2] = sR[j][r * 3 + 2];
-            sG[j][r * 4 + 3] = sJ[0][r];
-          }
-        } else {
-          const double t[3] = {sJ[j][0] - sJ[p][0], sJ[j][1] - sJ[p][1], sJ[j][2] - sJ[p][2]};
-          mano_link(sG[p], sR[j], t, sG[j]);
-        }
-      }
-      __syncthreads();
-    }
-    if (tid < 16) {
-      double A[12];
-      mano_rest(sG[tid], sJ[tid], A);
-#pragma unroll
-      for (int e = 0; e < 12; ++e) sA[tid][e] = (float)A[e];
-    }
+    mano_chain(L, tid);
     __syncthreads();
-    if (tid < 5) {      // the fingertips: csrc/mano.hip's skinning of one vertex
-      const int at = DENSE ? f_tips[side][tid] * 3 : tid * 3;
+    if (tid < 5) {      // the fingertips: the forward's skinning of one vertex
+      const int at = DENSE ? mano_tips[side][tid] * 3 : tid * 3;
       float Tm[12];
-#pragma unroll
-      for (int e = 0; e < 12; ++e) Tm[e] = 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float w = sW[tid][j];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) Tm[e] += sA[j][e] * w;
-      }
-      const float x = sV[at], y = sV[at + 1], z = sV[at + 2];
-      sTip[tid][0] = Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3];
-      sTip[tid][1] = Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7];
-      sTip[tid][2] = Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11];
+      mano_blend(sA, sW[tid], Tm);
+      mano_blend_apply(Tm, sV[at], sV[at + 1], sV[at + 2], sTip[tid]);
     }
     __syncthreads();
     if (tid < 63) {
-      const int j = tid / 3, d = tid % 3, src = f_reorder[j];
+      const int j = tid / 3, d = tid % 3, src = mano_reorder[j];
       sJtr[j][d] = src < 16 ? sG[src][d * 4 + 3] : (double)sTip[src - 16][d];
     }
     __syncthreads();
@@ -267,23 +185,12 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
         const float c0 = (float)cen[0], c1 = (float)cen[1], c2 = (float)cen[2];
         const float t0f = sP[FIT_TRANS], t1f = sP[FIT_TRANS + 1], t2f = sP[FIT_TRANS + 2];
         for (int v = tid; v < NV; v += FIT_THREADS) {
-          float Tm[12];
-#pragma unroll
-          for (int e = 0; e < 12; ++e) Tm[e] = 0.f;
-          const float* wrow = T.weights + v * 16;
-#pragma unroll
-          for (int j = 0; j < 16; ++j) {
-            const float w = wrow[j];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) Tm[e] += sA[j][e] * w;
-          }
-          const float x = sV[v * 3], y = sV[v * 3 + 1], z = sV[v * 3 + 2];
-          const float ox = Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3];
-          const float oy = Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7];
-          const float oz = Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11];
-          const float r0 = fit_vertex_residual(ox - c0, t0f, sYV[v * 3]);
-          const float r1 = fit_vertex_residual(oy - c1, t1f, sYV[v * 3 + 1]);
-          const float r2 = fit_vertex_residual(oz - c2, t2f, sYV[v * 3 + 2]);
+          float Tm[12], o[3];
+          mano_blend(sA, T.weights + v * 16, Tm);
+          mano_blend_apply(Tm, sV[v * 3], sV[v * 3 + 1], sV[v * 3 + 2], o);
+          const float r0 = fit_vertex_residual(o[0] - c0, t0f, sYV[v * 3]);
+          const float r1 = fit_vertex_residual(o[1] - c1, t1f, sYV[v * 3 + 1]);
+          const float r2 = fit_vertex_residual(o[2] - c2, t2f, sYV[v * 3 + 2]);
           const float g0 = 2.f * wv * r0, g1 = 2.f * wv * r1, g2 = 2.f * wv * r2;
           sGV[v * 3] = g0; sGV[v * 3 + 1] = g1; sGV[v * 3 + 2] = g2;
           s4[0] += g0; s4[1] += g1; s4[2] += g2;
@@ -294,7 +201,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
       }
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
-        const float s = fit_wave_sum(s4[d]);
+        const float s = wave_sum(s4[d]);
         if (lane == 0) sRed[wave][d] = s;
       }
     } else {
@@ -314,62 +221,12 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
     }
     __syncthreads();
 
-    // ---- the walk back: csrc/mano_grad.hip's, from the joints on ----
-    if (tid < 16) {
-      int at = 0;
-      for (int q = 0; q < 21; ++q)
-        if (f_reorder[q] == tid) at = q;
-      for (int e = 0; e < 12; ++e) sGG[tid][e] = (e & 3) == 3 ? (double)sGJtr[at][e >> 2] : 0.0;
-    } else if (tid >= 64 && tid < 64 + 15) {      // a fingertip is a skinned vertex: its cotangent lands there
-      const int q = (tid - 64) / 3, d = (tid - 64) % 3;
-      int at = 0;
-      for (int k = 0; k < 21; ++k)
-        if (f_reorder[k] == 16 + q) at = k;
-      if constexpr (DENSE) sGV[f_tips[side][q] * 3 + d] += sGJtr[at][d];
-      else sGV[q * 3 + d] = sGJtr[at][d];
-    }
+    // ---- the walk back (csrc/mano_stages.h): the backward's, from the joints on; the sparse level restricts the vertex sums
+    // to the five tips ----
+    mano_seed<DENSE>(L, sGJtr, sGV, side, tid);
     __syncthreads();
     if constexpr (DENSE) {
-      {
-        const int j = tid & 15, grp = tid >> 4;
-        float acc[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) acc[e] = 0.f;
-        for (int v = grp; v < NV; v += MANO_GRAD_GROUPS) {
-          const float w = T.weights[v * 16 + j];
-          const float x[4] = {sV[v * 3], sV[v * 3 + 1], sV[v * 3 + 2], 1.f};
-#pragma unroll
-          for (int r = 0; r < 3; ++r) {
-            const float wg = w * sGV[v * 3 + r];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[r * 4 + c] += wg * x[c];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 12; ++e) sPart[grp][j][e] = acc[e];
-      }
-      __syncthreads();
-      if (tid < 192) {
-        double s = 0.0;
-        for (int g = 0; g < MANO_GRAD_GROUPS; ++g) s += (double)sPart[g][tid / 12][tid % 12];
-        sGA[tid / 12][tid % 12] = s;
-      }
-      for (int v = tid; v < NV; v += FIT_THREADS) {
-        float Tm[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) Tm[e] = 0.f;
-        const float* wrow = T.weights + v * 16;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float w = wrow[j];
-#pragma unroll
-          for (int e = 0; e < 12; ++e) Tm[e] += sA[j][e] * w;
-        }
-        const float g0 = sGV[v * 3], g1 = sGV[v * 3 + 1], g2 = sGV[v * 3 + 2];
-        sGV[v * 3] = Tm[0] * g0 + Tm[4] * g1 + Tm[8] * g2;
-        sGV[v * 3 + 1] = Tm[1] * g0 + Tm[5] * g1 + Tm[9] * g2;
-        sGV[v * 3 + 2] = Tm[2] * g0 + Tm[6] * g1 + Tm[10] * g2;
-      }
+      mano_skin_backward(T, L, sV, sGV, sPart, tid);
     } else {
       if (tid < 192) {      // gA[j] over the five tips, ascending
         const int j = tid / 12, e = tid % 12, r = e >> 2, c = e & 3;
@@ -381,54 +238,14 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
       __syncthreads();
       if (tid < 5) {
         float Tm[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) Tm[e] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const float w = sW[tid][j];
-#pragma unroll
-          for (int e = 0; e < 12; ++e) Tm[e] += sA[j][e] * w;
-        }
-        const float g0 = sGV[tid * 3], g1 = sGV[tid * 3 + 1], g2 = sGV[tid * 3 + 2];
-        sGV[tid * 3] = Tm[0] * g0 + Tm[4] * g1 + Tm[8] * g2;
-        sGV[tid * 3 + 1] = Tm[1] * g0 + Tm[5] * g1 + Tm[9] * g2;
-        sGV[tid * 3 + 2] = Tm[2] * g0 + Tm[6] * g1 + Tm[10] * g2;
+        mano_blend(sA, sW[tid], Tm);
+        mano_blend_apply_t(Tm, sGV[tid * 3], sGV[tid * 3 + 1], sGV[tid * 3 + 2], sGV + tid * 3);
       }
     }
     __syncthreads();
-    if (tid < 16) mano_rest_backward(sG[tid], sJ[tid], sGA[tid], sGG[tid], sGJ[tid]);
-    __syncthreads();
-    for (int level = 2; level >= 0; --level) {
-      if (tid < 16 && f_depth[tid] == level) {
-        const int p = tid;
-        for (int j = p + 1; j < 16; ++j) {
-          if (f_parent[j] != p) continue;
-          const double t[3] = {sJ[j][0] - sJ[p][0], sJ[j][1] - sJ[p][1], sJ[j][2] - sJ[p][2]};
-          double gt[3];
-          mano_link_backward(sG[p], sR[j], t, sGG[j], sGG[p], sGR[j], gt);
-          for (int d = 0; d < 3; ++d) {
-            sGJ[j][d] += gt[d];
-            sGJ[p][d] -= gt[d];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (tid < 12) {      // the root: G_0 = [R_0 | J_0]
-      const int r = tid >> 2, c = tid & 3;
-      if (c < 3) sGR[0][r * 3 + c] = sGG[0][tid];
-      else sGJ[0][r] += sGG[0][tid];
-    }
-    __syncthreads();
+    mano_chain_backward(L, tid);
     if constexpr (DENSE) {
-      for (int k = wave; k < 135; k += 4) {
-        const float* prow = T.posedirs_t + (size_t)k * NV3;
-        float s = 0.f;
-#pragma unroll 4
-        for (int i = lane; i < NV3; i += 64) s += prow[i] * sGV[i];
-        s = fit_wave_sum(s);
-        if (lane == 0) sGR[1 + k / 9][k % 9] += (double)s;
-      }
+      mano_pose_blend_backward(T, L, sGV, lane, wave);
     } else {
       if (tid < 135) {
         float s = 0.f;
@@ -438,11 +255,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
       }
     }
     __syncthreads();
-    if (tid < 16) {
-      double ga[3];
-      mano_rodrigues_backward(sAA[tid], sGR[tid], ga);
-      sGrad[3 * tid] = (float)ga[0]; sGrad[3 * tid + 1] = (float)ga[1]; sGrad[3 * tid + 2] = (float)ga[2];
-    }
+    mano_rotations_backward(L, sGrad, tid);
     if (tid >= 128 && tid < 131) {      // trans: the joints' share, then the vertices'
       const int d = tid - 128;
       sGrad[FIT_TRANS + d] = (float)(sSum[1 + d] + (double)((sRed[0][d] + sRed[1][d]) + (sRed[2][d] + sRed[3][d])));
@@ -450,22 +263,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
       sGrad[FIT_CAM + tid - 131] = (float)sSum[4 + tid - 131];
     }
     if constexpr (DENSE) {
-      for (int i = tid; i < NV3; i += FIT_THREADS) {
-        const int v = i / 3, d = i - 3 * v;
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) s += T.jreg[j * NV + v] * (float)sGJ[j][d];
-        sGV[i] += s;
-      }
-      __syncthreads();
-      for (int k = wave; k < 10; k += 4) {
-        const float* srow = T.shapedirs_t + (size_t)k * NV3;
-        float s = 0.f;
-#pragma unroll 4
-        for (int i = lane; i < NV3; i += 64) s += srow[i] * sGV[i];
-        s = fit_wave_sum(s);
-        if (lane == 0) sGrad[FIT_BETAS + k] = s;
-      }
+      mano_shape_backward(T, L, sGV, sGrad + FIT_BETAS, tid, lane, wave);
     } else {
       if (tid >= 64 && tid < 74) {      // g_betas[k] = shapedirs[k, tips] . g_vposed + J_dirs[k] . gJ
         const int k = tid - 64;
@@ -482,7 +280,7 @@ __global__ __launch_bounds__(FIT_THREADS, DENSE ? 1 : 2) void mano_fit_kernel(co
     if (tid < FIT_PARAMS) {
       double g = (double)sGrad[tid];
       double reg = fit_prior(tid, (double)sP[tid], sPrior[tid], a.lam_pose, a.lam_beta, &g);
-      reg = fit_wave_sum(reg);
+      reg = wave_sum(reg);
       const float gf = (float)g;
       sGrad[tid] = gf;
       const double t = (double)t0 + (double)step;

@@ -3,9 +3,8 @@
 // Plain C++, no HIP: tools/mano_grad_check.cpp compiles it alone and holds every backward to central differences of its
 // forward in double; ACRMI_HD (csrc/roi_plan.h) is `__host__ __device__` when the translation unit is HIP.
 //
-// The forward pieces repeat csrc/mano.hip's statements operation by operation; templates over the scalar type: the kernel
-// runs this joint level in double (csrc/mano_grad.hip says why), the float instantiation is the forward kernel's
-// arithmetic.  The backward pieces are the chain rule through exactly those operations, the 1e-8 inside the norm included:
+// The forward pieces are csrc/mano.hip's statements: mano_kernel calls their float instantiation, the backward and the
+// fitter run this joint level in double (csrc/mano_grad.hip says why) through csrc/mano_stages.h.  The backward pieces are the chain rule through exactly those operations, the 1e-8 inside the norm included:
 // it makes the map smooth at a zero axis-angle, and its derivative is taken as it stands.  Matrices are row major; a rigid
 // transform is its upper 3 x 4 block [R | t], 12 values.
 //

@@ -12,7 +12,7 @@ namespace acrmi {
 constexpr int NV = 778, NV3 = 2334;
 
 // The five fingertip vertices (mano/manolayer.py:244-247), thumb to little finger, [left, right]: the initialiser of the
-// kernel's __constant__ copy and of the host's.
+// device table (csrc/mano_stages.h's mano_tips, beside the rest of the kinematic tree) and of the host's.
 #define ACRMI_MANO_TIPS {{745, 317, 445, 556, 673}, {745, 317, 444, 556, 673}}
 constexpr int MANO_TIPS[2][5] = ACRMI_MANO_TIPS;
 
